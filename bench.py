@@ -2,7 +2,11 @@
 """bench.py -- DoF-updates/s of one Newmark step (Newton x (assembly + CG) + Newmark updates) of the
 neo-Hookean solver on a synthetic 3D Q2 block (BASELINE.json metric).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the headline line.  --full adds everything else the benchmark
+measures: the live CPU baseline, the live HBM-traffic passes, the further configurations (config.with_*), the streaming
+calibration, and for N > 1 the weak-scaling field.  --dump-outputs DIR writes what the last timed step computed as .npy files.
 
 works as a bare command for every N: with N > 1 and no WORLD_SIZE in the environment it starts the N ranks itself
 as child processes (`python -m torch.distributed.run ...`, before anything touches the GPU) and relays rank 0's
@@ -12,8 +16,8 @@ A step = one full Newmark step on the resident mesh under the ramped constant in
 (0,-2e3,0) Pa (ramp over the first 10 steps).  Rank 0 prints ONE JSON line.
 
 N > 1: the headline workload is BASELINE configuration 4 as written -- the ONE 59^3-cell block (5,055,477 DoFs)
-domain-decomposed over the N GPUs ("scaling": "strong"); the weak-scaling number (one 59^3 block per GPU) is
-measured afterwards and reported as a second field, `weak_scaling`.
+domain-decomposed over the N GPUs ("scaling": "strong"); with --full the weak-scaling number (one 59^3 block per GPU)
+is measured afterwards and reported as a second field, `weak_scaling`.
 """
 import argparse
 import importlib.util
@@ -31,6 +35,11 @@ MF_FLOPS_PER_LANE = 712.0  # FP64 flop per lane of a cell's wavefront in mf_spmv
 # wave instructions) x 64 lanes / (205,379 cells x 64 lanes), profiles/r05/pmc_counters_mf_spmv_n59.json
 MF27_FLOPS_PER_LANE = 642.0  # mf_spmv27, per lane of a wavefront of TWO cells: 2 x 267 FMA + 96 MUL + 12 ADD FP64 wave instructions
 CPU_FULL_RUN = os.path.join(ROOT, "profiles", "r02", "cpu_baseline_config3_full.json")  # unit counts of a whole CPU step (deterministic)
+# wall-clock guards of the --full run's CPU leg and counter passes (MI_BENCH_CPU_BUDGET_S / MI_BENCH_PMC_BUDGET_S override
+# them): the whole --full run has to end within 10 minutes, the CPU leg's fallback sample included
+CPU_BUDGET_S = 300
+PMC_BUDGET_S = 120
+DUMP_BYTES_MAX = 64 * 10 ** 6  # --dump-outputs: all files together
 
 
 def _pkg():
@@ -171,7 +180,7 @@ def cpu_baseline(cells, its_a, its_b, budget_s, config4):
         configures it, and (B) CG+Jacobi -- ~200 s on a 64-core socket;
       * BASELINE configuration 4 (59^3 cells, the metric's own mesh): ONE Newton iteration (one assembly + one linear
         solve from zero with (A) and with (B)) -- ~310 s.
-    `budget_s` (MI_BENCH_CPU_BUDGET_S, default 900) is a wall-clock guard over both: a leg that would not fit is
+    `budget_s` (MI_BENCH_CPU_BUDGET_S, default CPU_BUDGET_S) is a wall-clock guard over both: a leg that would not fit is
     replaced by the bounded sample of round 3 (one assembly, its_a / its_b iterations, scaled with the step's unit
     counts from the committed full run) resp. skipped, and `sample` says so.  Nothing here is read from a committed file
     unless the guard fired."""
@@ -266,7 +275,7 @@ def pmc_reduce(root):
 
 
 def pmc_traffic(cells, budget_s):
-    """LIVE in the default run (round 6; `roofline.traffic` was null until round 5): one Newmark step of the headline
+    """LIVE in the --full run (round 6; `roofline.traffic` was null until round 5): one Newmark step of the headline
     configuration in three CHILD processes under `rocprofv3 --pmc <counter>` -- one counter per pass, nothing but --pmc, as the
     MI355X guide prescribes -- started while this process has not touched the GPU.  Returns (per-kernel dict or None, note)."""
     import shutil
@@ -294,6 +303,37 @@ def pmc_traffic(cells, budget_s):
 
 
 # ---------------------------------------------------------------------------------------------- GPU side
+def dump_outputs(outdir, G, info):
+    """--dump-outputs: what a caller of the timed path holds after its last step, as float64 .npy files.  A run's inputs are
+    fixed by its arguments (synthetic mesh, ramped traction), so the files of two builds compare one to one.  A vector
+    longer than its share of DUMP_BYTES_MAX is written as its entries at a fixed, seeded set of indices."""
+    import numpy as np
+    M = _pkg()
+
+    def sample(a, cap, seed):
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        if a.shape[0] <= cap:
+            return a
+        return a[np.sort(np.random.default_rng(seed).choice(a.shape[0], size=cap, replace=False))]
+
+    # shares of the limit: the displacement whole up to 5.2 M DoFs (42 MB; 59^3 cells: 5,055,477), velocity and acceleration
+    # 8.4 MB each at the same indices, the interface displacement 2.1 MB
+    u_cap, va_cap, if_cap = 5 * 2 ** 20, 2 ** 20, 2 ** 18 // 3
+    rec = [info.newton_iterations, info.assemblies, info.lin_its_total, info.converged, info.res_norm, info.res_abs,
+           info.upd_norm, info.upd_abs] + [info.lin_its[i] for i in range(min(info.newton_iterations, 16))]
+    out = {"displacement": sample(G.get(M.V_U), u_cap, 1),
+           "velocity": sample(G.get(M.V_V), va_cap, 2),
+           "acceleration": sample(G.get(M.V_A), va_cap, 2),
+           "interface_displacement": sample(G.get_interface_displacement(), if_cap, 3),  # (nodes, dim): what preCICE receives
+           # newton iterations, assemblies, CG iterations, converged, residual / update norms (relative, absolute), CG
+           # iterations of each Newton iteration
+           "step_record": np.array(rec, dtype=np.float64)}
+    assert sum(a.nbytes for a in out.values()) <= DUMP_BYTES_MAX
+    os.makedirs(outdir, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(outdir, name + ".npy"), a)
+
+
 def free_port():
     s = socket.socket()
     s.bind(("127.0.0.1", 0))
@@ -358,40 +398,53 @@ def main():
                     help="Gauss points per direction of the multigrid smoother's fine-level operator: 3 (the library's default since "
                          "round 6: the full-order rule of Q2 elements, mf_spmv27 with two cells per wave; a preconditioner-side choice, "
                          "all fp64 -- the CG's operator, the residuals and the assembly keep the reference's 4, qf_cell(p+2)) or 4; the "
-                         "default run reports the other one as config.with_smoother_quadrature_4")
+                         "--full run reports the other one as config.with_smoother_quadrature_4")
     ap.add_argument("--fine-level", choices=["assembled", "matrix-free"], default="assembled",
                     help="assembled (default; the north-star path: global tangent scattered by colours + sell_spmv) or matrix-free: "
                          "no assembled fine tangent at all -- a tangent assembly writes point records, residual and the nodes' "
-                         "diagonal blocks, every fine-level product runs on mf_spmv (tuning \"fine_level\" 1); the default run "
+                         "diagonal blocks, every fine-level product runs on mf_spmv (tuning \"fine_level\" 1); the --full run "
                          "reports it as config.with_matrix_free_fine_level over the same step window")
     ap.add_argument("--cg-start", choices=["zero", "previous-update", "previous-step", "extrapolated"], default="previous-step",
                     help="start vector of the linear solves: previous-step (default, what the executable sets: the j-th solve of "
                          "a step starts from the solution of the j-th solve of the previous step), extrapolated (the same over "
                          "two steps), zero, or previous-update as the reference's loop has it (nonlinear_elasticity.cc:419,472: "
-                         "the previous Newton update of the step); the stopping rule is the same; the N = 1 line reports the "
-                         "other choices as further measurements")
+                         "the previous Newton update of the step); the stopping rule is the same; the N = 1 line of --full "
+                         "reports the other choices as further measurements")
     ap.add_argument("--slabs", type=int, default=1, help="diagnostic: cut the mesh into this many slabs on ONE GPU")
     ap.add_argument("--scaling", choices=["weak", "strong"], default="strong",
                     help="N GPUs: strong = the one cells^3 block (BASELINE configuration 4) is cut into N parts (default); "
                          "weak = every GPU gets its own cells^3 block of a beam (cells x cells x N*cells)")
-    ap.add_argument("--no-weak", action="store_true", help="N > 1: skip the second (weak-scaling) measurement")
+    ap.add_argument("--no-weak", action="store_true", help="with --full, N > 1: skip the second (weak-scaling) measurement")
     ap.add_argument("--no-rccl", action="store_true",
                     help="diagnostic: with N ranks every rank solves its own copy of the single-GPU problem (no RCCL "
                          "communicator); exercises launcher, rendezvous and reporting on a box with fewer GPUs than ranks")
     ap.add_argument("--cpu-cells", type=int, default=34,
-                    help="cells per side of the CPU-baseline sample (34 = BASELINE configuration 3; 0: skip)")
+                    help="with --full: cells per side of the CPU-baseline sample (34 = BASELINE configuration 3; 0: skip)")
     ap.add_argument("--cpu-its", type=str, default="8,30", help="CG iterations timed by the CPU sample: SSOR,Jacobi")
     ap.add_argument("--no-cpu-config4", action="store_true",
                     help="skip the CPU leg on the metric's own mesh (BASELINE configuration 4, 59^3 cells: ONE Newton iteration = one "
-                         "assembly + CG+Jacobi and CG+SSOR solves, ~5 minutes on a 64-core socket), which the default run includes")
+                         "assembly + CG+Jacobi and CG+SSOR solves, ~5 minutes on a 64-core socket), which the --full run includes")
     ap.add_argument("--cpu-config4", action="store_true", help=argparse.SUPPRESS)  # (round 3's opt-in; now the default)
     ap.add_argument("--cpu-worker", type=str, default=None, help=argparse.SUPPRESS)
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)  # child of pmc_traffic(): one step, no output
     ap.add_argument("--no-sides", action="store_true",
-                    help="profiling runs: skip the further measurements beside the headline (config.with_*), so that a kernel trace "
-                         "of the process holds the kernels of ONE path")
-    ap.add_argument("--no-pmc", action="store_true", help="skip the live HBM-traffic passes (three child runs under rocprofv3 --pmc)")
+                    help="with --full, for profiling runs: skip the further measurements beside the headline (config.with_*), so "
+                         "that a kernel trace of the process holds the kernels of ONE path")
+    ap.add_argument("--no-pmc", action="store_true",
+                    help="with --full: skip the live HBM-traffic passes (three child runs under rocprofv3 --pmc)")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything beside the headline as well: the CPU baseline (cpu_baseline), the live HBM-traffic "
+                         "passes (roofline.traffic), the further measurements (config.with_*), the streaming calibration and the "
+                         "committed-profile figures in `roofline`, and for N > 1 the weak-scaling field.  Without it a run sets "
+                         "up, warms up, times the steps and prints the headline line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them computed (rank 0's subdomain for N > 1) as "
+                         "DIR/<name>.npy in float64: displacement, velocity, acceleration, the interface displacement the "
+                         "adapter hands to preCICE, and the step's Newton/CG record; vectors too long for %d MB in all are "
+                         "written as a fixed seeded sample of their entries" % (DUMP_BYTES_MAX // 10 ** 6))
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.cpu_worker:  # child of cpu_baseline(): CPU only
         c, a, b, full = (int(x) for x in args.cpu_worker.split(","))
@@ -402,18 +455,18 @@ def main():
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
-    # The CPU leg runs FIRST, in child processes started while this process has not touched the GPU (no torch import, no
-    # HIP context): a fork + exec out of a process that holds a HIP context is the fragile order.  It needs no GPU.
+    # --full: the CPU leg runs FIRST, in child processes started while this process has not touched the GPU (no torch
+    # import, no HIP context): a fork + exec out of a process that holds a HIP context is the fragile order.  It needs no GPU.
     cpu_leg = None
-    if rank == 0 and world == 1 and args.cpu_cells > 0:
+    if args.full and rank == 0 and world == 1 and args.cpu_cells > 0:
         its_a, its_b = (int(x) for x in args.cpu_its.split(","))
-        budget = float(os.environ.get("MI_BENCH_CPU_BUDGET_S", "900"))
+        budget = float(os.environ.get("MI_BENCH_CPU_BUDGET_S", str(CPU_BUDGET_S)))
         cpu_leg = cpu_baseline(args.cpu_cells, its_a, its_b, budget, not args.no_cpu_config4 and args.cells == 59)
 
     # ... and so do the counter passes for `roofline.traffic`: children under rocprofv3, this process still GPU-free
-    pmc, pmc_note = None, "not collected (N > 1, --slabs, --no-pmc or a child itself)"
-    if rank == 0 and world == 1 and args.slabs == 1 and not args.no_pmc and not args.pmc_child and args.cells >= 24:
-        pmc, pmc_note = pmc_traffic(args.cells, float(os.environ.get("MI_BENCH_PMC_BUDGET_S", "300")))
+    pmc, pmc_note = None, "not collected (run without --full, N > 1, --slabs, --no-pmc or a child itself)"
+    if args.full and rank == 0 and world == 1 and args.slabs == 1 and not args.no_pmc and not args.pmc_child and args.cells >= 24:
+        pmc, pmc_note = pmc_traffic(args.cells, float(os.environ.get("MI_BENCH_PMC_BUDGET_S", str(PMC_BUDGET_S))))
 
     import torch
     import torch.distributed as dist
@@ -506,7 +559,7 @@ def main():
                                                         "cg_iterations", "cg_solves", "mg_refresh")}
         cnt["mg_refresh_every"] = G.get_tuning("mg_refresh_every")
         r = {"G": G, "elapsed": elapsed, "lin_its_last": lin_its_last, "counts": cnt, "newton": newton, "cg_its": cg_its, "assemblies": assemblies, "nz": nz,
-             "tm": G.timings(), "comm": G.comm_info(), "per_rank_s": per_rank}
+             "tm": G.timings(), "comm": G.comm_info(), "per_rank_s": per_rank, "info": info}
         return r
 
     if args.pmc_child:  # one Newmark step of the headline configuration under the counters, nothing to report
@@ -514,6 +567,8 @@ def main():
         return
     R = measure(args.scaling, n, args.steps, args.warmup, uid)
     G, elapsed, tm, nz = R["G"], R["elapsed"], R["tm"], R["nz"]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, G, R["info"])
     out = None
     if rank == 0:
         nnzb = G.nnz // 9
@@ -730,7 +785,7 @@ def main():
             "GB_per_s": step_bytes / 1e9 / (ms_step * 1e-3), "frac": step_bytes / 1e9 / (ms_step * 1e-3) / HBM_PEAK_GBS,
             "ms_fine_products_precond_per_step": tm["spmv_precond"][0] / args.steps,
             "ms_fine_products_cg_per_step": spmv_ms / args.steps}
-        if world == 1 and args.slabs == 1 and args.fine_level == "assembled":
+        if args.full and world == 1 and args.slabs == 1 and args.fine_level == "assembled":
             # streaming calibration in the SAME process: a pure read of the 8*nnz-byte block-CSR value array (the box's
             # achievable HBM ceiling; boxes of the pool differ on the gather-heavy product, not on this kernel)
             G.set_tuning("spmv_variant", 13)
@@ -769,7 +824,7 @@ def main():
             out["roofline"]["assemble_q2sf_traffic"] = {"bytes_per_colour_launch": t_asm[0], "launches": t_asm[1],
                                                         "bytes_per_tangent_assembly": 8 * t_asm[0], "source": how_live}
         pmc_file = os.path.join(ROOT, "profiles", "r05", "pmc_bench_n59.json")
-        if world == 1 and args.slabs == 1 and n == 59 and os.path.exists(pmc_file):
+        if args.full and world == 1 and args.slabs == 1 and n == 59 and os.path.exists(pmc_file):
             # NOT a measurement of this run: per-launch HBM traffic of the same command under `rocprofv3 --pmc`
             # (tools/pmc_bench.sh), as committed with the round's profiles; `roofline.traffic` itself stays null because
             # PMC counters cannot be collected from inside this process
@@ -796,7 +851,7 @@ def main():
             out["roofline"]["reference_profiles"] = ref
     del G, R
     # ---- second field for N > 1: weak scaling (one cells^3 block per GPU)
-    if world > 1 and not replicas and not args.no_weak and args.scaling == "strong":
+    if args.full and world > 1 and not replicas and not args.no_weak and args.scaling == "strong":
         uid2 = None
         box = [M.comm_unique_id() if rank == 0 else None]
         dist.broadcast_object_list(box, src=0)
@@ -808,7 +863,7 @@ def main():
                                    "workload": "%dx%dx%d cells (%d^3 per GPU)" % (n, n, W["nz"], n),
                                    "cg_iterations_per_step": W["cg_its"] / args.steps}
         del W
-    if world == 1 and args.slabs == 1 and not args.no_sides:
+    if args.full and world == 1 and args.slabs == 1 and not args.no_sides:
         # Further measurements beside the headline, each over the SAME step window as the headline (the same warm-up
         # steps, the same ramp phase, the same coarse-operator refreshes inside the window): `steps` / `warmup` in every
         # sub-object say so.  (Until round 5 these ran 3 steps after 1 warm-up and were indicative only.)
@@ -876,7 +931,7 @@ def main():
                 r4["ms_smoother_fine_product"] = tm4["spmv_precond"][0] / max(tm4["spmv_precond"][1], 1)
                 r4["note"] = note
                 out["config"]["with_matrix_free_fine_level_smoother_quadrature_4"] = r4
-    if rank == 0 and world == 1 and args.cpu_cells > 0:
+    if cpu_leg is not None:
         # the GPU on the CPU sample's own configuration, beside it
         if args.cpu_cells != n or args.slabs != 1:
             S = measure("strong", args.cpu_cells, 3, 1, None)

@@ -22,7 +22,7 @@ def _run(args):
 
 @gpu
 def test_bench_json_line_contract():
-    d = _run(["--cells", "8", "--steps", "2", "--warmup", "1", "--cpu-cells", "3"])
+    d = _run(["--cells", "8", "--steps", "2", "--warmup", "1", "--cpu-cells", "3", "--full"])
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
               "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline"):
         assert k in d, k
@@ -57,6 +57,45 @@ def test_bench_json_line_contract():
     assert mf["diagonal_block_passes_per_step"] == 1.0 and mf["tangent_assemblies_per_step"] >= 1.0
     assert d["config"]["with_matrix_free_fine_level_diagonal_every_tangent"]["diagonal_block_passes_per_step"] == mf["tangent_assemblies_per_step"]
     assert d["config"]["fine_level"] == "assembled" and d["config"]["per_rank_ms_per_step"] == [d["ms_per_step"]]
+
+
+@gpu
+def test_bench_plain_run_is_the_headline_and_dumps_its_outputs(tmp_path):
+    """without --full the line holds the headline alone (no CPU leg, no counter passes, no further measurements);
+    --dump-outputs writes the last timed step's state, the same from run to run with the same arguments"""
+    import numpy as np
+    dumps = []
+    for k in range(2):
+        d = _run(["--cells", "8", "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path / str(k))])
+        for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup", "config", "roofline"):
+            assert key in d, key
+        assert d["steps"] == 3 and d["warmup"] == 1 and d["dtype"] == "f64" and d["higher_is_better"] is True
+        assert abs(d["value"] - d["config"]["n_dofs"] / (d["ms_per_step"] * 1e-3)) / d["value"] < 1e-9
+        assert "cpu_baseline" not in d and not [k for k in d["config"] if k.startswith("with_")]
+        assert d["roofline"]["traffic"] is None and "calibration_stream_read" not in d["roofline"]
+        files = {f.stem: np.load(f) for f in sorted((tmp_path / str(k)).glob("*.npy"))}
+        assert set(files) == {"displacement", "velocity", "acceleration", "interface_displacement", "step_record"}
+        assert all(a.dtype == np.float64 and np.isfinite(a).all() for a in files.values())
+        assert sum(a.nbytes for a in files.values()) <= 64 * 10 ** 6
+        n = d["config"]["n_dofs"]
+        assert files["displacement"].shape == (n,) and files["velocity"].shape == (n,) and files["interface_displacement"].shape[1] == 3
+        rec = files["step_record"]
+        assert rec[3] == 1 and rec[0] >= 1 and list(rec[8:]) == d["config"]["cg_iterations_last_step"]
+        assert np.abs(files["displacement"]).max() > 0
+        dumps.append(files)
+    for name, a in dumps[0].items():
+        b = dumps[1][name]
+        assert np.allclose(a, b, rtol=1e-12, atol=1e-12 * np.abs(a).max()), name
+
+
+def test_bench_options_full_and_dump_outputs_exist():
+    """CPU test: the two options of the bench's command line"""
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], cwd=ROOT, capture_output=True, text=True,
+                         timeout=120)
+    assert out.returncode == 0 and "--full" in out.stdout and "--dump-outputs" in out.stdout, out.stderr[-2000:]
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], cwd=ROOT, capture_output=True, text=True,
+                         timeout=120)
+    assert out.returncode == 2 and "--steps" in out.stderr
 
 
 @gpu
