@@ -375,6 +375,18 @@ namespace mi_detail
     return c->d_ke ? 1 : 0;
   }
 
+  // the smoother's fine-level products run mf_spmv27 on the 27-point records of the current tangent.  The one test for it:
+  // enqueue_spmv's dispatch (with the call's own conditions: a smoother product, not the CG's) and the
+  // "smoother_quadrature_active" query both read it.  The element form carries the smoother's products only where the
+  // fine level is matrix-free or the smoother multiplies with element data in fp64 storage; the records and the slot
+  // arrays must exist; the opt-in fp32 smoother products keep the 64-point kernel.
+  bool smoother_runs_q27(const mi_ctx *c)
+  {
+    return c->smoother_points == 3 && c->qrec27_valid && element_form(c) == 2 && c->mf_slots && c->d_mf_yc &&
+           !c->active_sell_vals && (c->mf_fine || (c->ebe != 0 && c->precond_storage == 64)) &&
+           !(c->smoother_precision == 32 && c->qrec32_valid);
+  }
+
   bool mf_gather_fusable(const mi_ctx *c)
   {
     return element_form(c) == 2 && c->ebe == 2 && c->mf_slots && c->d_mf_yc && c->precond_storage == 64 &&
@@ -405,8 +417,7 @@ namespace mi_detail
         // while the halo is in flight, the others as part 2; every cell still writes its own slots, so the sum is the same
         // smoother quadrature 3: the smoother's products (never the CG's) from the 27-point records, two cells per wave, in the
         // same launches over layers
-        const bool q27 = smoother && !ebe_for_cg && c->smoother_points == 3 && c->qrec27_valid && kind == 2 && c->mf_slots && c->d_mf_yc &&
-                         !(c->smoother_precision == 32 && c->qrec32_valid); // (the opt-in fp32 smoother products keep the 64-point kernel)
+        const bool q27 = smoother && !ebe_for_cg && smoother_runs_q27(c);
         const bool mf_split = part != 0 && kind == 2 && c->mf_slots && c->d_mf_yc && c->lat.ncol > 0 && c->team->mf_overlap &&
                               !(ebe_for_cg && !mf_all);
         if (part == 1 && !mf_split)
@@ -2812,6 +2823,12 @@ int mi_spmv(mi_ctx *c, const double *x_host, double *y_host)
       if (int e = mg_apply(T))
         return e;
     }
+  else if (T.size > 1 && c->spmv_as_smoother) // the smoother's form on slabs: the two parts around a halo exchange, as in the V-cycle
+    {
+      if (int e = team_spmv(T, [](mi_ctx *m) { return m; }, [](mi_ctx *m) { return m->work(W_P); },
+                            [](mi_ctx *m) { return m->work(W_Q); }, nullptr, true))
+        return e;
+    }
   else
     for (mi_ctx *m : T.members)
       enqueue_spmv(m, m->work(W_P), m->work(W_Q), nullptr, nullptr, nullptr, 0, m->spmv_as_smoother != 0);
@@ -3095,7 +3112,7 @@ int mi_get_tuning(mi_ctx *c, const char *key, int *value)
   else if (k == "smoother_quadrature")
     *value = m->smoother_points;
   else if (k == "smoother_quadrature_active") // 3: the smoother's fine-level products run on the 27-point records of the current tangent
-    *value = (m->smoother_points == 3 && m->qrec27_valid && element_form(m) == 2) ? 3 : 4;
+    *value = smoother_runs_q27(m) ? 3 : 4;
   else if (k == "experiments") // 1: built with -DMI_EXPERIMENTS (environment hooks and A/B kernel instantiations compiled in)
 #ifdef MI_EXPERIMENTS
     *value = 1;

@@ -85,6 +85,17 @@ def q1_jacobian(dim, verts, xi):
     return Jm
 
 
+def q1_map(dim, verts, xi):
+    """X(xi) of the d-linear map through the 2^dim vertices"""
+    X = np.zeros(dim)
+    for v in range(1 << dim):
+        phi = 1.0
+        for d in range(dim):
+            phi *= xi[d] if (v >> d) & 1 else 1 - xi[d]
+        X += phi * verts[v]
+    return X
+
+
 # ------------------------------------------------------------------ material + cell (nonlinear)
 def material(dim, mu, nu, F):
     kappa = 2 * mu * (1 + nu) / (3 * (1 - 2 * nu))
@@ -105,15 +116,19 @@ def material(dim, mu, nu, F):
     return tau, Jc_vol + Jc_iso
 
 
-def cell(dim, p, verts, u, acc, mu, nu, rho, alpha1, body):
+def cell(dim, p, verts, u, acc, mu, nu, rho, alpha1, body, nq=None, fold_to_identity=False):
+    """K_e, r_e of one cell with nq Gauss points per direction (default p + 2, the reference's qf_cell, :74).
+    fold_to_identity: a point with det F <= 0 takes F = I (the undeformed state), the rule of the device's 27-point
+    smoother records (mf_records27); the reference itself asserts det F > 0 there (:935)."""
     nodes = feq_nodes(p)
-    qx, qw = gauss01(p + 2)
+    nq = p + 2 if nq is None else nq
+    qx, qw = gauss01(nq)
     npc = (p + 1) ** dim
     Ke = np.zeros((npc * dim, npc * dim))
     re = np.zeros(npc * dim)
     U = u.reshape(npc, dim)
     A = acc.reshape(npc, dim)
-    for q in np.ndindex(*([p + 2] * dim)):
+    for q in np.ndindex(*([nq] * dim)):
         qi = q[::-1]  # x fastest
         xi = np.array([qx[k] for k in qi])
         w = np.prod([qw[k] for k in qi])
@@ -122,6 +137,8 @@ def cell(dim, p, verts, u, acc, mu, nu, rho, alpha1, body):
         G = dN @ np.linalg.inv(Jm)  # reference-configuration gradients
         JxW = np.linalg.det(Jm) * w
         F = np.eye(dim) + U.T @ G
+        if fold_to_identity and not np.linalg.det(F) > 0:
+            F = np.eye(dim)
         Fi = np.linalg.inv(F)
         g = G @ Fi  # spatial gradients
         tau, Jc = material(dim, mu, nu, F)
@@ -199,7 +216,10 @@ def neumann_cell(dim, p, verts, u_total, traction, faces, pull_back=True):
 
 # ------------------------------------------------------------------ box mesh
 class Mesh:
-    def __init__(self, dim, p, reps, lo, hi, roles):
+    """perturb: (nverts, dim) offsets of the cell vertices, vertices lexicographic on the (reps+1)^dim lattice (x fastest),
+    the layout Context(perturb=...) and oracle_lib.Problem take; nodes then follow the d-linear map of their cell"""
+
+    def __init__(self, dim, p, reps, lo, hi, roles, perturb=None):
         self.dim, self.p = dim, p
         self.reps = list(reps)[:dim]
         self.lo, self.hi = np.array(lo[:dim], float), np.array(hi[:dim], float)
@@ -217,6 +237,12 @@ class Mesh:
         for c in np.ndindex(*self.reps[::-1]):
             ci = c[::-1]
             verts = np.array([[self.lo[d] + h[d] * (ci[d] + ((v >> d) & 1)) for d in range(dim)] for v in range(1 << dim)])
+            if perturb is not None:
+                for v in range(1 << dim):
+                    vid = 0
+                    for d in reversed(range(dim)):
+                        vid = vid * (self.reps[d] + 1) + ci[d] + ((v >> d) & 1)
+                    verts[v] = verts[v] + perturb[vid]
             conn = np.zeros(self.npc, int)
             for a in range(self.npc):
                 ai = [(a // (p + 1) ** d) % (p + 1) for d in range(dim)]
@@ -225,7 +251,10 @@ class Mesh:
                 for d in reversed(range(dim)):
                     node = node * self.nn[d] + idx[d]
                 conn[a] = node
-                self.coords[node] = [self.lo[d] + h[d] * (ci[d] + nodes1[ai[d]]) for d in range(dim)]
+                if perturb is None:
+                    self.coords[node] = [self.lo[d] + h[d] * (ci[d] + nodes1[ai[d]]) for d in range(dim)]
+                else:
+                    self.coords[node] = q1_map(dim, verts, np.array([nodes1[ai[d]] for d in range(dim)]))
             bfaces = {}
             for f in range(2 * dim):
                 d, side = f // 2, f % 2
@@ -326,6 +355,127 @@ class Solid:
         self.v = self.a4 * delta + self.a5 * self.v_old + self.a6 * self.a_old
         self.u_old, self.v_old, self.a_old = self.u.copy(), self.v.copy(), self.a.copy()
         return log
+
+
+# ------------------------------------------------------------------ matrix-free operator (vectorised over cells and points)
+def material_batch(dim, mu, nu, F):
+    """material() over a stack of deformation gradients F[..., dim, dim]: tau[..., dim, dim], Jc[..., dim, dim, dim, dim]"""
+    kappa = 2 * mu * (1 + nu) / (3 * (1 - 2 * nu))
+    I = np.eye(dim)
+    J = np.linalg.det(F)
+    e2 = (..., None, None)
+    e4 = (..., None, None, None, None)
+    bbar = (J ** (-2.0 / dim))[e2] * (F @ np.swapaxes(F, -1, -2))
+    IxI = np.einsum("ij,kl->ijkl", I, I)
+    S = 0.5 * (np.einsum("ik,jl->ijkl", I, I) + np.einsum("il,jk->ijkl", I, I))
+    devP = S - IxI / dim
+    tau_bar = mu * bbar
+    tau_iso = np.einsum("ijkl,...kl->...ij", devP, tau_bar)
+    p = kappa / 2 * (J - 1 / J)
+    tau = (p * J)[e2] * I + tau_iso
+    d2 = kappa / 2 * (1 + 1 / J**2)
+    Jc_vol = J[e4] * ((p + J * d2)[e4] * IxI - 2 * p[e4] * S)
+    Jc_iso = (2 / dim) * np.trace(tau_bar, axis1=-2, axis2=-1)[e4] * devP - (2 / dim) * (
+        np.einsum("...ij,kl->...ijkl", tau_iso, I) + np.einsum("ij,...kl->...ijkl", I, tau_iso))
+    return tau, Jc_vol + Jc_iso
+
+
+def _rule(dim, p, nq):
+    """points xi[Q, dim] (x fastest), weights w[Q], N[Q, A], dN[Q, A, dim] of the nq^dim Gauss rule"""
+    nodes = feq_nodes(p)
+    qx, qw = gauss01(nq)
+    pts = [q[::-1] for q in np.ndindex(*([nq] * dim))]
+    xi = np.array([[qx[k] for k in qi] for qi in pts])
+    w = np.array([np.prod([qw[k] for k in qi]) for qi in pts])
+    sh = [shape_at(dim, p, nodes, x) for x in xi]
+    return xi, w, np.array([a for a, _ in sh]), np.array([b for _, b in sh])
+
+
+def _q1_jacobians(dim, verts, xi):
+    """dX/dxi[E, Q, dim, dim] of the d-linear maps of cells verts[E, 2^dim, dim] at the points xi[Q, dim]"""
+    dphi = np.ones((len(xi), 1 << dim, dim))
+    for v in range(1 << dim):
+        for j in range(dim):
+            dphi[:, v, j] = 1.0 if (v >> j) & 1 else -1.0
+            for d in range(dim):
+                if d != j:
+                    dphi[:, v, j] *= xi[:, d] if (v >> d) & 1 else 1 - xi[:, d]
+    return np.einsum("evi,qvj->eqij", verts, dphi)
+
+
+class Operator:
+    """y = sum_e K_e(nq) x_e, the tangent of cell() applied cell by cell without forming K_e or K, over a Mesh.
+    u_total: u + du (get_total_solution, :580-588).  Columns of constrained dofs are masked; a constrained row gets the
+    diagonal entry the ASSEMBLED matrix has there, sum_e |K_e(i,i)| with the reference's p + 2 points (:769-773) whatever
+    nq is -- the rule of the device's matrix-free products, which read those entries from the assembled fine level.
+    fold_to_identity as in cell(); .folded[E, Q] marks the points that took F = I, .detF[E, Q] the det F they had.
+    cdiag: .cdiag of an Operator of the same mesh and u_total at the default rule (spares computing it again)."""
+
+    def __init__(self, mesh, u_total, mu=0.5e6, nu=0.4, rho=1000.0, alpha1=1.0 / (0.25 * 0.005**2), nq=None,
+                 fold_to_identity=False, cdiag=None):
+        m, dim, p = mesh, mesh.dim, mesh.p
+        self.m, self.mass = m, rho * alpha1
+        self.nq = p + 2 if nq is None else nq
+        self.conn = np.array([c for c, _, _ in m.cells])
+        self.verts = np.array([v for _, v, _ in m.cells])
+        self.u_total = np.asarray(u_total, float)
+        self.mu, self.nu = mu, nu
+        (self.N, self.g, self.JxW, self.tau, self.Jc, self.detF, self.folded) = self._points(self.nq, fold_to_identity)
+        if cdiag is not None:
+            self.cdiag = cdiag
+            return
+        if self.nq == p + 2 and not fold_to_identity:
+            dg = self._diag(self.N, self.g, self.JxW, self.tau, self.Jc)
+        else:
+            dg = self._diag(*self._points(p + 2, False)[:5])
+        # distribute_local_to_global's constrained diagonal: |K_e(i,i)|, the cell's mean |K_e(j,j)| where that is 0
+        dg = np.abs(dg)
+        dg = np.where(dg != 0, dg, dg.mean(axis=1, keepdims=True))
+        self.cdiag = np.zeros(m.n)
+        np.add.at(self.cdiag, (self.conn[:, :, None] * dim + np.arange(dim)).reshape(len(self.conn), -1), dg)
+
+    def _points(self, nq, fold):
+        dim = self.m.dim
+        xi, w, N, dN = _rule(dim, self.m.p, nq)
+        Jm = _q1_jacobians(dim, self.verts, xi)
+        G = np.einsum("qak,eqkj->eqaj", dN, np.linalg.inv(Jm))  # reference-configuration gradients
+        JxW = np.linalg.det(Jm) * w
+        U = self.u_total.reshape(-1, dim)[self.conn]  # [E, A, dim]
+        F = np.eye(dim) + np.einsum("eai,eqaj->eqij", U, G)
+        detF = np.linalg.det(F)
+        folded = ~(detF > 0) if fold else np.zeros(detF.shape, bool)
+        F[folded] = np.eye(dim)
+        g = G @ np.linalg.inv(F)  # spatial gradients [E, Q, A, dim]
+        tau, Jc = material_batch(dim, self.mu, self.nu, F)
+        return N, g, JxW, tau, Jc, detF, folded
+
+    def _diag(self, N, g, JxW, tau, Jc):
+        """K_e(i,i), i = (a, c): [E, A * dim]"""
+        dim = self.m.dim
+        # sym_i : Jc : sym_i with sym_i = (e_c (x) g_a + g_a (x) e_c) / 2, no symmetry of Jc assumed
+        d = np.zeros(g.shape[:3] + (dim,))
+        for c in range(dim):
+            d[..., c] = 0.25 * (np.einsum("eqjl,eqaj,eqal->eqa", Jc[:, :, c, :, c, :], g, g) +
+                                np.einsum("eqjk,eqaj,eqak->eqa", Jc[:, :, c, :, :, c], g, g) +
+                                np.einsum("eqil,eqai,eqal->eqa", Jc[:, :, :, c, c, :], g, g) +
+                                np.einsum("eqik,eqai,eqak->eqa", Jc[:, :, :, c, :, c], g, g))
+        d += (np.einsum("eqaj,eqjk,eqak->eqa", g, tau, g) + self.mass * N[None] ** 2)[..., None]
+        return np.einsum("eqac,eq->eac", d, JxW).reshape(len(g), -1)
+
+    def __call__(self, x):
+        m, dim = self.m, self.m.dim
+        X = (np.asarray(x, float) * ~m.constrained).reshape(-1, dim)[self.conn]  # [E, A, dim]
+        Gx = np.einsum("eac,eqaj->eqcj", X, self.g)  # spatial gradient of x
+        T = np.einsum("eqijkl,eqkl->eqij", self.Jc, 0.5 * (Gx + np.swapaxes(Gx, -1, -2)))
+        Z = 0.5 * (T + np.swapaxes(T, -1, -2)) + Gx @ self.tau  # material + geometric (g_a tau g_b) parts
+        ye = np.einsum("eqcj,eqaj,eq->eac", Z, self.g, self.JxW)
+        ye += self.mass * np.einsum("qa,qb,ebc,eq->eac", self.N, self.N, X, self.JxW, optimize=True)
+        y = np.zeros((m.nnodes, dim))
+        np.add.at(y, self.conn, ye)
+        y = y.reshape(-1)
+        c = m.constrained
+        y[c] = self.cdiag[c] * np.asarray(x, float)[c]
+        return y
 
 
 # ------------------------------------------------------------------ linear model

@@ -110,8 +110,8 @@ def _nonlinear(name, tol_u, tol_va, start=0, distorted=False, dim=3, degree=2, s
     # 3D Q2: the matrix-free smoother was what ran; the other elements smooth with the assembled matrix
     if slabs == 1 or fine_level:  # (a slab of a quarter of this block is below the size at which the matrix-free form is chosen)
         assert G.get_tuning("smoother_operator_active") == (2 if (dim, degree) == (3, 2) else 0)
-        if (dim, degree) == (3, 2) and smoother_precision == 64:  # ... from the 27-point records unless asked otherwise
-            assert G.get_tuning("smoother_quadrature_active") == (quadrature or 3)
+        if (dim, degree) == (3, 2):  # ... from the 27-point records unless asked otherwise; the fp32 products keep 64 points
+            assert G.get_tuning("smoother_quadrature_active") == (4 if smoother_precision == 32 else (quadrature or 3))
     if fine_level:  # nothing was assembled: no matrix to export
         with pytest.raises(M.MiError):
             G.csr()
