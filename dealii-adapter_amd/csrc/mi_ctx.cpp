@@ -364,12 +364,14 @@ namespace mi_detail
     return MI_OK;
   }
 
-  // which unassembled form of the current tangent the element products use: 2 quadrature-point records (mf_spmv),
-  // 1 element tangents (ebe_spmv), 0 none
+  // which unassembled form of the current tangent the element products use: 2 quadrature-point records (mf_spmv, or
+  // mf_spmv_q3 on a Q3 fine level), 1 element tangents (ebe_spmv), 0 none
   int element_form(const mi_ctx *c)
   {
     if (!c->ke_valid)
       return 0;
+    if (c->d_qrec_q3)
+      return 2;
     if (c->d_qrec && (c->ebe == 2 || !c->d_ke))
       return 2;
     return c->d_ke ? 1 : 0;
@@ -417,14 +419,16 @@ namespace mi_detail
         // while the halo is in flight, the others as part 2; every cell still writes its own slots, so the sum is the same
         // smoother quadrature 3: the smoother's products (never the CG's) from the 27-point records, two cells per wave, in the
         // same launches over layers
+        // a Q3 fine level (one slab): every product of the level, the smoother's included, is mf_spmv_q3 in one launch
+        const bool q3  = c->d_qrec_q3 != nullptr;
         const bool q27 = smoother && !ebe_for_cg && smoother_runs_q27(c);
         const bool mf_split = part != 0 && kind == 2 && c->mf_slots && c->d_mf_yc && c->lat.ncol > 0 && c->team->mf_overlap &&
-                              !(ebe_for_cg && !mf_all);
+                              !(ebe_for_cg && !mf_all) && !q3;
         if (part == 1 && !mf_split)
           return;
         mi::EbeParams e{c->d_ke, c->d_conn, c->d_node_first, x, y};
         mi::MfParams  f{};
-        f.qrec    = c->d_qrec;
+        f.qrec    = q3 ? c->d_qrec_q3 : c->d_qrec;
         // opt-in "smoother_precision" 32: the SMOOTHER's products in fp32 arithmetic on fp32 records (residuals, start-vector
         // products and mi_spmv keep the fp64 form)
         f.qrec32  = (smoother && c->smoother_precision == 32 && c->qrec32_valid) ? c->d_qrec32 : nullptr;
@@ -505,6 +509,12 @@ namespace mi_detail
                   }
                 layers(0, zlo, false);
                 layers(zhi, nzl, false);
+              }
+            else if (q3)
+              {
+                const int t = sample ? tic(c0, MI_T_EBE_LAUNCH, true) : -1;
+                mi::launch_mf_spmv_q3(f, int32_t(c->mesh.ncells), c->stream, t >= 0 ? c0->stamps[size_t(t)].a : nullptr,
+                                      t >= 0 ? c0->stamps[size_t(t)].b : nullptr);
               }
             else if (q27)
               {
@@ -804,8 +814,9 @@ namespace mi_detail
   int enqueue_assembly(mi_ctx *c, bool residual_only)
   {
     // tangent_matrix = 0 (:1054) is implied: the first cell that touches a block stores instead of adding
-    // (system_rhs = 0, :1055 -- except where residual_gather writes every entry of it: the one-launch point pass)
-    if (!(c->mf_fine && c->mf_point_slots && c->d_mf_yc))
+    // (system_rhs = 0, :1055 -- except where residual_gather writes every entry of it: the one-launch point pass, 3D Q2)
+    const bool one_launch = c->mf_fine && c->mf_point_slots && c->d_mf_yc && !c->d_qrec_q3;
+    if (!one_launch)
       HIPCHK(c, hipMemsetAsync(c->vec(MI_V_SYSTEM_RHS), 0, size_t(c->n) * sizeof(double), c->stream));
     HIPCHK(c, hipMemsetAsync(c->d_sc + SC_INVERTED, 0, sizeof(double), c->stream));
     mi::AsmParams p  = asm_params(c);
@@ -819,13 +830,12 @@ namespace mi_detail
         p.variant       = 0;
         p.ke            = nullptr;
       }
-    if (residual_only) // the convergence check's pass leaves the records of the last tangent alone
-      p.qrec = nullptr, p.qrec32 = nullptr;
+    if (residual_only || c->d_qrec_q3) // the convergence check's pass leaves the records of the last tangent alone; Q3:
+      p.qrec = nullptr, p.qrec32 = nullptr;   // mf_records_q3 writes them below
     mi_ctx       *c0 = c->team->members[0];
     const int     t0 = tic(c0, residual_only ? MI_T_ASSEMBLE_RESIDUAL : MI_T_ASSEMBLE_CELLS);
     // matrix-free fine level: the point pass over ALL cells in one launch (residual into the cells' slots, summed per node in
     // processing order: the product's slots and its order), then the Neumann faces colour by colour on the summed vector
-    const bool one_launch = c->mf_fine && c->mf_point_slots && c->d_mf_yc;
     const bool faces_one_launch = c->face_slots && c->n_fn > 0;
     if (one_launch)
       {
@@ -872,9 +882,16 @@ namespace mi_detail
                                 c->stream);
         c->qrec27_valid = true;
       }
+    if (c->d_qrec_q3) // Q3 fine level: F, J^(-2/3), 1/J at the 125 points of the assembly's rule, from the state of the residual
+      {
+        mi::MfParams f{};
+        f.conn = c->d_conn, f.cverts = c->d_cverts, f.cellbox = c->d_cellbox, f.tab1d = c->d_tab;
+        mi::launch_mf_records_q3(f, c->vec(MI_V_TOTAL_DISPLACEMENT), c->vec(MI_V_SOLUTION_DELTA), c->d_qrec_q3, int32_t(c->mesh.ncells),
+                                 c->stream);
+      }
     // which kernel ran: assemble_q2sf (sum factorised; it alone writes the fp32 records) or the node-pair form
     const bool q2sf = c->dim == 3 && c->degree == 2 && (p.variant == 0 || (p.variant >= 3 && p.variant <= 8));
-    c->ke_valid     = (c->d_ke && q2sf && !c->mf_fine) || c->d_qrec;
+    c->ke_valid     = (c->d_ke && q2sf && !c->mf_fine) || c->d_qrec || c->d_qrec_q3;
     c->qrec32_valid = p.qrec32 != nullptr && q2sf;
     if (mf_tangent && c->mf_diag_lag && c->mf_diag_fresh) // the step's first tangent formed the blocks: kept ("mf_diag_lag")
       {
@@ -889,7 +906,14 @@ namespace mi_detail
         f.qrec = c->d_qrec, f.tab1d = c->d_tab, f.cverts = c->d_cverts, f.cellbox = c->d_cellbox, f.dst = c->d_mf_dst;
         f.mu = c->mat.mu, f.kappa = c->kappa, f.mass = c->alpha[1] * c->mat.rho;
         const int td = tic(c0, MI_T_ASSEMBLE_DIAG);
-        mi::launch_mf_diag(f, c->d_diag_slots, int32_t(c->mesh.ncells), c->stream);
+        if (c->d_qrec_q3)
+          {
+            f.qrec        = c->d_qrec_q3;
+            f.slot_inline = c->slots_layout == 1;
+            mi::launch_mf_diag_q3(f, c->d_diag_slots, int32_t(c->mesh.ncells), c->stream);
+          }
+        else
+          mi::launch_mf_diag(f, c->d_diag_slots, int32_t(c->mesh.ncells), c->stream);
         mi::launch_mf_diag_gather(c->d_diag_slots, c->d_mf_slot_base, c->d_mf_src, c->d_cmask, c->d_diagpos_mf, c->d_diag_blk, c->work(W_DINV),
                                   c->d_dinv_blk, c->d_dinv_sym6, c->mesh.nnodes, c->stream);
         toc(c0, td);
@@ -925,17 +949,18 @@ namespace mi_detail
     // slots for the single-launch product: rank of every (cell, local node) among the cells of the node, in
     // processing order (colour-sorted cell order: the order in which the colour-by-colour update adds them)
     const int64_t        nc = c->mesh.ncells, nn = c->mesh.nnodes;
-    std::vector<int32_t> base(size_t(nn) + 1, 0), dst(size_t(nc) * 27), fill(size_t(nn), 0);
+    const int            npc = c->mesh.npc; // 27 (Q2) or 64 (Q3)
+    std::vector<int32_t> base(size_t(nn) + 1, 0), dst(size_t(nc) * npc), fill(size_t(nn), 0);
     for (int64_t e = 0; e < nc; ++e)
-      for (int a = 0; a < 27; ++a)
-        ++base[size_t(c->mesh.conn[size_t(e) * 27 + a]) + 1];
+      for (int a = 0; a < npc; ++a)
+        ++base[size_t(c->mesh.conn[size_t(e) * npc + a]) + 1];
     for (int64_t n = 0; n < nn; ++n)
       base[size_t(n) + 1] += base[size_t(n)];
     for (int64_t e = 0; e < nc; ++e)
-      for (int a = 0; a < 27; ++a)
+      for (int a = 0; a < npc; ++a)
         {
-          const int32_t n = c->mesh.conn[size_t(e) * 27 + a];
-          dst[size_t(e) * 27 + a] = base[size_t(n)] + fill[size_t(n)]++;
+          const int32_t n = c->mesh.conn[size_t(e) * npc + a];
+          dst[size_t(e) * npc + a] = base[size_t(n)] + fill[size_t(n)]++;
         }
     // cell-major layout ("mf_slots_cell_major" 1): a cell stores its 81 results as one contiguous run, the gathers read a
     // node's contributions through slot_src (their positions, in processing order)
@@ -946,8 +971,12 @@ namespace mi_detail
     // line of nodes alone (cell-major: a 128-byte line holds pieces of two node lines, fetched through two XCDs' L2);
     // the product stores 72-byte pieces, the pieces of consecutive cells next to each other
     std::vector<int32_t> src;
+    // (Q3: always cell-major -- mf_spmv_q3 and mf_diag_q3 store a cell's results as one run; "mf_slots_cell_major" and the
+    // smoother's quadrature do not apply)
     int layout = c->slots_cell_major >= 0 ? c->slots_cell_major : (c->smoother_points == 3 ? 1 : 0);
     if (layout == 2 && !(c->lat.ncol > 0 && !c->lat_rows_host.empty()))
+      layout = 1;
+    if (npc != 27)
       layout = 1;
     c->slots_layout = layout;
     if (layout)
@@ -981,7 +1010,7 @@ namespace mi_detail
     if (rc)
       return rc;
     if (!c->d_mf_yc)
-      HIPCHK(c, hipMalloc((void **)&c->d_mf_yc, size_t(nc) * 27 * 3 * sizeof(double)));
+      HIPCHK(c, hipMalloc((void **)&c->d_mf_yc, size_t(nc) * npc * 3 * sizeof(double)));
     
     return MI_OK;
   }
@@ -1000,6 +1029,8 @@ namespace mi_detail
     return MI_OK;
   }
 
+  int upload_cellbox(mi_ctx *c);
+
   // quadrature-point records for the matrix-free product (3D Q2) + the geometry class of the local cells
   int alloc_point_records(mi_ctx *c)
   {
@@ -1008,6 +1039,16 @@ namespace mi_detail
     if (int r27 = alloc_records27(c))
       return r27;
     HIPCHK(c, hipMalloc((void **)&c->d_qrec, size_t(c->mesh.ncells) * mi::MF_NREC * 64 * sizeof(double)));
+    if (int rs = build_slot_tables(c))
+      return rs;
+    return upload_cellbox(c);
+  }
+
+  // the geometry class of the local cells: when every one is an axis-parallel box, d_cellbox = 1/h and the volume per cell
+  int upload_cellbox(mi_ctx *c)
+  {
+    if (c->d_cellbox)
+      return MI_OK;
     bool box = c->dim == 3;
     for (int64_t e = 0; e < c->mesh.ncells && box; ++e)
       {
@@ -1016,8 +1057,6 @@ namespace mi_detail
           for (int d = 0; d < 3; ++d)
             box = box && cv[v * 3 + d] == cv[(((v >> d) & 1) ? 7 : 0) * 3 + d];
       }
-    if (int rs = build_slot_tables(c))
-      return rs;
     if (box) // 1/h and the volume per cell, so that the product needs no division for its geometry
       {
         std::vector<double> cb(size_t(c->mesh.ncells) * 4);
@@ -1035,20 +1074,35 @@ namespace mi_detail
     return MI_OK;
   }
 
+  // the Q3 fine level's records (mf_records_q3), slots and cell geometry
+  int alloc_records_q3(mi_ctx *c)
+  {
+    if (!c->d_qrec_q3)
+      HIPCHK(c, hipMalloc((void **)&c->d_qrec_q3, size_t(c->mesh.ncells) * mi::MF_NREC * mi::MF_Q3_QS * sizeof(double)));
+    if (!c->d_mf_dst)
+      if (int rs = build_slot_tables(c))
+        return rs;
+    return upload_cellbox(c);
+  }
+
   // tuning "fine_level": 1 = the fine level matrix-free end to end (see mi_ctx::mf_fine), 0 = assembled (default).  Takes
   // effect with the next tangent assembly; the assembled tangent's 8 bytes per non-zero are released / allocated again.
+  // 3D Q2 on any team; 3D Q3 on an undecomposed mesh (mf_spmv_q3)
   int set_fine_level(mi_ctx *c, int on)
   {
     if ((on != 0) == (c->mf_fine != 0))
       return MI_OK;
+    const bool q3 = c->dim == 3 && c->degree == 3;
     if (on)
       {
-        if (c->dim != 3 || c->degree != 2)
-          return fail(c, MI_EINVAL, "the matrix-free fine level exists for 3D Q2 meshes only");
+        if (c->dim != 3 || (c->degree != 2 && c->degree != 3))
+          return fail(c, MI_EINVAL, "the matrix-free fine level exists for 3D Q2 and Q3 meshes only");
+        if (q3 && c->team->size != 1)
+          return fail(c, MI_EINVAL, "the matrix-free fine level of 3D Q3 meshes runs on an undecomposed mesh only");
         if (c->precond_storage != 64 || c->solver_direct)
           return fail(c, MI_EINVAL, "the matrix-free fine level excludes \"precond_storage\" 32 and \"solver_type\" 1");
-        int rc = alloc_point_records(c);
-        if (rc == MI_OK && !c->d_node_first)
+        int rc = q3 ? alloc_records_q3(c) : alloc_point_records(c);
+        if (rc == MI_OK && !q3 && !c->d_node_first)
           rc = upload(c, &c->d_node_first, c->mesh.node_first);
         if (rc)
           return rc;
@@ -1061,7 +1115,7 @@ namespace mi_detail
             if ((rc = upload(c, &c->d_diagpos_mf, dp)))
               return rc;
             HIPCHK(c, hipMalloc((void **)&c->d_diag_blk, nn * 9 * sizeof(double)));
-            HIPCHK(c, hipMalloc((void **)&c->d_diag_slots, size_t(c->mesh.ncells) * 27 * 6 * sizeof(double)));
+            HIPCHK(c, hipMalloc((void **)&c->d_diag_slots, size_t(c->mesh.ncells) * c->mesh.npc * 6 * sizeof(double)));
           }
         if (!c->d_dinv_blk)
           HIPCHK(c, hipMalloc((void **)&c->d_dinv_blk, nn * 9 * sizeof(double)));
@@ -1077,6 +1131,20 @@ namespace mi_detail
       {
         HIPCHK(c, hipMalloc((void **)&c->d_vals, c->vals_doubles * sizeof(double)));
         HIPCHK(c, hipMemsetAsync(c->d_vals, 0, c->vals_doubles * sizeof(double), c->stream));
+        if (q3) // the Q3 records, slots and diagonal blocks go with the level: the assembled path uses none of them
+          {
+            HIPCHK(c, hipStreamSynchronize(c->stream));
+            for (double **p : {&c->d_qrec_q3, &c->d_diag_blk, &c->d_diag_slots, &c->d_mf_yc})
+              {
+                HIPCHK(c, hipFree(*p));
+                *p = nullptr;
+              }
+            for (int32_t **p : {&c->d_diagpos_mf, &c->d_mf_dst, &c->d_mf_slot_base, &c->d_mf_src})
+              {
+                HIPCHK(c, hipFree(*p));
+                *p = nullptr;
+              }
+          }
       }
     c->mf_fine      = on ? 1 : 0;
     c->mf_diag_fresh = false;
@@ -1553,7 +1621,7 @@ namespace mi_detail
                     c->d_saved,     c->d_part,      c->d_sc,          c->d_iface_buf,   c->d_off,         c->d_cmask,
                     c->d_sell_perm, c->d_sell_len,  c->d_sell_col,    c->d_sell_off,    c->d_rowinfo, c->d_rowwx, c->d_sell_wx, c->d_band, c->d_band_work, c->d_band_perm,
                     c->d_own_if_nodes, c->d_own_if_slots, c->d_sell_vals32, c->d_dinv_blk, c->d_dinv_sym6, c->d_sell_box, c->d_ke, c->d_node_first, c->d_qrec, c->d_qrec32, c->d_cellbox, c->d_mf_yc, c->d_mf_dst, c->d_mf_slot_base, c->d_mf_src, c->d_lat_rows,
-                    c->d_qrec27, c->d_tab27, c->d_diag_blk, c->d_diag_slots, c->d_diagpos_mf, c->d_face_slots, c->d_fn_ids, c->d_fn_start, c->d_fn_src,
+                    c->d_qrec27, c->d_tab27, c->d_qrec_q3, c->d_diag_blk, c->d_diag_slots, c->d_diagpos_mf, c->d_face_slots, c->d_fn_ids, c->d_fn_start, c->d_fn_src,
                     c->d_pred[0][0], c->d_pred[0][1], c->d_pred[1][0], c->d_pred[1][1], c->d_pred[2][0], c->d_pred[2][1], c->d_pred[3][0], c->d_pred[3][1],
                     c->d_pred_saved[0][0], c->d_pred_saved[0][1], c->d_pred_saved[1][0], c->d_pred_saved[1][1], c->d_pred_saved[2][0],
                     c->d_pred_saved[2][1], c->d_pred_saved[3][0], c->d_pred_saved[3][1]};
@@ -2894,7 +2962,8 @@ int mi_set_tuning(mi_ctx *c, const char *key, int value)
                 return rc;
             }
           m->qrec27_valid = false;
-          m->ke_valid     = false; // takes effect with the next tangent
+          if (!m->d_qrec_q3)
+            m->ke_valid = false; // takes effect with the next tangent (a Q3 fine level: no effect)
           m->mg_stale = m->mg_force = true;
           continue;
         }
@@ -3219,7 +3288,7 @@ int mi_bench_spmv(mi_ctx *c, int reps, double *ms_per_launch)
   hipEventDestroy(a);
   hipEventDestroy(b);
   *ms_per_launch = double(ms) / std::max(1, reps);
-  if (mi::exp_env("MI_MF_STAMPS") && c->spmv_variant == 4 && element_form(c) == 2 && c->mf_slots && c->d_mf_yc && c->d_cellbox)
+  if (mi::exp_env("MI_MF_STAMPS") && c->spmv_variant == 4 && element_form(c) == 2 && c->mf_slots && c->d_mf_yc && c->d_cellbox && c->d_qrec)
     {
       // diagnostic: where a wavefront of the matrix-free product spends its life (shader-clock stamps of lane 0 at the
       // stage boundaries), averaged over all cells of one launch

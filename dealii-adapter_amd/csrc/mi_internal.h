@@ -187,7 +187,12 @@ struct mi_ctx
   // assembly is the residual pass that also writes the point records (assemble_q2sf<true>) + the nodes' diagonal blocks
   // from those records (mf_diag); the CG's product, start-vector and residual products and the smoother all run on
   // mf_spmv; d_vals is released.  Same results as the assembled level [REF nonlinear_elasticity.cc:1044-1087, 1153-1191].
+  // 3D Q3 (one slab): the same level on mf_spmv_q3.  The residual pass is the generic element kernel's (assemble_cells with
+  // residual_only, the assembled path's bits); the records come after it from u + du (mf_records_q3, 125 points: d_qrec_q3),
+  // the diagonal blocks from mf_diag_q3.  "smoother_quadrature", "smoother_precision" 32 and "mf_slots_cell_major" have no
+  // effect there: the smoother multiplies with the CG's 125-point product, the slots are cell-major.
   int       mf_fine = 0;
+  double   *d_qrec_q3 = nullptr; // [ncells][MF_NREC][MF_Q3_QS] (3D Q3, "fine_level" 1 only; released with "fine_level" 0)
   // "mf_diag_lag" 1 (what bench.py and the executable set beside "fine_level" 1): the diagonal blocks -- the smoother's D,
   // the Jacobi diagonal -- are formed at the FIRST tangent of a time step and kept over its Newton iterations, as the coarse
   // operators are ("mg_lag"); a preconditioner-side policy: the operator (records) and the residual are always current
@@ -196,7 +201,7 @@ struct mi_ctx
   int       mf_diag_lag = 0;
   bool      mf_diag_fresh = false; // the blocks belong to this time step (cleared by mi_newton_begin_step)
   double   *d_diag_blk   = nullptr; // [nnodes][9] diagonal blocks under the assembled matrix's constraint rule
-  double   *d_diag_slots = nullptr; // [ncells * 27][6] the cells' contributions (slot order = processing order)
+  double   *d_diag_slots = nullptr; // [ncells * nodes per cell][6] the cells' contributions (slot order = processing order)
   int32_t  *d_diagpos_mf = nullptr; // [nnodes] the node's own id where it has a row here, else -1: d_diag_blk read as `vals`
   size_t    vals_doubles = 0;       // size of d_vals (released while mf_fine, allocated again with "fine_level" 0)
   int       ebe = 2;          // tuning "smoother_operator": 2 matrix-free from the quadrature-point records, 1 element

@@ -278,6 +278,13 @@ namespace mi
   // matrix-free fine level (round 6): the nodes' diagonal blocks from the point records -- every cell into its own slots
   // [nslots][6] (MfParams::dst), then summed per node under the assembled matrix's constraint rule (see mf_diag)
   void launch_mf_diag(const MfParams &p, double *slots6, int32_t cell_count, hipStream_t s);
+  // matrix-free fine level of 3D Q3 meshes (see mf_spmv_q3): records [ncells][MF_NREC][MF_Q3_QS] at the 125 points of the
+  // assembly's rule from u + du, the product into the cells' slots [nslots][3] (64 per cell), the diagonal blocks into
+  // [nslots][6].  One workgroup per cell; the records' pointer is MfParams::qrec, the 1D tables MfParams::tab1d (Q3, 5 points)
+  constexpr int MF_Q3_QS = 128; // points per record field (125 used)
+  void launch_mf_records_q3(const MfParams &p, const double *u, const double *du, double *rec, int32_t cell_count, hipStream_t s);
+  void launch_mf_spmv_q3(const MfParams &p, int32_t cell_count, hipStream_t s, hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr);
+  void launch_mf_diag_q3(const MfParams &p, double *slots6, int32_t cell_count, hipStream_t s);
   // the matrix-free fine level's point pass over ALL cells in one launch (assemble_q2sf<true> with the residual into slots:
   // AsmParams::res_slots / slot_dst; cell_begin = 0, cell_count = all) and the sum of the slots into system_rhs
   void launch_point_pass_slots(const AsmParams &p, hipStream_t s);

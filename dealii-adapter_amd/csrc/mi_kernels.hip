@@ -3930,6 +3930,455 @@ namespace mi
       }
   }
 
+  // ------------------------------------------------------------------ matrix-free fine level for 3D Q3
+  // The product of mf_spmv for cubic elements: 64 nodes per cell, the assembly's 125 points (qf_cell(5), 5 per direction).
+  // One workgroup of 128 threads = one cell; a thread owns one quadrature point (threads 125-127 mirror point 124 and store
+  // nothing).  Records [cell][MF_NREC][MFQ3_QS] (F[9], J^(-2/3), 1/J, padded to 128 points), written by mf_records_q3 from
+  // u + du after the residual pass.  Sum factorisation one direction at a time (4 nodes <-> 5 points); in the passes that
+  // contract towards or away from the nodes a thread owns one line and produces all outputs along the contracted direction,
+  // so the 1D tables are uniform (scalar) operands:
+  //   E1  item (c,k,j):   x-line -> A_S / A_D [c,k,j][qx]                              48 items, 40 multiply-adds
+  //   E2  item (c,k,qx):  contract j -> B_DS / B_SD / B_SS [c,k][qy][qx]               60 items, 60
+  //   E3  item = point:   contract k -> H[c][l] = d x_c / d xi_l, V[c] = x_c           125 items, 48
+  //   point (mf_spmv's algebra: neo_hooke_from_F on the record, Q = JxW S M^T, mass)   125 items
+  //   I3  item (c,qy,qx): contract qz -> C_DS / C_SD / C_SS [c,k][qy][qx]              75 items, 80
+  //   I2  item (c,k,qx):  contract qy -> E_D / E_S [c,k,j][qx]                         60 items, 60
+  //   I1  item (c,k,j):   contract qx -> the 192 results into the cell's slots         48 items, 40
+  // LDS: two regions used in turn, R0 (1536 doubles: A, Q, E) and R1 (900: X, B, C) -- 19.5 kB, 8 workgroups per CU.
+  // Constrained dofs as mf_spmv: x masked on the way in; the gathers give their rows diag(K) x from the diagonal blocks.
+  constexpr int MFQ3_NPC = 64, MFQ3_NQ = 125, MFQ3_QS = MF_Q3_QS, MFQ3_NT = 128;
+  constexpr int MFQ3_R0 = 12 * MFQ3_QS, MFQ3_R1 = 900;
+  // 1D tables of the assembly's Q3 rule (Tables1D(3, 5).packed()): N1[5][4] at 0, dN1[5][4] at 20, qw[5] at 40, qx[5] at 45
+  constexpr int MFQ3_TD = 20, MFQ3_TW = 40, MFQ3_TX = 45;
+
+  // geometry at point (qx, qy, qz): Ji = Jinv (row-major), detJ
+  template <bool BOX>
+  __device__ __forceinline__ void mfq3_geometry(const MfParams &prm, const int64_t cell, const int qx, const int qy, const int qz,
+                                                double Ji[9], double &detJ)
+  {
+    if constexpr (BOX)
+      {
+        const double *__restrict__ cb = prm.cellbox + cell * 4;
+#pragma unroll
+        for (int k = 0; k < 9; ++k)
+          Ji[k] = 0.0;
+        Ji[0] = cb[0], Ji[4] = cb[1], Ji[8] = cb[2];
+        detJ  = cb[3];
+      }
+    else
+      {
+        const double *__restrict__ cv = prm.cverts + cell * 24;
+        const double xiq[3] = {prm.tab1d[MFQ3_TX + qx], prm.tab1d[MFQ3_TX + qy], prm.tab1d[MFQ3_TX + qz]};
+        double       verts[24], Jm[9];
+#pragma unroll
+        for (int k = 0; k < 24; ++k)
+          verts[k] = cv[k];
+        q1_jacobian<3>(verts, xiq, Jm);
+        detJ = det3x3(Jm);
+        inv3x3(Jm, detJ, Ji);
+      }
+  }
+
+  // E1 + E2 + E3: the 192 gathered values X[c*64 + a] (a = (k*4+j)*4+i, in R1) -> H, V at point `it`.  A goes to R0, B to R1
+  // over X.  Ends with a barrier: R0 and R1 are free.
+  __device__ __forceinline__ void mfq3_gradients(const double *__restrict__ tab, const double *__restrict__ sT, double *__restrict__ R0,
+                                                 double *__restrict__ R1, const int t, const int it, double H[3][3], double V[3])
+  {
+    double S[5][4], D[5][4]; // uniform: scalar registers
+#pragma unroll
+    for (int q = 0; q < 5; ++q)
+#pragma unroll
+      for (int a = 0; a < 4; ++a)
+        {
+          S[q][a] = tab[q * 4 + a];
+          D[q][a] = tab[MFQ3_TD + q * 4 + a];
+        }
+    if (t < 48) // E1: line (c,k,j) = t, its four values along x
+      {
+        const double x0 = R1[t * 4], x1 = R1[t * 4 + 1], x2 = R1[t * 4 + 2], x3 = R1[t * 4 + 3];
+#pragma unroll
+        for (int qx = 0; qx < 5; ++qx)
+          {
+            R0[t * 5 + qx]       = S[qx][0] * x0 + S[qx][1] * x1 + S[qx][2] * x2 + S[qx][3] * x3; // A_S
+            R0[240 + t * 5 + qx] = D[qx][0] * x0 + D[qx][1] * x1 + D[qx][2] * x2 + D[qx][3] * x3; // A_D
+          }
+      }
+    __syncthreads();
+    if (t < 60) // E2: item (c,k,qx): t = ck * 5 + qx
+      {
+        const int ck = t / 5, qx = t - 5 * ck;
+        double    as[4], ad[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          {
+            as[j] = R0[(ck * 4 + j) * 5 + qx];
+            ad[j] = R0[240 + (ck * 4 + j) * 5 + qx];
+          }
+#pragma unroll
+        for (int qy = 0; qy < 5; ++qy)
+          {
+            const int o = ck * 25 + qy * 5 + qx;
+            R1[o]       = S[qy][0] * ad[0] + S[qy][1] * ad[1] + S[qy][2] * ad[2] + S[qy][3] * ad[3]; // d/dx
+            R1[300 + o] = D[qy][0] * as[0] + D[qy][1] * as[1] + D[qy][2] * as[2] + D[qy][3] * as[3]; // d/dy
+            R1[600 + o] = S[qy][0] * as[0] + S[qy][1] * as[1] + S[qy][2] * as[2] + S[qy][3] * as[3]; // value / d/dz
+          }
+      }
+    __syncthreads();
+    // E3: item = point it = qz * 25 + q25 (this thread's row qz of the tables from LDS)
+    const int qz = it / 25, q25 = it - 25 * qz;
+    double    sz[4], dz[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+      {
+        sz[k] = sT[qz * 4 + k];
+        dz[k] = sT[MFQ3_TD + qz * 4 + k];
+      }
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+      {
+        H[c][0] = H[c][1] = H[c][2] = V[c] = 0.0;
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+          {
+            const int    o   = (c * 4 + k) * 25 + q25;
+            const double bds = R1[o], bsd = R1[300 + o], bss = R1[600 + o];
+            H[c][0] = fma(sz[k], bds, H[c][0]);
+            H[c][1] = fma(sz[k], bsd, H[c][1]);
+            H[c][2] = fma(dz[k], bss, H[c][2]);
+            V[c]    = fma(sz[k], bss, V[c]);
+          }
+      }
+    __syncthreads(); // B is consumed
+  }
+
+  // F, J^(-2/3), 1/J at the 125 points from u + du (the state the Q3 tangent is linearised at), one workgroup per cell
+  template <bool BOX>
+  __global__ __launch_bounds__(MFQ3_NT, BOX ? 4 : 2) void mf_records_q3(MfParams prm, const double *__restrict__ u, const double *__restrict__ du,
+                                                              double *__restrict__ rec)
+  {
+    __shared__ double R0[MFQ3_R0], R1[MFQ3_R1], sT[40];
+    const int     t    = threadIdx.x, it = t < MFQ3_NQ ? t : MFQ3_NQ - 1;
+    const int64_t cell = blockIdx.x;
+    if (t < 40)
+      sT[t] = prm.tab1d[t];
+    if (t < MFQ3_NPC)
+      {
+        const int32_t node = prm.conn[cell * MFQ3_NPC + t];
+#pragma unroll
+        for (int c = 0; c < 3; ++c)
+          R1[c * MFQ3_NPC + t] = u[int64_t(node) * 3 + c] + du[int64_t(node) * 3 + c]; // get_total_solution, :580-588
+      }
+    __syncthreads();
+    double H[3][3], V[3];
+    mfq3_gradients(prm.tab1d, sT, R0, R1, t, it, H, V);
+    const int qz = it / 25, qy = (it - 25 * qz) / 5, qx = it - 25 * qz - 5 * qy;
+    double    Ji[9], detJ, F[9];
+    mfq3_geometry<BOX>(prm, cell, qx, qy, qz, Ji, detJ);
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+      for (int j = 0; j < 3; ++j)
+        F[i * 3 + j] = H[i][0] * Ji[0 * 3 + j] + H[i][1] * Ji[1 * 3 + j] + H[i][2] * Ji[2 * 3 + j];
+    F[0] += 1.0, F[4] += 1.0, F[8] += 1.0;
+    // (det F <= 0 is reported by the residual pass at these same points, nonlinear_elasticity.cc:935)
+    const double J = det3x3(F), rJ = 1.0 / J, Jm = 1.0 / (cbrt(J) * cbrt(J));
+    if (t < MFQ3_NQ)
+      {
+        double *__restrict__ g = rec + cell * int64_t(MF_NREC * MFQ3_QS) + t;
+#pragma unroll
+        for (int k = 0; k < 9; ++k)
+          g[k * MFQ3_QS] = F[k];
+        g[9 * MFQ3_QS]  = Jm;
+        g[10 * MFQ3_QS] = rJ;
+      }
+  }
+
+  template <bool BOX>
+  __global__ __launch_bounds__(MFQ3_NT, 4) void mf_spmv_q3(MfParams prm)
+  {
+    __shared__ double R0[MFQ3_R0], R1[MFQ3_R1], sT[40];
+    const int     t    = threadIdx.x, it = t < MFQ3_NQ ? t : MFQ3_NQ - 1;
+    const int64_t cell = blockIdx.x;
+    if (t < 40)
+      sT[t] = prm.tab1d[t];
+    // gather x (constrained entries masked)
+    if (t < MFQ3_NPC)
+      {
+        const int32_t node = prm.conn[cell * MFQ3_NPC + t];
+        const int     cm   = prm.cmask[node];
+#pragma unroll
+        for (int c = 0; c < 3; ++c)
+          R1[c * MFQ3_NPC + t] = ((cm >> c) & 1) ? 0.0 : prm.x[int64_t(node) * 3 + c];
+      }
+    // this thread's record: consumed after the gradient passes
+    double rec[MF_NREC];
+    {
+      const double *__restrict__ rp = prm.qrec + cell * int64_t(MF_NREC * MFQ3_QS) + it;
+#pragma unroll
+      for (int f = 0; f < MF_NREC; ++f)
+        rec[f] = __builtin_nontemporal_load(&rp[f * MFQ3_QS]);
+    }
+    __syncthreads();
+    double H[3][3], V[3];
+    mfq3_gradients(prm.tab1d, sT, R0, R1, t, it, H, V);
+    // ---- point stage: Q = JxW S M^T (as mf_spmv), 12 numbers per point into R0: Q[(i*4+l)][q]
+    {
+      const int qz = it / 25, qy = (it - 25 * qz) / 5, qx = it - 25 * qz - 5 * qy;
+      const double wq = prm.tab1d[MFQ3_TW + qx] * prm.tab1d[MFQ3_TW + qy] * prm.tab1d[MFQ3_TW + qz];
+      double       Finv[9], tau[6], tiso[6], cII, cS, Ji[9], detJ, M[9];
+      neo_hooke_from_F<3>(rec, det3x3(rec), rec[9], rec[10], prm.mu, prm.kappa, Finv, tau, tiso, cII, cS);
+      mfq3_geometry<BOX>(prm, cell, qx, qy, qz, Ji, detJ);
+#pragma unroll
+      for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j)
+          M[i * 3 + j] = BOX ? Ji[i * 4] * Finv[i * 3 + j] :
+                               Ji[i * 3 + 0] * Finv[0 * 3 + j] + Ji[i * 3 + 1] * Finv[1 * 3 + j] + Ji[i * 3 + 2] * Finv[2 * 3 + j];
+      const double w = detJ * wq, wcII = w * cII, cs2 = 0.5 * cS;
+      double       h[3][3];
+#pragma unroll
+      for (int j = 0; j < 3; ++j)
+#pragma unroll
+        for (int k = 0; k < 3; ++k)
+          h[j][k] = H[j][0] * M[k] + H[j][1] * M[3 + k] + H[j][2] * M[6 + k];
+      const double pv  = (tau[0] + tau[1] + tau[2]) * (1.0 / 3.0);
+      const double ti0 = tau[0] - pv, ti1 = tau[1] - pv, ti2 = tau[2] - pv;
+      const double trh = h[0][0] + h[1][1] + h[2][2];
+      const double th  = ti0 * h[0][0] + ti1 * h[1][1] + ti2 * h[2][2] + tau[3] * (h[0][1] + h[1][0]) + tau[4] * (h[0][2] + h[2][0]) +
+                        tau[5] * (h[1][2] + h[2][1]);
+      const double aI = wcII * trh - (2.0 / 3.0) * w * th;
+      const double m3 = -(2.0 / 3.0) * trh;
+      const double Tt[3][3] = {{tau[0], tau[3], tau[4]}, {tau[3], tau[1], tau[5]}, {tau[4], tau[5], tau[2]}};
+      const double Ti[3][3] = {{ti0, tau[3], tau[4]}, {tau[3], ti1, tau[5]}, {tau[4], tau[5], ti2}};
+      const double wm       = prm.mass * w;
+#pragma unroll
+      for (int i = 0; i < 3; ++i)
+        {
+          double Sm[3];
+#pragma unroll
+          for (int j = 0; j < 3; ++j)
+            {
+              const double v = m3 * Ti[i][j] + cs2 * (h[i][j] + h[j][i]) + h[i][0] * Tt[0][j] + h[i][1] * Tt[1][j] + h[i][2] * Tt[2][j];
+              Sm[j]          = w * v + (i == j ? aI : 0.0);
+            }
+          // (threads 125-127 write the padding entries 125-127 of every row, which nobody reads)
+#pragma unroll
+          for (int l = 0; l < 3; ++l)
+            R0[(i * 4 + l) * MFQ3_QS + t] = Sm[0] * M[l * 3] + Sm[1] * M[l * 3 + 1] + Sm[2] * M[l * 3 + 2];
+          R0[(i * 4 + 3) * MFQ3_QS + t] = wm * V[i];
+        }
+    }
+    __syncthreads();
+    double S[5][4], D[5][4]; // uniform: scalar registers
+#pragma unroll
+    for (int q = 0; q < 5; ++q)
+#pragma unroll
+      for (int a = 0; a < 4; ++a)
+        {
+          S[q][a] = prm.tab1d[q * 4 + a];
+          D[q][a] = prm.tab1d[MFQ3_TD + q * 4 + a];
+        }
+    // ---- I3: contract qz.  item (c, q25 = qy*5+qx): C_DS / C_SD / C_SS [c,k][q25] at {0, 300, 600} of R1
+    if (t < 75)
+      {
+        const int c = t / 25, q25 = t - 25 * c;
+        double    v[4][5];
+#pragma unroll
+        for (int d = 0; d < 4; ++d)
+#pragma unroll
+          for (int z = 0; z < 5; ++z)
+            v[d][z] = R0[(c * 4 + d) * MFQ3_QS + z * 25 + q25];
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+          {
+            double cds = 0.0, csd = 0.0, css = 0.0;
+#pragma unroll
+            for (int z = 0; z < 5; ++z)
+              {
+                cds = fma(S[z][k], v[0][z], cds);
+                csd = fma(S[z][k], v[1][z], csd);
+                css = fma(D[z][k], v[2][z], css);
+                css = fma(S[z][k], v[3][z], css);
+              }
+            const int o = (c * 4 + k) * 25 + q25;
+            R1[o]       = cds;
+            R1[300 + o] = csd;
+            R1[600 + o] = css;
+          }
+      }
+    __syncthreads();
+    // ---- I2: contract qy.  item (c,k,qx): t = ck * 5 + qx; E_D / E_S [c,k,j][qx] at {0, 240} of R0
+    if (t < 60)
+      {
+        const int ck = t / 5, qx = t - 5 * ck;
+        double    cds[5], csd[5], css[5];
+#pragma unroll
+        for (int qy = 0; qy < 5; ++qy)
+          {
+            const int o = ck * 25 + qy * 5 + qx;
+            cds[qy]     = R1[o];
+            csd[qy]     = R1[300 + o];
+            css[qy]     = R1[600 + o];
+          }
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          {
+            double ed = 0.0, es = 0.0;
+#pragma unroll
+            for (int qy = 0; qy < 5; ++qy)
+              {
+                ed = fma(S[qy][j], cds[qy], ed);
+                es = fma(D[qy][j], csd[qy], es);
+                es = fma(S[qy][j], css[qy], es);
+              }
+            R0[(ck * 4 + j) * 5 + qx]       = ed;
+            R0[240 + (ck * 4 + j) * 5 + qx] = es;
+          }
+      }
+    __syncthreads();
+    // ---- I1: contract qx, results into the cell's slots.  item = line (c,k,j) = t, its four nodes i
+    if (t < 48)
+      {
+        const int c = t >> 4, kj = t & 15;
+        double    ed[5], es[5];
+#pragma unroll
+        for (int qx = 0; qx < 5; ++qx)
+          {
+            ed[qx] = R0[t * 5 + qx];
+            es[qx] = R0[240 + t * 5 + qx];
+          }
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+          {
+            double yv = 0.0;
+#pragma unroll
+            for (int qx = 0; qx < 5; ++qx)
+              {
+                yv = fma(D[qx][i], ed[qx], yv);
+                yv = fma(S[qx][i], es[qx], yv);
+              }
+            const int     a    = kj * 4 + i;
+            const int64_t slot = prm.slot_inline ? cell * MFQ3_NPC + a : int64_t(prm.dst[cell * MFQ3_NPC + a]);
+            prm.yc[slot * 3 + c] = yv;
+          }
+      }
+  }
+
+  // the nodes' 3x3 diagonal blocks from the Q3 records, into the cells' slots [nslots][6] (as mf_diag).  Stage 1, thread =
+  // point: the material response, 20 numbers per point to LDS.  Stage 2, thread = (node a, half h): half 0 takes the points
+  // of the planes qz = 0..2, half 1 those of qz = 3..4; the halves meet in LDS (half 0 + half 1, a fixed order).
+  constexpr int DGQ3_NF = 21; // DG_NF numbers + 1 pad (an odd stride)
+  template <bool BOX>
+  __global__ __launch_bounds__(MFQ3_NT, 3) void mf_diag_q3(MfParams prm, double *__restrict__ slots6)
+  {
+    __shared__ double sF[MFQ3_NQ * DGQ3_NF], sR[MFQ3_NPC * 6], sT[40];
+    const int     t    = threadIdx.x, it = t < MFQ3_NQ ? t : MFQ3_NQ - 1;
+    const int64_t cell = blockIdx.x;
+    if (t < 40)
+      sT[t] = prm.tab1d[t];
+    // ---- stage 1: thread = point
+    {
+      double rec[MF_NREC];
+      const double *__restrict__ rp = prm.qrec + cell * int64_t(MF_NREC * MFQ3_QS) + it;
+#pragma unroll
+      for (int f = 0; f < MF_NREC; ++f)
+        rec[f] = rp[f * MFQ3_QS];
+      const int    qz = it / 25, qy = (it - 25 * qz) / 5, qx = it - 25 * qz - 5 * qy;
+      const double wq = prm.tab1d[MFQ3_TW + qx] * prm.tab1d[MFQ3_TW + qy] * prm.tab1d[MFQ3_TW + qz];
+      double       Finv[9], tau[6], tiso[6], cII, cS, Ji[9], detJ, M[9];
+      neo_hooke_from_F<3>(rec, det3x3(rec), rec[9], rec[10], prm.mu, prm.kappa, Finv, tau, tiso, cII, cS);
+      mfq3_geometry<BOX>(prm, cell, qx, qy, qz, Ji, detJ);
+#pragma unroll
+      for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j)
+          M[i * 3 + j] = BOX ? Ji[i * 4] * Finv[i * 3 + j] :
+                               Ji[i * 3 + 0] * Finv[0 * 3 + j] + Ji[i * 3 + 1] * Finv[1 * 3 + j] + Ji[i * 3 + 2] * Finv[2 * 3 + j];
+      const double w  = detJ * wq;
+      const double pv = tau[0] - tiso[0]; // kappa/2 (J^2 - 1)
+      if (t < MFQ3_NQ)
+        {
+          double *o = sF + t * DGQ3_NF;
+#pragma unroll
+          for (int k = 0; k < 9; ++k)
+            o[k] = M[k];
+#pragma unroll
+          for (int k = 0; k < 6; ++k)
+            o[9 + k] = tau[k];
+          o[15] = 0.5 * w * (cII + 0.5 * cS + (4.0 / 3.0) * pv);
+          o[16] = (2.0 / 3.0) * w;
+          o[17] = 0.5 * cS * w;
+          o[18] = w;
+          o[19] = prm.mass * w;
+        }
+    }
+    __syncthreads();
+    // ---- stage 2: thread = (a, h); the lane's rows of the x / y tables in registers, the z rows per plane from LDS
+    const int a = t & 63, h = t >> 6;
+    const int a1 = a & 3, a2 = (a >> 2) & 3, a3 = a >> 4;
+    double    Sx[5], Dx[5], Sy[5], Dy[5];
+#pragma unroll
+    for (int q = 0; q < 5; ++q)
+      {
+        Sx[q] = sT[q * 4 + a1];
+        Dx[q] = sT[MFQ3_TD + q * 4 + a1];
+        Sy[q] = sT[q * 4 + a2];
+        Dy[q] = sT[MFQ3_TD + q * 4 + a2];
+      }
+    double K[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0}; // xx yy zz xy xz yz (as mf_diag)
+    double Kiso = 0.0;
+    const int z0 = h ? 3 : 0, z1 = h ? 5 : 3;
+    for (int z = z0; z < z1; ++z)
+      {
+        const double Sz = sT[z * 4 + a3], Dz = sT[MFQ3_TD + z * 4 + a3];
+#pragma unroll
+        for (int qy = 0; qy < 5; ++qy)
+          {
+            const double syz = Sy[qy] * Sz, dyz = Dy[qy] * Sz, sdz = Sy[qy] * Dz;
+#pragma unroll
+            for (int qx = 0; qx < 5; ++qx)
+              {
+                const double *__restrict__ f = sF + (z * 25 + qy * 5 + qx) * DGQ3_NF;
+                const double d0 = Dx[qx] * syz, d1 = Sx[qx] * dyz, d2 = Sx[qx] * sdz, N = Sx[qx] * syz;
+                double       g[3], tg[3], v[3];
+#pragma unroll
+                for (int j = 0; j < 3; ++j)
+                  g[j] = fma(d2, f[6 + j], fma(d1, f[3 + j], d0 * f[j]));
+                sym_mul(f + 9, g, tg);
+                const double gg = fma(g[2], g[2], fma(g[1], g[1], g[0] * g[0]));
+                const double gt = fma(g[2], tg[2], fma(g[1], tg[1], g[0] * tg[0]));
+                const double dd = fma(f[19] * N, N, fma(f[18], gt, f[17] * gg));
+#pragma unroll
+                for (int j = 0; j < 3; ++j)
+                  v[j] = fma(-f[16], tg[j], f[15] * g[j]);
+                Kiso += dd;
+                K[0] = fma(g[0], v[0], K[0]);
+                K[1] = fma(g[1], v[1], K[1]);
+                K[2] = fma(g[2], v[2], K[2]);
+                K[3] = fma(g[0], v[1], fma(v[0], g[1], K[3]));
+                K[4] = fma(g[0], v[2], fma(v[0], g[2], K[4]));
+                K[5] = fma(g[1], v[2], fma(v[1], g[2], K[5]));
+              }
+          }
+      }
+#pragma unroll
+    for (int e = 0; e < 3; ++e)
+      K[e] = fma(2.0, K[e], Kiso);
+    if (h == 1)
+#pragma unroll
+      for (int e = 0; e < 6; ++e)
+        sR[a * 6 + e] = K[e];
+    __syncthreads();
+    if (h == 0)
+      {
+        const int64_t slot = prm.slot_inline ? cell * MFQ3_NPC + a : int64_t(prm.dst[cell * MFQ3_NPC + a]);
+        double *__restrict__ o = slots6 + slot * 6;
+#pragma unroll
+        for (int e = 0; e < 6; ++e)
+          o[e] = K[e] + sR[a * 6 + e];
+      }
+  }
+
   // system_rhs from the cells' residual slots (point pass in one launch): rhs = 0 - r_1 - r_2 - ... in slot order, the
   // subtractions of the colour-by-colour update in their order; constrained rows get no rhs (:769-773).  One thread per dof.
   __global__ __launch_bounds__(256) void residual_gather(const double *__restrict__ slots3, const int32_t *__restrict__ slot_base,
@@ -6820,6 +7269,30 @@ namespace mi
       hipLaunchKernelGGL(mf_diag<true>, dim3(q.xcd_chunk * 8), dim3(64), 0, s, q, slots6);
     else
       hipLaunchKernelGGL(mf_diag<false>, dim3(q.xcd_chunk * 8), dim3(64), 0, s, q, slots6);
+  }
+  void launch_mf_records_q3(const MfParams &p, const double *u, const double *du, double *rec, int32_t cell_count, hipStream_t s)
+  {
+    if (cell_count <= 0)
+      return;
+    auto *kern = p.cellbox ? mf_records_q3<true> : mf_records_q3<false>;
+    hipLaunchKernelGGL(kern, dim3(cell_count), dim3(MFQ3_NT), 0, s, p, u, du, rec);
+  }
+  void launch_mf_spmv_q3(const MfParams &p, int32_t cell_count, hipStream_t s, hipEvent_t ev_start, hipEvent_t ev_stop)
+  {
+    if (cell_count <= 0)
+      return;
+    auto *kern = p.cellbox ? mf_spmv_q3<true> : mf_spmv_q3<false>;
+    if (ev_start || ev_stop)
+      hipExtLaunchKernelGGL(kern, dim3(cell_count), dim3(MFQ3_NT), 0, s, ev_start, ev_stop, 0, p);
+    else
+      hipLaunchKernelGGL(kern, dim3(cell_count), dim3(MFQ3_NT), 0, s, p);
+  }
+  void launch_mf_diag_q3(const MfParams &p, double *slots6, int32_t cell_count, hipStream_t s)
+  {
+    if (cell_count <= 0)
+      return;
+    auto *kern = p.cellbox ? mf_diag_q3<true> : mf_diag_q3<false>;
+    hipLaunchKernelGGL(kern, dim3(cell_count), dim3(MFQ3_NT), 0, s, p, slots6);
   }
   void launch_mf_diag_gather(const double *slots6, const int32_t *slot_base, const int32_t *slot_src, const uint8_t *cmask,
                              const int32_t *diagpos, double *blk, double *dinv, double *dinv_blk, double *sym6, int64_t nnodes, hipStream_t s)

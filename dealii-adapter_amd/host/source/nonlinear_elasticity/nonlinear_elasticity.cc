@@ -200,7 +200,7 @@ namespace Nonlinear_Elasticity
       device->check(mi_set_tuning(device->ctx(), "cg_warm_start", e ? std::max(0, std::min(3, std::atoi(e))) : 2), "mi_set_tuning");
       if (const char *f = std::getenv("MI_CORRECT_FACE_F")) // "--correct-face-F" (SURVEY section 9); default: the reference's quirk
         device->check(mi_set_tuning(device->ctx(), "correct_face_F", std::atoi(f) != 0), "mi_set_tuning");
-      if (const char *f = std::getenv("MI_FINE_LEVEL")) // 1: the fine level matrix-free end to end (3D Q2 meshes)
+      if (const char *f = std::getenv("MI_FINE_LEVEL")) // 1: the fine level matrix-free end to end (3D Q2, and 3D Q3 on one slab)
         {
           if (std::atoi(f) != 0 && mi_set_tuning(device->ctx(), "fine_level", 1) != MI_OK)
             std::cout << "MI_FINE_LEVEL ignored: " << mi_last_error(device->ctx()) << std::endl;

@@ -288,13 +288,16 @@ int mi_set_profiling(mi_ctx *ctx, int enable);
  *  correct_face_F       0 | 1                      Neumann pull-back with F of CELL point fq (the reference's quirk,    MI_CORRECT_FACE_F
  *                                                  :825-827) | with F at the face point
  *  OPERATOR FORMS
- *  fine_level           0 | 1                      3D Q2: the fine level assembled (global tangent + sell_spmv: the     -
- *                                                  north-star path) | matrix-free end to end: a tangent assembly writes
- *                                                  point records, residual and the nodes' diagonal blocks only; the CG's
- *                                                  product, residual / start-vector products and the smoother run on
- *                                                  mf_spmv; the assembled tangent's memory is released.  Same results
- *                                                  (nonlinear_elasticity.cc:1044-1087, 1153-1191); excludes
- *                                                  "solver_type" 1, "precond_storage" 32 and matrix export
+ *  fine_level           0 | 1                      3D Q2 and Q3 (Q3: one slab): the fine level assembled (global        -
+ *                                                  tangent + sell_spmv: the north-star path) | matrix-free end to end: a
+ *                                                  tangent assembly writes point records, residual and the nodes'
+ *                                                  diagonal blocks only; the CG's product, residual / start-vector
+ *                                                  products and the smoother run on mf_spmv (Q3: mf_spmv_q3, 125 points;
+ *                                                  "smoother_quadrature", "smoother_precision" 32 and
+ *                                                  "mf_slots_cell_major" have no effect there); the assembled tangent's
+ *                                                  memory is released.  Same results (nonlinear_elasticity.cc:1044-1087,
+ *                                                  1153-1191); excludes "solver_type" 1, "precond_storage" 32 and matrix
+ *                                                  export
  *  mf_diag_lag          0 | 1                      "fine_level" 1: diagonal blocks (smoother's D, Jacobi diagonal) at     -
  *                                                  every tangent | at the first tangent of a time step, kept over its
  *                                                  Newton iterations (what bench.py and the executable set)
