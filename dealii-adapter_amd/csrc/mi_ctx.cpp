@@ -395,6 +395,17 @@ namespace mi_detail
            !c->active_sell_vals && c->d_dinv_blk;
   }
 
+  // what every launch of a matrix-free kernel takes from the context as it stands: mesh tables, 1D tables, material, the 27-point
+  // records.  The call sites add what depends on the call: qrec / qrec32, vals / diagpos, x / y, the slot fields, sel_*, stamps.
+  mi::MfParams mf_params(const mi_ctx *c)
+  {
+    mi::MfParams f{};
+    f.conn = c->d_conn, f.first = c->d_node_first, f.cmask = c->d_cmask, f.cverts = c->d_cverts, f.cellbox = c->d_cellbox;
+    f.tab1d = c->d_tab, f.tab27 = c->d_tab27, f.lat = c->lat, f.qrec27 = c->d_qrec27;
+    f.mu = c->mat.mu, f.kappa = c->kappa, f.mass = c->alpha[1] * c->mat.rho;
+    return f;
+  }
+
   // y = K x on the owned rows (+ optional fused dot partials); x and y are whole local vectors.
   // part: 0 all rows, 1 interior rows only (no ghost columns: may run while the halo is in flight), 2 boundary rows
   void enqueue_spmv(mi_ctx *c, const double *x, double *y, const double *dotv, double *partials, const int32_t *done,
@@ -427,27 +438,15 @@ namespace mi_detail
         if (part == 1 && !mf_split)
           return;
         mi::EbeParams e{c->d_ke, c->d_conn, c->d_node_first, x, y};
-        mi::MfParams  f{};
+        mi::MfParams  f = mf_params(c);
         f.qrec    = q3 ? c->d_qrec_q3 : c->d_qrec;
         // opt-in "smoother_precision" 32: the SMOOTHER's products in fp32 arithmetic on fp32 records (residuals, start-vector
         // products and mi_spmv keep the fp64 form)
         f.qrec32  = (smoother && c->smoother_precision == 32 && c->qrec32_valid) ? c->d_qrec32 : nullptr;
-        f.qrec27  = c->d_qrec27;
-        f.tab27   = c->d_tab27;
-        f.conn    = c->d_conn;
-        f.first   = c->d_node_first;
-        f.cmask   = c->d_cmask;
         f.vals    = c->mf_fine ? c->d_diag_blk : c->d_vals;      // (diagonal entries of constrained dofs)
         f.diagpos = c->mf_fine ? c->d_diagpos_mf : c->d_diagpos;
-        f.tab1d   = c->d_tab;
-        f.cverts  = c->d_cverts;
-        f.mu      = c->mat.mu;
-        f.kappa   = c->kappa;
-        f.cellbox = c->d_cellbox;
         f.x       = x;
         f.y       = y;
-        f.mass    = c->alpha[1] * c->mat.rho;
-        f.lat     = c->lat;
         const bool one_launch = kind == 2 && c->mf_slots && c->d_mf_yc;
         if (one_launch)
           {
@@ -876,19 +875,13 @@ namespace mi_detail
     c->qrec27_valid = false;
     if (c->smoother_points == 3 && c->d_qrec && c->d_qrec27) // the smoother's own records: F, J^(-2/3), 1/J at the 27 points
       {
-        mi::MfParams f{};
-        f.conn = c->d_conn, f.cverts = c->d_cverts, f.cellbox = c->d_cellbox, f.tab27 = c->d_tab27, f.lat = c->lat;
-        mi::launch_mf_records27(f, c->vec(MI_V_TOTAL_DISPLACEMENT), c->vec(MI_V_SOLUTION_DELTA), c->d_qrec27, int32_t(c->mesh.ncells),
-                                c->stream);
+        mi::launch_mf_records27(mf_params(c), c->vec(MI_V_TOTAL_DISPLACEMENT), c->vec(MI_V_SOLUTION_DELTA), c->d_qrec27,
+                                int32_t(c->mesh.ncells), c->stream);
         c->qrec27_valid = true;
       }
     if (c->d_qrec_q3) // Q3 fine level: F, J^(-2/3), 1/J at the 125 points of the assembly's rule, from the state of the residual
-      {
-        mi::MfParams f{};
-        f.conn = c->d_conn, f.cverts = c->d_cverts, f.cellbox = c->d_cellbox, f.tab1d = c->d_tab;
-        mi::launch_mf_records_q3(f, c->vec(MI_V_TOTAL_DISPLACEMENT), c->vec(MI_V_SOLUTION_DELTA), c->d_qrec_q3, int32_t(c->mesh.ncells),
-                                 c->stream);
-      }
+      mi::launch_mf_records_q3(mf_params(c), c->vec(MI_V_TOTAL_DISPLACEMENT), c->vec(MI_V_SOLUTION_DELTA), c->d_qrec_q3,
+                               int32_t(c->mesh.ncells), c->stream);
     // which kernel ran: assemble_q2sf (sum factorised; it alone writes the fp32 records) or the node-pair form
     const bool q2sf = c->dim == 3 && c->degree == 2 && (p.variant == 0 || (p.variant >= 3 && p.variant <= 8));
     c->ke_valid     = (c->d_ke && q2sf && !c->mf_fine) || c->d_qrec || c->d_qrec_q3;
@@ -902,9 +895,8 @@ namespace mi_detail
     if (mf_tangent)
       {
         c->mf_diag_fresh = true;
-        mi::MfParams f{};
-        f.qrec = c->d_qrec, f.tab1d = c->d_tab, f.cverts = c->d_cverts, f.cellbox = c->d_cellbox, f.dst = c->d_mf_dst;
-        f.mu = c->mat.mu, f.kappa = c->kappa, f.mass = c->alpha[1] * c->mat.rho;
+        mi::MfParams f = mf_params(c);
+        f.qrec = c->d_qrec, f.dst = c->d_mf_dst;
         const int td = tic(c0, MI_T_ASSEMBLE_DIAG);
         if (c->d_qrec_q3)
           {
@@ -3296,10 +3288,8 @@ int mi_bench_spmv(mi_ctx *c, int reps, double *ms_per_launch)
       unsigned long long *d_st  = nullptr;
       HIPCHK(c, hipMalloc((void **)&d_st, size_t(ncell) * 8 * sizeof(unsigned long long)));
       HIPCHK(c, hipMemsetAsync(d_st, 0, size_t(ncell) * 8 * sizeof(unsigned long long), c->stream));
-      mi::MfParams f{};
-      f.qrec = c->d_qrec, f.conn = c->d_conn, f.first = c->d_node_first, f.cmask = c->d_cmask, f.vals = c->d_vals;
-      f.diagpos = c->d_diagpos, f.tab1d = c->d_tab, f.cverts = c->d_cverts, f.mu = c->mat.mu, f.kappa = c->kappa;
-      f.cellbox = c->d_cellbox, f.x = c->work(W_P), f.y = c->work(W_Q), f.mass = c->alpha[1] * c->mat.rho, f.lat = c->lat;
+      mi::MfParams f = mf_params(c);
+      f.qrec = c->d_qrec, f.vals = c->d_vals, f.diagpos = c->d_diagpos, f.x = c->work(W_P), f.y = c->work(W_Q);
       f.yc = c->d_mf_yc, f.dst = c->d_mf_dst, f.slot_base = c->d_mf_slot_base, f.slot_src = c->d_mf_src, f.stamps = d_st;
       mi::launch_mf_spmv(f, 0, int32_t(ncell), c->stream);
       std::vector<unsigned long long> st(size_t(ncell) * 8);

@@ -2704,6 +2704,114 @@ namespace mi
       }
   }
 
+  // ------------------------------------------------------------------ matrix-free kernels: what they share
+  // One definition each of what the three families -- 64-point Q2 (mf_spmv, mf_diag), 27-point smoother (mf_records27,
+  // mf_spmv27), Q3 (mf_records_q3, mf_spmv_q3, mf_diag_q3) -- do at a quadrature point: mf_geometry, MF_M, MF_POINT_ALGEBRA /
+  // MF_POINT_SM, MF_RECORD_TAIL here; MF_DIAG_POINT, MF_DIAG_ACCUMULATE at mf_diag.  The sum-factorisation passes, the LDS
+  // layouts and the lane mappings stay with the kernels.  The geometry is a function; the tensor algebra is text expanded in
+  // place, so that every kernel hands the optimiser its statements in the order it always did (its register allocation
+  // depends on that order: profiles/mf_shared_point/README.md).  The text works on names in the caller's scope (T: the
+  // kernel's arithmetic type; all #undef'd behind mf_diag_q3):
+  //   macro               reads                                              declares / writes
+  //   MF_RECORD_TAIL      H[3][3], Ji[9]                                     F[9], J, rJ, Jm; the record at its g_
+  //   MF_M                Ji[9], Finv[9]                                     writes M[9] (declared by the caller)
+  //   MF_POINT_ALGEBRA    H[3][3], M[9], tau[6], w, wcII                     h[3][3], pv, ti0-2, trh, th, aI, m3, Tt, Ti
+  //   MF_POINT_SM(i, j)   w, cs2 and what MF_POINT_ALGEBRA declared          (an expression)
+  //   MF_POINT_Q(Sm, l)   M[9], its row Sm[3] of JxW S                       (an expression)
+  //   MF_DIAG_POINT       rec[11], wq, cell, prm                             Finv, tau, tiso, cII, cS, Ji, detJ, M, w, pv; o_[20]
+  //   MF_DIAG_ACCUMULATE  f[20], d0, d1, d2, N                               updates K[6], Kiso (g, tg, v, gg, gt, dd in a block)
+  // geometry of `cell` at the unit-cell point xi: Ji = Jinv (row-major), detJ.  BOX (every cell an axis-parallel box): 1/hx,
+  // 1/hy, 1/hz on the diagonal and hx hy hz from MfParams::cellbox -- uniform, scalar loads, xi is not read; otherwise the
+  // Jacobian of the trilinear map at xi as in the assembly (fp64 only)
+  template <bool BOX, typename T>
+  __device__ __forceinline__ void mf_geometry(const MfParams &prm, const int64_t cell, const T *xi, T Ji[9], T &detJ)
+  {
+    if constexpr (BOX)
+      {
+        const double *__restrict__ cb = prm.cellbox + cell * 4;
+#pragma unroll
+        for (int k = 0; k < 9; ++k)
+          Ji[k] = 0.0;
+        Ji[0] = cb[0], Ji[4] = cb[1], Ji[8] = cb[2];
+        detJ  = cb[3];
+      }
+    else
+      {
+        const double *__restrict__ cv = prm.cverts + cell * 24; // uniform: scalar loads
+        T verts[24], Jm[9];
+#pragma unroll
+        for (int k = 0; k < 24; ++k)
+          verts[k] = cv[k];
+        q1_jacobian<3>(verts, xi, Jm);
+        detJ = det3x3(Jm);
+        inv3x3(Jm, detJ, Ji);
+      }
+  }
+  // ... at point (qx, qy, qz) of a tensor rule with the 1D points tx[]
+  template <bool BOX>
+  __device__ __forceinline__ void mf_geometry(const MfParams &prm, const int64_t cell, const double *tx, const int qx, const int qy, const int qz,
+                                              double Ji[9], double &detJ)
+  {
+    const double xiq[3] = {tx[qx], tx[qy], tx[qz]}; // (BOX: not read, so not loaded)
+    mf_geometry<BOX>(prm, cell, xiq, Ji, detJ);
+  }
+
+  // the tail of the record kernels, from H and Ji in scope: F = I + H Jinv, J = det F, then F[9], J^(-2/3), 1/J into the record
+  // at g_ (fields STRIDE_ apart) where store_ holds.  FOLD_: a point with det F <= 0 takes the undeformed state.
+#define MF_RECORD_TAIL(FOLD_, store_, g_, STRIDE_)                                                                     \
+  double F[9];                                                                                                         \
+  _Pragma("unroll") for (int i_ = 0; i_ < 3; ++i_)                                                                     \
+    _Pragma("unroll") for (int j_ = 0; j_ < 3; ++j_)                                                                   \
+      F[i_ * 3 + j_] = H[i_][0] * Ji[0 * 3 + j_] + H[i_][1] * Ji[1 * 3 + j_] + H[i_][2] * Ji[2 * 3 + j_];              \
+  F[0] += 1.0, F[4] += 1.0, F[8] += 1.0;                                                                               \
+  double J = det3x3(F);                                                                                                \
+  if (FOLD_)                                                                                                           \
+    {                                                                                                                  \
+      const bool folded = !(J > 0.0);                                                                                  \
+      _Pragma("unroll") for (int k_ = 0; k_ < 9; ++k_)                                                                 \
+        F[k_] = folded ? (k_ % 4 == 0 ? 1.0 : 0.0) : F[k_];                                                            \
+      J = folded ? 1.0 : J;                                                                                            \
+    }                                                                                                                  \
+  const double rJ = 1.0 / J, Jm = 1.0 / (cbrt(J) * cbrt(J));                                                           \
+  if (store_)                                                                                                          \
+    {                                                                                                                  \
+      double *__restrict__ g = (g_);                                                                                   \
+      _Pragma("unroll") for (int k_ = 0; k_ < 9; ++k_)                                                                 \
+        g[k_ * (STRIDE_)] = F[k_];                                                                                     \
+      g[9 * (STRIDE_)]  = Jm;                                                                                          \
+      g[10 * (STRIDE_)] = rJ;                                                                                          \
+    }
+  // M = Jinv F^-1 from Ji and Finv in scope (BOX: Jinv is diagonal).  OUTER_, INNER_ are i_, j_ (row by row) or j_, i_ (column
+  // by column, the 64-point kernels): the order in which a kernel forms the nine entries decides its instruction schedule
+#define MF_M(BOX_, OUTER_, INNER_)                                                                                               \
+  _Pragma("unroll") for (int OUTER_ = 0; OUTER_ < 3; ++OUTER_)                                                                   \
+    _Pragma("unroll") for (int INNER_ = 0; INNER_ < 3; ++INNER_)                                                                 \
+      M[i_ * 3 + j_] = (BOX_) ? Ji[i_ * 4] * Finv[i_ * 3 + j_] :                                                                 \
+                                Ji[i_ * 3 + 0] * Finv[0 * 3 + j_] + Ji[i_ * 3 + 1] * Finv[1 * 3 + j_] + Ji[i_ * 3 + 2] * Finv[2 * 3 + j_];
+  // the point stage of the products, Q = JxW S M^T (the formulas at mf_spmv).
+  // MF_POINT_ALGEBRA declares, from H = sum_b x_b (x) grad_xi N_b, M, tau, w = JxW and wcII = w c_II in scope: h = H M, aI, m3,
+  // Tt = tau, Ti = dev tau; MF_POINT_SM(i, j) is then entry (i, j) of JxW S (cs2 = c_S / 2 in scope) and, with Sm one row of
+  // it, MF_POINT_Q(Sm, l) entry l of that row of Q = (JxW S) M^T.  Each kernel stores Q into its own LDS layout; the mass term
+  // stays with it too.
+#define MF_POINT_ALGEBRA(T_)                                                                                  \
+  T_ h[3][3];                                                                                                 \
+  _Pragma("unroll") for (int j_ = 0; j_ < 3; ++j_)                                                            \
+    _Pragma("unroll") for (int k_ = 0; k_ < 3; ++k_)                                                          \
+      h[j_][k_] = H[j_][0] * M[k_] + H[j_][1] * M[3 + k_] + H[j_][2] * M[6 + k_];                             \
+  const T_ pv  = (tau[0] + tau[1] + tau[2]) * T_(1.0 / 3.0); /* tau_iso = dev tau */                          \
+  const T_ ti0 = tau[0] - pv, ti1 = tau[1] - pv, ti2 = tau[2] - pv;                                           \
+  const T_ trh = h[0][0] + h[1][1] + h[2][2];                                                                 \
+  const T_ th  = ti0 * h[0][0] + ti1 * h[1][1] + ti2 * h[2][2] + tau[3] * (h[0][1] + h[1][0]) +               \
+                 tau[4] * (h[0][2] + h[2][0]) + tau[5] * (h[1][2] + h[2][1]);                                 \
+  const T_ aI = wcII * trh - T_(2.0 / 3.0) * w * th;                                                          \
+  const T_ m3 = T_(-(2.0 / 3.0)) * trh;                                                                       \
+  const T_ Tt[3][3] = {{tau[0], tau[3], tau[4]}, {tau[3], tau[1], tau[5]}, {tau[4], tau[5], tau[2]}};         \
+  const T_ Ti[3][3] = {{ti0, tau[3], tau[4]}, {tau[3], ti1, tau[5]}, {tau[4], tau[5], ti2}};
+#define MF_POINT_SM(T_, i, j)                                                                                                  \
+  (w * (m3 * Ti[i][j] + cs2 * (h[i][j] + h[j][i]) + h[i][0] * Tt[0][j] + h[i][1] * Tt[1][j] + h[i][2] * Tt[2][j]) + \
+   ((i) == (j) ? aI : T_(0.0)))
+#define MF_POINT_Q(Sm_, l) ((Sm_)[0] * M[(l) * 3] + (Sm_)[1] * M[(l) * 3 + 1] + (Sm_)[2] * M[(l) * 3 + 2])
+
   // ------------------------------------------------------------------ matrix-free product from quadrature-point records
   // y += sum over the cells of one colour of P_e^T K_e P_e x WITHOUT K_e: the assembly leaves, per cell and quadrature
   // point, the state its tangent is linearised at (F, J^(-2/3), 1/J: MF_NREC x 64 doubles = 5.6 kB per 3D Q2 cell against
@@ -2717,8 +2825,8 @@ namespace mi
   // time (3 nodes <-> 4 points); in every pass a lane owns one line and produces ALL outputs along the contracted
   // direction, so the 1D tables are scalar operands and every intermediate is written to LDS once.
   // One wavefront = one cell = its 64 quadrature points.  Update of y as in ebe_spmv (colours, first touch stores).
-  // Geometry: BOX (every cell an axis-parallel box, the reference's grids) takes 1/h and the volume from the cell's
-  // corner vertices; otherwise the Jacobian of the trilinear map is evaluated at the point as in the assembly.
+  // Geometry (mf_geometry): BOX (every cell an axis-parallel box, the reference's grids) takes 1/h and the volume from the
+  // cell's corner vertices; otherwise the Jacobian of the trilinear map is evaluated at the point as in the assembly.
   // Constrained dofs: x is masked on the way in; their rows receive diag(K) x from the assembled tangent at the first touch
   // (|K_e(i,i)| summed over the cells is what the assembly put there), nothing otherwise.
   // SLOTS: instead of updating y colour by colour, every cell stores its 81 results in its own slots of a
@@ -2847,15 +2955,10 @@ namespace mi
         xiq[1] = prm.tab1d[28 + ((lane >> 2) & 3)];
         xiq[2] = prm.tab1d[28 + qz];
       }
-    // the cell's geometry (BOX): 1/hx, 1/hy, 1/hz, hx hy hz -- uniform, scalar loads
-    T cbox[4] = {0.0, 0.0, 0.0, 0.0};
+    // the cell's geometry (BOX: uniform, scalar loads -- here; otherwise at the point, in the point stage)
+    T Ji[9], detJ = 0.0;
     if constexpr (BOX)
-      {
-        const double *__restrict__ cb = prm.cellbox + cell * 4;
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-          cbox[k] = cb[k];
-      }
+      mf_geometry<true>(prm, cell, xiq, Ji, detJ); // (xiq: not read on boxes)
     MF_STAMP(0); // (after every uniform load: the clock read is a scalar-memory instruction with side effects, and loads
                  // behind it would no longer be scalar)
     // ---- gather x (constrained entries masked): X[c][a] at c*27 + a, a = (k*3 + j)*3 + i
@@ -2949,74 +3052,32 @@ namespace mi
     MF_STAMP(2); // gradients at the points
     if constexpr (BOX) // the mass term first: it needs only the cell's volume, and V dies before the tensor algebra
       {
-        const T wm = mass_t * cbox[3] * wq;
+        const T wm = mass_t * detJ * wq;
 #pragma unroll
         for (int i = 0; i < 3; ++i)
           s0[(i * 4 + 3) * 64 + (lane ^ ((i & 1) << 4))] = wm * V[i];
       }
-    // ---- quadrature point: Q = JxW S M^T
+    // ---- quadrature point: Q = JxW S M^T (MF_POINT_ALGEBRA)
     {
       T M[9], tau[6], w, wcII, cs2;
       {
         const T *F = rec;
-        T        Finv[9], tiso[6], cII, cS, Ji[9], detJ;
+        T        Finv[9], tiso[6], cII, cS;
         neo_hooke_from_F<3>(F, det3x3(F), rec[9], rec[10], mu_t, kappa_t, Finv, tau, tiso, cII, cS);
-        if constexpr (BOX)
-          {
-            const T rx = cbox[0], ry = cbox[1], rz = cbox[2];
-            detJ            = cbox[3];
-#pragma unroll
-            for (int k = 0; k < 3; ++k)
-              {
-                M[k]     = rx * Finv[k];
-                M[3 + k] = ry * Finv[3 + k];
-                M[6 + k] = rz * Finv[6 + k];
-              }
-          }
-        else
-          {
-            const double *__restrict__ cv = prm.cverts + cell * 24; // uniform: scalar loads
-            T verts[24], Jm[9];
-#pragma unroll
-            for (int k = 0; k < 24; ++k)
-              verts[k] = cv[k];
-            q1_jacobian<3>(verts, xiq, Jm);
-            detJ = det3x3(Jm);
-            inv3x3(Jm, detJ, Ji);
-#pragma unroll
-            for (int i = 0; i < 3; ++i)
-#pragma unroll
-              for (int j = 0; j < 3; ++j)
-                M[i * 3 + j] = Ji[i * 3 + 0] * Finv[0 * 3 + j] + Ji[i * 3 + 1] * Finv[1 * 3 + j] + Ji[i * 3 + 2] * Finv[2 * 3 + j];
-          }
+        if constexpr (!BOX)
+          mf_geometry<false>(prm, cell, xiq, Ji, detJ);
+        MF_M(BOX, j_, i_)
         w    = detJ * wq;
         wcII = w * cII;
         cs2  = T(0.5) * cS;
       }
-      T        h[3][3];
-#pragma unroll
-      for (int j = 0; j < 3; ++j)
-#pragma unroll
-        for (int k = 0; k < 3; ++k)
-          h[j][k] = H[j][0] * M[k] + H[j][1] * M[3 + k] + H[j][2] * M[6 + k];
-      const T pv  = (tau[0] + tau[1] + tau[2]) * T(1.0 / 3.0); // tau_iso = dev tau
-      const T ti0 = tau[0] - pv, ti1 = tau[1] - pv, ti2 = tau[2] - pv;
-      const T trh = h[0][0] + h[1][1] + h[2][2];
-      const T th  = ti0 * h[0][0] + ti1 * h[1][1] + ti2 * h[2][2] + tau[3] * (h[0][1] + h[1][0]) +
-                        tau[4] * (h[0][2] + h[2][0]) + tau[5] * (h[1][2] + h[2][1]);
-      const T aI = wcII * trh - T(2.0 / 3.0) * w * th;
-      const T m3 = T(-(2.0 / 3.0)) * trh;
-      const T Tt[3][3] = {{tau[0], tau[3], tau[4]}, {tau[3], tau[1], tau[5]}, {tau[4], tau[5], tau[2]}};
-      const T Ti[3][3] = {{ti0, tau[3], tau[4]}, {tau[3], ti1, tau[5]}, {tau[4], tau[5], ti2}};
+      MF_POINT_ALGEBRA(T)
       T       Sm[3][3];
 #pragma unroll
       for (int i = 0; i < 3; ++i)
 #pragma unroll
         for (int j = 0; j < 3; ++j)
-          {
-            T v = m3 * Ti[i][j] + cs2 * (h[i][j] + h[j][i]) + h[i][0] * Tt[0][j] + h[i][1] * Tt[1][j] + h[i][2] * Tt[2][j];
-            Sm[i][j] = w * v + (i == j ? aI : T(0.0));
-          }
+          Sm[i][j] = MF_POINT_SM(T, i, j);
       const T wm = mass_t * w;
 #pragma unroll
       for (int i = 0; i < 3; ++i)
@@ -3024,7 +3085,7 @@ namespace mi
           const int ql = lane ^ ((i & 1) << 4);
 #pragma unroll
           for (int l = 0; l < 3; ++l)
-            s0[(i * 4 + l) * 64 + ql] = Sm[i][0] * M[l * 3] + Sm[i][1] * M[l * 3 + 1] + Sm[i][2] * M[l * 3 + 2];
+            s0[(i * 4 + l) * 64 + ql] = MF_POINT_Q(Sm[i], l);
           if constexpr (!BOX)
             s0[(i * 4 + 3) * 64 + ql] = wm * V[i];
         }
@@ -3337,6 +3398,47 @@ namespace mi
   // numbers (xx yy zz xy xz yz) go to the cell's slot of the node (MfParams::dst, as the product's results): no two
   // cells share a slot, so ONE launch covers all colours, and mf_diag_gather sums the slots of a node in processing order.
   constexpr int DG_NF = 20; // M[9], tau[6], (c_II + c_S/2 + 4/3 p) w / 2, 2/3 w, c_S/2 w, w, alpha_1 rho w
+  // stage 1 at one point, from rec, wq, cell and prm in scope: the record's material response (the assembly's own function), the
+  // geometry at point (qx_, qy_, qz_) of the rule with the 1D points tx_, M = Jinv F^-1 (MF_M in the order MO_, MI_) -> the DG_NF numbers at o_ where store_ holds
+#define MF_DIAG_POINT(BOX_, MO_, MI_, tx_, qx_, qy_, qz_, store_, o_)                                          \
+  double Finv[9], tau[6], tiso[6], cII, cS, Ji[9], detJ, M[9];                                                  \
+  neo_hooke_from_F<3>(rec, det3x3(rec), rec[9], rec[10], prm.mu, prm.kappa, Finv, tau, tiso, cII, cS);          \
+  mf_geometry<BOX_>(prm, cell, tx_, qx_, qy_, qz_, Ji, detJ);                                                   \
+  MF_M(BOX_, MO_, MI_)                                                                                          \
+  const double w  = detJ * wq;                                                                                  \
+  const double pv = tau[0] - tiso[0]; /* kappa/2 (J^2 - 1) */                                                   \
+  if (store_)                                                                                                   \
+    {                                                                                                           \
+      double *o = (o_);                                                                                         \
+      _Pragma("unroll") for (int k_ = 0; k_ < 9; ++k_) o[k_] = M[k_];                                           \
+      _Pragma("unroll") for (int k_ = 0; k_ < 6; ++k_) o[9 + k_] = tau[k_];                                     \
+      o[15] = 0.5 * w * (cII + 0.5 * cS + (4.0 / 3.0) * pv);                                                    \
+      o[16] = (2.0 / 3.0) * w;                                                                                  \
+      o[17] = 0.5 * cS * w;                                                                                     \
+      o[18] = w;                                                                                                \
+      o[19] = prm.mass * w;                                                                                     \
+    }
+  // stage 2, one (point, node) pair: f = the point's DG_NF numbers, (d0, d1, d2) = grad_xi N_a and N = N_a at the point, all in
+  // scope.  K: xx yy zz xy xz yz -- the diagonal as sum of g_i v_i (doubled, + the isotropic part Kiso, by the kernel at the end)
+#define MF_DIAG_ACCUMULATE                                                      \
+  {                                                                             \
+    double g[3], tg[3], v[3];                                                   \
+    _Pragma("unroll") for (int j_ = 0; j_ < 3; ++j_)                            \
+      g[j_] = fma(d2, f[6 + j_], fma(d1, f[3 + j_], d0 * f[j_]));               \
+    sym_mul(f + 9, g, tg);                                                      \
+    const double gg = fma(g[2], g[2], fma(g[1], g[1], g[0] * g[0]));            \
+    const double gt = fma(g[2], tg[2], fma(g[1], tg[1], g[0] * tg[0]));         \
+    const double dd = fma(f[19] * N, N, fma(f[18], gt, f[17] * gg));            \
+    _Pragma("unroll") for (int j_ = 0; j_ < 3; ++j_)                            \
+      v[j_] = fma(-f[16], tg[j_], f[15] * g[j_]);                               \
+    Kiso += dd;                                                                 \
+    K[0] = fma(g[0], v[0], K[0]);                                               \
+    K[1] = fma(g[1], v[1], K[1]);                                               \
+    K[2] = fma(g[2], v[2], K[2]);                                               \
+    K[3] = fma(g[0], v[1], fma(v[0], g[1], K[3]));                              \
+    K[4] = fma(g[0], v[2], fma(v[0], g[2], K[4]));                              \
+    K[5] = fma(g[1], v[2], fma(v[1], g[2], K[5]));                              \
+  }
   template <bool BOX>
   __global__ __launch_bounds__(64, 3) void mf_diag(MfParams prm, double *__restrict__ slots6)
   {
@@ -3364,52 +3466,7 @@ namespace mi
         rec[f] = rp[f * 64];
       const int    qz = lane >> 4;
       const double wq = prm.tab1d[24 + (lane & 3)] * prm.tab1d[24 + ((lane >> 2) & 3)] * prm.tab1d[24 + qz];
-      double       Finv[9], tau[6], tiso[6], cII, cS, M[9], detJ;
-      neo_hooke_from_F<3>(rec, det3x3(rec), rec[9], rec[10], prm.mu, prm.kappa, Finv, tau, tiso, cII, cS);
-      if constexpr (BOX)
-        {
-          const double *__restrict__ cb = prm.cellbox + cell * 4;
-          const double rx = cb[0], ry = cb[1], rz = cb[2];
-          detJ            = cb[3];
-#pragma unroll
-          for (int k = 0; k < 3; ++k)
-            {
-              M[k]     = rx * Finv[k];
-              M[3 + k] = ry * Finv[3 + k];
-              M[6 + k] = rz * Finv[6 + k];
-            }
-        }
-      else
-        {
-          const double *__restrict__ cv = prm.cverts + cell * 24;
-          double verts[24], Jm[9], Ji[9];
-          const double xiq[3] = {prm.tab1d[28 + (lane & 3)], prm.tab1d[28 + ((lane >> 2) & 3)], prm.tab1d[28 + qz]};
-#pragma unroll
-          for (int k = 0; k < 24; ++k)
-            verts[k] = cv[k];
-          q1_jacobian<3>(verts, xiq, Jm);
-          detJ = det3x3(Jm);
-          inv3x3(Jm, detJ, Ji);
-#pragma unroll
-          for (int i = 0; i < 3; ++i)
-#pragma unroll
-            for (int j = 0; j < 3; ++j)
-              M[i * 3 + j] = Ji[i * 3 + 0] * Finv[0 * 3 + j] + Ji[i * 3 + 1] * Finv[1 * 3 + j] + Ji[i * 3 + 2] * Finv[2 * 3 + j];
-        }
-      const double w  = detJ * wq;
-      const double pv = tau[0] - tiso[0]; // kappa/2 (J^2 - 1)
-      double      *o  = sF + (lane >> 5) * DG_HALF + (lane & 31) * DG_NF;
-#pragma unroll
-      for (int k = 0; k < 9; ++k)
-        o[k] = M[k];
-#pragma unroll
-      for (int k = 0; k < 6; ++k)
-        o[9 + k] = tau[k];
-      o[15] = 0.5 * w * (cII + 0.5 * cS + (4.0 / 3.0) * pv);
-      o[16] = (2.0 / 3.0) * w;
-      o[17] = 0.5 * cS * w;
-      o[18] = w;
-      o[19] = prm.mass * w;
+      MF_DIAG_POINT(BOX, j_, i_, prm.tab1d + 28, lane & 3, (lane >> 2) & 3, qz, true, sF + (lane >> 5) * DG_HALF + (lane & 31) * DG_NF)
     }
     __syncthreads();
     // ---- stage 2: lane = (a, h)
@@ -3445,24 +3502,7 @@ namespace mi
             {
               const double *__restrict__ f = fb + (z * 16 + qy * 4 + qx) * DG_NF;
               const double d0 = Dx[qx] * syz, d1 = Sx[qx] * dyz, d2 = Sx[qx] * sdz, N = Sx[qx] * syz;
-              double       g[3], t[3], v[3];
-#pragma unroll
-              for (int j = 0; j < 3; ++j)
-                g[j] = fma(d2, f[6 + j], fma(d1, f[3 + j], d0 * f[j]));
-              sym_mul(f + 9, g, t);
-              const double gg = fma(g[2], g[2], fma(g[1], g[1], g[0] * g[0]));
-              const double gt = fma(g[2], t[2], fma(g[1], t[1], g[0] * t[0]));
-              const double dd = fma(f[19] * N, N, fma(f[18], gt, f[17] * gg));
-#pragma unroll
-              for (int j = 0; j < 3; ++j)
-                v[j] = fma(-f[16], t[j], f[15] * g[j]);
-              Kiso += dd;
-              K[0] = fma(g[0], v[0], K[0]);
-              K[1] = fma(g[1], v[1], K[1]);
-              K[2] = fma(g[2], v[2], K[2]);
-              K[3] = fma(g[0], v[1], fma(v[0], g[1], K[3]));
-              K[4] = fma(g[0], v[2], fma(v[0], g[2], K[4]));
-              K[5] = fma(g[1], v[2], fma(v[1], g[2], K[5]));
+              MF_DIAG_ACCUMULATE
             }
         }
 #pragma unroll
@@ -3554,15 +3594,16 @@ namespace mi
   // synchronises, then the outputs go on top of them; X = the 81 gathered values):
   //   E12  item (c,k,qx): x-line values of plane (c,k) -> B_DS / B_SD / B_SS [c,k][qy][qx]         27 + 18 multiply-adds
   //   E3   item = point:  H[c][l] = d x_c / d xi_l, V[c] = x_c                                      36
-  //   point (mf_spmv's: neo_hooke_from_F on the 27-point record, Q = JxW S M^T, mass)               ~150
+  //   point (neo_hooke_from_F on the 27-point record, MF_M, MF_POINT_ALGEBRA: Q = JxW S M^T, mass)  ~150
   //   I3   item (c,qy,qx): contract qz -> C_DS / C_SD / C_SS [c][k][qy][qx]                         36
   //   I2   item (c,k,qx):  contract qy -> E_D / E_S [c,k][j][qx]                                    27
-  //   I1   item (c,k,j):   contract qx -> the 81 results into the cell's slots (as mf_spmv)         18
-  // mf_records27 runs E12 + E3 on u + du and stores F, J^(-2/3), 1/J of the 27 points: [cell][11][27].
+  //   I1   item (c,k,j):   contract qx -> the 81 results into the cell's slots (MfParams::dst)      18
+  // mf_records27 runs E12 + E3 on u + du and stores F, J^(-2/3), 1/J of the 27 points (MF_RECORD_TAIL): [cell][11][27].
+  // Geometry: mf_geometry.
 #ifndef MF27_OCC
 #define MF27_OCC 5 // waves per SIMD of mf_spmv27 on box meshes: 96 VGPRs with one spilled double (0.196 -> 0.190 ms); 6 spills 76 bytes
 #endif
-#ifndef MF27_ABL
+#if defined(MI_EXPERIMENTS) && !defined(MF27_ABL) // (experiments build only: the release kernel holds none of these branches)
 #define MF27_ABL 0 // timing-only ablations (wrong results): 2 no result stores, 4 every cell reads the records of cell 0 / 1, 8 ... gathers their x
 #endif
   constexpr int Q27 = 27, H27 = 336; // points per cell; doubles of LDS per half-wave (R = 324, padded: the halves 16 banks apart; the
@@ -3633,34 +3674,6 @@ namespace mi
       }
     __syncthreads(); // B is consumed
   }
-  // geometry of the cell at point (qx, qy, qz) of the 27-point rule: Ji = Jinv (row-major), detJ
-  template <bool BOX>
-  __device__ __forceinline__ void mf27_geometry(const MfParams &prm, const int64_t cell, const int it, double Ji[9], double &detJ)
-  {
-    if constexpr (BOX)
-      {
-        const double *__restrict__ cb = prm.cellbox + cell * 4;
-#pragma unroll
-        for (int k = 0; k < 9; ++k)
-          Ji[k] = 0.0;
-        Ji[0] = cb[0], Ji[4] = cb[1], Ji[8] = cb[2];
-        detJ  = cb[3];
-      }
-    else
-      {
-        const double *__restrict__ cv = prm.cverts + cell * 24;
-        const int    qz = it / 9, qy = (it - 9 * qz) / 3, qx = it - 9 * qz - 3 * qy;
-        const double xiq[3] = {prm.tab27[21 + qx], prm.tab27[21 + qy], prm.tab27[21 + qz]};
-        double       verts[24], Jm[9];
-#pragma unroll
-        for (int k = 0; k < 24; ++k)
-          verts[k] = cv[k];
-        q1_jacobian<3>(verts, xiq, Jm);
-        detJ = det3x3(Jm);
-        inv3x3(Jm, detJ, Ji);
-      }
-  }
-
   template <bool BOX, bool LAT>
   __global__ __launch_bounds__(64, 4) void mf_records27(MfParams prm, const double *__restrict__ u, const double *__restrict__ du,
                                                         double *__restrict__ rec27)
@@ -3696,32 +3709,12 @@ namespace mi
     mf27_gradients(S27, D27, prm.tab27, R, X, it, act, H, V);
     if (!act)
       return;
-    double Ji[9], detJ, gu[9], F[9];
-    mf27_geometry<BOX>(prm, cell, it, Ji, detJ);
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-      for (int j = 0; j < 3; ++j)
-        gu[i * 3 + j] = H[i][0] * Ji[0 * 3 + j] + H[i][1] * Ji[1 * 3 + j] + H[i][2] * Ji[2 * 3 + j];
-#pragma unroll
-    for (int k = 0; k < 9; ++k)
-      F[k] = gu[k];
-    F[0] += 1.0, F[4] += 1.0, F[8] += 1.0;
-    double J = det3x3(F);
+    const int qz = it / 9, qy = (it - 9 * qz) / 3, qx = it - 9 * qz - 3 * qy;
+    double Ji[9], detJ;
+    mf_geometry<BOX>(prm, cell, prm.tab27 + 21, qx, qy, qz, Ji, detJ);
     // (the assembly reports det F <= 0 at ITS 64 points, nonlinear_elasticity.cc:935; a point of this rule that folds where
     // none of those does takes the undeformed state: the smoother's operator stays finite and positive definite)
-    const bool folded = !(J > 0.0);
-#pragma unroll
-    for (int k = 0; k < 9; ++k)
-      F[k] = folded ? (k % 4 == 0 ? 1.0 : 0.0) : F[k];
-    J = folded ? 1.0 : J;
-    const double rJ = 1.0 / J, Jm = 1.0 / (cbrt(J) * cbrt(J));
-    double *__restrict__ g = rec27 + cell * int64_t(MF_NREC * Q27) + it;
-#pragma unroll
-    for (int k = 0; k < 9; ++k)
-      g[k * Q27] = F[k];
-    g[9 * Q27]  = Jm;
-    g[10 * Q27] = rJ;
+    MF_RECORD_TAIL(true, true, rec27 + cell * int64_t(MF_NREC * Q27) + it, Q27)
   }
 
   template <bool BOX, bool LAT>
@@ -3749,6 +3742,11 @@ namespace mi
               }
           cell = int64_t(p0) + (l - b);
         }
+#ifdef MI_EXPERIMENTS // the cell whose x is gathered, the cell whose records are read: see MF27_ABL
+    const int64_t xcell = (MF27_ABL & 8) ? int64_t(cw) : cell, rcell = (MF27_ABL & 4) ? int64_t(cw) : cell;
+#else
+    const int64_t xcell = cell, rcell = cell;
+#endif
     constexpr bool act = true;
     double *const R = s_lds + cw * H27, *const X = R + 243;
     // gather x (constrained entries masked) and this lane's record
@@ -3763,7 +3761,7 @@ namespace mi
         int32_t node;
         if constexpr (LAT)
           {
-            const int32_t node0 = lattice_node0(prm.lat, (MF27_ABL & 8) ? int64_t(cw) : cell);
+            const int32_t node0 = lattice_node0(prm.lat, xcell);
             const int     k9 = it / 9, r9 = it - 9 * k9, j3 = r9 / 3, i3 = r9 - 3 * j3;
             node               = node0 + i3 + j3 * prm.lat.nn0 + k9 * prm.lat.nn01;
           }
@@ -3773,7 +3771,7 @@ namespace mi
 #pragma unroll
         for (int c = 0; c < 3; ++c)
           X[c * Q27 + it] = ((cm >> c) & 1) ? 0.0 : prm.x[int64_t(node) * 3 + c];
-        const double *__restrict__ rp = prm.qrec27 + ((MF27_ABL & 4) ? int64_t(cw) : cell) * int64_t(MF_NREC * Q27) + it;
+        const double *__restrict__ rp = prm.qrec27 + rcell * int64_t(MF_NREC * Q27) + it;
 #pragma unroll
         for (int f = 0; f < MF_NREC; ++f)
           rec[f] = __builtin_nontemporal_load(&rp[f * Q27]);
@@ -3787,42 +3785,23 @@ namespace mi
     __syncthreads();
     double H[3][3], V[3];
     mf27_gradients(S27, D27, prm.tab27, R, X, it, act, H, V);
-    // ---- point stage: Q = JxW S M^T (as mf_spmv), 12 numbers per point on top of B
+    // ---- point stage: Q = JxW S M^T (MF_POINT_ALGEBRA), 12 numbers per point on top of B
     {
       const int    qz = it / 9, qy = (it - 9 * qz) / 3, qx = it - 9 * qz - 3 * qy;
       const double wq = act ? prm.tab27[18 + qx] * prm.tab27[18 + qy] * prm.tab27[18 + qz] : 0.0;
       double       Finv[9], tau[6], tiso[6], cII, cS, Ji[9], detJ = 1.0, M[9];
       neo_hooke_from_F<3>(rec, det3x3(rec), rec[9], rec[10], prm.mu, prm.kappa, Finv, tau, tiso, cII, cS);
       if (act)
-        mf27_geometry<BOX>(prm, cell, it, Ji, detJ);
+        mf_geometry<BOX>(prm, cell, prm.tab27 + 21, qx, qy, qz, Ji, detJ);
       else
         {
 #pragma unroll
           for (int k = 0; k < 9; ++k)
             Ji[k] = 0.0;
         }
-#pragma unroll
-      for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j)
-          M[i * 3 + j] = BOX ? Ji[i * 4] * Finv[i * 3 + j] :
-                               Ji[i * 3 + 0] * Finv[0 * 3 + j] + Ji[i * 3 + 1] * Finv[1 * 3 + j] + Ji[i * 3 + 2] * Finv[2 * 3 + j];
+      MF_M(BOX, i_, j_)
       const double w = detJ * wq, wcII = w * cII, cs2 = 0.5 * cS;
-      double       h[3][3];
-#pragma unroll
-      for (int j = 0; j < 3; ++j)
-#pragma unroll
-        for (int k = 0; k < 3; ++k)
-          h[j][k] = H[j][0] * M[k] + H[j][1] * M[3 + k] + H[j][2] * M[6 + k];
-      const double pv  = (tau[0] + tau[1] + tau[2]) * (1.0 / 3.0);
-      const double ti0 = tau[0] - pv, ti1 = tau[1] - pv, ti2 = tau[2] - pv;
-      const double trh = h[0][0] + h[1][1] + h[2][2];
-      const double th  = ti0 * h[0][0] + ti1 * h[1][1] + ti2 * h[2][2] + tau[3] * (h[0][1] + h[1][0]) + tau[4] * (h[0][2] + h[2][0]) +
-                        tau[5] * (h[1][2] + h[2][1]);
-      const double aI = wcII * trh - (2.0 / 3.0) * w * th;
-      const double m3 = -(2.0 / 3.0) * trh;
-      const double Tt[3][3] = {{tau[0], tau[3], tau[4]}, {tau[3], tau[1], tau[5]}, {tau[4], tau[5], tau[2]}};
-      const double Ti[3][3] = {{ti0, tau[3], tau[4]}, {tau[3], ti1, tau[5]}, {tau[4], tau[5], ti2}};
+      MF_POINT_ALGEBRA(double)
       const double wm       = prm.mass * w;
       if (act)
 #pragma unroll
@@ -3831,13 +3810,10 @@ namespace mi
             double Sm[3];
 #pragma unroll
             for (int j = 0; j < 3; ++j)
-              {
-                const double v = m3 * Ti[i][j] + cs2 * (h[i][j] + h[j][i]) + h[i][0] * Tt[0][j] + h[i][1] * Tt[1][j] + h[i][2] * Tt[2][j];
-                Sm[j]          = w * v + (i == j ? aI : 0.0);
-              }
+                Sm[j] = MF_POINT_SM(double, i, j);
 #pragma unroll
             for (int l = 0; l < 3; ++l)
-              R[(i * 4 + l) * Q27 + it] = Sm[0] * M[l * 3] + Sm[1] * M[l * 3 + 1] + Sm[2] * M[l * 3 + 2];
+              R[(i * 4 + l) * Q27 + it] = MF_POINT_Q(Sm, l);
             R[(i * 4 + 3) * Q27 + it] = wm * V[i];
           }
     }
@@ -3924,7 +3900,9 @@ namespace mi
                 yv = fma(D27[qx][i], ed[qx], yv);
                 yv = fma(S27[qx][i], es[qx], yv);
               }
+#ifdef MI_EXPERIMENTS // (MF27_ABL & 2: the store stays in the code, never taken)
             if (!(MF27_ABL & 2) || yv == -1.2345678e30)
+#endif
               prm.yc[int64_t(ydst[i]) * 3 + lc] = yv;
           }
       }
@@ -3940,44 +3918,17 @@ namespace mi
   //   E1  item (c,k,j):   x-line -> A_S / A_D [c,k,j][qx]                              48 items, 40 multiply-adds
   //   E2  item (c,k,qx):  contract j -> B_DS / B_SD / B_SS [c,k][qy][qx]               60 items, 60
   //   E3  item = point:   contract k -> H[c][l] = d x_c / d xi_l, V[c] = x_c           125 items, 48
-  //   point (mf_spmv's algebra: neo_hooke_from_F on the record, Q = JxW S M^T, mass)   125 items
+  //   point (neo_hooke_from_F on the record, MF_M, MF_POINT_ALGEBRA: Q = JxW S M^T, mass) 125 items
   //   I3  item (c,qy,qx): contract qz -> C_DS / C_SD / C_SS [c,k][qy][qx]              75 items, 80
   //   I2  item (c,k,qx):  contract qy -> E_D / E_S [c,k,j][qx]                         60 items, 60
   //   I1  item (c,k,j):   contract qx -> the 192 results into the cell's slots         48 items, 40
   // LDS: two regions used in turn, R0 (1536 doubles: A, Q, E) and R1 (900: X, B, C) -- 19.5 kB, 8 workgroups per CU.
-  // Constrained dofs as mf_spmv: x masked on the way in; the gathers give their rows diag(K) x from the diagonal blocks.
+  // Constrained dofs: x masked on the way in; the gathers give their rows diag(K) x from the diagonal blocks.
+  // Geometry: mf_geometry; records: MF_RECORD_TAIL; diagonal blocks: MF_DIAG_POINT, MF_DIAG_ACCUMULATE.
   constexpr int MFQ3_NPC = 64, MFQ3_NQ = 125, MFQ3_QS = MF_Q3_QS, MFQ3_NT = 128;
   constexpr int MFQ3_R0 = 12 * MFQ3_QS, MFQ3_R1 = 900;
   // 1D tables of the assembly's Q3 rule (Tables1D(3, 5).packed()): N1[5][4] at 0, dN1[5][4] at 20, qw[5] at 40, qx[5] at 45
   constexpr int MFQ3_TD = 20, MFQ3_TW = 40, MFQ3_TX = 45;
-
-  // geometry at point (qx, qy, qz): Ji = Jinv (row-major), detJ
-  template <bool BOX>
-  __device__ __forceinline__ void mfq3_geometry(const MfParams &prm, const int64_t cell, const int qx, const int qy, const int qz,
-                                                double Ji[9], double &detJ)
-  {
-    if constexpr (BOX)
-      {
-        const double *__restrict__ cb = prm.cellbox + cell * 4;
-#pragma unroll
-        for (int k = 0; k < 9; ++k)
-          Ji[k] = 0.0;
-        Ji[0] = cb[0], Ji[4] = cb[1], Ji[8] = cb[2];
-        detJ  = cb[3];
-      }
-    else
-      {
-        const double *__restrict__ cv = prm.cverts + cell * 24;
-        const double xiq[3] = {prm.tab1d[MFQ3_TX + qx], prm.tab1d[MFQ3_TX + qy], prm.tab1d[MFQ3_TX + qz]};
-        double       verts[24], Jm[9];
-#pragma unroll
-        for (int k = 0; k < 24; ++k)
-          verts[k] = cv[k];
-        q1_jacobian<3>(verts, xiq, Jm);
-        detJ = det3x3(Jm);
-        inv3x3(Jm, detJ, Ji);
-      }
-  }
 
   // E1 + E2 + E3: the 192 gathered values X[c*64 + a] (a = (k*4+j)*4+i, in R1) -> H, V at point `it`.  A goes to R0, B to R1
   // over X.  Ends with a barrier: R0 and R1 are free.
@@ -4072,25 +4023,10 @@ namespace mi
     double H[3][3], V[3];
     mfq3_gradients(prm.tab1d, sT, R0, R1, t, it, H, V);
     const int qz = it / 25, qy = (it - 25 * qz) / 5, qx = it - 25 * qz - 5 * qy;
-    double    Ji[9], detJ, F[9];
-    mfq3_geometry<BOX>(prm, cell, qx, qy, qz, Ji, detJ);
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-      for (int j = 0; j < 3; ++j)
-        F[i * 3 + j] = H[i][0] * Ji[0 * 3 + j] + H[i][1] * Ji[1 * 3 + j] + H[i][2] * Ji[2 * 3 + j];
-    F[0] += 1.0, F[4] += 1.0, F[8] += 1.0;
+    double    Ji[9], detJ;
+    mf_geometry<BOX>(prm, cell, prm.tab1d + MFQ3_TX, qx, qy, qz, Ji, detJ);
     // (det F <= 0 is reported by the residual pass at these same points, nonlinear_elasticity.cc:935)
-    const double J = det3x3(F), rJ = 1.0 / J, Jm = 1.0 / (cbrt(J) * cbrt(J));
-    if (t < MFQ3_NQ)
-      {
-        double *__restrict__ g = rec + cell * int64_t(MF_NREC * MFQ3_QS) + t;
-#pragma unroll
-        for (int k = 0; k < 9; ++k)
-          g[k * MFQ3_QS] = F[k];
-        g[9 * MFQ3_QS]  = Jm;
-        g[10 * MFQ3_QS] = rJ;
-      }
+    MF_RECORD_TAIL(false, t < MFQ3_NQ, rec + cell * int64_t(MF_NREC * MFQ3_QS) + t, MFQ3_QS)
   }
 
   template <bool BOX>
@@ -4121,35 +4057,16 @@ namespace mi
     __syncthreads();
     double H[3][3], V[3];
     mfq3_gradients(prm.tab1d, sT, R0, R1, t, it, H, V);
-    // ---- point stage: Q = JxW S M^T (as mf_spmv), 12 numbers per point into R0: Q[(i*4+l)][q]
+    // ---- point stage: Q = JxW S M^T (MF_POINT_ALGEBRA), 12 numbers per point into R0: Q[(i*4+l)][q]
     {
       const int qz = it / 25, qy = (it - 25 * qz) / 5, qx = it - 25 * qz - 5 * qy;
       const double wq = prm.tab1d[MFQ3_TW + qx] * prm.tab1d[MFQ3_TW + qy] * prm.tab1d[MFQ3_TW + qz];
       double       Finv[9], tau[6], tiso[6], cII, cS, Ji[9], detJ, M[9];
       neo_hooke_from_F<3>(rec, det3x3(rec), rec[9], rec[10], prm.mu, prm.kappa, Finv, tau, tiso, cII, cS);
-      mfq3_geometry<BOX>(prm, cell, qx, qy, qz, Ji, detJ);
-#pragma unroll
-      for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j)
-          M[i * 3 + j] = BOX ? Ji[i * 4] * Finv[i * 3 + j] :
-                               Ji[i * 3 + 0] * Finv[0 * 3 + j] + Ji[i * 3 + 1] * Finv[1 * 3 + j] + Ji[i * 3 + 2] * Finv[2 * 3 + j];
+      mf_geometry<BOX>(prm, cell, prm.tab1d + MFQ3_TX, qx, qy, qz, Ji, detJ);
+      MF_M(BOX, i_, j_)
       const double w = detJ * wq, wcII = w * cII, cs2 = 0.5 * cS;
-      double       h[3][3];
-#pragma unroll
-      for (int j = 0; j < 3; ++j)
-#pragma unroll
-        for (int k = 0; k < 3; ++k)
-          h[j][k] = H[j][0] * M[k] + H[j][1] * M[3 + k] + H[j][2] * M[6 + k];
-      const double pv  = (tau[0] + tau[1] + tau[2]) * (1.0 / 3.0);
-      const double ti0 = tau[0] - pv, ti1 = tau[1] - pv, ti2 = tau[2] - pv;
-      const double trh = h[0][0] + h[1][1] + h[2][2];
-      const double th  = ti0 * h[0][0] + ti1 * h[1][1] + ti2 * h[2][2] + tau[3] * (h[0][1] + h[1][0]) + tau[4] * (h[0][2] + h[2][0]) +
-                        tau[5] * (h[1][2] + h[2][1]);
-      const double aI = wcII * trh - (2.0 / 3.0) * w * th;
-      const double m3 = -(2.0 / 3.0) * trh;
-      const double Tt[3][3] = {{tau[0], tau[3], tau[4]}, {tau[3], tau[1], tau[5]}, {tau[4], tau[5], tau[2]}};
-      const double Ti[3][3] = {{ti0, tau[3], tau[4]}, {tau[3], ti1, tau[5]}, {tau[4], tau[5], ti2}};
+      MF_POINT_ALGEBRA(double)
       const double wm       = prm.mass * w;
 #pragma unroll
       for (int i = 0; i < 3; ++i)
@@ -4157,14 +4074,11 @@ namespace mi
           double Sm[3];
 #pragma unroll
           for (int j = 0; j < 3; ++j)
-            {
-              const double v = m3 * Ti[i][j] + cs2 * (h[i][j] + h[j][i]) + h[i][0] * Tt[0][j] + h[i][1] * Tt[1][j] + h[i][2] * Tt[2][j];
-              Sm[j]          = w * v + (i == j ? aI : 0.0);
-            }
+              Sm[j] = MF_POINT_SM(double, i, j);
           // (threads 125-127 write the padding entries 125-127 of every row, which nobody reads)
 #pragma unroll
           for (int l = 0; l < 3; ++l)
-            R0[(i * 4 + l) * MFQ3_QS + t] = Sm[0] * M[l * 3] + Sm[1] * M[l * 3 + 1] + Sm[2] * M[l * 3 + 2];
+            R0[(i * 4 + l) * MFQ3_QS + t] = MF_POINT_Q(Sm, l);
           R0[(i * 4 + 3) * MFQ3_QS + t] = wm * V[i];
         }
     }
@@ -4285,32 +4199,7 @@ namespace mi
         rec[f] = rp[f * MFQ3_QS];
       const int    qz = it / 25, qy = (it - 25 * qz) / 5, qx = it - 25 * qz - 5 * qy;
       const double wq = prm.tab1d[MFQ3_TW + qx] * prm.tab1d[MFQ3_TW + qy] * prm.tab1d[MFQ3_TW + qz];
-      double       Finv[9], tau[6], tiso[6], cII, cS, Ji[9], detJ, M[9];
-      neo_hooke_from_F<3>(rec, det3x3(rec), rec[9], rec[10], prm.mu, prm.kappa, Finv, tau, tiso, cII, cS);
-      mfq3_geometry<BOX>(prm, cell, qx, qy, qz, Ji, detJ);
-#pragma unroll
-      for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j)
-          M[i * 3 + j] = BOX ? Ji[i * 4] * Finv[i * 3 + j] :
-                               Ji[i * 3 + 0] * Finv[0 * 3 + j] + Ji[i * 3 + 1] * Finv[1 * 3 + j] + Ji[i * 3 + 2] * Finv[2 * 3 + j];
-      const double w  = detJ * wq;
-      const double pv = tau[0] - tiso[0]; // kappa/2 (J^2 - 1)
-      if (t < MFQ3_NQ)
-        {
-          double *o = sF + t * DGQ3_NF;
-#pragma unroll
-          for (int k = 0; k < 9; ++k)
-            o[k] = M[k];
-#pragma unroll
-          for (int k = 0; k < 6; ++k)
-            o[9 + k] = tau[k];
-          o[15] = 0.5 * w * (cII + 0.5 * cS + (4.0 / 3.0) * pv);
-          o[16] = (2.0 / 3.0) * w;
-          o[17] = 0.5 * cS * w;
-          o[18] = w;
-          o[19] = prm.mass * w;
-        }
+      MF_DIAG_POINT(BOX, i_, j_, prm.tab1d + MFQ3_TX, qx, qy, qz, t < MFQ3_NQ, sF + t * DGQ3_NF)
     }
     __syncthreads();
     // ---- stage 2: thread = (a, h); the lane's rows of the x / y tables in registers, the z rows per plane from LDS
@@ -4340,24 +4229,7 @@ namespace mi
               {
                 const double *__restrict__ f = sF + (z * 25 + qy * 5 + qx) * DGQ3_NF;
                 const double d0 = Dx[qx] * syz, d1 = Sx[qx] * dyz, d2 = Sx[qx] * sdz, N = Sx[qx] * syz;
-                double       g[3], tg[3], v[3];
-#pragma unroll
-                for (int j = 0; j < 3; ++j)
-                  g[j] = fma(d2, f[6 + j], fma(d1, f[3 + j], d0 * f[j]));
-                sym_mul(f + 9, g, tg);
-                const double gg = fma(g[2], g[2], fma(g[1], g[1], g[0] * g[0]));
-                const double gt = fma(g[2], tg[2], fma(g[1], tg[1], g[0] * tg[0]));
-                const double dd = fma(f[19] * N, N, fma(f[18], gt, f[17] * gg));
-#pragma unroll
-                for (int j = 0; j < 3; ++j)
-                  v[j] = fma(-f[16], tg[j], f[15] * g[j]);
-                Kiso += dd;
-                K[0] = fma(g[0], v[0], K[0]);
-                K[1] = fma(g[1], v[1], K[1]);
-                K[2] = fma(g[2], v[2], K[2]);
-                K[3] = fma(g[0], v[1], fma(v[0], g[1], K[3]));
-                K[4] = fma(g[0], v[2], fma(v[0], g[2], K[4]));
-                K[5] = fma(g[1], v[2], fma(v[1], g[2], K[5]));
+                MF_DIAG_ACCUMULATE
               }
           }
       }
@@ -4378,6 +4250,14 @@ namespace mi
           o[e] = K[e] + sR[a * 6 + e];
       }
   }
+  // (the last matrix-free kernel: the shared text ends here)
+#undef MF_RECORD_TAIL
+#undef MF_M
+#undef MF_POINT_ALGEBRA
+#undef MF_POINT_SM
+#undef MF_POINT_Q
+#undef MF_DIAG_POINT
+#undef MF_DIAG_ACCUMULATE
 
   // system_rhs from the cells' residual slots (point pass in one launch): rhs = 0 - r_1 - r_2 - ... in slot order, the
   // subtractions of the colour-by-colour update in their order; constrained rows get no rhs (:769-773).  One thread per dof.
