@@ -717,6 +717,32 @@ namespace mi
       *cz = 2 * int32_t(rz) + R.pz; // the cell's layer along the last lattice direction
     return R.base + int32_t(rx) * L.sx + int32_t(ry) * L.sy + int32_t(rz) * L.sz;
   }
+  // the same in two parts, for a wave with two uniform cells (mf27_node): both rows are asked for before either is used, so
+  // the two scalar loads may travel together (the compiler at hand still waits for the first before it issues the second).
+  // (Kept beside lattice_node0, not under it: composing lattice_node0 of the parts gives the kernels that call it another
+  // instruction schedule.)
+  // the colour of position p, and where that colour begins
+  __device__ __forceinline__ int lattice_colour(const CellLattice &L, const int32_t p, int32_t &begin)
+  {
+    int col = 0;
+#pragma unroll
+    for (int c = 1; c < 8; ++c)
+      col += (p >= L.begin[c]) ? 1 : 0; // empty trailing colours begin at ncells
+    begin = L.begin[0];
+#pragma unroll
+    for (int c = 1; c < 8; ++c)
+      begin = (p >= L.begin[c]) ? L.begin[c] : begin;
+    return col;
+  }
+  // first node of the r-th cell of the colour with row R
+  __device__ __forceinline__ int32_t lattice_row_node0(const CellLattice &L, const CellLatticeRow &R, const uint32_t r)
+  {
+    const uint32_t rz  = uint32_t((uint64_t(r) * R.magic_mxy) >> 42);
+    const uint32_t rem = r - rz * uint32_t(R.mxy);
+    const uint32_t ry  = uint32_t((uint64_t(rem) * R.magic_mx) >> 42);
+    const uint32_t rx  = rem - ry * uint32_t(R.mx);
+    return R.base + int32_t(rx) * L.sx + int32_t(ry) * L.sy + int32_t(rz) * L.sz;
+  }
 
   // ------------------------------------------------------------------ 3D Q2 cell assembly, sum factorised (default)
   // Same element tangent, residual and scatter as assemble_cells, a third of its arithmetic.  With g_a = M^T grad_xi N_a,
@@ -2720,24 +2746,32 @@ namespace mi
   //   MF_POINT_Q(Sm, l)   M[9], its row Sm[3] of JxW S                       (an expression)
   //   MF_DIAG_POINT       rec[11], wq, cell, prm                             Finv, tau, tiso, cII, cS, Ji, detJ, M, w, pv; o_[20]
   //   MF_DIAG_ACCUMULATE  f[20], d0, d1, d2, N                               updates K[6], Kiso (g, tg, v, gg, gt, dd in a block)
+  // geometry of an axis-parallel box from its four numbers cb = 1/hx, 1/hy, 1/hz, hx hy hz: a cell's entry of
+  // MfParams::cellbox, or a copy of it in LDS (the 27-point kernels)
+  template <typename T>
+  __device__ __forceinline__ void mf_box_geometry(const double *__restrict__ cb, T Ji[9], T &detJ)
+  {
+#pragma unroll
+    for (int k = 0; k < 9; ++k)
+      Ji[k] = 0.0;
+    Ji[0] = cb[0], Ji[4] = cb[1], Ji[8] = cb[2];
+    detJ  = cb[3];
+  }
   // geometry of `cell` at the unit-cell point xi: Ji = Jinv (row-major), detJ.  BOX (every cell an axis-parallel box): 1/hx,
-  // 1/hy, 1/hz on the diagonal and hx hy hz from MfParams::cellbox -- uniform, scalar loads, xi is not read; otherwise the
-  // Jacobian of the trilinear map at xi as in the assembly (fp64 only)
+  // 1/hy, 1/hz on the diagonal and hx hy hz from MfParams::cellbox, xi is not read; otherwise the Jacobian of the trilinear
+  // map at xi as in the assembly (fp64 only).  The loads are scalar where `cell` is uniform (one cell per wave or per
+  // workgroup: the 64-point and the Q3 kernels).  The 27-point kernels run two cells per wave, one per half, so `cell` is a
+  // per-lane value there and these would be vector loads in the middle of the kernel: their BOX instances fetch cellbox
+  // with the wave's first batch of loads instead and call mf_box_geometry on the copy (mf27_stage_box); their general
+  // instances read cverts here, per lane
   template <bool BOX, typename T>
   __device__ __forceinline__ void mf_geometry(const MfParams &prm, const int64_t cell, const T *xi, T Ji[9], T &detJ)
   {
     if constexpr (BOX)
-      {
-        const double *__restrict__ cb = prm.cellbox + cell * 4;
-#pragma unroll
-        for (int k = 0; k < 9; ++k)
-          Ji[k] = 0.0;
-        Ji[0] = cb[0], Ji[4] = cb[1], Ji[8] = cb[2];
-        detJ  = cb[3];
-      }
+      mf_box_geometry(prm.cellbox + cell * 4, Ji, detJ);
     else
       {
-        const double *__restrict__ cv = prm.cverts + cell * 24; // uniform: scalar loads
+        const double *__restrict__ cv = prm.cverts + cell * 24; // (scalar loads where `cell` is uniform)
         T verts[24], Jm[9];
 #pragma unroll
         for (int k = 0; k < 24; ++k)
@@ -3617,24 +3651,84 @@ namespace mi
       S27[q_][a_] = (t_)[q_ * 3 + a_];                  \
       D27[q_][a_] = (t_)[9 + q_ * 3 + a_];              \
     }
-  // E12 + E3 of one half-wave: X (81 values [c][a], a = (k*3+j)*3+i) -> H, V at point `it` (lanes it < 27)
-  __device__ __forceinline__ void mf27_gradients(const double (&S27)[3][3], const double (&D27)[3][3], const double *__restrict__ tab,
-                                                 double *__restrict__ R, const double *__restrict__ X, const int it, const bool act, double H[3][3],
-                                                 double V[3])
+  // Loads.  A wave's life is mostly waiting for memory (about 560 vector instructions in 9 us), so every global load of
+  // these kernels belongs to ONE batch at the head of the wave, issued back to back and waited for once, before the first
+  // barrier; nothing is loaded behind it (general geometry: cverts, in the point stage, excepted -- and the unit-cell points
+  // of mf_records27).  (A workgroup is one wave, so the compiler drops the barriers; "the first barrier" is the gather's LDS
+  // store.)  What that takes:
+  //   - the wave's two cells, pair*2 and min(pair*2+1, count-1), are uniform, so the first nodes of both are computed with
+  //     scalar operands (their lattice rows come through the scalar cache) and the half selects: the batch of vector loads
+  //     depends on no vector load (ids from the connectivity: on that one);
+  //   - x is loaded for every node and masked by a SELECT on the constraint bits once both have arrived (a load under the mask
+  //     waits for the mask first; a product with the mask would let a constrained entry's NaN through);
+  //   - this lane's rows of the 1D tables are part of the batch (mf27_table_rows); its quadrature weight is selected from the
+  //     three uniform weights in the point stage (see there for what the compiler makes of it);
+  //   - BOX: the cell's four numbers are fetched with the batch and parked in the half's LDS pad, from where the point stage
+  //     takes them (mf27_stage_box, MF27_BOX) -- no registers held across the gradient stages.
+  constexpr int MF27_BOX = 324; // R[MF27_BOX .. +4): 1/hx, 1/hy, 1/hz, hx hy hz of the half's cell (no stage writes R beyond 323)
+  // position of selected cell l of a launch over some layers of a slab (MfParams::sel_n > 0, as in mf_spmv): l uniform
+  __device__ __forceinline__ int64_t mf27_sel_position(const MfParams &prm, const int32_t l)
   {
-    const int ck = it / 3, qx = it - 3 * ck; // E12 item
-    // this lane's rows of the tables (row qx for the x-contraction, row qz for the z-contraction): per-lane loads -- a select
-    // over the uniform tables turns into a dynamically indexed private array, i.e. scratch
-    const int qzl = it / 9;
-    double    sx[3], dx[3], sz[3], dz[3];
+    int32_t b = prm.sel_begin[0], p0 = prm.sel_pos0[0];
+#pragma unroll
+    for (int c = 1; c < 8; ++c)
+      if (l >= prm.sel_begin[c])
+        {
+          b  = prm.sel_begin[c];
+          p0 = prm.sel_pos0[c];
+        }
+    return int64_t(p0) + (l - b);
+  }
+  // node `it` of the half's cell: by arithmetic from the two cells' first nodes (both scalar), or from the connectivity
+  template <bool LAT>
+  __device__ __forceinline__ int32_t mf27_node(const MfParams &prm, const int64_t cell0, const int64_t cell1, const int cw, const int it)
+  {
+    if constexpr (LAT)
+      {
+        const int32_t        p0 = int32_t(cell0), p1 = int32_t(cell1);
+        int32_t              b0, b1;
+        const int            c0 = lattice_colour(prm.lat, p0, b0), c1 = lattice_colour(prm.lat, p1, b1);
+        const CellLatticeRow R0 = prm.lat.rows[c0], R1 = prm.lat.rows[c1]; // (uniform: scalar loads)
+        const int32_t        n0 = lattice_row_node0(prm.lat, R0, uint32_t(p0 - b0)), n1 = lattice_row_node0(prm.lat, R1, uint32_t(p1 - b1));
+        const int            k9 = it / 9, r9 = it - 9 * k9, j3 = r9 / 3, i3 = r9 - 3 * j3;
+        return (cw ? n1 : n0) + i3 + j3 * prm.lat.nn0 + k9 * prm.lat.nn01;
+      }
+    else
+      return prm.conn[(cw ? cell1 : cell0) * Q27 + it];
+  }
+  // this lane's rows of the tables: row qx = it % 3 for the x-contraction (E12), row qz = it / 9 for the z-contraction (E3).
+  // Per-lane loads -- a select over the uniform tables turns into a dynamically indexed private array, i.e. scratch
+  __device__ __forceinline__ void mf27_table_rows(const double *__restrict__ tab, const int it, double sx[3], double dx[3], double sz[3],
+                                                  double dz[3])
+  {
+    const int qx = it - 3 * (it / 3), qzl = it / 9;
 #pragma unroll
     for (int i = 0; i < 3; ++i)
       {
-        sx[i] = tab[(act ? qx : 0) * 3 + i];
-        dx[i] = tab[9 + (act ? qx : 0) * 3 + i];
-        sz[i] = tab[(act ? qzl : 0) * 3 + i];
-        dz[i] = tab[9 + (act ? qzl : 0) * 3 + i];
+        sx[i] = tab[qx * 3 + i];
+        dx[i] = tab[9 + qx * 3 + i];
+        sz[i] = tab[qzl * 3 + i];
+        dz[i] = tab[9 + qzl * 3 + i];
       }
+  }
+  // BOX: lane il of a half loads number k = il & 3 of its cell's four and parks it at pad[k] once the batch has arrived.  Every
+  // lane does (lanes with the same k store the same value to the same place): a store by the idle lanes alone would be a
+  // branch, and the compiler moves the load into it, behind the gather and with a wait of its own
+  __device__ __forceinline__ double mf27_load_box(const MfParams &prm, const int64_t cell, const int il)
+  {
+    return prm.cellbox[cell * 4 + (il & 3)];
+  }
+  __device__ __forceinline__ void mf27_stage_box(double *__restrict__ R, const int il, const double bx)
+  {
+    R[MF27_BOX + (il & 3)] = bx;
+  }
+  // E12 + E3 of one half-wave: X (81 values [c][a], a = (k*3+j)*3+i) -> H, V at point `it` (lanes it < 27); sx, dx, sz, dz:
+  // mf27_table_rows
+  __device__ __forceinline__ void mf27_gradients(const double (&S27)[3][3], const double (&D27)[3][3], const double (&sx)[3],
+                                                 const double (&dx)[3], const double (&sz)[3], const double (&dz)[3], double *__restrict__ R,
+                                                 const double *__restrict__ X, const int it, const bool act, double H[3][3], double V[3])
+  {
+    const int ck = it / 3; // E12 item (ck, qx): the planes' x-lines, with the lane's rows sx, dx of the tables
     if (act)
       {
         double as[3], ad[3];
@@ -3681,37 +3775,45 @@ namespace mi
     __shared__ double s_lds[2 * H27];
     // (idle lanes -- five per half, and the second half of the last wave of an odd cell count -- MIRROR work item 26 / the last
     // cell: they compute and store the same numbers to the same places as the lane they mirror, so no stage needs a branch)
-    const int     lane = threadIdx.x, cw = lane >> 5, it = (lane & 31) < Q27 ? (lane & 31) : Q27 - 1;
+    const int     lane = threadIdx.x, cw = lane >> 5, il = lane & 31, it = il < Q27 ? il : Q27 - 1;
     const int64_t pair = int64_t(blockIdx.x & 7) * prm.xcd_chunk + (blockIdx.x >> 3);
     if (pair * 2 >= prm.count)
       return;
-    const int64_t cell = pair * 2 + cw < prm.count ? pair * 2 + cw : int64_t(prm.count) - 1;
+    const int64_t cell0 = pair * 2, cell1 = pair * 2 + 1 < prm.count ? pair * 2 + 1 : int64_t(prm.count) - 1; // uniform
+    const int64_t cell = cw ? cell1 : cell0;
     constexpr bool act = true;
     double *const R = s_lds + cw * H27, *const X = R + 243;
     MF27_TABLES(prm.tab27)
-    if (act)
-      {
-        int32_t node;
-        if constexpr (LAT)
-          {
-            const int32_t node0 = lattice_node0(prm.lat, cell);
-            const int     k9 = it / 9, r9 = it - 9 * k9, j3 = r9 / 3, i3 = r9 - 3 * j3;
-            node               = node0 + i3 + j3 * prm.lat.nn0 + k9 * prm.lat.nn01;
-          }
-        else
-          node = prm.conn[cell * Q27 + it];
+    // the batch of loads (see "Loads" above): u and du of this lane's node, its table rows, BOX: the cell's box
+    const int32_t node = mf27_node<LAT>(prm, cell0, cell1, cw, it);
+    double        uv[3], dv[3], sx[3], dx[3], sz[3], dz[3], bx = 0.0;
 #pragma unroll
-        for (int c = 0; c < 3; ++c)
-          X[c * Q27 + it] = u[int64_t(node) * 3 + c] + du[int64_t(node) * 3 + c]; // get_total_solution, :580-588
-      }
+    for (int c = 0; c < 3; ++c)
+      uv[c] = u[int64_t(node) * 3 + c];
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+      dv[c] = du[int64_t(node) * 3 + c];
+    if constexpr (BOX)
+      bx = mf27_load_box(prm, cell, il);
+    mf27_table_rows(prm.tab27, it, sx, dx, sz, dz);
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+      X[c * Q27 + it] = uv[c] + dv[c]; // get_total_solution, :580-588
+    if constexpr (BOX)
+      mf27_stage_box(R, il, bx);
     __syncthreads();
     double H[3][3], V[3];
-    mf27_gradients(S27, D27, prm.tab27, R, X, it, act, H, V);
+    mf27_gradients(S27, D27, sx, dx, sz, dz, R, X, it, act, H, V);
     if (!act)
       return;
-    const int qz = it / 9, qy = (it - 9 * qz) / 3, qx = it - 9 * qz - 3 * qy;
     double Ji[9], detJ;
-    mf_geometry<BOX>(prm, cell, prm.tab27 + 21, qx, qy, qz, Ji, detJ);
+    if constexpr (BOX)
+      mf_box_geometry(R + MF27_BOX, Ji, detJ);
+    else
+      {
+        const int qz = it / 9, qy = (it - 9 * qz) / 3, qx = it - 9 * qz - 3 * qy;
+        mf_geometry<false>(prm, cell, prm.tab27 + 21, qx, qy, qz, Ji, detJ);
+      }
     // (the assembly reports det F <= 0 at ITS 64 points, nonlinear_elasticity.cc:935; a point of this rule that folds where
     // none of those does takes the undeformed state: the smoother's operator stays finite and positive definite)
     MF_RECORD_TAIL(true, true, rec27 + cell * int64_t(MF_NREC * Q27) + it, Q27)
@@ -3723,82 +3825,82 @@ namespace mi
     __shared__ double s_lds[2 * H27];
     // (idle lanes -- five per half, and the second half of the last wave of an odd cell count -- MIRROR work item 26 / the last
     // cell: they compute and store the same numbers to the same places as the lane they mirror, so no stage needs a branch)
-    const int     lane = threadIdx.x, cw = lane >> 5, it = (lane & 31) < Q27 ? (lane & 31) : Q27 - 1;
+    const int     lane = threadIdx.x, cw = lane >> 5, il = lane & 31, it = il < Q27 ? il : Q27 - 1;
     const int64_t pair = int64_t(blockIdx.x & 7) * prm.xcd_chunk + (blockIdx.x >> 3);
     if (pair * 2 >= prm.count)
       return;
-    int64_t cell = pair * 2 + cw < prm.count ? pair * 2 + cw : int64_t(prm.count) - 1;
+    int64_t cell0 = pair * 2, cell1 = pair * 2 + 1 < prm.count ? pair * 2 + 1 : int64_t(prm.count) - 1; // uniform
     if constexpr (LAT)
-      if (prm.sel_n > 0) // a launch over some layers of a slab (as mf_spmv): `cell` counts the selected cells, colour by colour
+      if (prm.sel_n > 0) // a launch over some layers of a slab (as mf_spmv): the cells count the selected cells, colour by colour
         {
-          const int32_t l = int32_t(cell);
-          int32_t       b = prm.sel_begin[0], p0 = prm.sel_pos0[0];
-#pragma unroll
-          for (int c = 1; c < 8; ++c)
-            if (l >= prm.sel_begin[c])
-              {
-                b  = prm.sel_begin[c];
-                p0 = prm.sel_pos0[c];
-              }
-          cell = int64_t(p0) + (l - b);
+          cell0 = mf27_sel_position(prm, int32_t(cell0));
+          cell1 = mf27_sel_position(prm, int32_t(cell1));
         }
-#ifdef MI_EXPERIMENTS // the cell whose x is gathered, the cell whose records are read: see MF27_ABL
-    const int64_t xcell = (MF27_ABL & 8) ? int64_t(cw) : cell, rcell = (MF27_ABL & 4) ? int64_t(cw) : cell;
+    const int64_t cell = cw ? cell1 : cell0;
+#ifdef MI_EXPERIMENTS // the cells whose x is gathered, the cell whose records are read: see MF27_ABL
+    const int64_t xcell0 = (MF27_ABL & 8) ? int64_t(0) : cell0, xcell1 = (MF27_ABL & 8) ? int64_t(1) : cell1;
+    const int64_t rcell = (MF27_ABL & 4) ? int64_t(cw) : cell;
 #else
-    const int64_t xcell = cell, rcell = cell;
+    const int64_t xcell0 = cell0, xcell1 = cell1, rcell = cell;
 #endif
     constexpr bool act = true;
     double *const R = s_lds + cw * H27, *const X = R + 243;
-    // gather x (constrained entries masked) and this lane's record
-    double rec[MF_NREC];
-#pragma unroll
-    for (int f = 0; f < MF_NREC; ++f)
-      rec[f] = 0.0;
-    rec[0] = rec[4] = rec[8] = rec[9] = rec[10] = 1.0; // (idle lanes: the identity, no NaN in flight)
-    int32_t ydst[3] = {0, 0, 0};
-    if (act)
-      {
-        int32_t node;
-        if constexpr (LAT)
-          {
-            const int32_t node0 = lattice_node0(prm.lat, xcell);
-            const int     k9 = it / 9, r9 = it - 9 * k9, j3 = r9 / 3, i3 = r9 - 3 * j3;
-            node               = node0 + i3 + j3 * prm.lat.nn0 + k9 * prm.lat.nn01;
-          }
-        else
-          node = prm.conn[cell * Q27 + it];
-        const int cm = prm.cmask[node];
-#pragma unroll
-        for (int c = 0; c < 3; ++c)
-          X[c * Q27 + it] = ((cm >> c) & 1) ? 0.0 : prm.x[int64_t(node) * 3 + c];
-        const double *__restrict__ rp = prm.qrec27 + rcell * int64_t(MF_NREC * Q27) + it;
-#pragma unroll
-        for (int f = 0; f < MF_NREC; ++f)
-          rec[f] = __builtin_nontemporal_load(&rp[f * Q27]);
-        // I1's item of this lane: line (c,k,j) = it, its three nodes i (cell-major slots: no table to read)
-        const int lkj = it - 9 * (it / 9);
-#pragma unroll
-        for (int i = 0; i < 3; ++i)
-          ydst[i] = prm.slot_inline ? int32_t(cell) * Q27 + lkj * 3 + i : prm.dst[cell * Q27 + lkj * 3 + i];
-      }
     MF27_TABLES(prm.tab27)
+    // the batch of loads (see "Loads" above): x and the constraint bits of this lane's node, BOX: the cell's box, the table rows
+    // and weights, this lane's record, the slots of its results where they are not arithmetic
+    const int32_t node = mf27_node<LAT>(prm, LAT ? xcell0 : cell0, LAT ? xcell1 : cell1, cw, it);
+    double        xv[3], sx[3], dx[3], sz[3], dz[3], bx = 0.0;
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+      xv[c] = prm.x[int64_t(node) * 3 + c];
+    const int cm = prm.cmask[node];
+    if constexpr (BOX)
+      bx = mf27_load_box(prm, cell, il);
+    mf27_table_rows(prm.tab27, it, sx, dx, sz, dz);
+    const int    qz = it / 9, qy = (it - 9 * qz) / 3, qx = it - 9 * qz - 3 * qy; // this lane's point
+    double       rec[MF_NREC];
+    {
+      const double *__restrict__ rp = prm.qrec27 + rcell * int64_t(MF_NREC * Q27) + it;
+#pragma unroll
+      for (int f = 0; f < MF_NREC; ++f)
+        rec[f] = __builtin_nontemporal_load(&rp[f * Q27]);
+    }
+    // I1's item of this lane: line (c,k,j) = it, its three nodes i (cell-major slots: no table to read)
+    int32_t   ydst[3];
+    const int lkj = it - 9 * (it / 9);
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+      ydst[i] = prm.slot_inline ? int32_t(cell) * Q27 + lkj * 3 + i : prm.dst[cell * Q27 + lkj * 3 + i];
+    // the gather: constrained entries masked by a select (never a product: they may hold anything)
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+      X[c * Q27 + it] = ((cm >> c) & 1) ? 0.0 : xv[c];
+    if constexpr (BOX)
+      mf27_stage_box(R, il, bx);
     __syncthreads();
     double H[3][3], V[3];
-    mf27_gradients(S27, D27, prm.tab27, R, X, it, act, H, V);
+    mf27_gradients(S27, D27, sx, dx, sz, dz, R, X, it, act, H, V);
     // ---- point stage: Q = JxW S M^T (MF_POINT_ALGEBRA), 12 numbers per point on top of B
     {
-      const int    qz = it / 9, qy = (it - 9 * qz) / 3, qx = it - 9 * qz - 3 * qy;
-      const double wq = act ? prm.tab27[18 + qx] * prm.tab27[18 + qy] * prm.tab27[18 + qz] : 0.0;
-      double       Finv[9], tau[6], tiso[6], cII, cS, Ji[9], detJ = 1.0, M[9];
+      // the point's weight qw[qx] qw[qy] qw[qz] (and, general geometry, its coordinates) by selection among the three uniform
+      // values of the table: no address and no value held across the gradient stages.  (The compiler at hand turns each
+      // selection into one per-lane load from a selected address, here: three 8-byte loads of one cache line that every wave
+      // reads, the only global loads left behind the batch on boxes.  Declaring the values uniform with readfirstlane makes
+      // them scalar operands, 92 registers; not measured yet -- profiles/smoother_load_batch/README.md)
+#define MF27_PICK(t_, q_) ((q_) == 0 ? (t_)[0] : (q_) == 1 ? (t_)[1] : (t_)[2])
+      const double *__restrict__ qw = prm.tab27 + 18;
+      const double wq = MF27_PICK(qw, qx) * MF27_PICK(qw, qy) * MF27_PICK(qw, qz);
+      double Finv[9], tau[6], tiso[6], cII, cS, Ji[9], detJ = 1.0, M[9];
       neo_hooke_from_F<3>(rec, det3x3(rec), rec[9], rec[10], prm.mu, prm.kappa, Finv, tau, tiso, cII, cS);
-      if (act)
-        mf_geometry<BOX>(prm, cell, prm.tab27 + 21, qx, qy, qz, Ji, detJ);
+      if constexpr (BOX)
+        mf_box_geometry(R + MF27_BOX, Ji, detJ);
       else
         {
-#pragma unroll
-          for (int k = 0; k < 9; ++k)
-            Ji[k] = 0.0;
+          const double *__restrict__ tq = prm.tab27 + 21;
+          const double xiq[3] = {MF27_PICK(tq, qx), MF27_PICK(tq, qy), MF27_PICK(tq, qz)};
+          mf_geometry<false>(prm, cell, xiq, Ji, detJ);
         }
+#undef MF27_PICK
       MF_M(BOX, i_, j_)
       const double w = detJ * wq, wcII = w * cII, cs2 = 0.5 * cS;
       MF_POINT_ALGEBRA(double)
