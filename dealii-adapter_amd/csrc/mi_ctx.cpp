@@ -224,9 +224,6 @@ namespace mi_detail
     p.qrec32  = (c->d_qrec && c->smoother_precision == 32) ? c->d_qrec32 : nullptr;
     p.cellbox = c->d_cellbox;
     p.box_geometry = c->asm_box_geometry;
-    p.from_records = c->d_qrec ? c->asm_split : 0;
-    if (p.from_records) // both kernels of the pair take the node ids by lattice arithmetic (as mf_spmv)
-      p.lat = c->lat;
     p.inverted = c->d_sc + SC_INVERTED;
     p.correct_face_F = c->correct_face_F;
     p.axmap    = 0;
@@ -3053,22 +3050,8 @@ int mi_set_tuning(mi_ctx *c, const char *key, int value)
         m->small_cg = value;
       else if (k == "halo_overlap" && (value == 0 || value == 1))
         c->team->overlap = value;
-      else if (k == "asm_variant" && value >= 0 && value <= 9)
-        {
-#ifndef MI_EXPERIMENTS
-          if (value >= 3 && value <= 8)
-            return fail(c, MI_EINVAL, "asm_variant %d is an A/B instantiation of the experiments build (make EXPERIMENTS=1)", value);
-#endif
-          m->asm_variant = value;
-        }
-      else if (k == "asm_split" && value >= 0 && value <= 2) // 3D Q2 with point records: the fused kernel (0) | point pass + tangent
-        {                                                     // from the records, all waves (1) / wave 0 (2): profiles/r06/asm_split_ab_n59.txt
-#ifndef MI_EXPERIMENTS
-          if (value != 0)
-            return fail(c, MI_EINVAL, "asm_split %d is an A/B instantiation of the experiments build (make EXPERIMENTS=1)", value);
-#endif
-          m->asm_split = value;
-        }
+      else if (k == "asm_variant" && ((value >= 0 && value <= 2) || value == 9))
+        m->asm_variant = value;
       else if (k == "mg_refresh_every" && value >= 1 && value <= 1000)
         m->mg_refresh_every = value;
       else if (k == "mg_lag" && (value == 0 || value == 1))
@@ -3343,7 +3326,7 @@ int mi_bench_assemble(mi_ctx *c, int reps, double *ms_per_assembly)
   hipEventDestroy(a);
   hipEventDestroy(b);
   *ms_per_assembly = double(ms) / std::max(1, reps);
-  if (mi::exp_env("MI_ASM_STAMPS") && !c->mf_fine && c->dim == 3 && c->degree == 2 && (c->asm_variant == 0 || (c->asm_variant >= 3 && c->asm_variant <= 8)))
+  if (mi::exp_env("MI_ASM_STAMPS") && !c->mf_fine && c->dim == 3 && c->degree == 2 && c->asm_variant == 0)
     {
       // diagnostic: where a workgroup of the sum-factorised element kernel spends its life (shader-clock stamps of one
       // tangent wave at the phase boundaries), averaged over the cells of the first colour

@@ -260,8 +260,6 @@ struct mi_ctx
   bool                  mg_force = true; // rebuild them at the next solve (set at the start of every time step)
   int                   asm_variant = 0;
   int                   asm_box_geometry = 1; // assemble_q2sf on a mesh of axis-parallel boxes: 1/h and the volume instead of the trilinear map
-  int                   asm_split = 0;   // experiments build: 3D Q2 with point records: the tangent in two kernels (1 / 2; measured
-                                         // slower than the fused kernel, profiles/r06/asm_split_ab_n59.txt)
   int                   mg_lag   = 1;    // 1: keep the coarse operators over the Newton iterations of one step
   // ... and over time steps: refreshed at the first solve of every k-th step, or before the next solve when one
   // needed a quarter (at least 2) more iterations than the first solve after the last refresh (mg_its_ref)

@@ -289,11 +289,10 @@ namespace mi
   //   phase A: per-QP kinematics/material records -> LDS (4 lanes per QP)
   //   per chunk of QC points: phase B (qp,node) records g, m, v, n -> LDS; main loop; residual
   //   epilogue: read-modify-write of the cell's blocks into the global block-CSR (colouring => race free)
-  // ABL (timing only, results wrong): 1 = no tangent scatter, 2 = no main loop and no scatter, 3 = scatter only
-  // ABL = 4 (production): RESIDUAL ONLY -- phases A/B and the residual, bit-identical with the full kernel's residual;
-  //          the tangent is neither formed nor touched.  Serves the Newton convergence check (:446-469), whose
-  //          assembly is never multiplied when the check passes.
-  template <int DIM, int P, int QSPLIT, int NT, int QC, int MINW = 1, int ABL = 0>
+  // RES_ONLY: phases A/B and the residual, bit-identical with the full kernel's residual; the tangent is neither
+  //          formed nor touched.  Serves the Newton convergence check (:446-469), whose assembly is never multiplied
+  //          when the check passes.
+  template <int DIM, int P, int QSPLIT, int NT, int QC, int MINW = 1, bool RES_ONLY = false>
   __global__ __launch_bounds__(NT, MINW) void assemble_cells(AsmParams prm)
   {
     using E = Elem<DIM, P>;
@@ -303,7 +302,7 @@ namespace mi
     static_assert(NPC * DIM <= NT, "residual needs one thread per local dof");
     // the tile grid is covered in NPASS passes of TPP tiles (one pass for every element up to 3D Q2; 3D Q3/Q4 have
     // 528 / 2016 tiles: each pass repeats the cheap phase B and accumulates its own tiles)
-    constexpr int TPP = NT / QSPLIT, NPASS = (ABL == 4) ? 1 : (E::NTILES + TPP - 1) / TPP;
+    constexpr int TPP = NT / QSPLIT, NPASS = RES_ONLY ? 1 : (E::NTILES + TPP - 1) / TPP;
 
     __shared__ double s_N1[NQ1 * NP1], s_dN1[NQ1 * NP1], s_qw[NQ1], s_qx[NQ1];
     __shared__ double s_u[NPC * 3], s_a[NPC * 3], s_verts[NV * DIM];
@@ -313,7 +312,7 @@ namespace mi
     constexpr int NDS = NPCP * RN + NDPAD;
     // one buffer for the point records and the (point, node) records: after the main loop it stages the cell's element
     // tangent for a coalesced store (3D Q2: 3402 of its 4304 doubles)
-    constexpr int NSTAGE = (DIM == 3 && P == 2 && ABL == 0) ? 9 * EBE_NBLK : 0;
+    constexpr int NSTAGE = (DIM == 3 && P == 2 && !RES_ONLY) ? 9 * EBE_NBLK : 0;
     constexpr int NBIG   = (NQ * RQ + QC * NDS > NSTAGE) ? NQ * RQ + QC * NDS : NSTAGE;
     __shared__ __attribute__((aligned(16))) double s_big[NBIG];
     double *const s_qp = s_big, *const s_nd = s_big + NQ * RQ;
@@ -443,7 +442,7 @@ namespace mi
 #pragma unroll
             for (int i = 0; i < 3; ++i)
               r[Q_FACC + i] = prm.rho * w * (acc[i] - prm.body[i]);
-            if constexpr (DIM == 3 && P == 2 && ABL == 0)
+            if constexpr (DIM == 3 && P == 2 && !RES_ONLY)
               if (prm.qrec) // the state the tangent is linearised at, for the matrix-free product (mf_spmv)
                 {
                   double *__restrict__ g = prm.qrec + cell * int64_t(MF_NREC * 64) + q;
@@ -510,7 +509,7 @@ namespace mi
         __syncthreads();
 
         // ---- main loop: accumulate the 2x2 tile over this lane's share of the chunk
-        if (active && ABL != 2 && ABL != 3 && ABL != 4)
+        if (active && !RES_ONLY)
           {
             for (int qq = qslot; qq < QC; qq += QSPLIT)
               {
@@ -586,7 +585,7 @@ namespace mi
       }
 
     // ---- reduce the QSPLIT partial tiles
-    if constexpr (ABL != 4)
+    if constexpr (!RES_ONLY)
       {
 #pragma unroll
         for (int o = 1; o < QSPLIT; o <<= 1)
@@ -609,15 +608,7 @@ namespace mi
     // ---- tangent scatter: lane `qslot` of a tile writes the blocks bl with bl % QSPLIT == qslot.
     // [DEAL.II distribute_local_to_global] constrained rows/cols are dropped, the diagonal of a constrained
     // dof receives |K_e(i,i)|.
-    if (ABL == 1 || ABL == 2 || ABL == 3)
-      {
-#pragma unroll
-        for (int b = 0; b < 4; ++b)
-#pragma unroll
-          for (int k = 0; k < DD; ++k)
-            asm volatile("" ::"v"(K[b][k]));
-      }
-    if (active && ABL != 1 && ABL != 2 && ABL != 4)
+    if (active && !RES_ONLY)
       {
         const uint16_t *__restrict__ offc = prm.off + cell * (NPC * NPC);
 #pragma unroll
@@ -681,7 +672,7 @@ namespace mi
               }
           }
       }
-    if constexpr (DIM == 3 && P == 2 && ABL == 0)
+    if constexpr (DIM == 3 && P == 2 && !RES_ONLY)
       if (prm.ke) // the staged element tangent: 3402 contiguous doubles per cell, coalesced
         {
           __syncthreads();
@@ -754,7 +745,7 @@ namespace mi
   // (tools/proto/sf_assembly.py checks algebra and decomposition against the independent mirror).
   // One workgroup of 4 waves per cell:
   //   wave 0, lane = quadrature point: u and the acceleration interpolated to the points by sum factorisation,
-  //     kinematics + material (neo_hooke_qp), the 81 coefficient fields + mu -> LDS, the point records for mf_spmv,
+  //     kinematics + material (neo_hooke_qp), the 45 coefficient fields + mu -> LDS, the point records for mf_spmv,
   //     then the residual  r_a = -sum_q (w tau M^T grad_xi N_a + N_a rho w (acc - b))  integrated by sum factorisation;
   //   waves 1-3, lane = (ij, (a1 >= b1), a2) [162 items]: for every qz: x-contraction of C along a line of 4 points
   //     (per-lane products N_a1 N_b1), y-contraction into 12 accumulators (a2 per lane, b2 unrolled; the (k==z, l==z)
@@ -772,27 +763,15 @@ namespace mi
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");                                                        \
       }                                                                                                               \
     while (0)
-  // XV (round 5; "asm_variant" 3-8 select the combinations for A/B, profiles/r05/asm_ab_*.txt).  The default is 4 | 128.
-  //   bit 2 (adopted): 45 coefficient fields instead of 81 by the major symmetry C^{ij}_{kl} = C^{ji}_{lk} (the tangent
-  //     changes at rounding level); the block table is built by wave 3 while it would otherwise wait for the prologue,
-  //     in LDS of its own (the 45 fields leave room); the acceleration is interpolated behind barrier (1), beside the
-  //     contractions (only the residual needs it).
-  //   bit 7 (adopted): branch-free scatter (see there): 381 instead of 836 vector and 50 instead of 810 scalar
-  //     instructions per wave, the scatter phase 5.0 k instead of 9.9 k clocks of a workgroup's life.
-  //   bit 0 (measured, not adopted): the contraction waves run a software pipeline over their 160 (qz, kl, qy) steps --
-  //     the LDS reads of step s + 4 are issued as soon as step s has consumed its ring slot -- with the (kl) loop ordered
-  //     by accumulator group (k == z, l == z), each group contracted along z as soon as it is complete (3 live
-  //     accumulators instead of 12); same bits.  The contraction phase shrinks (18.9 k -> 14.4 k clocks) and the other
-  //     phases of the three workgroups of a CU grow by as much: 7.68 against 7.67 ms per assembly.
-  //   bit 1 (measured, not adopted): wave 0 runs its prologue at raised priority: prologue 19.6 k -> 14.3 k clocks, the
-  //     contractions 18.9 k -> 22.2 k, 8.2 against 7.7 ms.
-  // assemble_q2sf, pipelined contraction: (kl) in the order of the accumulator groups (k == z, l == z) = (0,0): 0 1 3 4 and the
-  // mass field 9, (0,1): 2 5, (1,0): 6 7, (1,1): 8 -- within a group ascending, the groups in the order the unpipelined
-  // loop adds them into the tangent entries
-  __device__ __forceinline__ constexpr int q2sf_kl_order(const int pos)
-  {
-    return pos == 0 ? 0 : pos == 1 ? 1 : pos == 2 ? 3 : pos == 3 ? 4 : pos == 4 ? 9 : pos == 5 ? 2 : pos == 6 ? 5 : pos == 7 ? 6 : pos == 8 ? 7 : 8;
-  }
+  // The tangent form stores 45 coefficient fields instead of 81 by the major symmetry C^{ij}_{kl} = C^{ji}_{lk}; wave 3
+  // builds the block table in LDS of its own while it would otherwise wait for the prologue; the acceleration is
+  // interpolated behind barrier (1), beside the contractions (only the residual needs it); the scatter is branch free (see
+  // there).  Measured and not adopted -- removed from the source, af9d3a4 is the last commit that builds them:
+  //   the 81-field kernel and the branching scatter of round 4: DESIGN.md C.1, profiles/r05/asm_ab_*.txt
+  //   contraction waves as a software pipeline over their (qz, kl, qy) steps: DESIGN.md C.1, profiles/r05/asm_ab_*.txt
+  //   wave 0's prologue at raised priority: DESIGN.md C.1, profiles/r05/asm_ab_*.txt
+  //   the tangent from the point records in a kernel of its own, all waves or wave 0: DESIGN.md D.2 and the phase stamps
+  //     under profiles/r06 that it names
 
   // 45-field storage (major symmetry): pairs (i <= j) in the order 00 01 02 11 12 22; a diagonal pair holds the 6 fields
   // k <= l, an off-diagonal one all 9
@@ -809,25 +788,16 @@ namespace mi
     return q2sf_pair_base(i, j) + (i == j ? q2sf_sym6(k, l) : k * 3 + l);
   }
 
-  template <bool RES_ONLY, int XV = 0>
+  template <bool RES_ONLY, bool RSLOTS = false>
   __global__ __launch_bounds__(RES_ONLY ? 64 : 256, RES_ONLY ? 4 : 3) void assemble_q2sf(AsmParams prm)
   {
-    constexpr bool V2 = !RES_ONLY && (XV & 4) != 0, SLIM = !RES_ONLY && (XV & 128) != 0;
-    // bit 8 (round 6, the default where point records exist): the tangent FROM THE RECORDS.  The residual pass (RES_ONLY,
-    // one wave per cell at mf_spmv's occupancy) has gathered, differentiated and written F, J^(-2/3), 1/J of every point; this
-    // kernel starts there: ALL FOUR waves recompute the material response of the cell's 64 points from the records (lane =
-    // point, the assembly's own function, ~350 instructions), each writes a quarter of the 45 fields, and the contractions
-    // begin after ~5 k clocks instead of behind one wave's 18.8 k-clock chain of gather, gradients, kinematics and fields;
-    // wave 0 then builds the block table beside the contractions.  No residual here.
-    constexpr bool REC = !RES_ONLY && (XV & 256) != 0;
-    constexpr bool RECW0 = !RES_ONLY && (XV & 512) != 0; // (see wave 0)
-    static_assert(!REC || (V2 && SLIM), "the record form builds on the 45-field kernel with the branch-free scatter");
-    constexpr int NPC = 27, FS = 66, NF = V2 ? 46 : 82; // field stride (padded: fields of different ij on different banks), fields
+    static_assert(RES_ONLY || !RSLOTS, "the residual goes to slots in the residual-only form alone");
+    constexpr int NPC = 27, FS = 66, NF = 46; // field stride (padded: fields of different ij on different banks), fields
     constexpr int PS = 20, PW = 9 * PS, AO = 552;
     constexpr int MASSF = NF - 1;                       // the mass field
     __shared__ __attribute__((aligned(16))) double s_C[RES_ONLY ? 2 : (NF * FS > 9 * EBE_NBLK ? NF * FS : 9 * EBE_NBLK)]; // later the element tangent [9][378]
-    __shared__ __attribute__((aligned(16))) double s_w[REC ? 2 : 768 + 216];    // wave 0's scratch (as in mf_spmv)
-    __shared__ uint64_t s_tab[V2 ? NPC * NPC : 1];                              // V2: the block table (wave 3 builds it during the prologue)
+    __shared__ __attribute__((aligned(16))) double s_w[768 + 216];              // wave 0's scratch (as in mf_spmv)
+    __shared__ uint64_t s_tab[RES_ONLY ? 1 : NPC * NPC];                        // the block table (wave 3 builds it during the prologue)
     __shared__ int  s_conn[NPC];
     __shared__ int2 s_ri[RES_ONLY ? 1 : NPC]; // rowinfo of the cell's nodes (where their rows are in the global matrix)
     __shared__ int  s_cm[RES_ONLY ? 1 : NPC]; // their constraint bits
@@ -835,12 +805,11 @@ namespace mi
                                               // scatter then skips the per-entry masking: all but the boundary cells)
     typedef const volatile __attribute__((address_space(3))) double *lds_cvp;
     const int     tid  = int(threadIdx.x);
-    // RES_ONLY bit 10 (round 6, the matrix-free fine level's point pass): ALL cells in one launch -- the 81 residual
+    // RSLOTS (round 6, the matrix-free fine level's point pass): ALL cells in one launch -- the 81 residual
     // entries of a cell go to the cell's own slots (AsmParams::res_slots at the slots of MfParams::dst, as the matrix-free
     // product's results) instead of being subtracted from system_rhs colour by colour; residual_gather sums them per node in
     // processing order.  Workgroups of one XCD take a contiguous run of cells (as mf_spmv).
-    constexpr bool RSLOTS = RES_ONLY && (XV & 1024) != 0;
-    int64_t        cell   = prm.cell_begin + blockIdx.x;
+    int64_t cell = prm.cell_begin + blockIdx.x;
     if constexpr (RSLOTS)
       {
         const int64_t local = int64_t(blockIdx.x & 7) * prm.xcd_chunk + (blockIdx.x >> 3);
@@ -966,13 +935,12 @@ namespace mi
           s0[c * NPC + lane] = accn[c];
     };
 
-    // ---- while the tangent waves contract: where the 729 node-pair blocks of this cell go.  One 64-bit word per
-    // block (a, b) in wave 0's own scratch, which the residual no longer needs: bits 0-31 position of the block in
-    // the global matrix (base + g * gstride + kx, mi_mesh.hpp; 0xffffffff: the node has no row here), 32-40 its place
-    // in the lower-triangle image of the element tangent, 41 a >= b (else: the transposed block of (b, a)),
-    // 42 first touch in processing order (plain store), 43 a == b, 44-46 / 47-49 constraint bits of A / B.
+    // ---- where the 729 node-pair blocks of this cell go (wave 3, while wave 0 runs the prologue).  One 64-bit word per
+    // block (a, b): bits 0-31 position of the block in the global matrix (base + g * gstride + kx, mi_mesh.hpp; the
+    // TRASH block where the node has no row here), 32-40 its place in the lower-triangle image of the element tangent,
+    // 41 a >= b (else: the transposed block of (b, a)), 42 first touch in processing order (the ZERO block is loaded),
+    // 43 a == b, 44-46 / 47-49 constraint bits of A / B.
     auto build_table = [&](uint64_t *const tab) __attribute__((always_inline)) {
-    {
       const uint16_t *__restrict__ offc = prm.off + cell * (NPC * NPC);
       {
         const bool special = lane < NPC && (s_cm[lane] != 0 || s_ri[lane].x < 0);
@@ -993,7 +961,7 @@ namespace mi
               const int      a = blk / NPC, b = blk - NPC * a;
               const int2     ri = s_ri[a];
               const uint32_t pos = ri.x >= 0 ? uint32_t(ri.x + int32_t((o[r] >> 4) & 0x7ff) * ri.y + int32_t(o[r] & 15)) :
-                                               (SLIM ? prm.trash_blk : 0xffffffffu);
+                                               prm.trash_blk;
               const bool     low = a >= b;
               const int      hi = low ? a : b, lo = low ? b : a;
               tab[blk] = uint64_t(pos) | (uint64_t(hi * (hi + 1) / 2 + lo) << 32) | (uint64_t(low) << 41) |
@@ -1001,195 +969,12 @@ namespace mi
                          (uint64_t(s_cm[b]) << 47);
             }
         }
-    }
     };
 
-    if constexpr (REC)
-      {
-        // ================================================================= every wave: the fields from the point records
-        const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-        double    rec[MF_NREC];
-        {
-          const double *__restrict__ rp = prm.qrec + cell * int64_t(MF_NREC * 64) + lane;
-#pragma unroll
-          for (int f = 0; f < MF_NREC; ++f)
-            rec[f] = rp[f * 64];
-        }
-        int2 ri_l = make_int2(0, 0);
-        int  cm_l = 0;
-        if (tid < NPC) // wave 0: where the cell's rows are (for the block table it builds beside the contractions); kept in
-          {            // registers until the fields are out, so that the loads travel beside the arithmetic
-            int32_t node;
-            if (prm.lat.ncol > 0)
-              {
-                const int32_t node0 = lattice_node0(prm.lat, cell);
-                const int     k9 = lane / 9, r9 = lane - 9 * k9, j3 = r9 / 3, i3 = r9 - 3 * j3;
-                node               = node0 + i3 + j3 * prm.lat.nn0 + k9 * prm.lat.nn01;
-              }
-            else
-              node = prm.conn[cell * NPC + lane];
-            ri_l = prm.rowinfo[node];
-            cm_l = prm.cmask[node] & 7;
-          }
-        const int    qz = lane >> 4;
-        const double wq = prm.tab1d[24 + (lane & 3)] * prm.tab1d[24 + ((lane >> 2) & 3)] * prm.tab1d[24 + qz];
-        double       Mr[9], detJ;
-        double       Finv[9], tauq[6], tisoq[6], cII, cS;
-        neo_hooke_from_F<3>(rec, det3x3(rec), rec[9], rec[10], prm.mu, prm.kappa, Finv, tauq, tisoq, cII, cS);
-        if (prm.cellbox) // every local cell an axis-parallel box: 1/h and the volume
-          {
-            const double *__restrict__ cb = prm.cellbox + cell * 4;
-            const double rx = cb[0], ry = cb[1], rz = cb[2];
-            detJ            = cb[3];
-#pragma unroll
-            for (int k = 0; k < 3; ++k)
-              {
-                Mr[k]     = rx * Finv[k];
-                Mr[3 + k] = ry * Finv[3 + k];
-                Mr[6 + k] = rz * Finv[6 + k];
-              }
-          }
-        else
-          {
-            const double *__restrict__ cv = prm.cverts + cell * 24;
-            const double xiq[3] = {prm.tab1d[28 + (lane & 3)], prm.tab1d[28 + ((lane >> 2) & 3)], prm.tab1d[28 + qz]};
-            double       verts[24], Jm[9], Ji[9];
-#pragma unroll
-            for (int k = 0; k < 24; ++k)
-              verts[k] = cv[k];
-            q1_jacobian<3>(verts, xiq, Jm);
-            detJ = det3x3(Jm);
-            inv3x3(Jm, detJ, Ji);
-#pragma unroll
-            for (int i = 0; i < 3; ++i)
-#pragma unroll
-              for (int j = 0; j < 3; ++j)
-                Mr[i * 3 + j] = Ji[i * 3 + 0] * Finv[0 * 3 + j] + Ji[i * 3 + 1] * Finv[1 * 3 + j] + Ji[i * 3 + 2] * Finv[2 * 3 + j];
-          }
-        const double wr = detJ * wq;
-        const double Tq[3][3]  = {{tauq[0], tauq[3], tauq[4]}, {tauq[3], tauq[1], tauq[5]}, {tauq[4], tauq[5], tauq[2]}};
-        const double Tiq[3][3] = {{tisoq[0], tisoq[3], tisoq[4]}, {tisoq[3], tisoq[1], tisoq[5]}, {tisoq[4], tisoq[5], tisoq[2]}};
-        const double cs2       = 0.5 * cS;
-        double       Tm[3][3], A[3][3], B[3][3], E[3][3], MT[3][3], Sk[3][3] = {};
-#pragma unroll
-        for (int k = 0; k < 3; ++k)
-#pragma unroll
-          for (int i = 0; i < 3; ++i)
-            {
-              Tm[k][i] = (-2.0 / 3.0) * (Mr[k * 3] * Tiq[0][i] + Mr[k * 3 + 1] * Tiq[1][i] + Mr[k * 3 + 2] * Tiq[2][i]);
-              MT[k][i] = Mr[k * 3] * Tq[0][i] + Mr[k * 3 + 1] * Tq[1][i] + Mr[k * 3 + 2] * Tq[2][i]; // (M tau)_ki
-            }
-#pragma unroll
-        for (int k = 0; k < 3; ++k)
-#pragma unroll
-          for (int i = 0; i < 3; ++i)
-            {
-              A[k][i] = wr * (cII * Mr[k * 3 + i] + Tm[k][i]);
-              B[k][i] = wr * Mr[k * 3 + i];
-              E[k][i] = (wr * cs2) * Mr[k * 3 + i];
-            }
-        // the fields of the pair (i, j), i <= j (for i == j: k <= l, with S_kl on top) -- the expressions of the fused kernel
-        auto emit_pair = [&](auto I_, auto J_) __attribute__((always_inline)) {
-          constexpr int i = decltype(I_)::value, j = decltype(J_)::value;
-#pragma unroll
-          for (int k = 0; k < 3; ++k)
-#pragma unroll
-            for (int l = 0; l < 3; ++l)
-              {
-                if (i == j && k > l)
-                  continue;
-                double c = A[k][i] * Mr[l * 3 + j] + B[k][i] * Tm[l][j] + E[k][j] * Mr[l * 3 + i];
-                if (i == j)
-                  c += Sk[k][l];
-                s_C[q2sf_field(i, j, k, l) * FS + lane] = c;
-              }
-        };
-        using I0 = std::integral_constant<int, 0>;
-        using I1 = std::integral_constant<int, 1>;
-        using I2 = std::integral_constant<int, 2>;
-        if (wv == 0) // 18 fields (this wave has no contraction tables to set up)
-          {
-#pragma unroll
-            for (int k = 0; k < 3; ++k)
-#pragma unroll
-              for (int l = k; l < 3; ++l)
-                Sk[k][l] = E[k][0] * Mr[l * 3] + E[k][1] * Mr[l * 3 + 1] + E[k][2] * Mr[l * 3 + 2] +
-                           wr * (MT[k][0] * Mr[l * 3] + MT[k][1] * Mr[l * 3 + 1] + MT[k][2] * Mr[l * 3 + 2]);
-            emit_pair(I0{}, I0{});
-            emit_pair(I1{}, I1{});
-            emit_pair(I2{}, I2{});
-          }
-        else if (wv == 1)
-          {
-            emit_pair(I0{}, I1{});
-            s_C[MASSF * FS + lane] = prm.alpha1 * prm.rho * wr;
-          }
-        else if (wv == 2)
-          emit_pair(I0{}, I2{});
-        else
-          emit_pair(I1{}, I2{});
-        if (tid < NPC)
-          {
-            s_ri[lane] = ri_l;
-            s_cm[lane] = cm_l;
-          }
-      }
     if (tid < 64)
       {
-       if constexpr (!REC)
-       {
         // ================================================================= wave 0: quadrature points
-        if constexpr (!RES_ONLY && (XV & 2) != 0)
-          __builtin_amdgcn_s_setprio(3);
         double tiso[6], cII, cS;
-        if constexpr (RECW0)
-          {
-            // bit 9: wave 0 ALONE starts from the point records (no gather, no gradients, no kinematics: the point pass has
-            // done them) and forms all 45 fields as in the fused kernel; waves 1-3 carry no extra arithmetic
-            double rec[MF_NREC], Finv[9], detJ;
-            {
-              const double *__restrict__ rp = prm.qrec + cell * int64_t(MF_NREC * 64) + lane;
-#pragma unroll
-              for (int f = 0; f < MF_NREC; ++f)
-                rec[f] = rp[f * 64];
-            }
-            const int    qz = lane >> 4;
-            const double wq = prm.tab1d[24 + (lane & 3)] * prm.tab1d[24 + ((lane >> 2) & 3)] * prm.tab1d[24 + qz];
-            neo_hooke_from_F<3>(rec, det3x3(rec), rec[9], rec[10], prm.mu, prm.kappa, Finv, tau, tiso, cII, cS);
-            if (prm.cellbox)
-              {
-                const double *__restrict__ cb = prm.cellbox + cell * 4;
-                const double rx = cb[0], ry = cb[1], rz = cb[2];
-                detJ            = cb[3];
-#pragma unroll
-                for (int k = 0; k < 3; ++k)
-                  {
-                    M[k]     = rx * Finv[k];
-                    M[3 + k] = ry * Finv[3 + k];
-                    M[6 + k] = rz * Finv[6 + k];
-                  }
-              }
-            else
-              {
-                const double *__restrict__ cv = prm.cverts + cell * 24;
-                const double xiq[3] = {prm.tab1d[28 + (lane & 3)], prm.tab1d[28 + ((lane >> 2) & 3)], prm.tab1d[28 + qz]};
-                double       verts[24], Jm[9], Ji[9];
-#pragma unroll
-                for (int k = 0; k < 24; ++k)
-                  verts[k] = cv[k];
-                q1_jacobian<3>(verts, xiq, Jm);
-                detJ = det3x3(Jm);
-                inv3x3(Jm, detJ, Ji);
-#pragma unroll
-                for (int i = 0; i < 3; ++i)
-#pragma unroll
-                  for (int j = 0; j < 3; ++j)
-                    M[i * 3 + j] = Ji[i * 3 + 0] * Finv[0 * 3 + j] + Ji[i * 3 + 1] * Finv[1 * 3 + j] + Ji[i * 3 + 2] * Finv[2 * 3 + j];
-              }
-            w = detJ * wq;
-          }
-        else
-          {
         const int     qz = lane >> 4;
 #pragma unroll
         for (int k = 0; k < 3; ++k)
@@ -1213,11 +998,6 @@ namespace mi
             else
               node = prm.conn[cell * NPC + lane];
             s_conn[lane] = node;
-            if constexpr (!RES_ONLY && !V2)
-              {
-                s_ri[lane] = prm.rowinfo[node];
-                s_cm[lane] = prm.cmask[node] & 7;
-              }
 #pragma unroll
             for (int c = 0; c < 3; ++c)
               {
@@ -1226,10 +1006,11 @@ namespace mi
                 accn[c]            = prm.acc[g];
               }
           }
-        // ---- two interpolations to the points: pass 0 = u (gradients), pass 1 = acceleration (values; V2: after barrier
-        // (1), beside the contractions -- only the residual needs it)
+        // ---- two interpolations to the points: pass 0 = u (gradients), pass 1 = acceleration (values; only the residual
+        // needs it: the tangent form takes it after barrier (1), beside the contractions, the residual-only form has no
+        // contractions to put it beside and takes it here)
         interp(0);
-        if constexpr (!V2)
+        if constexpr (RES_ONLY)
           {
             stage_acc();
             interp(1);
@@ -1282,34 +1063,33 @@ namespace mi
           else
             {
 #pragma unroll
-          for (int i = 0; i < 3; ++i)
+              for (int i = 0; i < 3; ++i)
 #pragma unroll
-            for (int j = 0; j < 3; ++j)
-              M[i * 3 + j] = Ji[i * 3 + 0] * Finv[0 * 3 + j] + Ji[i * 3 + 1] * Finv[1 * 3 + j] + Ji[i * 3 + 2] * Finv[2 * 3 + j];
+                for (int j = 0; j < 3; ++j)
+                  M[i * 3 + j] = Ji[i * 3 + 0] * Finv[0 * 3 + j] + Ji[i * 3 + 1] * Finv[1 * 3 + j] + Ji[i * 3 + 2] * Finv[2 * 3 + j];
             }
           w = detJ * wq; // JxW of the reference configuration
           // (RES_ONLY with records: the tangent pass of the matrix-free fine level, round 6 -- the residual-only pass of
           // the Newton convergence check hands in no record pointer)
-            if (prm.qrec) // the state the tangent is linearised at, for the matrix-free product (mf_spmv)
-              {
-                double *__restrict__ g = prm.qrec + cell * int64_t(MF_NREC * 64) + lane;
+          if (prm.qrec) // the state the tangent is linearised at, for the matrix-free product (mf_spmv)
+            {
+              double *__restrict__ g = prm.qrec + cell * int64_t(MF_NREC * 64) + lane;
 #pragma unroll
-                for (int k = 0; k < 9; ++k)
-                  g[k * 64] = Fq[k];
-                g[9 * 64]  = Jmq;
-                g[10 * 64] = rJq;
-                if (prm.qrec32) // (opt-in fp32 smoother product)
-                  {
-                    float *__restrict__ g32 = prm.qrec32 + cell * int64_t(MF_NREC * 64) + lane;
+              for (int k = 0; k < 9; ++k)
+                g[k * 64] = Fq[k];
+              g[9 * 64]  = Jmq;
+              g[10 * 64] = rJq;
+              if (prm.qrec32) // (opt-in fp32 smoother product)
+                {
+                  float *__restrict__ g32 = prm.qrec32 + cell * int64_t(MF_NREC * 64) + lane;
 #pragma unroll
-                    for (int k = 0; k < 9; ++k)
-                      g32[k * 64] = float(Fq[k]);
-                    g32[9 * 64]  = float(Jmq);
-                    g32[10 * 64] = float(rJq);
-                  }
-              }
+                  for (int k = 0; k < 9; ++k)
+                    g32[k * 64] = float(Fq[k]);
+                  g32[9 * 64]  = float(Jmq);
+                  g32[10 * 64] = float(rJq);
+                }
+            }
         }
-          } // !RECW0
         MI_STAMPW(9, 0); // material
         const double T[3][3]  = {{tau[0], tau[3], tau[4]}, {tau[3], tau[1], tau[5]}, {tau[4], tau[5], tau[2]}};
         // ---- coefficient fields for the tangent waves
@@ -1350,18 +1130,17 @@ namespace mi
 #pragma unroll
                   for (int l = 0; l < 3; ++l)
                     {
-                      // V2: C^{ij}_{kl} = C^{ji}_{lk}, so only i <= j is stored, and for i == j only k <= l (45 fields)
-                      if (V2 && (i > j || (i == j && k > l)))
+                      // C^{ij}_{kl} = C^{ji}_{lk}, so only i <= j is stored, and for i == j only k <= l (45 fields)
+                      if (i > j || (i == j && k > l))
                         continue;
                       double c = A[k][i] * M[l * 3 + j] + B[k][i] * Tm[l][j] + E[k][j] * M[l * 3 + i];
                       if (i == j)
                         c += Sk[k][l];
-                      s_C[(V2 ? q2sf_field(i, j, k, l) : (i * 3 + j) * 9 + k * 3 + l) * FS + lane] = c;
+                      s_C[q2sf_field(i, j, k, l) * FS + lane] = c;
                     }
             s_C[MASSF * FS + lane] = prm.alpha1 * prm.rho * w;
           }
         MI_STAMPW(10, 0); // fields stored
-       } // !REC
       }
     else if constexpr (!RES_ONLY)
       {
@@ -1380,47 +1159,35 @@ namespace mi
             phi2[1][q]      = prm.tab1d[12 + q * 3 + a2];
           }
         mflag = (ci == cj) ? 1.0 : 0.0;
-        if constexpr (V2 && !REC)
-          if (tid >= 192) // wave 3, idle until barrier (1) otherwise: where the 729 node-pair blocks of this cell go
-            {
-              int32_t node;
-              if (prm.lat.ncol > 0)
-                {
-                  const int32_t node0 = lattice_node0(prm.lat, cell);
-                  const int     k9 = lane / 9, r9 = lane - 9 * k9, j3 = r9 / 3, i3 = r9 - 3 * j3;
-                  node               = node0 + i3 + j3 * prm.lat.nn0 + k9 * prm.lat.nn01;
-                }
-              else
-                node = lane < NPC ? prm.conn[cell * NPC + lane] : 0;
-              if (lane < NPC)
-                {
-                  s_ri[lane] = prm.rowinfo[node];
-                  s_cm[lane] = prm.cmask[node] & 7;
-                }
-              MI_WAVE_SYNC();
-              MI_STAMPW(11, 192); // wave 3: rowinfo there
-              build_table(s_tab);
-              MI_STAMPW(12, 192); // wave 3: table built
-            }
+        if (tid >= 192) // wave 3, idle until barrier (1) otherwise: where the 729 node-pair blocks of this cell go
+          {
+            int32_t node;
+            if (prm.lat.ncol > 0)
+              {
+                const int32_t node0 = lattice_node0(prm.lat, cell);
+                const int     k9 = lane / 9, r9 = lane - 9 * k9, j3 = r9 / 3, i3 = r9 - 3 * j3;
+                node               = node0 + i3 + j3 * prm.lat.nn0 + k9 * prm.lat.nn01;
+              }
+            else
+              node = lane < NPC ? prm.conn[cell * NPC + lane] : 0;
+            if (lane < NPC)
+              {
+                s_ri[lane] = prm.rowinfo[node];
+                s_cm[lane] = prm.cmask[node] & 7;
+              }
+            MI_WAVE_SYNC();
+            MI_STAMPW(11, 192); // wave 3: rowinfo there
+            build_table(s_tab);
+            MI_STAMPW(12, 192); // wave 3: table built
+          }
       }
-    if constexpr (!RES_ONLY && (XV & 2) != 0)
-      __builtin_amdgcn_s_setprio(0);
     if constexpr (!RES_ONLY)
       __syncthreads(); // (1) fields complete -- the one barrier every wave of the workgroup passes, outside the role branches
     MI_STAMP(1);
-    if constexpr (REC)
-      {
-        if (tid < 64) // wave 0, beside the contractions: the block table (its row info arrived with the records)
-          build_table(s_tab);
-      }
-    else if constexpr (RECW0)
-      {
-      }
-    else
     if (tid < 64)
       {
         const double T[3][3] = {{tau[0], tau[3], tau[4]}, {tau[3], tau[1], tau[5]}, {tau[4], tau[5], tau[2]}};
-        if constexpr (V2)
+        if constexpr (!RES_ONLY) // the acceleration: beside the contractions (only the residual needs it)
           {
             stage_acc();
             interp(1);
@@ -1528,11 +1295,6 @@ namespace mi
           }
         if constexpr (RES_ONLY)
           return;
-        if constexpr (!V2)
-          {
-            MI_WAVE_SYNC();
-            build_table(reinterpret_cast<uint64_t *>(s_w));
-          }
       }
     if constexpr (!RES_ONLY)
       {
@@ -1547,91 +1309,16 @@ namespace mi
               Kacc[a3][b3][b2] = 0.0;
         if (tid >= 64)
           {
-            const double *__restrict__ cb = s_C + ij * 9 * FS;
-            // V2 (45 fields): field of (kl) for this lane's (ci, cj): (ci, cj, k, l) for ci < cj, (cj, ci, l, k) for ci > cj,
+            // field of (kl) for this lane's (ci, cj): (ci, cj, k, l) for ci < cj, (cj, ci, l, k) for ci > cj,
             // (ci, ci, min, max) on the diagonal
             const int  pbase = q2sf_pair_base(ci < cj ? ci : cj, ci < cj ? cj : ci);
             const bool fdiag = ci == cj, fswap = ci > cj;
             auto       fld   = [&](const int kl) __attribute__((always_inline)) -> const double * {
               if (kl == 9)
                 return s_C + MASSF * FS;
-              if constexpr (V2)
-                {
-                  const int k = kl / 3, l = kl - 3 * k;
-                  return s_C + (pbase + (fdiag ? q2sf_sym6(k < l ? k : l, k < l ? l : k) : fswap ? l * 3 + k : kl)) * FS;
-                }
-              else
-                return cb + kl * FS;
+              const int k = kl / 3, l = kl - 3 * k;
+              return s_C + (pbase + (fdiag ? q2sf_sym6(k < l ? k : l, k < l ? l : k) : fswap ? l * 3 + k : kl)) * FS;
             };
-            if constexpr ((XV & 1) != 0)
-              {
-                // step (qz, pos = position of kl in the group order, qy); ring slot qy: the values of step (qz, pos, qy) are
-                // requested by step (qz, pos - 1, qy)
-                double2 ring[4][2];
-                double  acc[3] = {0.0, 0.0, 0.0};
-#pragma unroll
-                for (int qy = 0; qy < 4; ++qy)
-                  {
-                    const double *__restrict__ f_ = fld(q2sf_kl_order(0)) + qy * 4;
-                    ring[qy][0]                   = *reinterpret_cast<const double2 *>(f_);
-                    ring[qy][1]                   = *reinterpret_cast<const double2 *>(f_ + 2);
-                  }
-#pragma unroll
-                for (int qz = 0; qz < 4; ++qz)
-#pragma unroll
-                  for (int pos = 0; pos < 10; ++pos)
-                    {
-                      const int  kl = q2sf_kl_order(pos), k = kl / 3, l = kl - 3 * k;
-                      const bool mass = kl == 9;
-                      const int  kx = (!mass && k == 0), lx = (!mass && l == 0), ky = (!mass && k == 1), ly = (!mass && l == 1),
-                                kz = (!mass && k == 2), lz = (!mass && l == 2);
-                      // the step after this one in the same ring slot
-                      const int  npos = pos == 9 ? 0 : pos + 1, nqz = pos == 9 ? qz + 1 : qz, nkl = q2sf_kl_order(npos);
-                      const double *__restrict__ fn = fld(nkl) + nqz * 16;
-#pragma unroll
-                      for (int qy = 0; qy < 4; ++qy)
-                        {
-                          const double2 c01 = ring[qy][0], c23 = ring[qy][1];
-                          double        t   = P1[kx * 2 + lx][0] * c01.x;
-                          t                 = fma(P1[kx * 2 + lx][1], c01.y, t);
-                          t                 = fma(P1[kx * 2 + lx][2], c23.x, t);
-                          t                 = fma(P1[kx * 2 + lx][3], c23.y, t);
-                          if (nqz < 4) // the slot is free again: its next occupant has three steps to arrive
-                            {
-                              ring[qy][0] = *reinterpret_cast<const double2 *>(fn + qy * 4);
-                              ring[qy][1] = *reinterpret_cast<const double2 *>(fn + qy * 4 + 2);
-                            }
-                          if (mass)
-                            t *= mflag;
-                          const double ta = t * phi2[ky][qy];
-#pragma unroll
-                          for (int b2 = 0; b2 < 3; ++b2)
-                            acc[b2] = fma(ta, ly ? D[qy][b2] : S[qy][b2], acc[b2]);
-                          if ((qy & 1) == 1)
-                            __builtin_amdgcn_sched_barrier(0);
-                        }
-                      // last field of an accumulator group (kz, lz): positions 4 (kl = 9), 6 (5), 8 (7), 9 (8)
-                      if (pos == 4 || pos == 6 || pos == 8 || pos == 9)
-                        {
-#pragma unroll
-                          for (int b2 = 0; b2 < 3; ++b2)
-                            {
-                              const double v = acc[b2];
-                              acc[b2]        = 0.0;
-#pragma unroll
-                              for (int a3 = 0; a3 < 3; ++a3)
-                                {
-                                  const double va = v * (kz ? D[qz][a3] : S[qz][a3]);
-#pragma unroll
-                                  for (int b3 = 0; b3 < 3; ++b3)
-                                    Kacc[a3][b3][b2] = fma(va, lz ? D[qz][b3] : S[qz][b3], Kacc[a3][b3][b2]);
-                                }
-                            }
-                        }
-                    }
-              }
-            else
-              {
 #pragma unroll
             for (int qz = 0; qz < 4; ++qz)
               {
@@ -1682,7 +1369,6 @@ namespace mi
                           }
                       }
               }
-              }
           }
         MI_STAMP(2);
         __syncthreads(); // (2) fields consumed: the element tangent image goes on top of them
@@ -1714,115 +1400,55 @@ namespace mi
         // constrained dof receives |K_e(i,i)|.  Lane = ENTRY of a block: thread t owns entry e = t % 9 of block t / 9 of
         // every group of 28 blocks, so 9 consecutive lanes store one 72-byte block and a wave instruction covers 7 whole
         // blocks (round 2: one thread per block and nine 8-byte accesses each, i.e. 64 pieces of 64 different blocks per
-        // instruction).  Everything that depends on the block comes out of wave 0's table in one LDS read; what depends
+        // instruction).  Everything that depends on the block comes out of wave 3's table in one LDS read; what depends
         // on the entry is constant per thread.
         {
-          const uint64_t *const tab = V2 ? s_tab : reinterpret_cast<const uint64_t *>(s_w);
+          const uint64_t *const tab = s_tab;
           const int      tq = tid / 9, e = tid - 9 * tq, ei = e / 3, ej = e - 3 * ei;
           const int      src_low = e * EBE_NBLK, src_tr = (ej * 3 + ei) * EBE_NBLK; // image rows of the entry / its transpose
           const uint32_t cm      = (1u << ei) | (8u << ej);                          // constraint bits that kill this entry
           const bool     on_diag = ei == ej;
           double *const  vbase   = prm.vals + e;
-          const bool     plain   = s_plain != 0; // uniform: the table is complete since barrier (2)
-          if constexpr (SLIM)
+          const bool     plain   = s_plain != 0; // uniform: the table is complete since barrier (1)
+          // Branch-free form (round 5): a first touch loads the ZERO block behind the matrix instead of skipping its load, a
+          // node without a row here (ghost node of a slab) has the TRASH block as its position, so every lane runs the
+          // same straight-line code: per entry one table read with an immediate offset, a select, an address, a load; then
+          // the image value, an add, a store.  Threads 252-255 own no entry; of round 26 only block 728 exists (thread
+          // group 0).  The masking of constrained entries is a second instantiation for the few cells that need it.
+          if (tq < 28)
             {
-              // Branch-free form (round 5): a first touch loads the ZERO block behind the matrix instead of skipping its load, a
-              // node without a row here (ghost node of a slab) has the TRASH block as its position, so every lane runs the
-              // same straight-line code: per entry one table read with an immediate offset, a select, an address, a load; then
-              // the image value, an add, a store.  Threads 252-255 own no entry; of round 26 only block 728 exists (thread
-              // group 0).  The masking of constrained entries is a second instantiation for the few cells that need it.
-              if (tq < 28)
-                {
-                  const uint64_t *const tb = tab + tq;
-                  auto rounds = [&](auto plain_c) __attribute__((always_inline)) {
-                    constexpr bool PLAIN = decltype(plain_c)::value;
-                    double         old[27];
+              const uint64_t *const tb = tab + tq;
+              auto rounds = [&](auto plain_c) __attribute__((always_inline)) {
+                constexpr bool PLAIN = decltype(plain_c)::value;
+                double         old[27];
 #pragma unroll
-                    for (int r = 0; r < 27; ++r)
+                for (int r = 0; r < 27; ++r)
+                  {
+                    old[r] = 0.0;
+                    if (r < 26 || tq == 0)
                       {
-                        old[r] = 0.0;
-                        if (r < 26 || tq == 0)
-                          {
-                            const uint64_t t  = tb[r * 28];
-                            const uint32_t ld = ((t >> 42) & 1) ? prm.zero_blk : uint32_t(t);
-                            old[r]            = vbase[int64_t(ld) * 9];
-                          }
+                        const uint64_t t  = tb[r * 28];
+                        const uint32_t ld = ((t >> 42) & 1) ? prm.zero_blk : uint32_t(t);
+                        old[r]            = vbase[int64_t(ld) * 9];
                       }
+                  }
 #pragma unroll
-                    for (int r = 0; r < 27; ++r)
-                      if (r < 26 || tq == 0)
-                        {
-                          const uint64_t t  = tb[r * 28];
-                          const uint32_t fl = uint32_t(t >> 32);
-                          double         w_ = s_C[((fl >> 9) & 1 ? src_low : src_tr) + int(fl & 511)];
-                          if constexpr (!PLAIN)
-                            if ((fl >> 12) & cm)
-                              w_ = (((fl >> 11) & 1) && on_diag) ? fabs(w_) : 0.0;
-                          vbase[int64_t(uint32_t(t)) * 9] = w_ + old[r];
-                        }
-                  };
-                  if (plain)
-                    rounds(std::true_type{});
-                  else
-                    rounds(std::false_type{});
-                }
-            }
-          else
-            {
-          // phase A: the old values of every entry that is not a first touch, all requested before anything is stored
-          // (loads and stores share the wave's memory counter: a load issued after a store waits for that store).
-          // Batches of nine: the table words of a batch in one LDS round trip, then its nine loads.
-          double old[27];
-#pragma unroll
-          for (int bb = 0; bb < 27; bb += 9)
-            {
-              uint64_t t[9];
-#pragma unroll
-              for (int u = 0; u < 9; ++u)
-                {
-                  const int blk = (bb + u) * 28 + tq;
-                  t[u]          = tab[(tq < 28 && blk < NPC * NPC) ? blk : 0];
-                }
-#pragma unroll
-              for (int u = 0; u < 9; ++u)
-                {
-                  const int  blk = (bb + u) * 28 + tq;
-                  const bool rd  = tq < 28 && blk < NPC * NPC && (plain || uint32_t(t[u]) != 0xffffffffu) && !((t[u] >> 42) & 1);
-                  old[bb + u]    = rd ? vbase[int64_t(uint32_t(t[u])) * 9] : 0.0;
-                }
-            }
-          // phase B: masked entries out of the image, summed, stored; per batch two LDS round trips (table words, image)
-#pragma unroll
-          for (int bb = 0; bb < 27; bb += 9)
-            {
-              uint64_t t[9];
-              double   v[9];
-#pragma unroll
-              for (int u = 0; u < 9; ++u)
-                {
-                  const int blk = (bb + u) * 28 + tq;
-                  t[u]          = tab[(tq < 28 && blk < NPC * NPC) ? blk : 0];
-                }
-#pragma unroll
-              for (int u = 0; u < 9; ++u)
-                {
-                  const uint32_t fl = uint32_t(t[u] >> 32);
-                  v[u]              = s_C[((fl >> 9) & 1 ? src_low : src_tr) + int(fl & 511)];
-                }
-#pragma unroll
-              for (int u = 0; u < 9; ++u)
-                {
-                  const int      blk = (bb + u) * 28 + tq;
-                  const uint32_t fl  = uint32_t(t[u] >> 32);
-                  double         w_  = v[u];
-                  if (!plain && ((fl >> 12) & cm))
-                    w_ = (((fl >> 11) & 1) && on_diag) ? fabs(w_) : 0.0;
-                  if (tq < 28 && blk < NPC * NPC && (plain || uint32_t(t[u]) != 0xffffffffu))
+                for (int r = 0; r < 27; ++r)
+                  if (r < 26 || tq == 0)
                     {
-                      vbase[int64_t(uint32_t(t[u])) * 9] = w_ + old[bb + u];
+                      const uint64_t t  = tb[r * 28];
+                      const uint32_t fl = uint32_t(t >> 32);
+                      double         w_ = s_C[((fl >> 9) & 1 ? src_low : src_tr) + int(fl & 511)];
+                      if constexpr (!PLAIN)
+                        if ((fl >> 12) & cm)
+                          w_ = (((fl >> 11) & 1) && on_diag) ? fabs(w_) : 0.0;
+                      vbase[int64_t(uint32_t(t)) * 9] = w_ + old[r];
                     }
-                }
-            }
+              };
+              if (plain)
+                rounds(std::true_type{});
+              else
+                rounds(std::false_type{});
             }
           if (prm.ke) // the cell's own masked blocks (what entered the global matrix) for the element-tangent product: the
             {         // image is masked in place, in a pass of its own so that nothing above waits for LDS stores
@@ -2872,8 +2498,8 @@ namespace mi
   // T (round 5, opt-in "smoother_precision" 32): the scalar type of the arithmetic and of the records.  float: the records
   // come from prm.qrec32, x is converted on the way in, the results on the way out; vectors, slots and every other kernel
   // stay fp64 -- a preconditioner-only change (the production shape only).
-  template <bool BOX, bool SLOTS, bool LAT, int DBG = 0, int OCC = 4, typename T = double>
-  __global__ __launch_bounds__(64, OCC) void mf_spmv(MfParams prm, int64_t cell0) // OCC = 5 (96 VGPRs) spills 8 registers: A/B MI_MF_OCC=5
+  template <bool BOX, bool SLOTS, bool LAT, int DBG = 0, typename T = double>
+  __global__ __launch_bounds__(64, 4) void mf_spmv(MfParams prm, int64_t cell0) // (five waves per SIMD, 96 VGPRs, spill 8 registers)
   {
     static_assert(std::is_same<T, double>::value || (BOX && SLOTS && LAT && DBG == 0), "fp32 form: production shape only");
     constexpr bool STAMP = (DBG & 1) != 0;
@@ -6808,10 +6434,10 @@ namespace mi
   }
 
   // ------------------------------------------------------------------ launchers
-  template <int DIM, int P, int QSPLIT, int NT, int QC, int MINW = 1, int ABL = 0>
+  template <int DIM, int P, int QSPLIT, int NT, int QC, int MINW = 1, bool RES_ONLY = false>
   static void launch_asm(const AsmParams &p, hipStream_t s)
   {
-    hipLaunchKernelGGL((assemble_cells<DIM, P, QSPLIT, NT, QC, MINW, ABL>), dim3(p.cell_count), dim3(NT), 0, s, p);
+    hipLaunchKernelGGL((assemble_cells<DIM, P, QSPLIT, NT, QC, MINW, RES_ONLY>), dim3(p.cell_count), dim3(NT), 0, s, p);
   }
 
   // full kernel or its residual-only form (AsmParams::residual_only)
@@ -6819,7 +6445,7 @@ namespace mi
   static void launch_asm_sel(const AsmParams &p, hipStream_t s)
   {
     if (p.residual_only)
-      launch_asm<DIM, P, QSPLIT, NT, QC, 1, 4>(p, s);
+      launch_asm<DIM, P, QSPLIT, NT, QC, 1, true>(p, s);
     else
       launch_asm<DIM, P, QSPLIT, NT, QC>(p, s);
   }
@@ -6836,42 +6462,10 @@ namespace mi
           {
             case 0: // sum factorised (default): 4 waves per cell, 41 kB LDS
               if (p.residual_only)
-                hipLaunchKernelGGL((assemble_q2sf<true, 0>), dim3(p.cell_count), dim3(64), 0, s, p);
-#ifdef MI_EXPERIMENTS
-              else if (p.qrec && p.from_records)
-                {
-                  // round 6: the point pass (gather, gradients, kinematics, records, residual: one wave per cell), then the
-                  // tangent from the records
-                  hipLaunchKernelGGL((assemble_q2sf<true, 0>), dim3(p.cell_count), dim3(64), 0, s, p);
-                  if (p.from_records == 2) // wave 0 alone forms the fields from the records
-                    hipLaunchKernelGGL((assemble_q2sf<false, 644>), dim3(p.cell_count), dim3(256), 0, s, p);
-                  else                     // every wave a quarter of them
-                    hipLaunchKernelGGL((assemble_q2sf<false, 388>), dim3(p.cell_count), dim3(256), 0, s, p);
-                }
-#endif
+                hipLaunchKernelGGL((assemble_q2sf<true>), dim3(p.cell_count), dim3(64), 0, s, p);
               else
-                hipLaunchKernelGGL((assemble_q2sf<false, 132>), dim3(p.cell_count), dim3(256), 0, s, p);
+                hipLaunchKernelGGL((assemble_q2sf<false>), dim3(p.cell_count), dim3(256), 0, s, p);
               break;
-#ifdef MI_EXPERIMENTS // (A/B instantiations: profiles/r05/asm_ab_*.txt, profiles/r06/asm_split_ab_n59.txt)
-            case 3: // A/B: the kernel of round 4 (81 fields, block table by wave 0 behind the residual, branching scatter)
-              hipLaunchKernelGGL((assemble_q2sf<false, 0>), dim3(p.cell_count), dim3(256), 0, s, p);
-              break;
-            case 4: // A/B: default + pipelined contraction
-              hipLaunchKernelGGL((assemble_q2sf<false, 133>), dim3(p.cell_count), dim3(256), 0, s, p);
-              break;
-            case 5: // A/B: default + prologue at raised priority
-              hipLaunchKernelGGL((assemble_q2sf<false, 134>), dim3(p.cell_count), dim3(256), 0, s, p);
-              break;
-            case 6: // A/B: 45 fields + block table by wave 3 alone
-              hipLaunchKernelGGL((assemble_q2sf<false, 4>), dim3(p.cell_count), dim3(256), 0, s, p);
-              break;
-            case 7: // A/B: branch-free scatter alone
-              hipLaunchKernelGGL((assemble_q2sf<false, 128>), dim3(p.cell_count), dim3(256), 0, s, p);
-              break;
-            case 8: // A/B: round 4 + pipelined contraction
-              hipLaunchKernelGGL((assemble_q2sf<false, 1>), dim3(p.cell_count), dim3(256), 0, s, p);
-              break;
-#endif
             case 9: // node-pair form (the default until round 2): 16.4 ms per assembly at 5 M DoFs
               launch_asm_sel<3, 2, 2, 256, 8>(p, s);
               break;
@@ -7064,20 +6658,16 @@ namespace mi
 #ifdef MI_EXPERIMENTS
     if (q.stamps) // diagnostic: the production shape only (boxes, one launch, lattice ids or not)
       kern = q.lat.ncol > 0 ? mf_spmv<true, true, true, 1> : mf_spmv<true, true, false, 1>;
-    static const bool occ5 = exp_env("MI_MF_OCC") && atoi(exp_env("MI_MF_OCC")) == 5; // A/B: five waves per SIMD (spills)
-    if (occ5 && q.yc && q.cellbox && q.lat.ncol > 0 && !q.stamps)
-      kern = mf_spmv<true, true, true, 0, 5>;
     static const int dbg = exp_env("MI_MF_DBG") ? atoi(exp_env("MI_MF_DBG")) : 0; // timing-only ablations (wrong results)
     if (dbg && q.yc && q.cellbox && q.lat.ncol > 0)
       kern = dbg == 2 ? mf_spmv<true, true, true, 2> : dbg == 4 ? mf_spmv<true, true, true, 4> : dbg == 8 ? mf_spmv<true, true, true, 8> :
              dbg == 14 ? mf_spmv<true, true, true, 14> : dbg == 6 ? mf_spmv<true, true, true, 6> : kern;
 #else
-    constexpr bool occ5 = false;
-    constexpr int  dbg  = 0;
+    constexpr int dbg = 0;
 #endif
     // opt-in: fp32 arithmetic on fp32 records (the production shape; MfParams::qrec32 set by the caller for smoother products only)
-    if (q.qrec32 && !occ5 && !dbg && !q.stamps && q.yc && q.cellbox && q.lat.ncol > 0)
-      kern = mf_spmv<true, true, true, 0, 4, float>;
+    if (q.qrec32 && !dbg && !q.stamps && q.yc && q.cellbox && q.lat.ncol > 0)
+      kern = mf_spmv<true, true, true, 0, float>;
     if (ev_start || ev_stop)
       hipExtLaunchKernelGGL(kern, dim3(grid), dim3(64), 0, s, ev_start, ev_stop, 0, q, cell_begin);
     else
@@ -7208,7 +6798,7 @@ namespace mi
       return;
     AsmParams q = p;
     q.xcd_chunk = (p.cell_count + 7) / 8;
-    hipLaunchKernelGGL((assemble_q2sf<true, 1024>), dim3(q.xcd_chunk * 8), dim3(64), 0, s, q);
+    hipLaunchKernelGGL((assemble_q2sf<true, true>), dim3(q.xcd_chunk * 8), dim3(64), 0, s, q);
   }
   void launch_residual_gather(const double *slots3, const int32_t *slot_base, const int32_t *slot_src, const uint8_t *cmask, double *rhs,
                               int64_t ndofs, hipStream_t s)

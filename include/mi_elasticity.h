@@ -356,11 +356,8 @@ int mi_set_profiling(mi_ctx *ctx, int enable);
  *  cg_fused_dot         1 | 0                      p.q partials in the product's epilogue | separate reduction          MI_CG_FUSED_DOT
  *  small_cg             1 | 0                      matrices <= 1 MiB: whole Jacobi-PCG in one launch | three launches   MI_SMALL_CG
  *                                                  per iteration
- *  asm_variant          0 | 9 | 1,2 | 3 | 4-8      3D Q2 element kernel: sum factorised | node-pair form | its chunk    -
- *                                                  sizes | experiments build only: the sum-factorised kernel as of
- *                                                  round 4 | round-5 A/B combinations (profiles/r05/asm_ab_*.txt)
- *  asm_split            0 | 1 | 2                  experiments build only: the tangent as point pass + tangent kernel    -
- *                                                  from the point records (profiles/r06/asm_split_ab_n59.txt: slower)
+ *  asm_variant          0 | 9 | 1,2                3D Q2 element kernel: sum factorised | node-pair form | its chunk    -
+ *                                                  sizes (3-8, the A/B forms of rounds 4-5, were removed: DESIGN.md C.1)
  *  mg_fuse              1 | 0 | 2                  smoother update fused into the product on small levels | never |     MI_MG_FUSE
  *                                                  always
  *  mf_slots_cell_major  -1 | 0 | 1 | 2             result slots of the matrix-free kernels: follows smoother_quadrature     -
