@@ -189,6 +189,39 @@ namespace mi_detail
     return L;
   }
 
+  // The cells of a node by arithmetic (mi::SlotLattice), from the lattice the cells' node ids come from.  Needs the colours in
+  // ascending order of their parity triple (the gathers add in that order); checked against the slot tables by build_slot_tables.
+  mi::SlotLattice build_slot_lattice(const mi::HostMesh &m, const mi::CellLattice &L, const std::vector<mi::CellLatticeRow> &rows)
+  {
+    mi::SlotLattice S{};
+    if (L.ncol <= 0 || m.dim != 3 || m.p != 2 || rows.size() < size_t(L.ncol) || m.nnodes >= (int64_t(1) << 31) ||
+        m.ncells * 27 >= (int64_t(1) << 31))
+      return S;
+    for (int v = 0; v < 8; ++v)
+      S.begin[v] = -1, S.mx[v] = 1, S.mxy[v] = 1;
+    int last = -1;
+    for (int c = 0; c < L.ncol; ++c)
+      {
+        int ci[3];
+        mi::HostMesh::split(m.cell_orig[size_t(L.begin[c])], m.reps, 3, ci);
+        const int v = (ci[0] & 1) | ((ci[1] & 1) << 1) | ((ci[2] & 1) << 2);
+        if (v <= last)
+          return mi::SlotLattice{};
+        last        = v;
+        S.begin[v]  = L.begin[c];
+        S.mx[v]     = rows[size_t(c)].mx;
+        S.mxy[v]    = rows[size_t(c)].mxy;
+      }
+    for (int d = 0; d < 3; ++d)
+      S.nc[d] = m.reps[d];
+    S.nn0        = L.nn0;
+    S.nn01       = L.nn01;
+    S.magic_nn0  = ~uint64_t(0) / uint64_t(S.nn0) + 1; // floor(2^64 / d) + 1 (d >= 3 is no power of two: floor((2^64 - 1) / d) is the same)
+    S.magic_nn01 = ~uint64_t(0) / uint64_t(S.nn01) + 1;
+    S.ncol       = L.ncol;
+    return S;
+  }
+
   mi::AsmParams asm_params(mi_ctx *c)
   {
     mi::AsmParams p{};
@@ -392,6 +425,18 @@ namespace mi_detail
            !c->active_sell_vals && c->d_dinv_blk;
   }
 
+  // tuning "mf_gather_lattice": what the four slot gathers run as -- 0 the slot tables, 1 slot positions by arithmetic
+  // (mi::SlotLattice: lattice ids in use, cell-major slots, the formula equal to the tables on every node), 2 the same with
+  // the two Chebyshev gathers in node tiles, where the owned nodes are whole planes of the last lattice direction
+  int gather_lattice_mode(const mi_ctx *c)
+  {
+    if (c->gather_lattice == 0 || c->slot_lat.ncol == 0 || c->lat.ncol == 0 || c->slots_layout != 1)
+      return 0;
+    const int     want  = c->gather_lattice < 0 ? 2 : c->gather_lattice;
+    const int64_t plane = c->slot_lat.nn01, n0 = c->own0 / 3, nn = c->own_n / 3;
+    return (want >= 2 && nn > 0 && n0 % plane == 0 && nn % plane == 0) ? want : 1;
+  }
+
   // what every launch of a matrix-free kernel takes from the context as it stands: mesh tables, 1D tables, material, the 27-point
   // records.  The call sites add what depends on the call: qrec / qrec32, vals / diagpos, x / y, the slot fields, sel_*, stamps.
   mi::MfParams mf_params(const mi_ctx *c)
@@ -524,16 +569,20 @@ namespace mi_detail
                 mi::launch_mf_spmv(f, 0, int32_t(c->mesh.ncells), c->stream, t >= 0 ? c0->stamps[size_t(t)].a : nullptr,
                                    t >= 0 ? c0->stamps[size_t(t)].b : nullptr);
               }
+            // (lattice meshes: the slots' positions by arithmetic, the Chebyshev gathers in node tiles -- "mf_gather_lattice")
+            const int                gmode = gather_lattice_mode(c);
+            const mi::SlotLattice   *sl    = gmode ? &c->slot_lat : nullptr;
+            const bool               tw    = gmode >= 2;
             if (cheb && cheb->xnext) // the smoother's step on the owned nodes, straight from the slots (three-term form)
               mi::launch_mf_gather_cheb3(f, cheb->b, cheb->dinv6, cheb->xprev, x, cheb->xnext, cheb->c1, cheb->c2, c->own0 / 3,
-                                         c->own_n / 3, c->stream);
+                                         c->own_n / 3, c->stream, sl, tw);
             else if (cheb) // ... with the update vector d, in place / the residual
               mi::launch_mf_gather_cheb(f, cheb->b, cheb->dinv, cheb->d, const_cast<double *>(x), y, cheb->c1, cheb->c2,
-                                        c->own0 / 3, c->own_n / 3, c->stream);
+                                        c->own0 / 3, c->own_n / 3, c->stream, sl, tw);
             else if (ebe_for_cg) // the CG's q = K p: the slot sum and the partials of p.q in one launch
-              mi::launch_mf_gather_dot(f, int64_t(c->mesh.nnodes) * 3, dotv, partials, c->grid_gdot, c->own0, c->own_n, c->stream);
+              mi::launch_mf_gather_dot(f, int64_t(c->mesh.nnodes) * 3, dotv, partials, c->grid_gdot, c->own0, c->own_n, c->stream, sl);
             else
-              mi::launch_mf_gather(f, int64_t(c->mesh.nnodes) * 3, c->stream);
+              mi::launch_mf_gather(f, int64_t(c->mesh.nnodes) * 3, c->stream, sl);
           }
         else
         for (int col = 0; col < c->mesh.ncolours; ++col)
@@ -989,6 +1038,25 @@ namespace mi_detail
         for (size_t k = 0; k < dst.size(); ++k)
           src[size_t(dst[k])] = place[k];
         dst = place;
+      }
+    // cell-major slots of a lattice mesh: the formula the gathers would use instead of base / src, on EVERY node against
+    // the tables -- count and every position; any difference and the gathers keep the tables (a wrong formula must not
+    // become a read out of range)
+    c->slot_lat = mi::SlotLattice{};
+    if (layout == 1 && npc == 27)
+      {
+        mi::SlotLattice S = build_slot_lattice(c->mesh, c->lat_built, c->lat_rows_host);
+        for (int64_t n = 0; n < nn && S.ncol > 0; ++n)
+          {
+            int32_t   list[8];
+            const int cnt = mi::slot_lattice_list(S, uint32_t(n), list);
+            bool      same = cnt == base[size_t(n) + 1] - base[size_t(n)];
+            for (int q = 0; q < cnt && same; ++q)
+              same = list[q] == src[size_t(base[size_t(n)]) + q];
+            if (!same)
+              S = mi::SlotLattice{};
+          }
+        c->slot_lat = S;
       }
     const bool cell_major = layout != 0;
     int rc = upload(c, &c->d_mf_dst, dst);
@@ -3031,6 +3099,8 @@ int mi_set_tuning(mi_ctx *c, const char *key, int value)
         m->mf_slots = value;
       else if (k == "xcd_remap" && (value == 0 || value == 1))
         m->xcd_remap = value;
+      else if (k == "mf_gather_lattice" && value >= -1 && value <= 2) // slot gathers: 0 tables, 1 by arithmetic, 2 + node tiles, -1 default
+        m->gather_lattice = value;
       else if (k == "cell_lattice" && (value == 0 || value == 1)) // A/B: node ids by arithmetic (1, default) or from conn
         m->lat = value ? m->lat_built : mi::CellLattice{};
       else if (k == "sell_unroll" && value >= -2 && value <= 8 && value != 0)
@@ -3169,6 +3239,10 @@ int mi_get_tuning(mi_ctx *c, const char *key, int *value)
     *value = m->asm_variant;
   else if (k == "cell_lattice")
     *value = m->lat.ncol > 0 ? 1 : 0;
+  else if (k == "mf_gather_lattice")
+    *value = m->gather_lattice;
+  else if (k == "mf_gather_lattice_active") // what the slot gathers run as (0 until the slots exist)
+    *value = gather_lattice_mode(m);
   else if (k == "cut_axis") // the box direction the slabs are cut along: 1 / 2 / 3 = x / y / z, 0: not decomposed
     *value = c->team->size > 1 ? c->team->amap.ext_axis[c->team->dim - 1] + 1 : 0;
   else if (k == "cg_speculate")

@@ -158,6 +158,10 @@ struct mi_ctx
   mi::CellLattice lat_built;          // ... as built at creation (tuning "cell_lattice" 0 / 1 switches lat)
   mi::CellLatticeRow *d_lat_rows = nullptr; // its per-colour rows
   std::vector<mi::CellLatticeRow> lat_rows_host; // (host copy: layer ranges of a slab's product, enqueue_spmv)
+  mi::SlotLattice slot_lat;           // cell-major slots of a lattice mesh: a node's slot positions by arithmetic, as checked against
+                                      // the slot tables by build_slot_tables (ncol == 0: unavailable, the gathers read the tables)
+  int       gather_lattice = -1;      // tuning "mf_gather_lattice": 0 the gathers read the tables, 1 positions by arithmetic, 2 ... and
+                                      // the Chebyshev gathers in node tiles; -1 (default): 2 where it applies
   double   *d_cellbox = nullptr; // with d_qrec when every local cell is an axis-parallel box: [ncells][4] = 1/h, volume
   bool      ke_valid = false; // d_ke / d_qrec belong to the current tangent
   int64_t   ebe_products = 0; // element-tangent products so far (profiling samples every 6th)
@@ -283,6 +287,7 @@ namespace mi_detail
   int            direct_factor_solve(mi_ctx *c, const double *vals, const double *b, double *x, bool factor, bool solve);
   void           refresh_vals32(mi_ctx *c); // fp32-rounded copy of the current tangent (opt-in smoother storage), if stale
   int            element_form(const mi_ctx *c); // 2 quadrature-point records, 1 element tangents, 0 none (current tangent)
+  int            gather_lattice_mode(const mi_ctx *c); // what the slot gathers run as ("mf_gather_lattice_active")
   bool           mf_gather_fusable(const mi_ctx *c); // the smoother's product is the single-launch matrix-free form
   mi::SellParams sell_params(mi_ctx *c, const double *x, double *y, const double *dotv, double *partials,
                              const int32_t *done);

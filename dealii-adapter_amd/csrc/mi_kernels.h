@@ -41,6 +41,89 @@ namespace mi
     const CellLatticeRow *rows = nullptr; // [8] device
   };
 
+  // The other direction (slot gathers): the cells of a NODE and where their contributions lie, without reading slot_base /
+  // slot_src.  Cell-major slots (dst[cell][a] = cell * 27 + a) on a lattice of Q2 cells: node (i, j, k) = n = i + nn0 j + nn01 k
+  // with an odd coordinate lies inside one cell along that direction (local index 1), with an even one it is the last node
+  // (2) of cell h - 1 and the first (0) of cell h = i / 2, where those exist.  The colours are the parity triples of the
+  // cells in ascending order of  v = px | py << 1 | pz << 2  (those that occur), so "ascending colour-sorted position" --
+  // the processing order the slot tables hold -- is ascending v, and the cell of parity triple v sits at position
+  //   begin[v] + rz mxy[v] + ry mx[v] + rx,   r = (cell index - parity) / 2  per direction
+  // (the inverse of lattice_row_node0).  Tables by PARITY TRIPLE, in the kernel's argument block: every index is a
+  // compile-time constant after unrolling, so they are scalar registers.  n -> (i, j, k) by multiplications with
+  // floor(2^64 / d) + 1, upper half of the product (exact for n, d < 2^32: n e < 2^64 with e = M d - 2^64 <= d).
+  // Built by build_slot_lattice and checked node by node against the tables by build_slot_tables (mi_ctx.cpp): any
+  // difference leaves ncol = 0 and the gathers keep reading the tables.
+  struct SlotLattice
+  {
+    int32_t  ncol = 0;                 // 0: not available
+    int32_t  nc[3] = {};               // cells per direction
+    int32_t  nn0 = 0, nn01 = 0;        // nodes per line, per plane
+    uint64_t magic_nn0 = 0, magic_nn01 = 0;
+    int32_t  begin[8] = {}, mx[8] = {}, mxy[8] = {}; // by parity triple; begin -1: no cell has it
+  };
+  __host__ __device__ inline uint32_t slot_lattice_div(const uint32_t n, const uint64_t magic)
+  {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return uint32_t(__umul64hi(uint64_t(n), magic));
+#else
+    return uint32_t((static_cast<unsigned __int128>(n) * magic) >> 64);
+#endif
+  }
+  __host__ __device__ inline void slot_lattice_ijk(const SlotLattice &L, const uint32_t n, int32_t &i, int32_t &j, int32_t &k)
+  {
+    const uint32_t kk = slot_lattice_div(n, L.magic_nn01), rem = n - kk * uint32_t(L.nn01);
+    const uint32_t jj = slot_lattice_div(rem, L.magic_nn0);
+    i = int32_t(rem - jj * uint32_t(L.nn0)), j = int32_t(jj), k = int32_t(kk);
+  }
+  // one direction: the cell of parity P that holds node coordinate i -- its index within the colour's sub-lattice, the
+  // node's local index there, whether that cell exists (mesh faces and slab ends: it does not)
+  template <int P>
+  __host__ __device__ inline void slot_lattice_axis(const int32_t i, const int32_t ncells, int32_t &r, int32_t &l, bool &ok)
+  {
+    const int32_t h = i >> 1, odd = i & 1;
+    const bool    at_h = (h & 1) == P; // cell h has the parity (else cell h - 1 has)
+    r  = (h - (at_h ? 0 : 1)) >> 1;
+    l  = at_h ? odd : 2;
+    ok = at_h ? h < ncells : (odd == 0 && h >= 1);
+  }
+  // slot positions (cell position * 27 + local node) of the contributions to node (i, j, k), by parity triple = in
+  // processing order; -1: no contribution (never an address)
+  __host__ __device__ inline void slot_lattice_slots(const SlotLattice &L, const int32_t i, const int32_t j, const int32_t k,
+                                                     int32_t slot[8])
+  {
+    int32_t rx[2], lx[2], ry[2], ly[2], rz[2], lz[2];
+    bool    okx[2], oky[2], okz[2];
+    slot_lattice_axis<0>(i, L.nc[0], rx[0], lx[0], okx[0]);
+    slot_lattice_axis<1>(i, L.nc[0], rx[1], lx[1], okx[1]);
+    slot_lattice_axis<0>(j, L.nc[1], ry[0], ly[0], oky[0]);
+    slot_lattice_axis<1>(j, L.nc[1], ry[1], ly[1], oky[1]);
+    slot_lattice_axis<0>(k, L.nc[2], rz[0], lz[0], okz[0]);
+    slot_lattice_axis<1>(k, L.nc[2], rz[1], lz[1], okz[1]);
+#pragma unroll
+    for (int v = 0; v < 8; ++v)
+      {
+        const int  px = v & 1, py = (v >> 1) & 1, pz = v >> 2;
+        const bool ok = okx[px] && oky[py] && okz[pz] && L.begin[v] >= 0;
+        const int32_t pos = L.begin[v] + rz[pz] * L.mxy[v] + ry[py] * L.mx[v] + rx[px];
+        // (all ones over the position instead of a select of it: the eight positions stay straight-line code)
+        slot[v] = (pos * 27 + lx[px] + 3 * ly[py] + 9 * lz[pz]) | (ok ? 0 : -1);
+      }
+  }
+  // ... of node n as a list: the number of contributing cells, their positions in processing order (what slot_src holds in
+  // [slot_base[n], slot_base[n + 1]) with cell-major slots) -- the form build_slot_tables compares with the tables
+  __host__ __device__ inline int slot_lattice_list(const SlotLattice &L, const uint32_t n, int32_t list[8])
+  {
+    int32_t i, j, k, slot[8];
+    slot_lattice_ijk(L, n, i, j, k);
+    slot_lattice_slots(L, i, j, k, slot);
+    int cnt = 0;
+#pragma unroll
+    for (int v = 0; v < 8; ++v)
+      if (slot[v] >= 0)
+        list[cnt++] = slot[v];
+    return cnt;
+  }
+
   // arguments of assemble_cells / neumann_faces (device pointers unless noted)
   struct AsmParams
   {
@@ -270,10 +353,11 @@ namespace mi
   // writes those records from u + du
   void launch_mf_spmv27(const MfParams &p, int32_t cell_count, hipStream_t s, hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr);
   void launch_mf_records27(const MfParams &p, const double *u, const double *du, double *rec27, int32_t cell_count, hipStream_t s);
-  void launch_mf_gather(const MfParams &p, int64_t ndofs, hipStream_t s);
+  // (sl with ncol > 0, all four gathers: the lattice form -- slot positions by arithmetic, see SlotLattice)
+  void launch_mf_gather(const MfParams &p, int64_t ndofs, hipStream_t s, const SlotLattice *sl = nullptr);
   // ... with the partials of dotv . y over the owned dofs (fixed grid): the CG's product on the matrix-free fine level
   void launch_mf_gather_dot(const MfParams &p, int64_t ndofs, const double *dotv, double *partials, int grid, int64_t own0,
-                            int64_t own_n, hipStream_t s);
+                            int64_t own_n, hipStream_t s, const SlotLattice *sl = nullptr);
   // matrix-free fine level (round 6): the nodes' diagonal blocks from the point records -- every cell into its own slots
   // [nslots][6] (MfParams::dst), then summed per node under the assembled matrix's constraint rule (see mf_diag)
   void launch_mf_diag(const MfParams &p, double *slots6, int32_t cell_count, hipStream_t s);
@@ -293,9 +377,11 @@ namespace mi
                              const int32_t *diagpos, double *blk, double *dinv, double *dinv_blk, double *sym6, int64_t nnodes, hipStream_t s);
   // gather fused with the smoother's Chebyshev step (d != null: x += d in place) or residual (d == null: yres = b - K x)
   void launch_mf_gather_cheb3(const MfParams &p, const double *b, const double *dinv6, const double *xprev, const double *xcur,
-                              double *xnext, double c1, double c2, int64_t node0, int64_t nnodes, hipStream_t s);
+                              double *xnext, double c1, double c2, int64_t node0, int64_t nnodes, hipStream_t s,
+                              const SlotLattice *sl = nullptr, bool tiles = false);
   void launch_mf_gather_cheb(const MfParams &p, const double *b, const double *dinv, double *d, double *xio, double *yres,
-                             double c1, double c2, int64_t node0, int64_t nnodes, hipStream_t s);
+                             double c1, double c2, int64_t node0, int64_t nnodes, hipStream_t s, const SlotLattice *sl = nullptr,
+                             bool tiles = false);
   // coarsest multigrid level: dense inverse of the level's sliced-ELL matrix (n <= 96, -1 otherwise) and its application
   int  launch_dense_inverse_from_sell(int dim, const SellParams &p, int n, double *out, hipStream_t s);
   void launch_dense_apply(const double *inv, const double *b, double *x, int n, hipStream_t s);

@@ -3044,6 +3044,265 @@ namespace mi
       partials[blockIdx.x] = acc;
   }
 
+  // ---- the same four gathers on lattice meshes with cell-major slots (SlotLattice, mi_kernels.h): a node's contributions
+  // are found by arithmetic on its coordinates instead of through slot_base -> slot_src -> value.  Nothing depends on a
+  // loaded index any more, so cmask, the vector operands and the (one to eight) contributing slots go out as ONE batch of
+  // loads; the sum runs over the same values in the same order (ascending parity triple = ascending position), so every
+  // result has the bits of the table form.  Constrained dofs: the slots are read all the same (every cell writes all of
+  // its 81), then replaced.
+  __device__ __forceinline__ void mf_slot_load_lattice(const MfParams &prm, const int32_t (&slot)[8], const int c, double (&v)[8])
+  {
+#pragma unroll
+    for (int p = 0; p < 8; ++p)
+      v[p] = slot[p] >= 0 ? prm.yc[int64_t(slot[p]) * 3 + c] : 0.0;
+  }
+  __device__ __forceinline__ double mf_slot_add_lattice(const int32_t (&slot)[8], const double (&v)[8])
+  {
+    double s    = 0.0;
+    bool   have = false;
+#pragma unroll
+    for (int p = 0; p < 8; ++p)
+      if (slot[p] >= 0)
+        {
+          s    = have ? s + v[p] : v[p];
+          have = true;
+        }
+    return s;
+  }
+
+  __global__ __launch_bounds__(256) void mf_gather_lat(MfParams prm, SlotLattice sl, int64_t ndofs)
+  {
+    const int64_t g = int64_t(blockIdx.x) * 256 + threadIdx.x;
+    if (g >= ndofs)
+      return;
+    const int64_t n = g / 3;
+    const int     c = int(g - n * 3);
+    int32_t       i, j, k, slot[8];
+    double        v[8];
+    slot_lattice_ijk(sl, uint32_t(n), i, j, k);
+    slot_lattice_slots(sl, i, j, k, slot);
+    const uint8_t cm = prm.cmask[n];
+    mf_slot_load_lattice(prm, slot, c, v);
+    double s = mf_slot_add_lattice(slot, v);
+    if ((cm >> c) & 1)
+      {
+        const int32_t dp = prm.diagpos[n]; // -1: ghost node of a slab (its y is never read)
+        s                = dp >= 0 ? prm.vals[int64_t(dp) * 9 + c * 4] * prm.x[g] : 0.0;
+      }
+    prm.y[g] = s;
+  }
+
+  __global__ __launch_bounds__(256) void mf_gather_dot_lat(MfParams prm, SlotLattice sl, int64_t ndofs,
+                                                           const double *__restrict__ dotv, double *partials, int64_t own0,
+                                                           int64_t own_n)
+  {
+    __shared__ double s_red[4];
+    double            acc = 0.0;
+    const int64_t     per = ((ndofs + gridDim.x - 1) / gridDim.x + 255) / 256 * 256;
+    const int64_t     g0 = int64_t(blockIdx.x) * per, g1 = imin64(ndofs, g0 + per);
+    for (int64_t g = g0 + threadIdx.x; g < g1; g += 256)
+      {
+        const int64_t n = g / 3;
+        const int     c = int(g - n * 3);
+        int32_t       i, j, k, slot[8];
+        double        v[8];
+        slot_lattice_ijk(sl, uint32_t(n), i, j, k);
+        slot_lattice_slots(sl, i, j, k, slot);
+        const uint8_t cm   = prm.cmask[n];
+        const bool    own  = g >= own0 && g < own0 + own_n;
+        const double  dv   = own ? dotv[g] : 0.0;
+        mf_slot_load_lattice(prm, slot, c, v);
+        double s = mf_slot_add_lattice(slot, v);
+        if ((cm >> c) & 1)
+          {
+            const int32_t dp = prm.diagpos[n];
+            s                = dp >= 0 ? prm.vals[int64_t(dp) * 9 + c * 4] * prm.x[g] : 0.0;
+          }
+        prm.y[g] = s;
+        if (own)
+          acc = fma(dv, s, acc);
+      }
+    acc = block_sum<256>(acc, s_red);
+    if (threadIdx.x == 0)
+      partials[blockIdx.x] = acc;
+  }
+
+  // Which node a thread of the two Chebyshev gathers takes.  W == 0: 64 consecutive nodes of [node0, node0 + nnodes) per
+  // workgroup, as the table form.  W > 0 (node tiles; the range is whole planes of the last direction): a workgroup of
+  // 4 x W x 3 threads owns the 2 x 2 node lines (j in {2J, 2J+1}, k in {2K, 2K+1}) of one row of cells and walks a segment of
+  // MF_TILE_SEG nodes of them along x, W nodes of each line per step.  A cell's 648-byte run of slots holds nine 72-byte pieces,
+  // one per node line, and a 128-byte line of memory holds pieces of two or three of them: with one node line per workgroup
+  // those went through different workgroups (and L2s), 14 line fetches per cell for 5 lines of data; here the four node lines
+  // that meet in a row of cells fetch them through one workgroup's caches.  Every run of b / x / D^-1 along x stays W x 24 bytes
+  // long and is continued by the same workgroup's next step.
+  // W = 64 (768 threads, two steps per segment): measured against 16 and 32 at 59^3 cells, mf_gather_cheb3 75.3 | 79.2 | 77.4 us
+  // (profiles/slot_gather_lattice/README.md)
+  constexpr int MF_TILE_SEG = 128, MF_TILE_W = 64;
+  template <int W>
+  struct MfGatherMap
+  {
+    static constexpr int NT = W ? 12 * W : 192;
+    int32_t j = 0, k = 0, x0 = 0, xi = 0;
+    bool    line_in = false;
+    __device__ __forceinline__ MfGatherMap(const SlotLattice &sl, const int m, const int64_t node0, const int64_t nnodes)
+    {
+      if constexpr (W > 0)
+        {
+          const int32_t k0 = int32_t(slot_lattice_div(uint32_t(node0), sl.magic_nn01));
+          const int32_t k1 = k0 + int32_t(slot_lattice_div(uint32_t(nnodes), sl.magic_nn01));
+          const int     line = m / W;
+          xi      = m % W;
+          j       = int32_t(blockIdx.y) * 2 + (line & 1);
+          k       = ((k0 >> 1) + int32_t(blockIdx.z)) * 2 + (line >> 1);
+          x0      = int32_t(blockIdx.x) * MF_TILE_SEG;
+          line_in = j <= 2 * sl.nc[1] && k >= k0 && k < k1;
+        }
+    }
+    static __device__ __forceinline__ int steps() { return W ? MF_TILE_SEG / W : 1; }
+    // node of step st: false where the thread has none
+    __device__ __forceinline__ bool node(const SlotLattice &sl, const int st, const int m, const int64_t node0, const int64_t nnodes,
+                                         int64_t &n, int32_t &i, int32_t &jj, int32_t &kk) const
+    {
+      if constexpr (W > 0)
+        {
+          i  = x0 + st * W + xi;
+          jj = j, kk = k;
+          const bool in = line_in && i < sl.nn0;
+          n             = in ? int64_t(i) + int64_t(sl.nn0) * j + int64_t(sl.nn01) * k : node0;
+          return in;
+        }
+      else
+        {
+          const int64_t nl = int64_t(blockIdx.x) * 64 + m;
+          const bool    in = nl < nnodes;
+          n                = in ? node0 + nl : node0;
+          slot_lattice_ijk(sl, uint32_t(n), i, jj, kk);
+          return in;
+        }
+    }
+    // (uniform) whether step st + 1 has nodes
+    __device__ __forceinline__ bool more(const SlotLattice &sl, const int st) const
+    {
+      return W > 0 && st + 1 < steps() && x0 + (st + 1) * W < sl.nn0;
+    }
+  };
+
+  template <int W>
+  __global__ __launch_bounds__(MfGatherMap<W>::NT) void mf_gather_cheb_lat(MfParams prm, SlotLattice sl, const double *__restrict__ b,
+                                                                          const double *__restrict__ dinv, double *d, double *xio,
+                                                                          double *yres, double c1, double c2, int64_t node0,
+                                                                          int64_t nnodes)
+  {
+    constexpr int NT = MfGatherMap<W>::NT;
+    __shared__ double s_res[2][NT]; // (two buffers: a step's writes never meet the reads of the step before)
+    const int            ld = threadIdx.x, c = ld % 3, m = ld / 3;
+    const MfGatherMap<W> map(sl, m, node0, nnodes);
+    for (int st = 0;; ++st)
+      {
+        int64_t    n;
+        int32_t    i, j, k, slot[8];
+        double     v[8];
+        const bool in = map.node(sl, st, m, node0, nnodes, n, i, j, k);
+        const int64_t g = n * 3 + c;
+        double     res = 0.0, a0 = 0.0, a1 = 0.0, a2 = 0.0, dold = 0.0, xold = 0.0;
+        if (in)
+          {
+            slot_lattice_slots(sl, i, j, k, slot);
+            const uint8_t cm = prm.cmask[n];
+            const double  bv = b[g];
+            if (d)
+              {
+                a0 = dinv[g * 3], a1 = dinv[g * 3 + 1], a2 = dinv[g * 3 + 2];
+                dold = c1 != 0.0 ? d[g] : 0.0;
+                xold = xio[g];
+              }
+            mf_slot_load_lattice(prm, slot, c, v);
+            double q = mf_slot_add_lattice(slot, v);
+            if ((cm >> c) & 1)
+              q = prm.vals[int64_t(prm.diagpos[n]) * 9 + c * 4] * prm.x[g];
+            res = bv - q;
+          }
+        if (!d)
+          {
+            if (in)
+              yres[g] = res;
+          }
+        else
+          {
+            double *sr = s_res[st & 1];
+            sr[ld]     = res;
+            __syncthreads();
+            if (in)
+              {
+                const int r0 = (ld / 3) * 3;
+                double    s  = 0.0;
+                s += a0 * sr[r0];
+                s += a1 * sr[r0 + 1];
+                s += a2 * sr[r0 + 2];
+                const double dn = (c1 != 0.0 ? c1 * dold : 0.0) + c2 * s;
+                d[g]            = dn;
+                xio[g]          = xold + dn;
+              }
+          }
+        if (!map.more(sl, st))
+          break;
+      }
+  }
+
+  template <int W>
+  __global__ __launch_bounds__(MfGatherMap<W>::NT) void mf_gather_cheb3_lat(MfParams prm, SlotLattice sl, const double *__restrict__ b,
+                                                                           const double *__restrict__ dinv6, const double *xprev,
+                                                                           const double *__restrict__ xcur, double *xnext,
+                                                                           double c1, double c2, int64_t node0, int64_t nnodes)
+  {
+    constexpr int NT = MfGatherMap<W>::NT;
+    __shared__ double s_res[2][NT];
+    const int            ld = threadIdx.x, c = ld % 3, m = ld / 3;
+    const MfGatherMap<W> map(sl, m, node0, nnodes);
+    for (int st = 0;; ++st)
+      {
+        int64_t    n;
+        int32_t    i, j, k, slot[8];
+        double     v[8];
+        const bool in = map.node(sl, st, m, node0, nnodes, n, i, j, k);
+        const int64_t g = n * 3 + c;
+        double     res = 0.0, xc = 0.0, xp = 0.0, a0 = 0.0, a1 = 0.0, a2 = 0.0;
+        if (in)
+          {
+            slot_lattice_slots(sl, i, j, k, slot);
+            const uint8_t cm = prm.cmask[n];
+            // row c of the symmetric block (xx yy zz xy xz yz)
+            const double *q6 = dinv6 + n * 6;
+            a0               = q6[c == 0 ? 0 : (c == 1 ? 3 : 4)];
+            a1               = q6[c == 0 ? 3 : (c == 1 ? 1 : 5)];
+            a2               = q6[c == 0 ? 4 : (c == 1 ? 5 : 2)];
+            xc               = xcur[g];
+            xp               = (c1 != 0.0 && xprev) ? xprev[g] : 0.0;
+            const double bv  = b[g];
+            mf_slot_load_lattice(prm, slot, c, v);
+            double q = mf_slot_add_lattice(slot, v);
+            if ((cm >> c) & 1)
+              q = prm.vals[int64_t(prm.diagpos[n]) * 9 + c * 4] * xc;
+            res = bv - q;
+          }
+        double *sr = s_res[st & 1];
+        sr[ld]     = res;
+        __syncthreads();
+        if (in)
+          {
+            const int r0 = (ld / 3) * 3;
+            double    s  = 0.0;
+            s += a0 * sr[r0];
+            s += a1 * sr[r0 + 1];
+            s += a2 * sr[r0 + 2];
+            const double dn = (c1 != 0.0 ? c1 * (xc - xp) : 0.0) + c2 * s;
+            xnext[g]        = xc + dn;
+          }
+        if (!map.more(sl, st))
+          break;
+      }
+  }
+
   // ------------------------------------------------------------------ matrix-free fine level: the diagonal blocks (round 6)
   // With the fine level matrix-free end to end (tuning "fine_level" 1) nothing multiplies the assembled fine tangent any
   // more; what the level still needs of it are the 3x3 DIAGONAL blocks K_aa of every node: the block-Jacobi smoother's
@@ -3512,7 +3771,8 @@ namespace mi
       // values of the table: no address and no value held across the gradient stages.  (The compiler at hand turns each
       // selection into one per-lane load from a selected address, here: three 8-byte loads of one cache line that every wave
       // reads, the only global loads left behind the batch on boxes.  Declaring the values uniform with readfirstlane makes
-      // them scalar operands, 92 registers; not measured yet -- profiles/smoother_load_batch/README.md)
+      // them scalar operands, but <true, true> then compiles to 96 registers and 8 bytes of scratch: not taken --
+      // profiles/slot_gather_lattice/README.md)
 #define MF27_PICK(t_, q_) ((q_) == 0 ? (t_)[0] : (q_) == 1 ? (t_)[1] : (t_)[2])
       const double *__restrict__ qw = prm.tab27 + 18;
       const double wq = MF27_PICK(qw, qx) * MF27_PICK(qw, qy) * MF27_PICK(qw, qz);
@@ -6767,30 +7027,58 @@ namespace mi
       hipLaunchKernelGGL(dense_apply, dim3(1), dim3(128), 0, s, inv, b, x, n);
   }
 
+  // grid of the node-tile form (MfGatherMap<W>): x segments, pairs of node lines, pairs of the range's node planes
+  static dim3 mf_tile_grid(const SlotLattice &sl, int64_t node0, int64_t nnodes)
+  {
+    const int64_t k0 = node0 / sl.nn01, k1 = k0 + nnodes / sl.nn01;
+    return dim3(unsigned((sl.nn0 + MF_TILE_SEG - 1) / MF_TILE_SEG), unsigned(sl.nc[1] + 1), unsigned(((k1 - 1) >> 1) - (k0 >> 1) + 1));
+  }
+  // sl (with ncol > 0): the lattice form; tiles: in node tiles (the caller has checked that the range is whole planes)
   void launch_mf_gather_cheb(const MfParams &p, const double *b, const double *dinv, double *d, double *xio, double *yres,
-                             double c1, double c2, int64_t node0, int64_t nnodes, hipStream_t s)
+                             double c1, double c2, int64_t node0, int64_t nnodes, hipStream_t s, const SlotLattice *sl, bool tiles)
   {
     if (nnodes <= 0)
       return;
-    hipLaunchKernelGGL(mf_gather_cheb, dim3(int((nnodes + 63) / 64)), dim3(192), 0, s, p, b, dinv, d, xio, yres, c1, c2,
-                       node0, nnodes);
+    if (sl && sl->ncol > 0 && tiles)
+      hipLaunchKernelGGL(mf_gather_cheb_lat<MF_TILE_W>, mf_tile_grid(*sl, node0, nnodes), dim3(MfGatherMap<MF_TILE_W>::NT), 0, s, p,
+                         *sl, b, dinv, d, xio, yres, c1, c2, node0, nnodes);
+    else if (sl && sl->ncol > 0)
+      hipLaunchKernelGGL(mf_gather_cheb_lat<0>, dim3(int((nnodes + 63) / 64)), dim3(192), 0, s, p, *sl, b, dinv, d, xio, yres, c1, c2,
+                         node0, nnodes);
+    else
+      hipLaunchKernelGGL(mf_gather_cheb, dim3(int((nnodes + 63) / 64)), dim3(192), 0, s, p, b, dinv, d, xio, yres, c1, c2,
+                         node0, nnodes);
   }
   void launch_mf_gather_cheb3(const MfParams &p, const double *b, const double *dinv6, const double *xprev, const double *xcur,
-                              double *xnext, double c1, double c2, int64_t node0, int64_t nnodes, hipStream_t s)
+                              double *xnext, double c1, double c2, int64_t node0, int64_t nnodes, hipStream_t s,
+                              const SlotLattice *sl, bool tiles)
   {
     if (nnodes <= 0)
       return;
-    hipLaunchKernelGGL(mf_gather_cheb3, dim3(int((nnodes + 63) / 64)), dim3(192), 0, s, p, b, dinv6, xprev, xcur, xnext, c1, c2,
-                       node0, nnodes);
+    if (sl && sl->ncol > 0 && tiles)
+      hipLaunchKernelGGL(mf_gather_cheb3_lat<MF_TILE_W>, mf_tile_grid(*sl, node0, nnodes), dim3(MfGatherMap<MF_TILE_W>::NT), 0, s, p,
+                         *sl, b, dinv6, xprev, xcur, xnext, c1, c2, node0, nnodes);
+    else if (sl && sl->ncol > 0)
+      hipLaunchKernelGGL(mf_gather_cheb3_lat<0>, dim3(int((nnodes + 63) / 64)), dim3(192), 0, s, p, *sl, b, dinv6, xprev, xcur, xnext,
+                         c1, c2, node0, nnodes);
+    else
+      hipLaunchKernelGGL(mf_gather_cheb3, dim3(int((nnodes + 63) / 64)), dim3(192), 0, s, p, b, dinv6, xprev, xcur, xnext, c1, c2,
+                         node0, nnodes);
   }
-  void launch_mf_gather(const MfParams &p, int64_t ndofs, hipStream_t s)
+  void launch_mf_gather(const MfParams &p, int64_t ndofs, hipStream_t s, const SlotLattice *sl)
   {
-    hipLaunchKernelGGL(mf_gather, dim3(int((ndofs + 255) / 256)), dim3(256), 0, s, p, ndofs);
+    if (sl && sl->ncol > 0)
+      hipLaunchKernelGGL(mf_gather_lat, dim3(int((ndofs + 255) / 256)), dim3(256), 0, s, p, *sl, ndofs);
+    else
+      hipLaunchKernelGGL(mf_gather, dim3(int((ndofs + 255) / 256)), dim3(256), 0, s, p, ndofs);
   }
   void launch_mf_gather_dot(const MfParams &p, int64_t ndofs, const double *dotv, double *partials, int grid, int64_t own0,
-                            int64_t own_n, hipStream_t s)
+                            int64_t own_n, hipStream_t s, const SlotLattice *sl)
   {
-    hipLaunchKernelGGL(mf_gather_dot, dim3(grid), dim3(256), 0, s, p, ndofs, dotv, partials, own0, own_n);
+    if (sl && sl->ncol > 0)
+      hipLaunchKernelGGL(mf_gather_dot_lat, dim3(grid), dim3(256), 0, s, p, *sl, ndofs, dotv, partials, own0, own_n);
+    else
+      hipLaunchKernelGGL(mf_gather_dot, dim3(grid), dim3(256), 0, s, p, ndofs, dotv, partials, own0, own_n);
   }
   void launch_point_pass_slots(const AsmParams &p, hipStream_t s)
   {
