@@ -419,6 +419,16 @@ namespace mi_detail
            !(c->smoother_precision == 32 && c->qrec32_valid);
   }
 
+  // the smoother's fine-level products of a Q3 matrix-free level run mf_spmv_q3s on the 64-point records of the current
+  // tangent ("smoother_quadrature_q3" 4).  The one test for it, as smoother_runs_q27 is for Q2: enqueue_spmv's dispatch (with
+  // the call's own condition: a smoother product) and the "smoother_quadrature_q3_active" query both read it.  The rest of it is
+  // what takes a smoother product of the level into the one-launch branch of enqueue_spmv at all.
+  bool smoother_runs_q3s(const mi_ctx *c)
+  {
+    return c->smoother_points_q3 == 4 && c->qrec_q3s_valid && c->d_qrec_q3 && c->d_qrec_q3s && c->d_tab_q3s && c->mf_fine &&
+           element_form(c) == 2 && c->mf_slots && c->d_mf_yc && !c->active_sell_vals;
+  }
+
   bool mf_gather_fusable(const mi_ctx *c)
   {
     return element_form(c) == 2 && c->ebe == 2 && c->mf_slots && c->d_mf_yc && c->precond_storage == 64 &&
@@ -444,6 +454,7 @@ namespace mi_detail
     mi::MfParams f{};
     f.conn = c->d_conn, f.first = c->d_node_first, f.cmask = c->d_cmask, f.cverts = c->d_cverts, f.cellbox = c->d_cellbox;
     f.tab1d = c->d_tab, f.tab27 = c->d_tab27, f.lat = c->lat, f.qrec27 = c->d_qrec27;
+    f.qrec_q3s = c->d_qrec_q3s, f.tab_q3s = c->d_tab_q3s;
     f.mu = c->mat.mu, f.kappa = c->kappa, f.mass = c->alpha[1] * c->mat.rho;
     return f;
   }
@@ -472,8 +483,10 @@ namespace mi_detail
         // while the halo is in flight, the others as part 2; every cell still writes its own slots, so the sum is the same
         // smoother quadrature 3: the smoother's products (never the CG's) from the 27-point records, two cells per wave, in the
         // same launches over layers
-        // a Q3 fine level (one slab): every product of the level, the smoother's included, is mf_spmv_q3 in one launch
+        // a Q3 fine level (one slab): every product of the level is mf_spmv_q3 in one launch; the smoother's are mf_spmv_q3s on
+        // the 64-point records where "smoother_quadrature_q3" 4 holds (same slots, same gathers)
         const bool q3  = c->d_qrec_q3 != nullptr;
+        const bool q3s = q3 && smoother && !ebe_for_cg && smoother_runs_q3s(c);
         const bool q27 = smoother && !ebe_for_cg && smoother_runs_q27(c);
         const bool mf_split = part != 0 && kind == 2 && c->mf_slots && c->d_mf_yc && c->lat.ncol > 0 && c->team->mf_overlap &&
                               !(ebe_for_cg && !mf_all) && !q3;
@@ -554,8 +567,9 @@ namespace mi_detail
             else if (q3)
               {
                 const int t = sample ? tic(c0, MI_T_EBE_LAUNCH, true) : -1;
-                mi::launch_mf_spmv_q3(f, int32_t(c->mesh.ncells), c->stream, t >= 0 ? c0->stamps[size_t(t)].a : nullptr,
-                                      t >= 0 ? c0->stamps[size_t(t)].b : nullptr);
+                (q3s ? mi::launch_mf_spmv_q3s : mi::launch_mf_spmv_q3)(f, int32_t(c->mesh.ncells), c->stream,
+                                                                       t >= 0 ? c0->stamps[size_t(t)].a : nullptr,
+                                                                       t >= 0 ? c0->stamps[size_t(t)].b : nullptr);
               }
             else if (q27)
               {
@@ -928,6 +942,13 @@ namespace mi_detail
     if (c->d_qrec_q3) // Q3 fine level: F, J^(-2/3), 1/J at the 125 points of the assembly's rule, from the state of the residual
       mi::launch_mf_records_q3(mf_params(c), c->vec(MI_V_TOTAL_DISPLACEMENT), c->vec(MI_V_SOLUTION_DELTA), c->d_qrec_q3,
                                int32_t(c->mesh.ncells), c->stream);
+    c->qrec_q3s_valid = false;
+    if (c->smoother_points_q3 == 4 && c->d_qrec_q3 && c->d_qrec_q3s) // ... and the smoother's own, at the 64 points of the 4-point rule
+      {
+        mi::launch_mf_records_q3s(mf_params(c), c->vec(MI_V_TOTAL_DISPLACEMENT), c->vec(MI_V_SOLUTION_DELTA), c->d_qrec_q3s,
+                                  int32_t(c->mesh.ncells), c->stream);
+        c->qrec_q3s_valid = true;
+      }
     // which kernel ran: assemble_q2sf (sum factorised; it alone writes the fp32 records) or the node-pair form
     const bool q2sf = c->dim == 3 && c->degree == 2 && (p.variant == 0 || (p.variant >= 3 && p.variant <= 8));
     c->ke_valid     = (c->d_ke && q2sf && !c->mf_fine) || c->d_qrec || c->d_qrec_q3;
@@ -1142,6 +1163,37 @@ namespace mi_detail
     return upload_cellbox(c);
   }
 
+  // the Q3 smoother's own records and tables: they exist while "smoother_quadrature_q3" is 4 and the Q3 level exists,
+  // whichever of the two was set first
+  int alloc_records_q3s(mi_ctx *c)
+  {
+    if (c->d_qrec_q3s || c->smoother_points_q3 != 4 || !c->d_qrec_q3)
+      return MI_OK;
+    if (!c->d_tab_q3s)
+      {
+        mi::Tables1D t4;
+        t4.build(3, 4);
+        const int rc = upload(c, &c->d_tab_q3s, t4.packed());
+        if (rc)
+          return rc;
+      }
+    HIPCHK(c, hipMalloc((void **)&c->d_qrec_q3s, size_t(c->mesh.ncells) * mi::MF_NREC * 64 * sizeof(double)));
+    return MI_OK;
+  }
+  int free_records_q3s(mi_ctx *c)
+  {
+    c->qrec_q3s_valid = false;
+    if (!c->d_qrec_q3s && !c->d_tab_q3s)
+      return MI_OK;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    for (double **p : {&c->d_qrec_q3s, &c->d_tab_q3s})
+      {
+        HIPCHK(c, hipFree(*p));
+        *p = nullptr;
+      }
+    return MI_OK;
+  }
+
   // tuning "fine_level": 1 = the fine level matrix-free end to end (see mi_ctx::mf_fine), 0 = assembled (default).  Takes
   // effect with the next tangent assembly; the assembled tangent's 8 bytes per non-zero are released / allocated again.
   // 3D Q2 on any team; 3D Q3 on an undecomposed mesh (mf_spmv_q3)
@@ -1159,6 +1211,8 @@ namespace mi_detail
         if (c->precond_storage != 64 || c->solver_direct)
           return fail(c, MI_EINVAL, "the matrix-free fine level excludes \"precond_storage\" 32 and \"solver_type\" 1");
         int rc = q3 ? alloc_records_q3(c) : alloc_point_records(c);
+        if (rc == MI_OK && q3)
+          rc = alloc_records_q3s(c);
         if (rc == MI_OK && !q3 && !c->d_node_first)
           rc = upload(c, &c->d_node_first, c->mesh.node_first);
         if (rc)
@@ -1190,6 +1244,8 @@ namespace mi_detail
         HIPCHK(c, hipMemsetAsync(c->d_vals, 0, c->vals_doubles * sizeof(double), c->stream));
         if (q3) // the Q3 records, slots and diagonal blocks go with the level: the assembled path uses none of them
           {
+            if (int rf = free_records_q3s(c))
+              return rf;
             HIPCHK(c, hipStreamSynchronize(c->stream));
             for (double **p : {&c->d_qrec_q3, &c->d_diag_blk, &c->d_diag_slots, &c->d_mf_yc})
               {
@@ -1678,7 +1734,7 @@ namespace mi_detail
                     c->d_saved,     c->d_part,      c->d_sc,          c->d_iface_buf,   c->d_off,         c->d_cmask,
                     c->d_sell_perm, c->d_sell_len,  c->d_sell_col,    c->d_sell_off,    c->d_rowinfo, c->d_rowwx, c->d_sell_wx, c->d_band, c->d_band_work, c->d_band_perm,
                     c->d_own_if_nodes, c->d_own_if_slots, c->d_sell_vals32, c->d_dinv_blk, c->d_dinv_sym6, c->d_sell_box, c->d_ke, c->d_node_first, c->d_qrec, c->d_qrec32, c->d_cellbox, c->d_mf_yc, c->d_mf_dst, c->d_mf_slot_base, c->d_mf_src, c->d_lat_rows,
-                    c->d_qrec27, c->d_tab27, c->d_qrec_q3, c->d_diag_blk, c->d_diag_slots, c->d_diagpos_mf, c->d_face_slots, c->d_fn_ids, c->d_fn_start, c->d_fn_src,
+                    c->d_qrec27, c->d_tab27, c->d_qrec_q3, c->d_qrec_q3s, c->d_tab_q3s, c->d_diag_blk, c->d_diag_slots, c->d_diagpos_mf, c->d_face_slots, c->d_fn_ids, c->d_fn_start, c->d_fn_src,
                     c->d_pred[0][0], c->d_pred[0][1], c->d_pred[1][0], c->d_pred[1][1], c->d_pred[2][0], c->d_pred[2][1], c->d_pred[3][0], c->d_pred[3][1],
                     c->d_pred_saved[0][0], c->d_pred_saved[0][1], c->d_pred_saved[1][0], c->d_pred_saved[1][1], c->d_pred_saved[2][0],
                     c->d_pred_saved[2][1], c->d_pred_saved[3][0], c->d_pred_saved[3][1]};
@@ -3024,6 +3080,20 @@ int mi_set_tuning(mi_ctx *c, const char *key, int value)
           m->mg_stale = m->mg_force = true;
           continue;
         }
+      if (k == "smoother_quadrature_q3" && (value == 4 || value == 5))
+        {
+          // (matters on a 3D Q3 matrix-free level; elsewhere the key is remembered and takes effect if "fine_level" 1 is set later)
+          if (m->smoother_points_q3 == value)
+            continue;
+          m->smoother_points_q3 = value;
+          m->qrec_q3s_valid     = false; // the 64-point records are written by the next tangent assembly; until then: 125 points
+          const int rc = value == 4 ? alloc_records_q3s(m) : free_records_q3s(m);
+          if (rc)
+            return rc;
+          if (m->d_qrec_q3) // the eigenvalue estimates belong to the operator the smoother ran on
+            m->mg_stale = m->mg_force = true;
+          continue;
+        }
       if (k == "asm_box_geometry" && (value == 0 || value == 1)) // assemble_q2sf on meshes of boxes: geometry from 1/h | the trilinear map
         {
           m->asm_box_geometry = value;
@@ -3227,6 +3297,10 @@ int mi_get_tuning(mi_ctx *c, const char *key, int *value)
     *value = m->smoother_points;
   else if (k == "smoother_quadrature_active") // 3: the smoother's fine-level products run on the 27-point records of the current tangent
     *value = smoother_runs_q27(m) ? 3 : 4;
+  else if (k == "smoother_quadrature_q3")
+    *value = m->smoother_points_q3;
+  else if (k == "smoother_quadrature_q3_active") // 4: the next smoother product runs mf_spmv_q3s; 5: a Q3 matrix-free level on mf_spmv_q3; 0: neither
+    *value = smoother_runs_q3s(m) ? 4 : (m->d_qrec_q3 ? 5 : 0);
   else if (k == "experiments") // 1: built with -DMI_EXPERIMENTS (environment hooks and A/B kernel instantiations compiled in)
 #ifdef MI_EXPERIMENTS
     *value = 1;

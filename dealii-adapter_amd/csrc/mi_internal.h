@@ -194,9 +194,20 @@ struct mi_ctx
   // 3D Q3 (one slab): the same level on mf_spmv_q3.  The residual pass is the generic element kernel's (assemble_cells with
   // residual_only, the assembled path's bits); the records come after it from u + du (mf_records_q3, 125 points: d_qrec_q3),
   // the diagonal blocks from mf_diag_q3.  "smoother_quadrature", "smoother_precision" 32 and "mf_slots_cell_major" have no
-  // effect there: the smoother multiplies with the CG's 125-point product, the slots are cell-major.
+  // effect there: the slots are cell-major, and the smoother multiplies with the CG's 125-point product unless
+  // "smoother_quadrature_q3" is 4.
   int       mf_fine = 0;
   double   *d_qrec_q3 = nullptr; // [ncells][MF_NREC][MF_Q3_QS] (3D Q3, "fine_level" 1 only; released with "fine_level" 0)
+  // tuning "smoother_quadrature_q3" 4 (3D Q3 matrix-free level; default 5: the assembly's rule): the smoother's fine-level
+  // operator A' -- its products, the V-cycle's fine residual, the eigenvalue estimates: every enqueue_spmv with smoother ==
+  // true -- integrates the tangent with the element's full-order rule, 4 x 4 x 4 points (mf_spmv_q3s: one wave per cell), from
+  // records of its own written beside the assembly's by every tangent assembly (mf_records_q3s).  The CG's operator, start-vector
+  // and residual products, mi_spmv and the block-Jacobi D stay on the 125-point records.  The key is remembered on any context;
+  // records and tables exist while it is 4 AND the Q3 level exists (alloc_records_q3s / free_records_q3s).
+  int       smoother_points_q3 = 5;
+  double   *d_qrec_q3s = nullptr; // [ncells][MF_NREC][64]
+  double   *d_tab_q3s  = nullptr; // 1D tables of the 4-point rule for Q3
+  bool      qrec_q3s_valid = false; // d_qrec_q3s belongs to the current tangent (cleared by every change of the key)
   // "mf_diag_lag" 1 (what bench.py and the executable set beside "fine_level" 1): the diagonal blocks -- the smoother's D,
   // the Jacobi diagonal -- are formed at the FIRST tangent of a time step and kept over its Newton iterations, as the coarse
   // operators are ("mg_lag"); a preconditioner-side policy: the operator (records) and the residual are always current

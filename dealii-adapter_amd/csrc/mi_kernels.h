@@ -187,6 +187,8 @@ namespace mi
     const float    *qrec32;  // the same records rounded to fp32 (opt-in fp32 smoother product), or null
     const double   *qrec27;  // [ncells][MF_NREC][27] the records at the 27 points of the 3-point rule (smoother quadrature 3), or null
     const double   *tab27;   // N1[3][3], dN1[3][3], qw[3], qx[3] of that rule
+    const double   *qrec_q3s; // 3D Q3: [ncells][MF_NREC][64] the records at the 64 points of the 4-point rule ("smoother_quadrature_q3" 4), or null
+    const double   *tab_q3s;  // N1[4][4], dN1[4][4], qw[4], qx[4] of that rule
     const int32_t  *conn;    // [ncells][27] colour-sorted
     const uint32_t *first;   // as EbeParams
     const uint8_t  *cmask;   // [nnodes]
@@ -368,6 +370,11 @@ namespace mi
   void launch_mf_records_q3(const MfParams &p, const double *u, const double *du, double *rec, int32_t cell_count, hipStream_t s);
   void launch_mf_spmv_q3(const MfParams &p, int32_t cell_count, hipStream_t s, hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr);
   void launch_mf_diag_q3(const MfParams &p, double *slots6, int32_t cell_count, hipStream_t s);
+  // ... the multigrid smoother's operator on the element's full-order rule, 4 x 4 x 4 points (see mf_spmv_q3s): records
+  // [ncells][MF_NREC][64] of its own (MfParams::qrec_q3s, written by mf_records_q3s from u + du with the fold rule of
+  // mf_records27), the rule's 1D tables MfParams::tab_q3s; one wave per cell, the results into the same cell-major slots
+  void launch_mf_records_q3s(const MfParams &p, const double *u, const double *du, double *rec, int32_t cell_count, hipStream_t s);
+  void launch_mf_spmv_q3s(const MfParams &p, int32_t cell_count, hipStream_t s, hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr);
   // the matrix-free fine level's point pass over ALL cells in one launch (assemble_q2sf<true> with the residual into slots:
   // AsmParams::res_slots / slot_dst; cell_begin = 0, cell_count = all) and the sum of the slots into system_rhs
   void launch_point_pass_slots(const AsmParams &p, hipStream_t s);

@@ -2358,12 +2358,12 @@ namespace mi
 
   // ------------------------------------------------------------------ matrix-free kernels: what they share
   // One definition each of what the three families -- 64-point Q2 (mf_spmv, mf_diag), 27-point smoother (mf_records27,
-  // mf_spmv27), Q3 (mf_records_q3, mf_spmv_q3, mf_diag_q3) -- do at a quadrature point: mf_geometry, MF_M, MF_POINT_ALGEBRA /
-  // MF_POINT_SM, MF_RECORD_TAIL here; MF_DIAG_POINT, MF_DIAG_ACCUMULATE at mf_diag.  The sum-factorisation passes, the LDS
-  // layouts and the lane mappings stay with the kernels.  The geometry is a function; the tensor algebra is text expanded in
+  // mf_spmv27), Q3 (mf_records_q3, mf_spmv_q3, mf_diag_q3; mf_records_q3s, mf_spmv_q3s) -- do at a quadrature point:
+  // mf_geometry, MF_M, MF_POINT_ALGEBRA / MF_POINT_SM, MF_RECORD_TAIL here; MF_DIAG_POINT, MF_DIAG_ACCUMULATE at mf_diag.
+  // The sum-factorisation passes, the LDS layouts and the lane mappings stay with the kernels.  The geometry is a function; the tensor algebra is text expanded in
   // place, so that every kernel hands the optimiser its statements in the order it always did (its register allocation
   // depends on that order: profiles/mf_shared_point/README.md).  The text works on names in the caller's scope (T: the
-  // kernel's arithmetic type; all #undef'd behind mf_diag_q3):
+  // kernel's arithmetic type; all #undef'd behind mf_spmv_q3s):
   //   macro               reads                                              declares / writes
   //   MF_RECORD_TAIL      H[3][3], Ji[9]                                     F[9], J, rJ, Jm; the record at its g_
   //   MF_M                Ji[9], Finv[9]                                     writes M[9] (declared by the caller)
@@ -4236,6 +4236,323 @@ namespace mi
 #pragma unroll
         for (int e = 0; e < 6; ++e)
           o[e] = K[e] + sR[a * 6 + e];
+      }
+  }
+
+  // ------------------------------------------------------------------ Q3 fine level: the smoother's operator on the 4 x 4 x 4 rule
+  // "smoother_quadrature_q3" 4: the multigrid smoother's fine-level operator A' integrates the tangent with the element's
+  // full-order rule (4 Gauss points per direction) on records of its own [cell][MF_NREC][64] (mf_records_q3s, fold rule on,
+  // as mf_records27); the CG's operator, the residuals and the diagonal blocks keep the 125-point records.
+  // 64 points = 64 nodes = ONE WAVE PER CELL: no workgroup barrier anywhere -- a stage reads its lines into registers, the
+  // wave synchronises (MI_WAVE_SYNC: LDS operations of a wave retire in order), the stage writes its outputs IN PLACE of what
+  // the wave has just consumed.  One LDS region of MFQ3S_R doubles per wave carries every stage in turn, then the wave's copy
+  // of the 1D tables (40 doubles: the rows a lane needs by its own qz / qy / qx); a workgroup is MFQ3S_WPB independent waves.
+  //   gather  lane = node a                x masked -> X                                      64 items
+  //   E1  item (c,k,j):   x-line -> A_S / A_D [c,k,j][qx]                                     48 items, 32 multiply-adds
+  //   E2  item (c,k,qx):  contract j -> B_DS / B_SD / B_SS [c,k][qy][qx]                      48 items, 48
+  //   E3  item = point:   contract k -> H[c][l], V[c]                                         64 items, 48
+  //   point (neo_hooke_from_F on the record, MF_M, MF_POINT_ALGEBRA: Q = JxW S M^T, mass)     64 items
+  //   I3  item (c,qy,qx): contract qz -> C_DS / C_SD / C_SS [c,k][qy][qx]                     48 items, 64
+  //   I2  item (c,k,qx):  contract qy -> E_D / E_S [c,k,j][qx]                                48 items, 48
+  //   I1  item (c,k,j):   contract qx -> Y (a cell's 192 results as they lie in its slots)    48 items, 32
+  //   store   lane = 3 consecutive runs of 64 doubles of the cell's slots                     64 items
+  // In the 48-item stages lanes 48-63 mirror lanes 32-47: the same reads (broadcast) and the same values to the same
+  // addresses, no branch.  Every buffer a stage reads line by line is laid out ITEM-FASTEST, [position in the line][item],
+  // so that a wave's reads of one line position are consecutive doubles; the strides are padded so that the transposing
+  // writes of the stage before spread over the banks as well (ds_write_b64 goes in groups of 16 lanes over 16 double-wide
+  // banks, ds_read_b64 in halves of 32 lanes over 32):
+  //   X, A, E  [line position][48 items], stride MFQ3S_XS = 49: A / E written at (position + 4 ck) mod 16 -- 16 lanes, 16
+  //            banks (the gather's three writes of X, at (i + kj) mod 16, are up to 4-way: once per cell)
+  //   B, C     [c,k][16 points], plane stride MFQ3S_PS = 20: writes at (4 ck + qx) mod 16; E3 / I2 read consecutive points
+  //   Q        [c][4 rows][64 points], component stride MFQ3S_QC = 272: I3's half-wave (c = 0 | 1) reads banks 0-15 | 16-31
+  //   Y        result g = a * 3 + c at g + g / 12: I1 writes at 13 kj mod 16, the store reads runs of 64
+  constexpr int MFQ3S_NPC = 64, MFQ3S_NQ = 64;
+  constexpr int MFQ3S_XS = 49, MFQ3S_PS = 20, MFQ3S_QC = 272;
+  constexpr int MFQ3S_AD = 4 * MFQ3S_XS, MFQ3S_PW = 12 * MFQ3S_PS; // second line buffer (A_D, E_S); plane set (B_SD, B_SS at 1x, 2x)
+  constexpr int MFQ3S_R = 3 * MFQ3S_QC, MFQ3S_NTAB = 40;
+  static_assert(2 * MFQ3S_AD <= MFQ3S_R && 3 * MFQ3S_PW <= MFQ3S_R && 192 + 16 <= MFQ3S_R, "every stage fits the wave's region");
+  // 1D tables of the rule (Tables1D(3, 4).packed()): N1[4][4] at 0, dN1[4][4] at 16, qw[4] at 32, qx[4] at 36
+  constexpr int MFQ3S_TD = 16, MFQ3S_TW = 32, MFQ3S_TX = 36;
+  // waves (= cells) per workgroup.  The waves share nothing, so the number only sets how the dispatcher packs them on a CU
+  constexpr int MFQ3S_WPB = 4;
+
+  // this wave's cell, region and table copy; false: the wave lies beyond the launch's last cell (it leaves as a whole)
+  __device__ __forceinline__ bool mfq3s_wave(const MfParams &prm, double (*sR)[MFQ3S_R + MFQ3S_NTAB], int64_t &cell, double *&R, double *&sT)
+  {
+    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), t = threadIdx.x & 63; // (w uniform: the cell's loads stay scalar)
+    cell        = int64_t(blockIdx.x) * MFQ3S_WPB + w;
+    if (cell >= prm.count)
+      return false;
+    R  = sR[w];
+    sT = R + MFQ3S_R;
+    if (t < MFQ3S_NTAB)
+      sT[t] = prm.tab_q3s[t];
+    return true;
+  }
+  // where lane t = node a = (k*4+j)*4+i puts component c of its value: line position i of item (c,k,j)
+  __device__ __forceinline__ int mfq3s_xpos(const int t, const int c) { return (t & 3) * MFQ3S_XS + c * 16 + (t >> 2); }
+
+  // E1 + E2 + E3: X in R -> H, V at point t.  S, D: the tables in scalar registers.  Ends with R free.
+  __device__ __forceinline__ void mfq3s_gradients(const double (&S)[4][4], const double (&D)[4][4], const double *__restrict__ sT,
+                                                  double *__restrict__ R, const int t, const int ti, double H[3][3], double V[3])
+  {
+    const int ck = ti >> 2, lo = ti & 3; // ti = (c*4+k)*4 + (j | qx)
+    {                                    // E1: line (c,k,j) = ti, its four values along x
+      double x[4];
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+        x[i] = R[i * MFQ3S_XS + ti];
+      MI_WAVE_SYNC();
+#pragma unroll
+      for (int qx = 0; qx < 4; ++qx)
+        {
+          R[lo * MFQ3S_XS + ck * 4 + qx]            = S[qx][0] * x[0] + S[qx][1] * x[1] + S[qx][2] * x[2] + S[qx][3] * x[3]; // A_S
+          R[MFQ3S_AD + lo * MFQ3S_XS + ck * 4 + qx] = D[qx][0] * x[0] + D[qx][1] * x[1] + D[qx][2] * x[2] + D[qx][3] * x[3]; // A_D
+        }
+      MI_WAVE_SYNC();
+    }
+    { // E2: item (c,k,qx) = ti
+      double as[4], ad[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        {
+          as[j] = R[j * MFQ3S_XS + ti];
+          ad[j] = R[MFQ3S_AD + j * MFQ3S_XS + ti];
+        }
+      MI_WAVE_SYNC();
+#pragma unroll
+      for (int qy = 0; qy < 4; ++qy)
+        {
+          const int o          = ck * MFQ3S_PS + qy * 4 + lo;
+          R[o]                = S[qy][0] * ad[0] + S[qy][1] * ad[1] + S[qy][2] * ad[2] + S[qy][3] * ad[3]; // d/dx
+          R[MFQ3S_PW + o]     = D[qy][0] * as[0] + D[qy][1] * as[1] + D[qy][2] * as[2] + D[qy][3] * as[3]; // d/dy
+          R[2 * MFQ3S_PW + o] = S[qy][0] * as[0] + S[qy][1] * as[1] + S[qy][2] * as[2] + S[qy][3] * as[3]; // value / d/dz
+        }
+      MI_WAVE_SYNC();
+    }
+    // E3: item = point t = qz * 16 + q16 (this lane's row qz of the tables from the wave's copy)
+    const int qz = t >> 4, q16 = t & 15;
+    double    sz[4], dz[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+      {
+        sz[k] = sT[qz * 4 + k];
+        dz[k] = sT[MFQ3S_TD + qz * 4 + k];
+      }
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+      {
+        H[c][0] = H[c][1] = H[c][2] = V[c] = 0.0;
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+          {
+            const int    o   = (c * 4 + k) * MFQ3S_PS + q16;
+            const double bds = R[o], bsd = R[MFQ3S_PW + o], bss = R[2 * MFQ3S_PW + o];
+            H[c][0] = fma(sz[k], bds, H[c][0]);
+            H[c][1] = fma(sz[k], bsd, H[c][1]);
+            H[c][2] = fma(dz[k], bss, H[c][2]);
+            V[c]    = fma(sz[k], bss, V[c]);
+          }
+      }
+    MI_WAVE_SYNC(); // B is consumed
+  }
+
+  // F, J^(-2/3), 1/J at the 64 points of the 4-point rule from u + du, one wave per cell.  The rule's points lie between the
+  // assembly's: a state that is valid at all 125 points can be folded at one of these, and such a point takes the undeformed
+  // state (the smoother's operator stays positive definite; the residual pass reports det F <= 0 at ITS points)
+  template <bool BOX>
+  __global__ __launch_bounds__(64 * MFQ3S_WPB) void mf_records_q3s(MfParams prm, const double *__restrict__ u, const double *__restrict__ du,
+                                                                   double *__restrict__ rec)
+  {
+    __shared__ double sR[MFQ3S_WPB][MFQ3S_R + MFQ3S_NTAB];
+    const int t = threadIdx.x & 63, ti = t < 48 ? t : t - 16;
+    int64_t   cell;
+    double   *R, *sT;
+    if (!mfq3s_wave(prm, sR, cell, R, sT))
+      return;
+    {
+      const int32_t node = prm.conn[cell * MFQ3S_NPC + t];
+#pragma unroll
+      for (int c = 0; c < 3; ++c)
+        R[mfq3s_xpos(t, c)] = u[int64_t(node) * 3 + c] + du[int64_t(node) * 3 + c];
+    }
+    double S[4][4], D[4][4]; // uniform: scalar registers
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+#pragma unroll
+      for (int a = 0; a < 4; ++a)
+        {
+          S[q][a] = prm.tab_q3s[q * 4 + a];
+          D[q][a] = prm.tab_q3s[MFQ3S_TD + q * 4 + a];
+        }
+    MI_WAVE_SYNC();
+    double H[3][3], V[3];
+    mfq3s_gradients(S, D, sT, R, t, ti, H, V);
+    const int qz = t >> 4, qy = (t >> 2) & 3, qx = t & 3;
+    double    Ji[9], detJ;
+    mf_geometry<BOX>(prm, cell, sT + MFQ3S_TX, qx, qy, qz, Ji, detJ);
+    MF_RECORD_TAIL(true, true, rec + cell * int64_t(MF_NREC * MFQ3S_NQ) + t, MFQ3S_NQ)
+  }
+
+  template <bool BOX>
+  __global__ __launch_bounds__(64 * MFQ3S_WPB) void mf_spmv_q3s(MfParams prm)
+  {
+    __shared__ double sR[MFQ3S_WPB][MFQ3S_R + MFQ3S_NTAB];
+    const int t = threadIdx.x & 63, ti = t < 48 ? t : t - 16;
+    int64_t   cell;
+    double   *R, *sT;
+    if (!mfq3s_wave(prm, sR, cell, R, sT))
+      return;
+    // gather x (constrained entries masked)
+    {
+      const int32_t node = prm.conn[cell * MFQ3S_NPC + t];
+      const int     cm   = prm.cmask[node];
+#pragma unroll
+      for (int c = 0; c < 3; ++c)
+        R[mfq3s_xpos(t, c)] = ((cm >> c) & 1) ? 0.0 : prm.x[int64_t(node) * 3 + c];
+    }
+    // this lane's record: consumed after the gradient passes
+    double rec[MF_NREC];
+    {
+      const double *__restrict__ rp = prm.qrec_q3s + cell * int64_t(MF_NREC * MFQ3S_NQ) + t;
+#pragma unroll
+      for (int f = 0; f < MF_NREC; ++f)
+        rec[f] = __builtin_nontemporal_load(&rp[f * MFQ3S_NQ]);
+    }
+    double S[4][4], D[4][4]; // uniform: scalar registers
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+#pragma unroll
+      for (int a = 0; a < 4; ++a)
+        {
+          S[q][a] = prm.tab_q3s[q * 4 + a];
+          D[q][a] = prm.tab_q3s[MFQ3S_TD + q * 4 + a];
+        }
+    MI_WAVE_SYNC();
+    double H[3][3], V[3];
+    mfq3s_gradients(S, D, sT, R, t, ti, H, V);
+    // ---- point stage: Q = JxW S M^T (MF_POINT_ALGEBRA), 12 numbers per point: Q[i][l][t], the mass term in row 3
+    {
+      const int    qz = t >> 4, qy = (t >> 2) & 3, qx = t & 3;
+      const double wq = sT[MFQ3S_TW + qx] * sT[MFQ3S_TW + qy] * sT[MFQ3S_TW + qz];
+      double       Finv[9], tau[6], tiso[6], cII, cS, Ji[9], detJ, M[9];
+      neo_hooke_from_F<3>(rec, det3x3(rec), rec[9], rec[10], prm.mu, prm.kappa, Finv, tau, tiso, cII, cS);
+      mf_geometry<BOX>(prm, cell, sT + MFQ3S_TX, qx, qy, qz, Ji, detJ);
+      MF_M(BOX, i_, j_)
+      const double w = detJ * wq, wcII = w * cII, cs2 = 0.5 * cS;
+      MF_POINT_ALGEBRA(double)
+      const double wm = prm.mass * w;
+#pragma unroll
+      for (int i = 0; i < 3; ++i)
+        {
+          double Sm[3];
+#pragma unroll
+          for (int j = 0; j < 3; ++j)
+            Sm[j] = MF_POINT_SM(double, i, j);
+#pragma unroll
+          for (int l = 0; l < 3; ++l)
+            R[i * MFQ3S_QC + l * 64 + t] = MF_POINT_Q(Sm, l);
+          R[i * MFQ3S_QC + 3 * 64 + t] = wm * V[i];
+        }
+    }
+    MI_WAVE_SYNC();
+    const int ck = ti >> 2, lo = ti & 3;
+    { // ---- I3: contract qz.  item (c, q16 = qy*4+qx) = ti
+      const int c = ti >> 4, q16 = ti & 15;
+      double    v[4][4];
+#pragma unroll
+      for (int d = 0; d < 4; ++d)
+#pragma unroll
+        for (int z = 0; z < 4; ++z)
+          v[d][z] = R[c * MFQ3S_QC + d * 64 + z * 16 + q16];
+      MI_WAVE_SYNC();
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+        {
+          double cds = 0.0, csd = 0.0, css = 0.0;
+#pragma unroll
+          for (int z = 0; z < 4; ++z)
+            {
+              cds = fma(S[z][k], v[0][z], cds);
+              csd = fma(S[z][k], v[1][z], csd);
+              css = fma(D[z][k], v[2][z], css);
+              css = fma(S[z][k], v[3][z], css);
+            }
+          const int o         = (c * 4 + k) * MFQ3S_PS + q16;
+          R[o]                = cds;
+          R[MFQ3S_PW + o]     = csd;
+          R[2 * MFQ3S_PW + o] = css;
+        }
+      MI_WAVE_SYNC();
+    }
+    { // ---- I2: contract qy.  item (c,k,qx) = ti
+      double cds[4], csd[4], css[4];
+#pragma unroll
+      for (int qy = 0; qy < 4; ++qy)
+        {
+          const int o = ck * MFQ3S_PS + qy * 4 + lo;
+          cds[qy]     = R[o];
+          csd[qy]     = R[MFQ3S_PW + o];
+          css[qy]     = R[2 * MFQ3S_PW + o];
+        }
+      MI_WAVE_SYNC();
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        {
+          double ed = 0.0, es = 0.0;
+#pragma unroll
+          for (int qy = 0; qy < 4; ++qy)
+            {
+              ed = fma(S[qy][j], cds[qy], ed);
+              es = fma(D[qy][j], csd[qy], es);
+              es = fma(S[qy][j], css[qy], es);
+            }
+          R[lo * MFQ3S_XS + ck * 4 + j]            = ed;
+          R[MFQ3S_AD + lo * MFQ3S_XS + ck * 4 + j] = es;
+        }
+      MI_WAVE_SYNC();
+    }
+    { // ---- I1: contract qx.  item = line (c,k,j) = ti, its four nodes i
+      const int c = ti >> 4, kj = ti & 15;
+      double    ed[4], es[4];
+#pragma unroll
+      for (int qx = 0; qx < 4; ++qx)
+        {
+          ed[qx] = R[qx * MFQ3S_XS + ti];
+          es[qx] = R[MFQ3S_AD + qx * MFQ3S_XS + ti];
+        }
+      MI_WAVE_SYNC();
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+        {
+          double yv = 0.0;
+#pragma unroll
+          for (int qx = 0; qx < 4; ++qx)
+            {
+              yv = fma(D[qx][i], ed[qx], yv);
+              yv = fma(S[qx][i], es[qx], yv);
+            }
+          R[kj * 13 + i * 3 + c] = yv; // g = (kj*4+i)*3 + c at g + g / 12
+        }
+      MI_WAVE_SYNC();
+    }
+    // ---- the cell's 192 results into its slots: cell-major slots are one run of 192 doubles, three stores of 64
+    if (prm.slot_inline)
+      {
+        double *__restrict__ o = prm.yc + cell * int64_t(MFQ3S_NPC * 3);
+#pragma unroll
+        for (int r = 0; r < 3; ++r)
+          {
+            const int g = r * 64 + t;
+            o[g]        = R[g + g / 12];
+          }
+      }
+    else
+      {
+        const int64_t slot = prm.dst[cell * MFQ3S_NPC + t];
+#pragma unroll
+        for (int c = 0; c < 3; ++c)
+          prm.yc[slot * 3 + c] = R[t * 3 + c + t / 4];
       }
   }
   // (the last matrix-free kernel: the shared text ends here)
@@ -7153,6 +7470,28 @@ namespace mi
       return;
     auto *kern = p.cellbox ? mf_diag_q3<true> : mf_diag_q3<false>;
     hipLaunchKernelGGL(kern, dim3(cell_count), dim3(MFQ3_NT), 0, s, p, slots6);
+  }
+  void launch_mf_records_q3s(const MfParams &p, const double *u, const double *du, double *rec, int32_t cell_count, hipStream_t s)
+  {
+    if (cell_count <= 0)
+      return;
+    MfParams q = p;
+    q.count    = cell_count; // (the waves beyond the last cell leave)
+    auto *kern = q.cellbox ? mf_records_q3s<true> : mf_records_q3s<false>;
+    hipLaunchKernelGGL(kern, dim3((cell_count + MFQ3S_WPB - 1) / MFQ3S_WPB), dim3(64 * MFQ3S_WPB), 0, s, q, u, du, rec);
+  }
+  void launch_mf_spmv_q3s(const MfParams &p, int32_t cell_count, hipStream_t s, hipEvent_t ev_start, hipEvent_t ev_stop)
+  {
+    if (cell_count <= 0)
+      return;
+    MfParams q = p;
+    q.count    = cell_count;
+    auto *kern = q.cellbox ? mf_spmv_q3s<true> : mf_spmv_q3s<false>;
+    const dim3 grid((cell_count + MFQ3S_WPB - 1) / MFQ3S_WPB), block(64 * MFQ3S_WPB);
+    if (ev_start || ev_stop)
+      hipExtLaunchKernelGGL(kern, grid, block, 0, s, ev_start, ev_stop, 0, q);
+    else
+      hipLaunchKernelGGL(kern, grid, block, 0, s, q);
   }
   void launch_mf_diag_gather(const double *slots6, const int32_t *slot_base, const int32_t *slot_src, const uint8_t *cmask,
                              const int32_t *diagpos, double *blk, double *dinv, double *dinv_blk, double *sym6, int64_t nnodes, hipStream_t s)

@@ -207,6 +207,10 @@ namespace Nonlinear_Elasticity
           else if (std::atoi(f) != 0)
             device->check(mi_set_tuning(device->ctx(), "mf_diag_lag", 1), "mi_set_tuning");
         }
+      // 4: the multigrid smoother of a 3D Q3 matrix-free level integrates with the element's full-order rule (5: the assembly's)
+      if (const char *f = std::getenv("MI_SMOOTHER_QUADRATURE_Q3"))
+        if (mi_set_tuning(device->ctx(), "smoother_quadrature_q3", std::atoi(f)) != MI_OK)
+          std::cout << "MI_SMOOTHER_QUADRATURE_Q3 ignored: " << mi_last_error(device->ctx()) << std::endl;
     }
 
     std::cout << "Triangulation:"

@@ -293,6 +293,7 @@ int mi_set_profiling(mi_ctx *ctx, int enable);
  *                                                  tangent assembly writes point records, residual and the nodes'
  *                                                  diagonal blocks only; the CG's product, residual / start-vector
  *                                                  products and the smoother run on mf_spmv (Q3: mf_spmv_q3, 125 points;
+ *                                                  the smoother's rule there is "smoother_quadrature_q3";
  *                                                  "smoother_quadrature", "smoother_precision" 32 and
  *                                                  "mf_slots_cell_major" have no effect there); the assembled tangent's
  *                                                  memory is released.  Same results (nonlinear_elasticity.cc:1044-1087,
@@ -333,6 +334,14 @@ int mi_set_profiling(mi_ctx *ctx, int enable);
  *                                                  V-cycle's residual and eigenvalue estimate use it too) | the assembly's
  *                                                  4 x 4 x 4 (nonlinear_elasticity.cc:74).  Preconditioner side only, fp64:
  *                                                  the CG's operator, residuals and the assembly always integrate with 4
+ *  smoother_quadrature_q3  5 | 4                   ... on a 3D Q3 matrix-free level ("fine_level" 1): the assembly's          MI_SMOOTHER_QUADRATURE_Q3
+ *                                                  5 x 5 x 5 rule (mf_spmv_q3 on the assembly's records) | the full-order
+ *                                                  4 x 4 x 4 rule (mf_spmv_q3s, one wave per cell, records of its own with
+ *                                                  the fold rule; the V-cycle's residual and the eigenvalue estimates use
+ *                                                  it too).  Preconditioner side only: the CG's operator, residuals,
+ *                                                  mi_spmv and the block-Jacobi D keep 5.  Elsewhere accepted, remembered,
+ *                                                  no effect.  Read-back "smoother_quadrature_q3_active": 4 | 5 = the rule
+ *                                                  of the next smoother product on such a level, 0 elsewhere
  *  smoother_precision   64 | 32                    the smoother's matrix-free fine-level products in fp64 | in fp32      -
  *                                                  arithmetic on fp32 point records (opt-in; everything else stays fp64;
  *                                                  takes effect with the next tangent assembly)
