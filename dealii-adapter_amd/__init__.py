@@ -126,6 +126,13 @@ def lib():
         L.mi_spmv.argtypes = [vp, dp, dp]
         L.mi_get_diagonal_blocks.argtypes = [vp, dp]
         L.mi_get_diagonal_blocks.restype = C.c_int
+        L.mi_linear_setup.argtypes = [vp, C.c_double]
+        L.mi_linear_step.argtypes = [vp, C.c_int, C.c_double, C.c_int64, C.POINTER(C.c_int), dp]
+        L.mi_linear_matrix_get_csr.argtypes = [vp, C.c_int, C.POINTER(C.c_int64), i32p, dp]
+        L.mi_linear_apply.argtypes = [vp, C.c_int, dp, dp]
+        L.mi_linear_get_diagonal.argtypes = [vp, dp]
+        for f in ("mi_linear_setup", "mi_linear_step", "mi_linear_matrix_get_csr", "mi_linear_apply", "mi_linear_get_diagonal"):
+            getattr(L, f).restype = C.c_int
         L.mi_set_profiling.argtypes = [vp, C.c_int]
         L.mi_get_timings.argtypes = [vp, C.POINTER(Timings)]
         L.mi_partition_describe.restype = C.c_int
@@ -386,6 +393,40 @@ class Context:
         b = np.zeros((self.nnodes, self.dim, self.dim))
         self._chk(lib().mi_get_diagonal_blocks(self.h, _dp(b)))
         return b
+
+    # ---- linear model (mi_linear_setup / mi_linear_step); the operators follow the tuning key "linear_operator"
+    def linear_setup(self, theta):
+        self._chk(lib().mi_linear_setup(self.h, float(theta)))
+
+    def linear_step(self, data_consistent, abs_tol, max_it=None):
+        """one step; returns (CG iterations, residual)"""
+        its, res = C.c_int(0), C.c_double(0)
+        self._chk(lib().mi_linear_step(self.h, int(data_consistent), abs_tol, self.n * 10 if max_it is None else max_it,
+                                       C.byref(its), C.byref(res)))
+        return its.value, res.value
+
+    def linear_apply(self, which, x):
+        """y = K x (0), M x (1), A x (2) through the device kernels of the current set-up"""
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        y = np.zeros_like(x)
+        self._chk(lib().mi_linear_apply(self.h, which, _dp(x), _dp(y)))
+        return y
+
+    def linear_csr(self, which):
+        """K (0), M (1) or the constrained stepping matrix (2) of an assembled set-up"""
+        import scipy.sparse as sp
+        rp = np.zeros(self.n + 1, dtype=np.int64)
+        col = np.zeros(self.nnz, dtype=np.int32)
+        val = np.zeros(self.nnz)
+        self._chk(lib().mi_linear_matrix_get_csr(self.h, which, rp.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                 col.ctypes.data_as(C.POINTER(C.c_int32)), _dp(val)))
+        return sp.csr_matrix((val, col, rp), shape=(self.n, self.n))
+
+    def linear_diagonal(self):
+        """the Jacobi diagonal of the stepping matrix in use"""
+        d = np.zeros(self.n)
+        self._chk(lib().mi_linear_get_diagonal(self.h, _dp(d)))
+        return d
 
     def set_profiling(self, on=True):
         self._chk(lib().mi_set_profiling(self.h, int(on)))

@@ -335,7 +335,7 @@ namespace mi_detail
   // ("precond_storage" 32) keeps a second array, refreshed lazily before the first product with a new tangent.
   void refresh_vals32(mi_ctx *c)
   {
-    if (!c->vals32_stale || c->precond_storage != 32 || !c->d_sell_vals32)
+    if (!c->vals32_stale || c->precond_storage != 32 || !c->d_sell_vals32 || !c->d_vals) // (no tangent array: matrix-free set-ups)
       return;
     mi::launch_vals_to_f32(c->d_vals, c->d_sell_vals32, c->mesh.nvalblocks() * int64_t(c->dim * c->dim), c->stream);
     c->vals32_stale = false;
@@ -468,6 +468,24 @@ namespace mi_detail
     // product under "spmv_variant" 4); not for fused epilogues, fused dot products or the linear model's operators
     // (opt-in A/B "cg_operator" 1: the CG's own product as well, with p.q by a separate reduction -- then the
     // sliced-ELL copy of the tangent is never made)
+    // matrix-free linear model: (c_K K + c_M M) x into the cells' slots, then the slot sum -- with the partials of dotv . y
+    // for the CG's q = A p; rows of constrained dofs: diag(A) x (one slab: no parts)
+    if (c->active_linear_mf)
+      {
+        if (part == 1)
+          return;
+        const LinearMf &lm = *c->active_linear_mf;
+        mi::MfParams    f  = mf_params(c);
+        f.tab_q3s = lm.tab, f.vals = lm.diag, f.diagpos = lm.diagpos, f.cmask = lm.cmask, f.x = x, f.y = y;
+        f.yc = c->d_mf_yc, f.dst = c->d_mf_dst, f.slot_base = c->d_mf_slot_base, f.slot_src = c->d_mf_src;
+        f.slot_inline = c->slots_layout == 1;
+        mi::launch_mf_linear_q3(f, lm.op, int32_t(c->mesh.ncells), c->stream);
+        if (dotv)
+          mi::launch_mf_gather_dot(f, int64_t(c->mesh.nnodes) * 3, dotv, partials, c->grid_gdot, c->own0, c->own_n, c->stream);
+        else
+          mi::launch_mf_gather(f, int64_t(c->mesh.nnodes) * 3, c->stream);
+        return;
+      }
     const int  kind       = element_form(c);
     const bool mf_all     = c->mf_fine && !c->active_sell_vals; // matrix-free fine level: every product of the tangent
     const bool ebe_for_cg = dotv && (c->cg_operator == 1 || mf_all) && kind && !c->active_sell_vals && !cheb;
@@ -1268,11 +1286,54 @@ namespace mi_detail
     return MI_OK;
   }
 
+  // matrix-free linear model ("linear_operator" 1): what its products need beside the operators' own data -- the Q3 slot
+  // tables, the slots and the cell boxes, built where absent -- and the nonlinear tangent array released, as set_fine_level does
+  int linear_mf_prepare(mi_ctx *c)
+  {
+    if (!c->d_mf_dst || !c->d_mf_yc)
+      if (int rs = build_slot_tables(c))
+        return rs;
+    if (int rb = upload_cellbox(c))
+      return rb;
+    if (c->d_vals)
+      {
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        HIPCHK(c, hipFree(c->d_vals));
+        c->d_vals = nullptr;
+      }
+    c->linear_mf = true;
+    c->ke_valid  = false;
+    return MI_OK;
+  }
+  // ... and back: the tangent array exists again (zeroed, as at creation) unless the fine level is matrix-free itself
+  int linear_mf_leave(mi_ctx *c)
+  {
+    if (!c->linear_mf)
+      return MI_OK;
+    c->linear_mf = false;
+    if (!c->d_vals && !c->mf_fine)
+      {
+        HIPCHK(c, hipMalloc((void **)&c->d_vals, c->vals_doubles * sizeof(double)));
+        HIPCHK(c, hipMemsetAsync(c->d_vals, 0, c->vals_doubles * sizeof(double), c->stream));
+        c->vals32_stale = true;
+        c->mg_stale = c->mg_force = true;
+      }
+    return MI_OK;
+  }
+  // entry points that read or write the assembled tangent
+  int check_tangent_array(mi_ctx *c, const char *what)
+  {
+    for (mi_ctx *m : c->team->members)
+      if (m->linear_mf)
+        return fail(c, MI_EINVAL, "%s: the matrix-free linear model keeps no assembled tangent (\"linear_operator\" 0 and mi_linear_setup)", what);
+    return MI_OK;
+  }
+
   // the tangent's products on a matrix-free fine level need the point records of an assembly
   int check_mf_tangent(mi_ctx *c)
   {
     for (mi_ctx *m : c->team->members)
-      if (m->mf_fine && !m->active_sell_vals && element_form(m) != 2)
+      if (m->mf_fine && !m->active_sell_vals && !m->active_linear_mf && element_form(m) != 2)
         return fail(c, MI_EINVAL, "matrix-free fine level: no tangent has been assembled yet (mi_assemble first)");
     return MI_OK;
   }
@@ -1364,7 +1425,7 @@ namespace mi_detail
           // (its own, wider grid), or the separate reduction's
           const bool elem = (m->cg_operator == 1 || m->mf_fine) && element_form(m) && !m->active_sell_vals;
           const bool one  = elem && element_form(m) == 2 && m->mf_slots && m->d_mf_yc;
-          cg.npart_pq     = !m->cg_fused_dot ? m->grid_vec : one ? m->grid_gdot : elem ? m->grid_vec : m->grid_spmv;
+          cg.npart_pq     = !m->cg_fused_dot ? m->grid_vec : (one || m->active_linear_mf) ? m->grid_gdot : elem ? m->grid_vec : m->grid_spmv;
         }
         cg.totals   = dist ? m->d_sc + SC_TOT : nullptr;
         cgs.push_back(cg);
@@ -1399,7 +1460,7 @@ namespace mi_detail
     // (pays while one CU can stream the matrix from the L2 faster than three launches take: ~130 GB/s vs ~18 us,
     // i.e. up to ~1 MB of matrix values; measured with tools/small_case_latency.py)
     if (!dist && !use_mg && c0->small_cg && max_it > 0 && (c0->spmv_variant == 3 || c0->active_sell_vals) &&
-        !(c0->mf_fine && !c0->active_sell_vals) && // (the one-launch solver streams the assembled rows)
+        !(c0->mf_fine && !c0->active_sell_vals) && !c0->active_linear_mf && // (the one-launch solver streams the assembled rows)
         c0->mesh.sell_nblk64 * 64 * int64_t(c0->dim * c0->dim) * 8 <= SMALL_CG_MAX_MATRIX_BYTES)
       {
         mi::launch_cg_small(c0->dim, sell_params(c0, nullptr, nullptr, nullptr, nullptr, nullptr), cgs[0],
@@ -1624,7 +1685,7 @@ namespace mi_detail
             // the product the roofline figure is quoted on: when it is ONE launch of the production kernel its events
             // come from the dispatch itself (kernel start / end, as rocprofv3 reports them)
             const bool one_launch = !dist && c0->profiling && c0->spmv_variant == 3 && c0->sell_icol && c0->sell_unroll == 5 &&
-                                    !c0->active_sell_vals && c0->mesh.sell_nslices_interior == c0->mesh.sell_nslices &&
+                                    !c0->active_sell_vals && !c0->active_linear_mf && c0->mesh.sell_nslices_interior == c0->mesh.sell_nslices &&
                                     !((c0->cg_operator == 1 || c0->mf_fine) && element_form(c0));
             t = tic(c0, MI_T_SPMV, one_launch);
             if (one_launch && t >= 0)
@@ -2439,6 +2500,8 @@ int mi_update_acceleration(mi_ctx *c)
 
 static int assemble_impl(mi_ctx *c, bool residual_only, double *res_norm)
 {
+  if (int e = check_tangent_array(c, "mi_assemble"))
+    return e;
   HIPCHK(c, hipSetDevice(c->device));
   Team     &T  = *c->team;
   mi_ctx   *c0 = T.members[0];
@@ -2493,6 +2556,8 @@ int mi_comm_info(const mi_ctx *c, int *team_size, int *rccl_ranks)
 
 int mi_cg_solve(mi_ctx *c, double rel_tol, int64_t max_it, int *its, double *res)
 {
+  if (int e = check_tangent_array(c, "mi_cg_solve"))
+    return e;
   HIPCHK(c, hipSetDevice(c->device));
   if (rel_tol < 0)
     return fail(c, MI_EINVAL, "negative tolerance");
@@ -2593,6 +2658,8 @@ int mi_cg_solve(mi_ctx *c, double rel_tol, int64_t max_it, int *its, double *res
 // SparseDirectUMFPACK of the reference (nonlinear_elasticity.cc:1192-1200): factorise the current tangent and solve
 int mi_direct_solve(mi_ctx *c, double *res)
 {
+  if (int e = check_tangent_array(c, "mi_direct_solve"))
+    return e;
   HIPCHK(c, hipSetDevice(c->device));
   for (mi_ctx *m : c->team->members)
     {
@@ -2656,6 +2723,8 @@ int mi_newmark_step(mi_ctx *c, const mi_solver_desc *s, mi_step_info *info)
   if (!s || !info)
     return fail(c, MI_EINVAL, "null argument");
   const auto t_begin = std::chrono::steady_clock::now();
+  if (int e = check_tangent_array(c, "mi_newmark_step"))
+    return e;
   std::memset(info, 0, sizeof(*info));
   int rc = mi_newton_begin_step(c);
   if (rc)
@@ -2915,6 +2984,8 @@ int mi_vec_set(mi_ctx *c, int which, const double *host, int64_t n)
 
 int mi_matrix_get_csr(mi_ctx *c, int64_t *rowptr, int32_t *col, double *val)
 {
+  if (int e = check_tangent_array(c, "mi_matrix_get_csr"))
+    return e;
   if (c->team->size != 1)
     return fail(c, MI_EINVAL, "matrix export is only available on an undecomposed mesh");
   if (c->mf_fine)
@@ -2946,6 +3017,8 @@ int mi_matrix_get_csr(mi_ctx *c, int64_t *rowptr, int32_t *col, double *val)
 // order: out of the assembled tangent, or -- matrix-free fine level -- what mf_diag formed from the point records
 int mi_get_diagonal_blocks(mi_ctx *c, double *blocks)
 {
+  if (int e = check_tangent_array(c, "mi_get_diagonal_blocks"))
+    return e;
   Team &T = *c->team;
   HIPCHK(c, hipSetDevice(c->device));
   if (int e = check_mf_tangent(c))
@@ -2984,6 +3057,8 @@ int mi_get_diagonal_blocks(mi_ctx *c, double *blocks)
 // y = K x through the device kernels (global arrays)
 int mi_spmv(mi_ctx *c, const double *x_host, double *y_host)
 {
+  if (int e = check_tangent_array(c, "mi_spmv"))
+    return e;
   Team &T = *c->team;
   HIPCHK(c, hipSetDevice(c->device));
   if (int e = check_mf_tangent(c))
@@ -3115,8 +3190,20 @@ int mi_set_tuning(mi_ctx *c, const char *key, int value)
           m->mf_diag_fresh = false;
           continue;
         }
+      if (k == "linear_operator" && (value == 0 || value == 1))
+        {
+          // (checked on every member before any changes: a refused team keeps its assembled operators)
+          if (value == 1)
+            for (const mi_ctx *q : c->team->members)
+              if (c->team->size != 1 || q->dim != 3 || q->degree != 3)
+                return fail(c, MI_EINVAL, "the matrix-free linear model exists for 3D Q3 meshes on an undecomposed mesh only");
+          m->linear_operator = value;
+          continue;
+        }
       if (k == "fine_level" && (value == 0 || value == 1))
         {
+          if (m->linear_mf)
+            return fail(c, MI_EINVAL, "\"fine_level\": the matrix-free linear model shares the level's slots (\"linear_operator\" 0 and mi_linear_setup first)");
           const int rc = set_fine_level(m, value);
           if (rc)
             return fail(c, rc, "%s", m->err.c_str());
@@ -3291,6 +3378,10 @@ int mi_get_tuning(mi_ctx *c, const char *key, int *value)
     *value = (m->mf_slots && m->d_mf_yc) ? 1 : 0;
   else if (k == "fine_level")
     *value = m->mf_fine;
+  else if (k == "linear_operator")
+    *value = m->linear_operator;
+  else if (k == "linear_operator_active") // what the current linear set-up runs (0 without one)
+    *value = (m->linear && m->linear_mf) ? 1 : 0;
   else if (k == "mf_diag_lag")
     *value = m->mf_diag_lag;
   else if (k == "smoother_quadrature")
@@ -3384,6 +3475,8 @@ int mi_get_timings(mi_ctx *c, mi_timings *out)
 
 int mi_bench_spmv(mi_ctx *c, int reps, double *ms_per_launch)
 {
+  if (int e = check_tangent_array(c, "mi_bench_spmv"))
+    return e;
   HIPCHK(c, hipSetDevice(c->device));
   hipEvent_t a, b;
   HIPCHK(c, hipEventCreate(&a));
@@ -3451,6 +3544,8 @@ int mi_bench_spmv(mi_ctx *c, int reps, double *ms_per_launch)
 
 int mi_bench_assemble(mi_ctx *c, int reps, double *ms_per_assembly)
 {
+  if (int e = check_tangent_array(c, "mi_bench_assemble"))
+    return e;
   HIPCHK(c, hipSetDevice(c->device));
   hipEvent_t a, b;
   HIPCHK(c, hipEventCreate(&a));

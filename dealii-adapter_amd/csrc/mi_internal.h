@@ -51,6 +51,16 @@ namespace mi_detail
     double       *xnext = nullptr;
   };
   struct LinearModel; // mi_linear.cpp
+  // one operator of the matrix-free linear model ("linear_operator" 1, 3D Q3): what enqueue_spmv hands to mf_linear_q3 and the
+  // slot gathers.  K, M and the stepping matrix differ in `op` alone
+  struct LinearMf
+  {
+    mi::MfLinearOp op;
+    const double  *tab;     // 1D tables of the model's 4-point rule (MfParams::tab_q3s)
+    const double  *diag;    // [nnodes][9] diagonal of the stepping matrix, read as MfParams::vals ...
+    const int32_t *diagpos; // ... at [nnodes] the node's own id
+    const uint8_t *cmask;   // [nnodes] dofs whose row is diag x: the context's mask (stepping matrix) | none (K, M)
+  };
   struct Multigrid;   // mi_mg.cpp
 
   // the slab contexts that advance together (1 unless decomposed), see mi_ctx.cpp
@@ -256,6 +266,12 @@ struct mi_ctx
   // matrix / diagonal the SpMV and CG currently act on (tangent by default, linear-model operators otherwise)
   const double *active_sell_vals = nullptr;
   const double *active_dinv      = nullptr;
+  // tuning "linear_operator": 0 the linear model's K, M and stepping matrix assembled (sliced-ELL, active_sell_vals) | 1 matrix-free
+  // (3D Q3 on one slab: mf_linear_q3, active_linear_mf names the operator of the next product).  Read by the next mi_linear_setup;
+  // linear_mf: what the current set-up runs.  While it holds the context keeps NO assembled array: d_vals is released too
+  int           linear_operator = 0;
+  bool          linear_mf       = false;
+  const mi_detail::LinearMf *active_linear_mf = nullptr;
   std::vector<double> h_iface;   // host copy of the last interface values (linear model: consistent loading)
   mi_detail::LinearModel *linear = nullptr;
 
@@ -314,6 +330,12 @@ namespace mi_detail
               int expected_its = 0);    // multigrid-PCG: iterations the same solve took one time step earlier (0: unknown)
   int  team_size(const mi_ctx *c);
   void linear_destroy(mi_ctx *c);
+  int  build_slot_tables(mi_ctx *c);
+  int  upload_cellbox(mi_ctx *c);
+  // matrix-free linear model: slot tables, slots and cell boxes where absent, the tangent array released / allocated again
+  int  linear_mf_prepare(mi_ctx *c);
+  int  linear_mf_leave(mi_ctx *c);
+  mi::MfParams mf_params(const mi_ctx *c);
   int  create_member(Team &T, const mi_mesh_desc *md, const mi_material_desc *mat, const mi_newmark_desc *nm, int rank,
                      mi_ctx **out);
   void destroy_team(Team *T);

@@ -219,6 +219,14 @@ namespace mi
     int32_t         sel_n, sel_begin[9], sel_pos0[8];
   };
 
+  // matrix-free operator of the linear model on 3D Q3 cells (see mf_linear_q3): y = (c_K K + c_M M) x
+  struct MfLinearOp
+  {
+    double  lambda, mu, rho; // Lame parameters, density
+    double  c_K, c_M;        // K: 1, 0   M: 0, 1   stepping matrix: theta^2 dt^2, 1
+    int32_t masked;          // 1: x is read as zero at constrained dofs (the stepping matrix: its columns are dropped)
+  };
+
   // constant operators of the linear model (linear_elasticity.cc:248-374), one launch per colour
   struct LinAsmParams
   {
@@ -375,6 +383,13 @@ namespace mi
   // mf_records27), the rule's 1D tables MfParams::tab_q3s; one wave per cell, the results into the same cell-major slots
   void launch_mf_records_q3s(const MfParams &p, const double *u, const double *du, double *rec, int32_t cell_count, hipStream_t s);
   void launch_mf_spmv_q3s(const MfParams &p, int32_t cell_count, hipStream_t s, hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr);
+  // linear model, "linear_operator" 1 (3D Q3; see mf_linear_q3): the product (c_K K + c_M M) x into the cells' slots (MfParams::yc;
+  // the rule's 1D tables MfParams::tab_q3s), and the diagonal of that operator: every cell into the same slots, then summed per
+  // node into the diagonal entries of blk[nnodes][9] and inverted into dinv[ndofs]
+  void launch_mf_linear_q3(const MfParams &p, const MfLinearOp &op, int32_t cell_count, hipStream_t s, hipEvent_t ev_start = nullptr,
+                           hipEvent_t ev_stop = nullptr);
+  void launch_mf_linear_diag_q3(const MfParams &p, const MfLinearOp &op, int32_t cell_count, double *blk, double *dinv, int64_t ndofs,
+                                hipStream_t s);
   // the matrix-free fine level's point pass over ALL cells in one launch (assemble_q2sf<true> with the residual into slots:
   // AsmParams::res_slots / slot_dst; cell_begin = 0, cell_count = all) and the sum of the slots into system_rhs
   void launch_point_pass_slots(const AsmParams &p, hipStream_t s);

@@ -4357,105 +4357,11 @@ namespace mi
     MI_WAVE_SYNC(); // B is consumed
   }
 
-  // F, J^(-2/3), 1/J at the 64 points of the 4-point rule from u + du, one wave per cell.  The rule's points lie between the
-  // assembly's: a state that is valid at all 125 points can be folded at one of these, and such a point takes the undeformed
-  // state (the smoother's operator stays positive definite; the residual pass reports det F <= 0 at ITS points)
-  template <bool BOX>
-  __global__ __launch_bounds__(64 * MFQ3S_WPB) void mf_records_q3s(MfParams prm, const double *__restrict__ u, const double *__restrict__ du,
-                                                                   double *__restrict__ rec)
+  // I3 + I2 + I1 + store: Q in R (12 numbers per point: Q[i][l][t], the value term in row 3) -> the cell's 192 results in its
+  // slots.  S, D: the tables in scalar registers.
+  __device__ __forceinline__ void mfq3s_integrate(const MfParams &prm, const double (&S)[4][4], const double (&D)[4][4], double *__restrict__ R,
+                                                  const int t, const int ti, const int64_t cell)
   {
-    __shared__ double sR[MFQ3S_WPB][MFQ3S_R + MFQ3S_NTAB];
-    const int t = threadIdx.x & 63, ti = t < 48 ? t : t - 16;
-    int64_t   cell;
-    double   *R, *sT;
-    if (!mfq3s_wave(prm, sR, cell, R, sT))
-      return;
-    {
-      const int32_t node = prm.conn[cell * MFQ3S_NPC + t];
-#pragma unroll
-      for (int c = 0; c < 3; ++c)
-        R[mfq3s_xpos(t, c)] = u[int64_t(node) * 3 + c] + du[int64_t(node) * 3 + c];
-    }
-    double S[4][4], D[4][4]; // uniform: scalar registers
-#pragma unroll
-    for (int q = 0; q < 4; ++q)
-#pragma unroll
-      for (int a = 0; a < 4; ++a)
-        {
-          S[q][a] = prm.tab_q3s[q * 4 + a];
-          D[q][a] = prm.tab_q3s[MFQ3S_TD + q * 4 + a];
-        }
-    MI_WAVE_SYNC();
-    double H[3][3], V[3];
-    mfq3s_gradients(S, D, sT, R, t, ti, H, V);
-    const int qz = t >> 4, qy = (t >> 2) & 3, qx = t & 3;
-    double    Ji[9], detJ;
-    mf_geometry<BOX>(prm, cell, sT + MFQ3S_TX, qx, qy, qz, Ji, detJ);
-    MF_RECORD_TAIL(true, true, rec + cell * int64_t(MF_NREC * MFQ3S_NQ) + t, MFQ3S_NQ)
-  }
-
-  template <bool BOX>
-  __global__ __launch_bounds__(64 * MFQ3S_WPB) void mf_spmv_q3s(MfParams prm)
-  {
-    __shared__ double sR[MFQ3S_WPB][MFQ3S_R + MFQ3S_NTAB];
-    const int t = threadIdx.x & 63, ti = t < 48 ? t : t - 16;
-    int64_t   cell;
-    double   *R, *sT;
-    if (!mfq3s_wave(prm, sR, cell, R, sT))
-      return;
-    // gather x (constrained entries masked)
-    {
-      const int32_t node = prm.conn[cell * MFQ3S_NPC + t];
-      const int     cm   = prm.cmask[node];
-#pragma unroll
-      for (int c = 0; c < 3; ++c)
-        R[mfq3s_xpos(t, c)] = ((cm >> c) & 1) ? 0.0 : prm.x[int64_t(node) * 3 + c];
-    }
-    // this lane's record: consumed after the gradient passes
-    double rec[MF_NREC];
-    {
-      const double *__restrict__ rp = prm.qrec_q3s + cell * int64_t(MF_NREC * MFQ3S_NQ) + t;
-#pragma unroll
-      for (int f = 0; f < MF_NREC; ++f)
-        rec[f] = __builtin_nontemporal_load(&rp[f * MFQ3S_NQ]);
-    }
-    double S[4][4], D[4][4]; // uniform: scalar registers
-#pragma unroll
-    for (int q = 0; q < 4; ++q)
-#pragma unroll
-      for (int a = 0; a < 4; ++a)
-        {
-          S[q][a] = prm.tab_q3s[q * 4 + a];
-          D[q][a] = prm.tab_q3s[MFQ3S_TD + q * 4 + a];
-        }
-    MI_WAVE_SYNC();
-    double H[3][3], V[3];
-    mfq3s_gradients(S, D, sT, R, t, ti, H, V);
-    // ---- point stage: Q = JxW S M^T (MF_POINT_ALGEBRA), 12 numbers per point: Q[i][l][t], the mass term in row 3
-    {
-      const int    qz = t >> 4, qy = (t >> 2) & 3, qx = t & 3;
-      const double wq = sT[MFQ3S_TW + qx] * sT[MFQ3S_TW + qy] * sT[MFQ3S_TW + qz];
-      double       Finv[9], tau[6], tiso[6], cII, cS, Ji[9], detJ, M[9];
-      neo_hooke_from_F<3>(rec, det3x3(rec), rec[9], rec[10], prm.mu, prm.kappa, Finv, tau, tiso, cII, cS);
-      mf_geometry<BOX>(prm, cell, sT + MFQ3S_TX, qx, qy, qz, Ji, detJ);
-      MF_M(BOX, i_, j_)
-      const double w = detJ * wq, wcII = w * cII, cs2 = 0.5 * cS;
-      MF_POINT_ALGEBRA(double)
-      const double wm = prm.mass * w;
-#pragma unroll
-      for (int i = 0; i < 3; ++i)
-        {
-          double Sm[3];
-#pragma unroll
-          for (int j = 0; j < 3; ++j)
-            Sm[j] = MF_POINT_SM(double, i, j);
-#pragma unroll
-          for (int l = 0; l < 3; ++l)
-            R[i * MFQ3S_QC + l * 64 + t] = MF_POINT_Q(Sm, l);
-          R[i * MFQ3S_QC + 3 * 64 + t] = wm * V[i];
-        }
-    }
-    MI_WAVE_SYNC();
     const int ck = ti >> 2, lo = ti & 3;
     { // ---- I3: contract qz.  item (c, q16 = qy*4+qx) = ti
       const int c = ti >> 4, q16 = ti & 15;
@@ -4555,6 +4461,108 @@ namespace mi
           prm.yc[slot * 3 + c] = R[t * 3 + c + t / 4];
       }
   }
+
+  // F, J^(-2/3), 1/J at the 64 points of the 4-point rule from u + du, one wave per cell.  The rule's points lie between the
+  // assembly's: a state that is valid at all 125 points can be folded at one of these, and such a point takes the undeformed
+  // state (the smoother's operator stays positive definite; the residual pass reports det F <= 0 at ITS points)
+  template <bool BOX>
+  __global__ __launch_bounds__(64 * MFQ3S_WPB) void mf_records_q3s(MfParams prm, const double *__restrict__ u, const double *__restrict__ du,
+                                                                   double *__restrict__ rec)
+  {
+    __shared__ double sR[MFQ3S_WPB][MFQ3S_R + MFQ3S_NTAB];
+    const int t = threadIdx.x & 63, ti = t < 48 ? t : t - 16;
+    int64_t   cell;
+    double   *R, *sT;
+    if (!mfq3s_wave(prm, sR, cell, R, sT))
+      return;
+    {
+      const int32_t node = prm.conn[cell * MFQ3S_NPC + t];
+#pragma unroll
+      for (int c = 0; c < 3; ++c)
+        R[mfq3s_xpos(t, c)] = u[int64_t(node) * 3 + c] + du[int64_t(node) * 3 + c];
+    }
+    double S[4][4], D[4][4]; // uniform: scalar registers
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+#pragma unroll
+      for (int a = 0; a < 4; ++a)
+        {
+          S[q][a] = prm.tab_q3s[q * 4 + a];
+          D[q][a] = prm.tab_q3s[MFQ3S_TD + q * 4 + a];
+        }
+    MI_WAVE_SYNC();
+    double H[3][3], V[3];
+    mfq3s_gradients(S, D, sT, R, t, ti, H, V);
+    const int qz = t >> 4, qy = (t >> 2) & 3, qx = t & 3;
+    double    Ji[9], detJ;
+    mf_geometry<BOX>(prm, cell, sT + MFQ3S_TX, qx, qy, qz, Ji, detJ);
+    MF_RECORD_TAIL(true, true, rec + cell * int64_t(MF_NREC * MFQ3S_NQ) + t, MFQ3S_NQ)
+  }
+
+  template <bool BOX>
+  __global__ __launch_bounds__(64 * MFQ3S_WPB) void mf_spmv_q3s(MfParams prm)
+  {
+    __shared__ double sR[MFQ3S_WPB][MFQ3S_R + MFQ3S_NTAB];
+    const int t = threadIdx.x & 63, ti = t < 48 ? t : t - 16;
+    int64_t   cell;
+    double   *R, *sT;
+    if (!mfq3s_wave(prm, sR, cell, R, sT))
+      return;
+    // gather x (constrained entries masked)
+    {
+      const int32_t node = prm.conn[cell * MFQ3S_NPC + t];
+      const int     cm   = prm.cmask[node];
+#pragma unroll
+      for (int c = 0; c < 3; ++c)
+        R[mfq3s_xpos(t, c)] = ((cm >> c) & 1) ? 0.0 : prm.x[int64_t(node) * 3 + c];
+    }
+    // this lane's record: consumed after the gradient passes
+    double rec[MF_NREC];
+    {
+      const double *__restrict__ rp = prm.qrec_q3s + cell * int64_t(MF_NREC * MFQ3S_NQ) + t;
+#pragma unroll
+      for (int f = 0; f < MF_NREC; ++f)
+        rec[f] = __builtin_nontemporal_load(&rp[f * MFQ3S_NQ]);
+    }
+    double S[4][4], D[4][4]; // uniform: scalar registers
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+#pragma unroll
+      for (int a = 0; a < 4; ++a)
+        {
+          S[q][a] = prm.tab_q3s[q * 4 + a];
+          D[q][a] = prm.tab_q3s[MFQ3S_TD + q * 4 + a];
+        }
+    MI_WAVE_SYNC();
+    double H[3][3], V[3];
+    mfq3s_gradients(S, D, sT, R, t, ti, H, V);
+    // ---- point stage: Q = JxW S M^T (MF_POINT_ALGEBRA), 12 numbers per point: Q[i][l][t], the mass term in row 3
+    {
+      const int    qz = t >> 4, qy = (t >> 2) & 3, qx = t & 3;
+      const double wq = sT[MFQ3S_TW + qx] * sT[MFQ3S_TW + qy] * sT[MFQ3S_TW + qz];
+      double       Finv[9], tau[6], tiso[6], cII, cS, Ji[9], detJ, M[9];
+      neo_hooke_from_F<3>(rec, det3x3(rec), rec[9], rec[10], prm.mu, prm.kappa, Finv, tau, tiso, cII, cS);
+      mf_geometry<BOX>(prm, cell, sT + MFQ3S_TX, qx, qy, qz, Ji, detJ);
+      MF_M(BOX, i_, j_)
+      const double w = detJ * wq, wcII = w * cII, cs2 = 0.5 * cS;
+      MF_POINT_ALGEBRA(double)
+      const double wm = prm.mass * w;
+#pragma unroll
+      for (int i = 0; i < 3; ++i)
+        {
+          double Sm[3];
+#pragma unroll
+          for (int j = 0; j < 3; ++j)
+            Sm[j] = MF_POINT_SM(double, i, j);
+#pragma unroll
+          for (int l = 0; l < 3; ++l)
+            R[i * MFQ3S_QC + l * 64 + t] = MF_POINT_Q(Sm, l);
+          R[i * MFQ3S_QC + 3 * 64 + t] = wm * V[i];
+        }
+    }
+    MI_WAVE_SYNC();
+    mfq3s_integrate(prm, S, D, R, t, ti, cell);
+  }
   // (the last matrix-free kernel: the shared text ends here)
 #undef MF_RECORD_TAIL
 #undef MF_M
@@ -4563,6 +4571,131 @@ namespace mi
 #undef MF_POINT_Q
 #undef MF_DIAG_POINT
 #undef MF_DIAG_ACCUMULATE
+
+  // ------------------------------------------------------------------ linear model, 3D Q3: K, M and the stepping matrix without matrices
+  // "linear_operator" 1.  The linear model's rule is QGauss(p + 1) (linear_elasticity.cc:61): for Q3 the 4 x 4 x 4 points of
+  // mf_spmv_q3s -- one wave per cell, lane = point = node, its region layout, gradients (mfq3s_gradients) and integration
+  // (mfq3s_integrate) -- and here the rule is the model's own, so this is the assembled operator up to rounding.  The material is
+  // constant: no point record, the point stage is
+  //   G = H Jinv,  sigma = lambda tr(G) I + mu (G + G^T)  (:301-320 as assemble_linear_cells states it),
+  //   Q = JxW c_K sigma Jinv^T  into the three gradient rows,  JxW c_M rho V  into the value row,
+  // so  y_slots = (c_K K + c_M M) x:  K (1, 0), M (0, 1) and A = M + theta^2 dt^2 K (theta^2 dt^2, 1) from one kernel.  K and M
+  // are unconstrained in the assembled form too (only A drops entries), so x is masked at constrained dofs only where the
+  // launch says so (A); the rows of constrained dofs are replaced by diag(A) x in the gathers (mf_gather, mf_gather_dot).
+  template <bool BOX>
+  __global__ __launch_bounds__(64 * MFQ3S_WPB) void mf_linear_q3(MfParams prm, MfLinearOp op)
+  {
+    __shared__ double sR[MFQ3S_WPB][MFQ3S_R + MFQ3S_NTAB];
+    const int t = threadIdx.x & 63, ti = t < 48 ? t : t - 16;
+    int64_t   cell;
+    double   *R, *sT;
+    if (!mfq3s_wave(prm, sR, cell, R, sT))
+      return;
+    {
+      const int32_t node = prm.conn[cell * MFQ3S_NPC + t];
+      const int     cm   = op.masked ? prm.cmask[node] : 0;
+#pragma unroll
+      for (int c = 0; c < 3; ++c)
+        R[mfq3s_xpos(t, c)] = ((cm >> c) & 1) ? 0.0 : prm.x[int64_t(node) * 3 + c];
+    }
+    double S[4][4], D[4][4]; // uniform: scalar registers
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+#pragma unroll
+      for (int a = 0; a < 4; ++a)
+        {
+          S[q][a] = prm.tab_q3s[q * 4 + a];
+          D[q][a] = prm.tab_q3s[MFQ3S_TD + q * 4 + a];
+        }
+    MI_WAVE_SYNC();
+    double H[3][3], V[3];
+    mfq3s_gradients(S, D, sT, R, t, ti, H, V);
+    {
+      const int    qz = t >> 4, qy = (t >> 2) & 3, qx = t & 3;
+      const double wq = sT[MFQ3S_TW + qx] * sT[MFQ3S_TW + qy] * sT[MFQ3S_TW + qz];
+      double       Ji[9], detJ, G[3][3];
+      mf_geometry<BOX>(prm, cell, sT + MFQ3S_TX, qx, qy, qz, Ji, detJ);
+#pragma unroll
+      for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j)
+          G[i][j] = BOX ? H[i][j] * Ji[j * 4] : H[i][0] * Ji[j] + H[i][1] * Ji[3 + j] + H[i][2] * Ji[6 + j];
+      const double w = detJ * wq, wk = w * op.c_K, wm = w * op.c_M * op.rho;
+      const double ltr = op.lambda * (G[0][0] + G[1][1] + G[2][2]);
+#pragma unroll
+      for (int i = 0; i < 3; ++i)
+        {
+          double sg[3];
+#pragma unroll
+          for (int j = 0; j < 3; ++j)
+            sg[j] = wk * (op.mu * (G[i][j] + G[j][i]) + (i == j ? ltr : 0.0));
+#pragma unroll
+          for (int l = 0; l < 3; ++l)
+            R[i * MFQ3S_QC + l * 64 + t] = BOX ? sg[l] * Ji[l * 4] : sg[0] * Ji[l * 3] + sg[1] * Ji[l * 3 + 1] + sg[2] * Ji[l * 3 + 2];
+          R[i * MFQ3S_QC + 3 * 64 + t] = wm * V[i];
+        }
+    }
+    MI_WAVE_SYNC();
+    mfq3s_integrate(prm, S, D, R, t, ti, cell);
+  }
+
+  // diagonal of A = M + theta^2 dt^2 K per cell and node into the product's slots [nslots][3] (prm.yc), once per set-up:
+  //   A_(a,c)(a,c) = sum_q JxW (theta^2 dt^2 ((lambda + mu) g_a[c]^2 + mu g_a . g_a) + rho N_a^2),   g_a = Jinv^T grad_xi N_a.
+  // One wave per cell, lane = node a = (k*4+j)*4+i, a loop over the 64 points; written for clarity.  Nothing is dropped on the
+  // diagonal (a constrained dof keeps its own: MatrixTools::apply_boundary_values, :426-451).
+  template <bool BOX>
+  __global__ __launch_bounds__(64 * MFQ3S_WPB) void mf_linear_diag_q3(MfParams prm, MfLinearOp op)
+  {
+    const int     t    = threadIdx.x & 63;
+    const int64_t cell = int64_t(blockIdx.x) * MFQ3S_WPB + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    if (cell >= prm.count)
+      return;
+    const int     ia[3] = {t & 3, (t >> 2) & 3, t >> 4};
+    const double *tab   = prm.tab_q3s;
+    double        d[3]  = {0.0, 0.0, 0.0};
+    for (int q = 0; q < MFQ3S_NQ; ++q)
+      {
+        const int qi[3] = {q & 3, (q >> 2) & 3, q >> 4};
+        double    v[3], dv[3], Ji[9], detJ, g[3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k)
+          {
+            v[k]  = tab[qi[k] * 4 + ia[k]];
+            dv[k] = tab[MFQ3S_TD + qi[k] * 4 + ia[k]];
+          }
+        const double n = v[0] * v[1] * v[2], dn[3] = {dv[0] * v[1] * v[2], v[0] * dv[1] * v[2], v[0] * v[1] * dv[2]};
+        mf_geometry<BOX>(prm, cell, tab + MFQ3S_TX, qi[0], qi[1], qi[2], Ji, detJ);
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+          g[i] = dn[0] * Ji[i] + dn[1] * Ji[3 + i] + dn[2] * Ji[6 + i];
+        const double w  = detJ * tab[MFQ3S_TW + qi[0]] * tab[MFQ3S_TW + qi[1]] * tab[MFQ3S_TW + qi[2]];
+        const double gg = g[0] * g[0] + g[1] * g[1] + g[2] * g[2];
+#pragma unroll
+        for (int c = 0; c < 3; ++c)
+          d[c] += w * (op.c_K * ((op.lambda + op.mu) * g[c] * g[c] + op.mu * gg) + op.c_M * op.rho * n * n);
+      }
+    const int64_t slot = prm.slot_inline ? cell * MFQ3S_NPC + t : int64_t(prm.dst[cell * MFQ3S_NPC + t]);
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+      prm.yc[slot * 3 + c] = d[c];
+  }
+
+  // ... summed per node in slot order (= processing order of the cells) into the diagonal entries of the node's block
+  // blk[n][9] -- where the gathers read the diagonal of constrained dofs (MfParams::vals / diagpos) -- and 1 / diag into dinv.
+  // One thread per dof.
+  __global__ __launch_bounds__(256) void mf_linear_diag_gather(MfParams prm, double *__restrict__ blk, double *__restrict__ dinv, int64_t ndofs)
+  {
+    const int64_t g = int64_t(blockIdx.x) * 256 + threadIdx.x;
+    if (g >= ndofs)
+      return;
+    const int64_t n = g / 3;
+    const int     c = int(g - n * 3);
+    const double  s = mf_slot_sum(prm, prm.slot_base[n], prm.slot_base[n + 1], c);
+#pragma unroll
+    for (int j = 0; j < 3; ++j)
+      blk[n * 9 + c * 3 + j] = j == c ? s : 0.0;
+    dinv[g] = 1.0 / s;
+  }
 
   // system_rhs from the cells' residual slots (point pass in one launch): rhs = 0 - r_1 - r_2 - ... in slot order, the
   // subtractions of the colour-by-colour update in their order; constrained rows get no rhs (:769-773).  One thread per dof.
@@ -7492,6 +7625,30 @@ namespace mi
       hipExtLaunchKernelGGL(kern, grid, block, 0, s, ev_start, ev_stop, 0, q);
     else
       hipLaunchKernelGGL(kern, grid, block, 0, s, q);
+  }
+  void launch_mf_linear_q3(const MfParams &p, const MfLinearOp &op, int32_t cell_count, hipStream_t s, hipEvent_t ev_start, hipEvent_t ev_stop)
+  {
+    if (cell_count <= 0)
+      return;
+    MfParams q = p;
+    q.count    = cell_count;
+    auto *kern = q.cellbox ? mf_linear_q3<true> : mf_linear_q3<false>;
+    const dim3 grid((cell_count + MFQ3S_WPB - 1) / MFQ3S_WPB), block(64 * MFQ3S_WPB);
+    if (ev_start || ev_stop)
+      hipExtLaunchKernelGGL(kern, grid, block, 0, s, ev_start, ev_stop, 0, q, op);
+    else
+      hipLaunchKernelGGL(kern, grid, block, 0, s, q, op);
+  }
+  void launch_mf_linear_diag_q3(const MfParams &p, const MfLinearOp &op, int32_t cell_count, double *blk, double *dinv, int64_t ndofs,
+                                hipStream_t s)
+  {
+    if (cell_count <= 0)
+      return;
+    MfParams q = p;
+    q.count    = cell_count;
+    auto *kern = q.cellbox ? mf_linear_diag_q3<true> : mf_linear_diag_q3<false>;
+    hipLaunchKernelGGL(kern, dim3((cell_count + MFQ3S_WPB - 1) / MFQ3S_WPB), dim3(64 * MFQ3S_WPB), 0, s, q, op);
+    hipLaunchKernelGGL(mf_linear_diag_gather, dim3(int((ndofs + 255) / 256)), dim3(256), 0, s, q, blk, dinv, ndofs);
   }
   void launch_mf_diag_gather(const double *slots6, const int32_t *slot_base, const int32_t *slot_src, const uint8_t *cmask,
                              const int32_t *diagpos, double *blk, double *dinv, double *dinv_blk, double *sym6, int64_t nnodes, hipStream_t s)

@@ -6,6 +6,11 @@
 // layout of the tangent (x-line-interleaved block rows, mi_mesh.hpp); only the consistent-load operator of the interface
 // (interface-sized) is put together on the host.  The per-step path (assemble_rhs :378-454, solve :525-575, update_displacement :579-586) runs on the
 // device: fused vector kernels, 2 SpMVs (M v - K (theta(1-theta)dt^2 v + dt d)) and the warm-started PCG.
+//
+// Tuning "linear_operator" 1 (3D Q3, one slab): nothing is assembled.  K, M and the stepping matrix are one kernel
+// (mf_linear_q3: (c_K K + c_M M) x on the model's own 4 x 4 x 4 rule, one wave per cell) + the slot gathers; the set-up forms
+// the diagonal of the stepping matrix (mf_linear_diag_q3) and the body-force vector as M (b, b, ...), and releases the
+// nonlinear tangent array.  The per-step path is the same; the solve is the Jacobi-PCG whatever "solver_type" says.
 #include <cmath>
 #include <cstring>
 #include <map>
@@ -20,6 +25,14 @@ namespace mi_detail
     double *d_K = nullptr, *d_M = nullptr, *d_A = nullptr, *d_dinvA = nullptr, *d_body = nullptr;
     bool    body_force_enabled = false;
     bool    factored = false; // the banded Cholesky factor of the (constant) system matrix is in the context's band
+    // "linear_operator" 1: no d_K / d_M / d_A; the three operators as mf_linear_q3 runs them, the diagonal of the stepping
+    // matrix in the layout the slot gathers read (mi_ctx::d_diag_blk's), the rule's tables -- all the model's own, so that
+    // no key of the nonlinear path can take them away
+    bool     mf = false;
+    LinearMf op[3]; // K, M, stepping matrix
+    double  *d_diag = nullptr, *d_tab4 = nullptr;
+    int32_t *d_diagpos_mf = nullptr;
+    uint8_t *d_nomask = nullptr; // [nnodes] zeros: the constraint mask of K and M (no row replaced)
     // consistent-load operator on the interface nodes (scalar CSR over interface slots), :458-521
     std::vector<int32_t> B_rowptr, B_col;
     std::vector<double>  B_val;
@@ -29,9 +42,15 @@ namespace mi_detail
   {
     if (!c->linear)
       return;
-    for (double *p : {c->linear->d_K, c->linear->d_M, c->linear->d_A, c->linear->d_dinvA, c->linear->d_body})
+    for (double *p : {c->linear->d_K, c->linear->d_M, c->linear->d_A, c->linear->d_dinvA, c->linear->d_body, c->linear->d_diag,
+                      c->linear->d_tab4})
       if (p)
         hipFree(p);
+    if (c->linear->d_diagpos_mf)
+      hipFree(c->linear->d_diagpos_mf);
+    if (c->linear->d_nomask)
+      hipFree(c->linear->d_nomask);
+    c->active_linear_mf = nullptr;
     delete c->linear;
     c->linear = nullptr;
   }
@@ -62,32 +81,61 @@ using namespace mi_detail;
 
 extern "C" {
 
-// K, M, stepping matrix, load operator and body force of ONE slab: the launches run over the slab's local cells
-// (ghost layer included), which completes every owned row exactly as the tangent's assembly does
-static int linear_setup_member(mi_ctx *c, double theta)
+// "linear_operator" 1: nothing is assembled.  Slot tables, slots and cell boxes where absent; the rule's tables; the three
+// operators; the diagonal of the stepping matrix and its inverse; body = M (b, b, ...)
+static int linear_setup_matrix_free(mi_ctx *c, LinearModel &L, const mi::Tables1D &t, double lambda, double theta)
 {
-  linear_destroy(c);
-  c->linear      = new LinearModel;
-  LinearModel &L = *c->linear;
-  L.theta        = theta;
+  const mi::HostMesh &m  = c->mesh;
+  const size_t        nn = size_t(m.nnodes);
+  const double        mu = c->mat.mu, rho = c->mat.rho, dt = c->nm.delta_t;
+  if (int rc = linear_mf_prepare(c))
+    return rc;
+  if (int rc = upload(c, &L.d_tab4, t.packed()))
+    return rc;
+  std::vector<int32_t> dp(nn);
+  for (size_t n = 0; n < nn; ++n)
+    dp[n] = int32_t(n);
+  if (int rc = upload(c, &L.d_diagpos_mf, dp))
+    return rc;
+  HIPCHK(c, hipMalloc((void **)&L.d_nomask, nn));
+  HIPCHK(c, hipMemsetAsync(L.d_nomask, 0, nn, c->stream));
+  HIPCHK(c, hipMalloc((void **)&L.d_diag, nn * 9 * sizeof(double)));
+  HIPCHK(c, hipMalloc((void **)&L.d_dinvA, size_t(c->n) * sizeof(double)));
+  // K and M are unconstrained (assemble_linear_cells drops entries in A only): x unmasked, no row replaced
+  const double cK[3] = {1.0, 0.0, dt * dt * theta * theta}, cM[3] = {0.0, 1.0, 1.0};
+  for (int w = 0; w < 3; ++w)
+    L.op[w] = LinearMf{mi::MfLinearOp{lambda, mu, rho, cK[w], cM[w], w == 2 ? 1 : 0}, L.d_tab4, L.d_diag, L.d_diagpos_mf,
+                       w == 2 ? c->d_cmask : L.d_nomask};
+  mi::MfParams f = mf_params(c);
+  f.tab_q3s = L.d_tab4, f.yc = c->d_mf_yc, f.dst = c->d_mf_dst, f.slot_base = c->d_mf_slot_base, f.slot_src = c->d_mf_src;
+  f.slot_inline = c->slots_layout == 1;
+  mi::launch_mf_linear_diag_q3(f, L.op[2].op, int32_t(m.ncells), L.d_diag, L.d_dinvA, c->n, c->stream);
+  HIPCHK(c, hipGetLastError());
+  if (L.body_force_enabled)
+    {
+      // rho b int N_a = sum_b M_ab b: the shape functions sum to one (create_right_hand_side :358-373)
+      HIPCHK(c, hipMalloc((void **)&L.d_body, size_t(c->n) * sizeof(double)));
+      std::vector<double> b(size_t(c->n));
+      for (size_t g = 0; g < b.size(); ++g)
+        b[g] = c->mat.body_force[g % 3];
+      HIPCHK(c, hipMemcpy(c->work(W_P), b.data(), b.size() * sizeof(double), hipMemcpyHostToDevice));
+      c->active_linear_mf = &L.op[1];
+      enqueue_spmv(c, c->work(W_P), L.d_body, nullptr, nullptr, nullptr);
+      c->active_linear_mf = nullptr;
+      HIPCHK(c, hipGetLastError());
+    }
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return MI_OK;
+}
 
+// K, M, A assembled (tuning "linear_operator" 0) and the body-force vector
+static int linear_assemble_operators(mi_ctx *c, LinearModel &L, const mi::Tables1D &t, double lambda, double theta)
+{
   const mi::HostMesh &m   = c->mesh;
-  const int           dim = c->dim, npc = m.npc, DD = dim * dim;
-  const double        mu = c->mat.mu, nu = c->mat.nu, rho = c->mat.rho;
-  const double        lambda = 2 * mu * nu / (1 - 2 * nu); // parameters.cc:189
-  const double        dt     = c->nm.delta_t;
-
-  mi::Tables1D t;
-  t.build(c->degree, c->degree + 1); // quad_order = p+1 (linear_elasticity.cc:61)
-  int nqf = 1;
-  for (int d = 0; d < dim - 1; ++d)
-    nqf *= t.nq1;
-
-  double bn = 0;
-  for (int d = 0; d < 3; ++d)
-    bn += c->mat.body_force[d] * c->mat.body_force[d];
-  L.body_force_enabled = std::sqrt(bn) > 1e-15; // :62
-
+  const int           dim = c->dim, DD = dim * dim;
+  const double        mu = c->mat.mu, rho = c->mat.rho, dt = c->nm.delta_t;
+  if (int rc = linear_mf_leave(c))
+    return rc;
   // K, M, A = M + theta^2 dt^2 K with zero boundary values applied, and the body-force vector: on the device
   const size_t nval = std::max<size_t>(1, size_t(m.nvalblocks()) * DD);
   double      *d_tab = nullptr;
@@ -136,6 +184,37 @@ static int linear_setup_member(mi_ctx *c, double theta)
     HIPCHK(c, hipStreamSynchronize(c->stream));
     hipFree(d_tab);
   }
+  return MI_OK;
+}
+
+// K, M, stepping matrix, load operator and body force of ONE slab: the launches run over the slab's local cells
+// (ghost layer included), which completes every owned row exactly as the tangent's assembly does
+static int linear_setup_member(mi_ctx *c, double theta)
+{
+  linear_destroy(c);
+  c->linear      = new LinearModel;
+  LinearModel &L = *c->linear;
+  L.theta        = theta;
+
+  const mi::HostMesh &m   = c->mesh;
+  const int           dim = c->dim, npc = m.npc;
+  const double        mu = c->mat.mu, nu = c->mat.nu;
+  const double        lambda = 2 * mu * nu / (1 - 2 * nu); // parameters.cc:189
+
+  mi::Tables1D t;
+  t.build(c->degree, c->degree + 1); // quad_order = p+1 (linear_elasticity.cc:61)
+  int nqf = 1;
+  for (int d = 0; d < dim - 1; ++d)
+    nqf *= t.nq1;
+
+  double bn = 0;
+  for (int d = 0; d < 3; ++d)
+    bn += c->mat.body_force[d] * c->mat.body_force[d];
+  L.body_force_enabled = std::sqrt(bn) > 1e-15; // :62
+
+  L.mf = c->linear_operator == 1;
+  if (int rc = L.mf ? linear_setup_matrix_free(c, L, t, lambda, theta) : linear_assemble_operators(c, L, t, lambda, theta))
+    return rc;
 
   // consistent-load operator B_ab = int_interface N_a N_b dA (assemble_consistent_loading :458-521, no pull-back)
   {
@@ -208,13 +287,25 @@ static int linear_setup_member(mi_ctx *c, double theta)
       }
   }
 
-  // Jacobi diagonal of A
-  HIPCHK(c, hipMalloc((void **)&L.d_dinvA, size_t(c->n) * sizeof(double)));
-  mi::launch_extract_dinv(c->dim, L.d_A, c->d_diagpos, L.d_dinvA, m.nnodes, c->stream);
-  HIPCHK(c, hipGetLastError());
+  // Jacobi diagonal of A (matrix-free: formed above)
+  if (!L.mf)
+    {
+      HIPCHK(c, hipMalloc((void **)&L.d_dinvA, size_t(c->n) * sizeof(double)));
+      mi::launch_extract_dinv(c->dim, L.d_A, c->d_diagpos, L.d_dinvA, m.nnodes, c->stream);
+      HIPCHK(c, hipGetLastError());
+    }
   HIPCHK(c, hipMemsetAsync(c->d_vecs, 0, size_t(MI_V_COUNT) * size_t(c->n) * sizeof(double), c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return MI_OK;
+}
+
+// which operator the next products of a slab apply: 0 K, 1 M, 2 the stepping matrix; -1 none (back to the tangent)
+static void linear_select(mi_ctx *m, int which)
+{
+  LinearModel &L      = *m->linear;
+  m->active_sell_vals = (which < 0 || L.mf) ? nullptr : which == 0 ? L.d_K : which == 1 ? L.d_M : L.d_A;
+  m->active_linear_mf = (which < 0 || !L.mf) ? nullptr : &L.op[which];
+  m->active_dinv      = which == 2 ? L.d_dinvA : nullptr;
 }
 
 int mi_linear_setup(mi_ctx *c, double theta)
@@ -291,13 +382,13 @@ int mi_linear_step(mi_ctx *c, int data_consistent, double abs_tol, int64_t max_i
   auto self = [](mi_ctx *m) { return m; };
   int  rc;
   for (mi_ctx *m : T.members)
-    m->active_sell_vals = m->linear->d_M;
+    linear_select(m, 1);
   int t = tic(c0, MI_T_SPMV);
   rc    = team_spmv(
     T, self, [](mi_ctx *m) { return m->vec(MI_L_OLD_VELOCITY); }, [](mi_ctx *m) { return m->work(W_R); }, nullptr);
   toc(c0, t);
   for (mi_ctx *m : T.members)
-    m->active_sell_vals = m->linear->d_K;
+    linear_select(m, 0);
   t = tic(c0, MI_T_SPMV);
   if (!rc)
     rc = team_spmv(
@@ -311,12 +402,10 @@ int mi_linear_step(mi_ctx *c, int data_consistent, double abs_tol, int64_t max_i
   HIPCHK(c, hipGetLastError());
   // solve (:531-551): absolute tolerance, start vector = previous velocity
   for (mi_ctx *m : T.members)
-    {
-      m->active_sell_vals = m->linear->d_A;
-      m->active_dinv      = m->linear->d_dinvA;
-    }
+    linear_select(m, 2);
+  // (matrix-free: there is no matrix to factorise -- the PCG route, as for a system too large for the band solver)
   bool direct = false;
-  if (!rc && c0->solver_direct && T.size == 1 && direct_prepare(c0) == MI_OK)
+  if (!rc && c0->solver_direct && T.size == 1 && !c0->linear->mf && direct_prepare(c0) == MI_OK)
     {
       // "Solver type = Direct" (:553-559): the system matrix is constant, so it is factorised ONCE and a step is one
       // forward and one backward substitution
@@ -332,10 +421,7 @@ int mi_linear_step(mi_ctx *c, int data_consistent, double abs_tol, int64_t max_i
   if (!rc && !direct)
     rc = cg_run(c0, MI_L_VELOCITY, MI_L_SYSTEM_RHS, -abs_tol, max_it, its, res);
   for (mi_ctx *m : T.members)
-    {
-      m->active_sell_vals = nullptr;
-      m->active_dinv      = nullptr;
-    }
+    linear_select(m, -1);
   if (rc)
     return rc;
   for (size_t k = 0; k < T.members.size(); ++k)
@@ -350,6 +436,8 @@ int mi_linear_matrix_get_csr(mi_ctx *c, int which, int64_t *rowptr, int32_t *col
     return fail(c, MI_EINVAL, "linear model not set up or bad matrix id");
   if (team_size(c) != 1)
     return fail(c, MI_EINVAL, "matrix export is only available on an undecomposed mesh");
+  if (c->linear->mf)
+    return fail(c, MI_EINVAL, "matrix export: the matrix-free linear model keeps no assembled operator (\"linear_operator\" 0)");
   const int           D = c->dim, DD = D * D;
   const mi::HostMesh &m = c->mesh;
   HIPCHK(c, hipSetDevice(c->device));
@@ -371,6 +459,61 @@ int mi_linear_matrix_get_csr(mi_ctx *c, int which, int64_t *rowptr, int32_t *col
             }
       }
   rowptr[m.nnodes * D] = k;
+  return MI_OK;
+}
+
+// y = K x (0), M x (1) or A x (2) through the device kernels of the current mode: the sliced-ELL product on the assembled
+// arrays or mf_linear_q3 + mf_gather.  The product is timed as MI_T_SPMV (device stamps) when profiling is on.
+int mi_linear_apply(mi_ctx *c, int which, const double *x_host, double *y_host)
+{
+  if (!c->linear || which < 0 || which > 2 || !x_host || !y_host)
+    return fail(c, MI_EINVAL, "linear model not set up, bad operator id or null argument");
+  if (team_size(c) != 1)
+    return fail(c, MI_EINVAL, "mi_linear_apply is only available on an undecomposed mesh");
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipMemcpy(c->work(W_P), x_host, size_t(c->n) * sizeof(double), hipMemcpyHostToDevice));
+  linear_select(c, which);
+  const int t = tic(c, MI_T_SPMV);
+  enqueue_spmv(c, c->work(W_P), c->work(W_Q), nullptr, nullptr, nullptr);
+  toc(c, t);
+  linear_select(c, -1);
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipMemcpy(y_host, c->work(W_Q), size_t(c->n) * sizeof(double), hipMemcpyDeviceToHost));
+  return MI_OK;
+}
+
+// the Jacobi diagonal of the stepping matrix in use: the diagonal entries whose reciprocals the PCG multiplies with -- out of
+// the assembled array, or as mf_linear_diag_q3 formed them
+int mi_linear_get_diagonal(mi_ctx *c, double *diag_host)
+{
+  if (!c->linear || !diag_host)
+    return fail(c, MI_EINVAL, "linear model not set up or null argument");
+  if (team_size(c) != 1)
+    return fail(c, MI_EINVAL, "mi_linear_get_diagonal is only available on an undecomposed mesh");
+  const LinearModel &L = *c->linear;
+  const int          D = c->dim, DD = D * D;
+  const size_t       cnt = size_t(c->mesh.nnodes) * DD;
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  std::vector<double> blk(cnt);
+  if (L.mf)
+    HIPCHK(c, hipMemcpy(blk.data(), L.d_diag, cnt * sizeof(double), hipMemcpyDeviceToHost));
+  else
+    {
+      double *tmp = nullptr;
+      HIPCHK(c, hipMalloc((void **)&tmp, cnt * sizeof(double)));
+      mi::launch_gather_diag_blocks(D, L.d_A, c->d_diagpos, tmp, c->mesh.nnodes, c->stream);
+      const hipError_t e1 = hipStreamSynchronize(c->stream);
+      const hipError_t e2 = hipMemcpy(blk.data(), tmp, cnt * sizeof(double), hipMemcpyDeviceToHost);
+      hipFree(tmp);
+      HIPCHK(c, e1);
+      HIPCHK(c, e2);
+    }
+  for (int64_t n = 0; n < c->mesh.nnodes; ++n)
+    for (int k = 0; k < D; ++k)
+      diag_host[n * D + k] = blk[size_t(n) * DD + k * D + k];
   return MI_OK;
 }
 

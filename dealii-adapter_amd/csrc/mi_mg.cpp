@@ -104,7 +104,7 @@ namespace mi_detail
 
   bool mg_active(const mi_ctx *c)
   {
-    return c->precond == 1 && c->mg && c->mg->levels.size() > 1 && !c->active_sell_vals;
+    return c->precond == 1 && c->mg && c->mg->levels.size() > 1 && !c->active_sell_vals && !c->active_linear_mf;
   }
 
   namespace

@@ -95,7 +95,18 @@ namespace Linear_Elasticity
     if (const char *e = std::getenv("MI_DEVICE"))
       dev_id = std::atoi(e);
     device = std::make_unique<mi::Device>(mesh_desc, mat, nm, dev_id);
+    // MI_LINEAR_OPERATOR=1: K, M and the stepping matrix matrix-free (3D Q3 on one rank; a switch of this PROGRAM, handed on
+    // as a tuning key: the library itself reads no environment variable).  Refused elsewhere: said once, the run is assembled
+    if (const char *f = std::getenv("MI_LINEAR_OPERATOR"))
+      if (std::atoi(f) != 0 && mi_set_tuning(device->ctx(), "linear_operator", 1) != MI_OK)
+        std::cout << "MI_LINEAR_OPERATOR ignored: " << mi_last_error(device->ctx()) << std::endl;
     device->check(mi_linear_setup(device->ctx(), parameters.theta), "mi_linear_setup");
+    {
+      int mf = 0;
+      device->check(mi_get_tuning(device->ctx(), "linear_operator_active", &mf), "mi_get_tuning");
+      if (mf)
+        std::cout << "Linear operators: matrix-free (K, M and the stepping matrix on mf_linear_q3, nothing assembled)" << std::endl;
+    }
 
     std::cout << "Triangulation:"
               << "\n\t Number of active cells: " << mi_n_cells(device->ctx())

@@ -204,6 +204,12 @@ int mi_linear_setup(mi_ctx *ctx, double theta);
 int mi_linear_step(mi_ctx *ctx, int data_consistent, double abs_tol, int64_t max_it, int *its, double *res);
 /* K (0), M (1) or the constrained stepping matrix (2) as scalar CSR, for parity tests */
 int mi_linear_matrix_get_csr(mi_ctx *ctx, int which, int64_t *rowptr, int32_t *col, double *val);
+/* y = K x (0), M x (1) or A x (2) through the device kernels the current set-up runs, in either mode of "linear_operator"
+ * (host arrays of n_dofs; undecomposed mesh).  A: constrained columns dropped, row of a constrained dof = diag(A) x.  K, M:
+ * unconstrained, as assembled.  With profiling on, the product alone is timed under MI_T_SPMV. */
+int mi_linear_apply(mi_ctx *ctx, int which, const double *x_host, double *y_host);
+/* the Jacobi diagonal of the stepping matrix the PCG of mi_linear_step uses (n_dofs; undecomposed mesh) */
+int mi_linear_get_diagonal(mi_ctx *ctx, double *diag_host);
 
 /* per-vector device snapshots: what `old_state_data[i] = *state_variables[i]` (adapter.h:457-460) and its
  * inverse (:481-482) become when VectorType is a handle to a device-resident vector */
@@ -299,6 +305,19 @@ int mi_set_profiling(mi_ctx *ctx, int enable);
  *                                                  memory is released.  Same results (nonlinear_elasticity.cc:1044-1087,
  *                                                  1153-1191); excludes "solver_type" 1, "precond_storage" 32 and matrix
  *                                                  export
+ *  linear_operator      0 | 1                      linear model (mi_linear_setup / mi_linear_step): K, M and the stepping  -
+ *                                                  matrix assembled in the tangent's sliced-ELL layout | matrix-free on 3D
+ *                                                  Q3 meshes of one slab (elsewhere: MI_EINVAL, the key stays 0): one
+ *                                                  kernel, mf_linear_q3, applies (c_K K + c_M M) x on the model's own
+ *                                                  4 x 4 x 4 rule (linear_elasticity.cc:61), one wave per cell, no point
+ *                                                  record; the diagonal of the stepping matrix comes from mf_linear_diag_q3,
+ *                                                  the body force as M (b, b, ...).  Read by the next mi_linear_setup, which
+ *                                                  then keeps no assembled array: the nonlinear tangent array is released
+ *                                                  too, and mi_assemble, mi_newmark_step, mi_cg_solve, mi_spmv and the matrix
+ *                                                  exports return MI_EINVAL until a set-up with 0.  "solver_type" 1 takes
+ *                                                  the PCG route there; "fine_level" cannot change meanwhile.  Same
+ *                                                  operators up to rounding.  Read-back "linear_operator_active": what the
+ *                                                  current linear set-up runs (0 without one)
  *  mf_diag_lag          0 | 1                      "fine_level" 1: diagonal blocks (smoother's D, Jacobi diagonal) at     -
  *                                                  every tangent | at the first tangent of a time step, kept over its
  *                                                  Newton iterations (what bench.py and the executable set)
