@@ -66,6 +66,12 @@ class Timings(C.Structure):
     _fields_ = [("ms", C.c_double * T_COUNT), ("count", C.c_int64 * T_COUNT)]
 
 
+class MgLevelDesc(C.Structure):
+    _fields_ = [("degree", C.c_int32), ("reps", C.c_int32 * 3), ("n_dofs", C.c_int64), ("lmax", C.c_double),
+                ("interval_ratio", C.c_double), ("smoother_degree", C.c_int32), ("exact_solve", C.c_int32),
+                ("distributed", C.c_int32), ("reserved", C.c_int32)]
+
+
 class MiError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("mi_elasticity error %d: %s" % (code, msg))
@@ -148,6 +154,11 @@ def lib():
         L.mi_get_tuning.restype = C.c_int
         L.mi_bench_spmv.argtypes = [vp, C.c_int, dp]
         L.mi_bench_assemble.argtypes = [vp, C.c_int, dp]
+        L.mi_mg_n_levels.argtypes = [vp]
+        L.mi_mg_level_describe.argtypes = [vp, C.c_int, C.POINTER(MgLevelDesc)]
+        L.mi_mg_level_context.argtypes = [vp, C.c_int, C.POINTER(vp)]
+        for f in ("mi_mg_n_levels", "mi_mg_level_describe", "mi_mg_level_context"):
+            getattr(L, f).restype = C.c_int
         for f in ("mi_get_node_coords", "mi_get_constrained", "mi_get_interface_nodes", "mi_set_interface_traction",
                   "mi_get_interface_displacement", "mi_assemble", "mi_cg_solve", "mi_apply_newton_update",
                   "mi_newmark_step", "mi_vec_get", "mi_vec_set", "mi_matrix_get_csr", "mi_spmv", "mi_set_profiling",
@@ -210,6 +221,42 @@ def comm_unique_id():
     if rc != MI_OK:
         raise MiError(rc, lib().mi_last_error(None).decode())
     return buf.raw
+
+
+class LevelView:
+    """a level of the multigrid hierarchy, borrowed from its context (mi_mg_level_context): read methods only.  It dies with
+    the next rebuild of the hierarchy and with the context; close() does nothing."""
+
+    def __init__(self, owner, handle):
+        self._owner = owner  # keeps the context alive
+        self.h = handle
+        L = lib()
+        self.dim = owner.dim
+        self.n = L.mi_n_dofs(self.h)
+        self.nnodes = L.mi_n_nodes(self.h)
+        self.nnz = L.mi_nnz(self.h)
+
+    def close(self):
+        pass
+
+    def _chk(self, rc):
+        if rc != MI_OK:
+            raise MiError(rc, lib().mi_last_error(self.h).decode())
+
+    @property
+    def constrained(self):
+        return Context.constrained.fget(self)
+
+    def total_displacement(self):
+        """levels >= 1: the state the level's operator was assembled at (u + du interpolated down).  Level 0 is the fine
+        context itself and this is its V_U alone; its tangent was assembled at V_U + V_DELTA"""
+        return Context.get(self, V_U)
+
+    def csr(self):
+        return Context.csr(self)
+
+    def diagonal_blocks(self):
+        return Context.diagonal_blocks(self)
 
 
 class Context:
@@ -393,6 +440,22 @@ class Context:
         b = np.zeros((self.nnodes, self.dim, self.dim))
         self._chk(lib().mi_get_diagonal_blocks(self.h, _dp(b)))
         return b
+
+    # ---- the multigrid hierarchy as the last linear solve left it, read-only (tests)
+    def mg_n_levels(self):
+        return lib().mi_mg_n_levels(self.h)
+
+    def mg_level_describe(self, level):
+        d = MgLevelDesc()
+        self._chk(lib().mi_mg_level_describe(self.h, level, C.byref(d)))
+        return dict(degree=d.degree, reps=tuple(d.reps)[:self.dim], n_dofs=d.n_dofs, lmax=d.lmax,
+                    interval_ratio=d.interval_ratio, smoother_degree=d.smoother_degree, exact_solve=d.exact_solve,
+                    distributed=d.distributed)
+
+    def mg_level_context(self, level):
+        h = C.c_void_p()
+        self._chk(lib().mi_mg_level_context(self.h, level, C.byref(h)))
+        return LevelView(self, h)
 
     # ---- linear model (mi_linear_setup / mi_linear_step); the operators follow the tuning key "linear_operator"
     def linear_setup(self, theta):

@@ -3308,6 +3308,9 @@ int mi_set_tuning(mi_ctx *c, const char *key, int value)
               const int rc = mg_setup(m);
               if (rc)
                 return fail(c, rc, "%s", m->err.c_str());
+              // the new levels have no operators yet: the next solve builds them whatever "mg_lag" and the refresh interval say
+              m->mg_stale = m->mg_force = true;
+              m->mg_its_ref             = 0;
             }
         }
       else if (k == "cg_speculate_margin" && value >= 0 && value <= 16)

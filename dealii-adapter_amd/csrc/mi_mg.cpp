@@ -88,8 +88,13 @@ namespace mi_detail
     double coarse_ratio  = 60.0;
     int    power_its     = 15;   // first estimate
     int    krylov_its    = 40;   // ... and the steps of its Krylov companion (krylov_lmax)
-    int    power_its_update = 2; // refresh, continuing from the previous eigenvector (4 change nothing, 2.5 ms per step)
+    int    power_its_update = 2; // refresh, continuing from the previous eigenvector (4 change nothing, 2.5 ms per step).
+                                 // At least 2: the first iteration of a refresh only renormalises the kept vector to the
+                                 // D of the new tangent (estimate_lmax), its value is no estimate
     double lmax_safety   = 1.15;
+    bool   built         = false; // mg_update has completed on this hierarchy: every level has its operator and estimate
+                                  // (of the state of that update -- "mg_lag" keeps them over later tangents).  The read-only
+                                  // view (mi_mg_level_describe) answers only then
   };
 
   static inline bool is_dist(const Team &T, size_t l)
@@ -487,7 +492,12 @@ namespace mi_detail
       double lam = 0.0;
       int    rc;
       auto   ev_of = [l](mi_ctx *m) { return m->mg->levels[l].ev(); };
-      // The estimate |D^-1 A v| of a normalised v grows monotonically towards lambda_max.  A FIRST estimate runs until
+      // The estimate |D^-1 A v|_D of a v with |v|_D = 1 grows monotonically towards lambda_max and never passes it: D^-1 A is
+      // self-adjoint in the inner product of D, not in the Euclidean one, where |D^-1 A v|_2 is bounded by the 2-norm of
+      // D^-1 A only -- up to 6 % above lambda_max where the blocks of D differ from node to node, and an estimate that had
+      // passed lambda_max by 7e-5 was found against numpy's eigenvalue (tests/test_gpu_multigrid_reference.py).  With
+      // w = D^-1 q, q = A v: |w|_D^2 = w . D w = w . q, one dot product over the owned dofs (constrained dofs hold zeros in v,
+      // q and w).  A FIRST estimate runs until
       // three consecutive iterations each add less than 0.1 % (at least power_its, at most 300): a fixed count of 15 was
       // enough up to 28 M dofs but stopped 20 % short at 42 M (the top of the spectrum is a cluster that the iteration
       // enters late), and a Chebyshev smoother built on an interval that ends below lambda_max amplifies the modes
@@ -521,15 +531,15 @@ namespace mi_detail
                 mi::launch_blk_apply(c->dim, L.d(), L.q(), c->d_dinv_blk, c->mesh.nnodes, c->stream);
               else
                 mi::launch_vec_scale_mul(L.d(), L.q(), c->work(W_DINV), 1.0, c->n, c->stream); // w = D^-1 A v
-              // |w|^2 over the owned dofs of the level -> scalar slot 14 of the slab
-              mi::launch_masked_norm(c->dim, L.d() + c->own0, c->d_cmask + c->slab.own_begin, c->own_n, m->part(5),
-                                     m->grid_vec, m->d_sc + 14, c->stream);
+              // |w|_D^2 = w . q over the owned dofs of the level -> scalar slot 14 of the slab
+              mi::launch_dot_partials(L.d() + c->own0, L.q() + c->own0, c->own_n, m->part(5), m->grid_vec, c->stream);
+              mi::launch_finish_sum(m->part(5), m->grid_vec, m->d_sc + 14, c->stream);
             }
           if (dist && (rc = team_allreduce(T, 14, 1)))
             return rc;
           HIPCHK(c0, hipMemcpyAsync(c0->h_pinned, c0->d_sc + 14, sizeof(double), hipMemcpyDeviceToHost, c0->stream));
           HIPCHK(c0, hipStreamSynchronize(c0->stream));
-          const double nw = std::sqrt(c0->h_pinned[0]); // |D^-1 A v|, equal to lambda once |v| = 1
+          const double nw = std::sqrt(c0->h_pinned[0]); // |D^-1 A v|_D, equal to lambda once |v|_D = 1
           if (nw == 0.0)
             {
               // no unconstrained dof on this level (e.g. a one-cell coarse mesh between two clamped sides): the
@@ -542,7 +552,7 @@ namespace mi_detail
           lam = nw;
           if (mi::exp_env("MI_MG_VERBOSE"))
             fprintf(stderr, "mg level %d power iteration %d: |D^-1 A v| = %.6f\n", int(l), it, nw);
-          if (first && it >= 1) // iteration 0 only normalises the start vector
+          if (first && it >= 1) // iteration 0 only normalises the start vector (a refresh: to the D of the new tangent)
             {
               calm = (nw <= prev * 1.001) ? calm + 1 : 0;
               if (calm >= 3 && it >= mg0.power_its)
@@ -675,7 +685,7 @@ namespace mi_detail
     if (const char *e = mi::exp_env("MI_MG_SAFETY"))
       mg->lmax_safety = std::max(1.0, atof(e));
     if (const char *e = mi::exp_env("MI_MG_POWER_ITS"))
-      mg->power_its_update = std::max(1, atoi(e));
+      mg->power_its_update = std::max(2, atoi(e));
     if (const char *e = mi::exp_env("MI_MG_FACTOR"))
       mg->coarsen_factor = std::max(2, atoi(e));
     if (const char *e = mi::exp_env("MI_MG_COARSE_DEGREE"))
@@ -769,7 +779,10 @@ namespace mi_detail
         T->owns_stream  = false;
         T->md           = md;
         T->amap         = c->team->amap; // the levels' lattices lie over the box like the fine one (geometry only: their
-                                         // node ids never leave the library, so no permutation tables)
+                                         // node ids never leave the library, so no permutation tables -- but for
+                                         // mi_mg_level_context, which hands a level out on UNDECOMPOSED contexts only: their
+                                         // axis map is the identity.  On a team the lattice may lie rotated, and a level
+                                         // handed out there would speak internal node ids)
         T->iface_global = mi::global_interface_nodes(dim, p, md.reps, md.face_role);
         mi_ctx   *lc    = nullptr;
         const int rc    = create_member(*T, &md, &c->mat, &c->nm, dist_level ? c->slab.rank : 0, &lc);
@@ -785,6 +798,11 @@ namespace mi_detail
             return rc;
           }
         lc->precond = 0; // levels are never preconditioned themselves
+        if (!dist_level) // a whole level answers the read-only entry points like a context of its own (mi_mg_level_context)
+          {
+            T->nnodes_global = lc->mesh.nnodes;
+            T->n_global      = lc->n;
+          }
         MgLevel L;
         L.ctx  = lc;
         L.team = T;
@@ -899,7 +917,10 @@ namespace mi_detail
           return rc;
       }
     for (mi_ctx *m : T.members)
-      m->mg_stale = false;
+      {
+        m->mg_stale  = false;
+        m->mg->built = true;
+      }
     return MI_OK;
   }
 
@@ -1223,3 +1244,77 @@ namespace mi_detail
     return MI_OK;
   }
 } // namespace mi_detail
+
+// ---- read-only view of the hierarchy (tests; include/mi_elasticity.h)
+int mi_mg_n_levels(const mi_ctx *c)
+{
+  const mi_ctx *c0 = c->team->members[0];
+  return c0->mg ? int(c0->mg->levels.size()) : 0;
+}
+
+namespace
+{
+  // the level exists and its operators are those of a completed mg_update
+  int mg_view_check(mi_ctx *c, int level, const char *what)
+  {
+    using namespace mi_detail;
+    const mi_ctx *c0 = c->team->members[0];
+    if (!c0->mg)
+      return fail(c, MI_EINVAL, "%s: no multigrid hierarchy (\"precond\" 1 first)", what);
+    if (level < 0 || size_t(level) >= c0->mg->levels.size())
+      return fail(c, MI_EINVAL, "%s: level %d of %d", what, level, int(c0->mg->levels.size()));
+    for (const mi_ctx *m : c->team->members)
+      if (!m->mg || !m->mg->built)
+        return fail(c, MI_EINVAL, "%s: the hierarchy waits for its operators (a linear solve builds them)", what);
+    return MI_OK;
+  }
+} // namespace
+
+int mi_mg_level_describe(mi_ctx *c, int level, mi_mg_level_desc *out)
+{
+  using namespace mi_detail;
+  if (!out)
+    return fail(c, MI_EINVAL, "mi_mg_level_describe: null argument");
+  if (int e = mg_view_check(c, level, "mi_mg_level_describe"))
+    return e;
+  Team            &T  = *c->team;
+  const mi_ctx    *c0 = T.members[0];
+  const Multigrid &mg = *c0->mg;
+  const size_t     l = size_t(level), nl = mg.levels.size();
+  const MgLevel   &L  = mg.levels[l];
+  const bool       last = l + 1 == nl && nl > 1;
+  std::memset(out, 0, sizeof(*out));
+  const mi_mesh_desc &md = l == 0 ? T.md : L.team->md; // the undecomposed box as the lattice sees it
+  out->degree            = L.ctx->degree;
+  out->n_dofs            = int64_t(c0->dim);
+  for (int d = 0; d < 3; ++d)
+    out->reps[d] = 1;
+  for (int d = 0; d < c0->dim; ++d)
+    {
+      out->reps[T.amap.ext_axis[d]] = md.reps[d];
+      out->n_dofs *= int64_t(L.ctx->degree) * md.reps[d] + 1;
+    }
+  out->exact_solve = last && L.dense_inv ? 1 : 0;
+  out->distributed = is_dist(T, l) ? 1 : 0;
+  if (!out->exact_solve)
+    {
+      out->lmax            = L.lmax;
+      out->smoother_degree = last ? mg.coarse_degree : l == 0 ? mg.nu : (l == 1 && mg.nu_level1 > 0) ? mg.nu_level1 : mg.nu_coarse;
+      out->interval_ratio  = last ? mg.coarse_ratio : mg.smooth_ratio;
+    }
+  return MI_OK;
+}
+
+int mi_mg_level_context(mi_ctx *c, int level, mi_ctx **borrowed)
+{
+  using namespace mi_detail;
+  if (!borrowed)
+    return fail(c, MI_EINVAL, "mi_mg_level_context: null argument");
+  *borrowed = nullptr;
+  if (c->team->size != 1)
+    return fail(c, MI_EINVAL, "mi_mg_level_context: undecomposed contexts only");
+  if (int e = mg_view_check(c, level, "mi_mg_level_context"))
+    return e;
+  *borrowed = c->mg->levels[size_t(level)].ctx;
+  return MI_OK;
+}

@@ -244,6 +244,41 @@ int mi_spmv(mi_ctx *ctx, const double *x_host, double *y_host); /* y = K x throu
  * with "fine_level" 1, as formed from the point records.  One process only (single or emulated slabs). */
 int mi_get_diagonal_blocks(mi_ctx *ctx, double *blocks);
 
+/* ---- the multigrid hierarchy, read-only (tests) --------------------------------------------
+ * What the V-cycle of "spmv_as_smoother" 2 applies: the levels as the last linear solve left them.  Level 0 is the fine
+ * problem, the last level the coarsest.  Nothing here changes a level, a kernel or a tuning key. */
+typedef struct
+{
+  int32_t degree;          /* element degree of the level                                                        */
+  int32_t reps[3];         /* cells of the level's undecomposed box, in the directions of mi_mesh_desc           */
+  int64_t n_dofs;          /* dofs of the undecomposed level                                                     */
+  double  lmax;            /* the smoother's estimate of lambda_max(D^-1 A) incl. its safety factor; 0 on an
+                              exactly solved level                                                               */
+  double  interval_ratio;  /* the polynomial targets [lmax / interval_ratio, lmax]; 0 on an exactly solved level */
+  int32_t smoother_degree; /* Chebyshev steps before and after the coarse correction; on the coarsest level the
+                              degree of its polynomial, 0 where it is solved exactly                             */
+  int32_t exact_solve;     /* 1: the coarsest level, multiplied by its dense inverse                             */
+  int32_t distributed;     /* 1: the level is cut into the slabs of the team, 0: whole (replicated on a team)    */
+  int32_t reserved;
+} mi_mg_level_desc;
+/* levels of the hierarchy; 0 without one ("precond" 0, or no hierarchy built yet) */
+int mi_mg_n_levels(const mi_ctx *ctx);
+/* Works on teams; the values are those of slab 0.  MI_EINVAL without a hierarchy, for a level outside it, and while the
+ * hierarchy waits for its first operators (from its creation or a change of its shape -- "precond", "fine_level",
+ * "mg_coarsest", "mg_dense", "mg_dist_nodes" -- until a linear solve has built them): the description would be of operators
+ * that were never built.  Under "mg_lag" 1 the operators of an earlier tangent stay in use over later assemblies of a time
+ * step; the view then describes those, as the V-cycle applies them. */
+int mi_mg_level_describe(mi_ctx *ctx, int level, mi_mg_level_desc *out);
+/* The level's own context, for the read-only entry points: mi_n_dofs, mi_n_nodes, mi_nnz, mi_get_constrained, mi_vec_get
+ * (MI_V_TOTAL_DISPLACEMENT: on levels >= 1 the state the level was assembled at, u + du interpolated down; level 0 is `ctx`
+ * and holds u alone there, its tangent belongs to u + du), mi_matrix_get_csr, mi_get_diagonal_blocks.  Level 0 is
+ * `ctx` itself.  Undecomposed contexts only (MI_EINVAL on a team), and MI_EINVAL under the conditions of
+ * mi_mg_level_describe.
+ * LIFETIME: *borrowed belongs to the hierarchy.  It must not be destroyed, stepped, assembled, solved on or given to
+ * mi_set_tuning / mi_vec_set, and it dies with the next rebuild of the hierarchy ("precond", "fine_level", "mg_coarsest",
+ * "mg_dense", "mg_dist_nodes") and with mi_ctx_destroy(ctx). */
+int mi_mg_level_context(mi_ctx *ctx, int level, mi_ctx **borrowed);
+
 /* per-kernel-class device timings from HIP events on the context's stream */
 enum
 {

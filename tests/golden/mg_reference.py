@@ -1,0 +1,412 @@
+"""Independent numpy reference of the geometric multigrid V-cycle (dealii-adapter_amd/csrc/mi_mg.cpp), written from the
+description at the top of that file and not from its kernels.
+
+  hierarchy()        the shape of the hierarchy from (dim, degree, reps, mg_coarsest, mg_dense)
+  interp_1d()        linear interpolation in lattice index space, s = t (n_s - 1) / (n_t - 1), in exact integer arithmetic
+  Transfer           prolongation (fine constrained dofs zeroed), restriction (its transpose, coarse constrained dofs zeroed)
+                     and the state transfer (fine -> coarse with the coarse mask), as Kronecker products applied axis by axis
+  operator_matrix()  a mirror.Operator as a scipy CSR matrix, from the operator's own point data cell by cell (the operator
+                     applied to every unit vector, which operator_matrix_by_unit_vectors() does literally on small meshes)
+  Reference          the levels (all from mirror.py: Mi.Operator on the fine Mi.Mesh at u + du, Q1 Mi.Mesh boxes at the
+                     interpolated state below), D = the dim x dim node diagonal blocks, and the V-cycle over a generic dtype
+
+The smoother is the textbook Chebyshev iteration of the first kind for D^-1 A on [lmax / ratio, lmax] in its d-form
+(Saad, Iterative Methods for Sparse Linear Systems, algorithm 12.1): one form only.  The cycle: nu steps from zero, residual,
+restrict, recurse, prolongate and add, nu steps; nu = 3 on level 0 and 2 below; the last level is solved exactly (dense) or
+by 12 steps over [lmax / 60, lmax].  lmax per level is an argument: the one scalar the reference takes from outside.
+
+Precision: every product of the cycle runs in the dtype of the call (float64 or np.longdouble).  Level matrices are cast up
+and multiplied with np.add.at; block inverses, the Cholesky factor of the coarsest level and the transfers are written in
+plain array arithmetic, because LAPACK and scipy's sparse kernels exist in double only.
+"""
+import numpy as np
+import scipy.sparse as sp
+
+import mirror as Mi
+
+NU_FINE, NU_COARSE, RATIO = 3, 2, 20.0
+COARSE_DEGREE, COARSE_RATIO = 12, 60.0
+DENSE_MAX_DOFS = 384
+# the reference's own rounding: worst relmax between the float64 and the long double cycle over CASES (random right-hand side),
+# measured and asserted by tests/test_mirror_multigrid.py (8.98e-16).  The tolerance of the GPU tests rests on it.
+E_REF = 1.0e-15
+
+
+# ------------------------------------------------------------------ shape
+def hierarchy(dim, degree, reps, coarsest=4, dense=1):
+    """levels, finest first: dicts of degree, reps, n_dofs, exact (0/1), nu (smoother steps; polynomial degree on a coarsest
+    level that is not solved exactly, 0 on one that is) and ratio (0 where exact)"""
+    reps = [int(r) for r in reps[:dim]]
+    shapes = [(degree, tuple(reps))]
+    if degree > 1:
+        shapes.append((1, tuple(reps)))  # p -> 1 on the same cells
+    floor = min(2, coarsest)
+    while max(reps) > coarsest:
+        reps = [max(floor, -(-r // 2)) if r > floor else r for r in reps]
+        shapes.append((1, tuple(reps)))
+    out = []
+    for l, (p, rp) in enumerate(shapes):
+        n = dim * int(np.prod([p * r + 1 for r in rp]))
+        last = l + 1 == len(shapes) and len(shapes) > 1
+        exact = int(last and dense == 1 and n <= DENSE_MAX_DOFS)
+        if exact:
+            nu, ratio = 0, 0.0
+        elif last:
+            nu, ratio = COARSE_DEGREE, COARSE_RATIO
+        else:
+            nu, ratio = (NU_FINE if l == 0 else NU_COARSE), RATIO
+        out.append(dict(degree=p, reps=rp, n_dofs=n, exact=exact, nu=nu, ratio=ratio))
+    return out
+
+
+# ------------------------------------------------------------------ transfers
+def interp_1d(nt, ns, dtype=np.float64):
+    """[nt, ns]: values on a lattice of nt points from one of ns points over the same interval, linear in the index"""
+    P = np.zeros((nt, ns), dtype)
+    if ns == 1:
+        P[:, 0] = 1
+        return P
+    for t in range(nt):
+        num, den = (t * (ns - 1), nt - 1) if nt > 1 else (0, 1)
+        i = min(num // den, ns - 2)
+        w = dtype(num - i * den) / dtype(den)
+        P[t, i] += 1 - w
+        P[t, i + 1] += w
+    return P
+
+
+def _apply_axes(mats, v, nn_src, dim):
+    """(mats[dim-1] (x) ... (x) mats[0] (x) I_dim) v for a nodal vector v on the lattice nn_src (x fastest, dim components)"""
+    a = v.reshape(tuple(nn_src[::-1]) + (dim,))
+    for d in range(dim):
+        ax = dim - 1 - d
+        a = np.moveaxis(np.tensordot(mats[d], a, axes=([1], [ax])), 0, ax)
+    return a.reshape(-1)
+
+
+class Transfer:
+    def __init__(self, dim, nn_fine, nn_coarse, fine_constrained, coarse_constrained, dtype=np.float64):
+        self.dim, self.nf, self.nc = dim, list(nn_fine), list(nn_coarse)
+        self.P = [interp_1d(self.nf[d], self.nc[d], dtype) for d in range(dim)]
+        self.PT = [p.T.copy() for p in self.P]
+        self.S = [interp_1d(self.nc[d], self.nf[d], dtype) for d in range(dim)]
+        self.free_f, self.free_c = ~np.asarray(fine_constrained, bool), ~np.asarray(coarse_constrained, bool)
+
+    def prolong(self, xc):
+        return _apply_axes(self.P, xc, self.nc, self.dim) * self.free_f
+
+    def restrict(self, rf):
+        return _apply_axes(self.PT, rf * self.free_f, self.nf, self.dim) * self.free_c
+
+    def state(self, uf):
+        return _apply_axes(self.S, uf, self.nf, self.dim) * self.free_c
+
+
+# ------------------------------------------------------------------ level operators
+def operator_matrix(op):
+    """The matrix of a mirror.Operator (scipy CSR, float64): its element tangents K_e from the operator's own point data
+    (.g, .Jc, .tau, .N, .JxW, .mass), summed over the cells, rows and columns of constrained dofs replaced by .cdiag.
+    K_e(ac, bd) = sum_q JxW [g_a . S(c, ., d, .) . g_b + delta_cd (g_a tau g_b + mass N_a N_b)] with S the minor-symmetrised
+    Jc, which is Operator.__call__ on the unit vectors of a cell; the tests hold A x to op(x)."""
+    m = op.m
+    dim = m.dim
+    Jc = op.Jc
+    S = 0.25 * (Jc + np.swapaxes(Jc, -1, -2) + np.swapaxes(Jc, -3, -4) + np.swapaxes(np.swapaxes(Jc, -1, -2), -3, -4))
+    h = np.einsum("eqaj,eqcjdl->eqacdl", op.g, S)
+    Ke = np.einsum("eqacdl,eqbl,eq->eacbd", h, op.g, op.JxW, optimize=True)
+    sc = np.einsum("eqaj,eqjk,eqbk,eq->eab", op.g, op.tau, op.g, op.JxW, optimize=True)
+    sc += op.mass * np.einsum("qa,qb,eq->eab", op.N, op.N, op.JxW, optimize=True)
+    for c in range(dim):
+        Ke[:, :, c, :, c] += sc
+    E, A = op.conn.shape
+    dofs = (op.conn[:, :, None] * dim + np.arange(dim)).reshape(E, -1)
+    rows = np.repeat(dofs, A * dim, axis=1).reshape(-1)
+    cols = np.tile(dofs, (1, A * dim)).reshape(-1)
+    vals = Ke.reshape(-1).copy()
+    con = m.constrained
+    vals[con[rows] | con[cols]] = 0.0
+    cd = np.nonzero(con)[0]
+    M = sp.coo_matrix((np.concatenate([vals, op.cdiag[cd]]), (np.concatenate([rows, cd]), np.concatenate([cols, cd]))),
+                      shape=(m.n, m.n)).tocsr()
+    M.eliminate_zeros()
+    M.sort_indices()
+    return M
+
+
+def operator_matrix_by_unit_vectors(op):
+    """the same matrix, column by column (small meshes: the check of operator_matrix)"""
+    n = op.m.n
+    return sp.csr_matrix(np.stack([op(np.eye(n)[:, j]) for j in range(n)], -1))
+
+
+def node_blocks(A, dim):
+    """[n_nodes, dim, dim] diagonal blocks of a scipy matrix"""
+    base = np.arange(A.shape[0] // dim) * dim
+    return np.stack([np.stack([np.asarray(A[base + i, base + j]).ravel() for j in range(dim)], -1) for i in range(dim)], -2)
+
+
+def invert_blocks(B):
+    """inverses of [N, d, d] blocks (d = 2, 3) by the adjugate, in the dtype of B"""
+    d = B.shape[-1]
+    out = np.empty_like(B)
+    if d == 2:
+        det = B[:, 0, 0] * B[:, 1, 1] - B[:, 0, 1] * B[:, 1, 0]
+        out[:, 0, 0], out[:, 1, 1] = B[:, 1, 1] / det, B[:, 0, 0] / det
+        out[:, 0, 1], out[:, 1, 0] = -B[:, 0, 1] / det, -B[:, 1, 0] / det
+        return out
+    assert d == 3
+    cof = np.empty_like(B)
+    for i in range(3):
+        for j in range(3):
+            r, c = [k for k in range(3) if k != i], [k for k in range(3) if k != j]
+            cof[:, i, j] = (-1) ** (i + j) * (B[:, r[0], c[0]] * B[:, r[1], c[1]] - B[:, r[0], c[1]] * B[:, r[1], c[0]])
+    det = (B[:, 0, :] * cof[:, 0, :]).sum(-1)
+    return np.swapaxes(cof, 1, 2) / det[:, None, None]
+
+
+def spd_inverse(A):
+    """inverse of a dense symmetric positive definite matrix through its Cholesky factor, in the dtype of A"""
+    n = A.shape[0]
+    L = np.tril(A).copy()
+    for k in range(n):
+        L[k, k] = np.sqrt(L[k, k])
+        L[k + 1:, k] /= L[k, k]
+        L[k + 1:, k + 1:] -= np.tril(np.outer(L[k + 1:, k], L[k + 1:, k]))
+    Y = np.eye(n, dtype=A.dtype)
+    for k in range(n):  # L Y = I
+        Y[k] /= L[k, k]
+        Y[k + 1:] -= np.outer(L[k + 1:, k], Y[k])
+    for k in reversed(range(n)):  # L^T X = Y
+        Y[k] /= L[k, k]
+        Y[:k] -= np.outer(L[k, :k], Y[k])
+    return Y
+
+
+class _Level:
+    """one level in one dtype: the matrix as COO arrays, D^-1 as node blocks"""
+
+    def __init__(self, A, Dinv, dim, dtype):
+        coo = A.tocoo()
+        self.n, self.dim = A.shape[0], dim
+        self.rows, self.cols, self.vals = coo.row, coo.col, coo.data.astype(dtype)
+        self.Dinv = Dinv.astype(dtype)
+        self.dtype = dtype
+        self.inverse = None
+
+    def mult(self, x):
+        y = np.zeros(self.n, self.dtype)
+        np.add.at(y, self.rows, self.vals * x[self.cols])
+        return y
+
+    def dinv(self, r):
+        return (self.Dinv * r.reshape(-1, 1, self.dim)).sum(-1).reshape(-1)
+
+    def dense(self):
+        M = np.zeros((self.n, self.n), self.dtype)
+        np.add.at(M, (self.rows, self.cols), self.vals)
+        return M
+
+
+def chebyshev(L, b, x, steps, lmax, ratio):
+    """`steps` steps of the Chebyshev iteration for D^-1 A on [lmax / ratio, lmax] from x (None: zero), d-form"""
+    dt = L.dtype
+    beta = dt(lmax)
+    alpha = beta / dt(ratio)
+    theta, delta = (beta + alpha) / 2, (beta - alpha) / 2
+    sigma = theta / delta
+    rho = 1 / sigma
+    if x is None:
+        x, r = np.zeros(L.n, dt), b.copy()
+    else:
+        r = b - L.mult(x)
+    d = L.dinv(r) / theta
+    for k in range(steps):
+        x = x + d
+        if k + 1 == steps:
+            break
+        r = r - L.mult(d)
+        rho_new = 1 / (2 * sigma - rho)
+        d = rho_new * rho * d + (2 * rho_new / delta) * L.dinv(r)
+        rho = rho_new
+    return x
+
+
+class Reference:
+    """The hierarchy of one problem.  mesh: the fine Mi.Mesh; u_total: u + du; nq0 / fold0: the rule of the fine level's
+    smoother product (None: the assembly's p + 2); the smoother's D always comes from the assembly rule, as in the library.
+    coarse_from: None, or the fine u + du that the levels >= 1 are interpolated from instead of u_total (coarse operators
+    that lag behind the fine tangent)."""
+
+    def __init__(self, mesh, u_total, coarsest=4, dense=1, nq0=None, fold0=False, coarse_from=None, fine=None, **material):
+        m = mesh
+        dim = self.dim = m.dim
+        self.shape = hierarchy(dim, m.p, m.reps, coarsest, dense)
+        self.meshes, self.states, self.A, self.D = [m], [np.asarray(u_total, float)], [], []
+        if fine is not None:  # another Reference of the same mesh, state and rule: its fine level is this one's
+            A0, A_asm, D0 = fine.A[0], fine.A_assembled, fine.D[0]
+        else:
+            op_asm = Mi.Operator(m, u_total, **material)
+            A_asm = operator_matrix(op_asm)
+            if nq0 is None or (nq0 == m.p + 2 and not fold0):
+                A0 = A_asm
+            else:
+                A0 = operator_matrix(Mi.Operator(m, u_total, nq=nq0, fold_to_identity=fold0, cdiag=op_asm.cdiag, **material))
+            D0 = node_blocks(A_asm, dim)
+        self.A.append(A0)
+        self.D.append(D0)
+        self.A_assembled = A_asm
+        self.T = []
+        src = np.asarray(u_total if coarse_from is None else coarse_from, float)
+        for lv in self.shape[1:]:
+            mc = Mi.Mesh(dim, 1, lv["reps"], m.lo, m.hi, m.roles)
+            mf = self.meshes[-1]
+            t = Transfer(dim, mf.nn, mc.nn, mf.constrained, mc.constrained)
+            uc = t.state(src)
+            src = uc
+            Ac = operator_matrix(Mi.Operator(mc, uc, **material))
+            self.meshes.append(mc)
+            self.states.append(uc)
+            self.T.append(t)
+            self.A.append(Ac)
+            self.D.append(node_blocks(Ac, dim))
+        self._cache = {}
+
+    def lambda_true(self, l):
+        """largest eigenvalue of D^-1 A on level l"""
+        import scipy.sparse.linalg as spla
+        A, D, dim = self.A[l], self.D[l], self.dim
+        w, V = np.linalg.eigh(D)  # D^-1/2 by blocks
+        Dmh = np.einsum("nij,nj,nkj->nik", V, 1 / np.sqrt(w), V)
+        S = sp.bsr_matrix((Dmh, np.arange(len(Dmh)), np.arange(len(Dmh) + 1)), shape=A.shape).tocsr()
+        B = (S @ A @ S)
+        B = 0.5 * (B + B.T)
+        if A.shape[0] <= 1500:
+            return float(np.linalg.eigvalsh(B.toarray())[-1])
+        return float(spla.eigsh(B, k=1, which="LA", tol=1e-12, return_eigenvectors=False)[0])
+
+    def levels(self, dtype):
+        if dtype not in self._cache:
+            Ls = [_Level(A, invert_blocks(D.astype(dtype)), self.dim, dtype) for A, D in zip(self.A, self.D)]
+            if self.shape[-1]["exact"]:
+                Ls[-1].inverse = spd_inverse(Ls[-1].dense())
+            Ts = []
+            for t in self.T:
+                Ts.append(Transfer(self.dim, t.nf, t.nc, ~t.free_f, ~t.free_c, dtype))
+            self._cache[dtype] = (Ls, Ts)
+        return self._cache[dtype]
+
+    def vcycle(self, r, lmax, dtype=np.float64, nu=None, l=0):
+        """B r: one V-cycle on the right-hand side r; lmax[l] per smoothed level (ignored on an exact one);
+        nu: override of the smoother steps of every level but an inexact coarsest one (tests of the reference itself)"""
+        Ls, Ts = self.levels(dtype)
+        L, sh = Ls[l], self.shape[l]
+        b = np.asarray(r).astype(dtype)
+        if l + 1 == len(Ls) and len(Ls) > 1:
+            if sh["exact"]:
+                return L.inverse @ b
+            return chebyshev(L, b, None, sh["nu"], lmax[l], sh["ratio"])
+        k = sh["nu"] if nu is None else nu
+        x = chebyshev(L, b, None, k, lmax[l], sh["ratio"])
+        res = b - L.mult(x)
+        xc = self.vcycle(Ts[l].restrict(res), lmax, dtype, nu, l + 1)
+        x = x + Ts[l].prolong(xc)
+        return chebyshev(L, b, x, k, lmax[l], sh["ratio"])
+
+    def true_lmax(self, safety=1.15):
+        return [0.0 if sh["exact"] else safety * self.lambda_true(l) for l, sh in enumerate(self.shape)]
+
+
+# ------------------------------------------------------------------ the cases of tests/test_gpu_multigrid_reference.py
+# (here, so that tests/test_mirror_multigrid.py measures the reference's own rounding on the same inputs without a GPU)
+CL, IF, ZC = Mi.CLAMPED, Mi.INTERFACE, Mi.ZCLAMP
+ROLES_A = [CL, IF, IF, IF, ZC, IF]
+ROLES_B = [CL, IF, IF, IF, ZC, ZC]
+ROLES_2D = [CL, IF, IF, IF, 0, 0]
+A1 = 1.0 / (0.25 * 0.005**2)  # alpha_1 of the default Newmark parameters
+
+# keys: tuning keys set before "precond" 1.  nq0 / fold0: the rule of the fine level's smoother product (None: the assembled
+# matrix), which the GPU test also reads back from the library.  coarsest / dense: what the keys make of the defaults 4 / 1.
+CASES = {
+    "q2_654": dict(dim=3, p=2, reps=(6, 5, 4), kind="cube", roles=ROLES_A),
+    "q2_753_mf27": dict(dim=3, p=2, reps=(7, 5, 3), kind="distorted", roles=ROLES_B, keys=[("element_tangents", 2)], nq0=3,
+                        fold0=True),
+    "q2_543_mf_fine": dict(dim=3, p=2, reps=(5, 4, 3), kind="graded", roles=ROLES_A, keys=[("fine_level", 1)], nq0=3,
+                           fold0=True),
+    "q3_532_rule5": dict(dim=3, p=3, reps=(5, 3, 2), kind="cube", roles=ROLES_A,
+                         keys=[("fine_level", 1), ("smoother_quadrature_q3", 5)], nq0=5),
+    "q3_532_rule4": dict(dim=3, p=3, reps=(5, 3, 2), kind="cube", roles=ROLES_A,
+                         keys=[("fine_level", 1), ("smoother_quadrature_q3", 4)], nq0=4, fold0=True),
+    "q1_987": dict(dim=3, p=1, reps=(9, 8, 7), kind="cube", roles=ROLES_B),
+    "q2_444_coarsest2": dict(dim=3, p=2, reps=(4, 4, 4), kind="cube", roles=ROLES_A, keys=[("mg_coarsest", 2)], coarsest=2),
+    "q2_888": dict(dim=3, p=2, reps=(8, 8, 8), kind="cube", roles=ROLES_A),
+    "q2_444_polynomial": dict(dim=3, p=2, reps=(4, 4, 4), kind="cube", roles=ROLES_B,
+                              keys=[("mg_dense", 0), ("mg_coarsest", 1)], coarsest=1, dense=0),
+    "q2_1231": dict(dim=3, p=2, reps=(12, 3, 1), kind="cube", roles=ROLES_A),
+    "2d_q2_186": dict(dim=2, p=2, reps=(18, 6), kind="cube", roles=ROLES_2D),
+    "2d_q4_64": dict(dim=2, p=4, reps=(6, 4), kind="cube", roles=ROLES_2D),
+    "q2_4412_3slabs_z": dict(dim=3, p=2, reps=(4, 4, 12), kind="cube", roles=ROLES_A, slabs=3, cut_axis=3),
+    "q2_1244_2slabs_x": dict(dim=3, p=2, reps=(12, 4, 4), kind="cube", roles=ROLES_B, slabs=2, cut_axis=1),
+    "q2_4416_induced": dict(dim=3, p=2, reps=(4, 4, 16), kind="cube", roles=ROLES_A, slabs=2, cut_axis=3,
+                            keys=[("mg_dist_nodes", 0)]),
+}
+
+
+def geometry(kind, dim, reps, seed):
+    """lo, hi, perturb of a cube / graded / distorted mesh of reps cells"""
+    reps = np.array(reps[:dim])
+    lo = (0.0,) * dim
+    if kind == "cube":
+        return lo, tuple(0.1 * reps), None
+    h = np.array([0.13, 0.1, 0.07])[:dim]
+    hi = tuple(h * reps)
+    rng = np.random.default_rng(seed)
+    nv = reps + 1
+    vid = np.stack(np.unravel_index(np.arange(int(np.prod(nv))), tuple(nv[::-1])), -1)[:, ::-1]  # vertices, x fastest
+    if kind == "graded":  # rectilinear: every vertex plane moved along its own axis
+        planes = [0.3 * h[d] * rng.uniform(-1, 1, nv[d]) for d in range(dim)]
+        return lo, hi, np.stack([planes[d][vid[:, d]] for d in range(dim)], -1)
+    assert kind == "distorted"
+    return lo, hi, 0.08 * h.min() * rng.standard_normal((len(vid), dim))
+
+
+def case_mesh(name):
+    c = CASES[name]
+    lo, hi, perturb = geometry(c["kind"], c["dim"], c["reps"], seed=sum(c["reps"]))
+    return Mi.Mesh(c["dim"], c["p"], c["reps"], lo, hi, c["roles"], perturb=perturb), lo, hi, perturb
+
+
+def shear(X):
+    """a smooth deformation with shear (F != F^T, J != 1) that vanishes on x = min x and, in 3D, has u_z = 0 on both z faces"""
+    dim = X.shape[1]
+    L = np.ptp(X, axis=0).max()
+    s = (X - X.min(axis=0)) / L
+    u = np.zeros_like(X)
+    z = s[:, 2] if dim == 3 else 0.5 * s[:, 1]
+    u[:, 0] = s[:, 0] * (0.3 * s[:, 1] + 0.2 * z)
+    u[:, 1] = s[:, 0] * (0.25 + 0.3 * z**2)
+    if dim == 3:
+        tz = np.ptp(z)
+        u[:, 2] = s[:, 0] * z * (tz - z) * (0.6 * np.sin(3.0 * s[:, 1]) - 0.5)
+    return L * u.reshape(-1)
+
+
+def case_state(m, seed, amplitude=0.25):
+    """u, du: V_U and V_DELTA both non-zero on the free dofs -- a smooth shear plus small noise -- and V_U small and non-zero
+    on the constrained ones.  (At twice this amplitude the
+    tangent of the 8 x 8 x 8 cube is indefinite, smallest eigenvalue -865 against 1.5e6: no case for a CG.)"""
+    rng = np.random.default_rng(seed)
+    free = ~m.constrained
+    h = ((m.hi - m.lo) / np.array(m.reps)).min() / m.p
+    s = amplitude * shear(m.coords) * free
+    noise = 2e-3 * h * rng.standard_normal(m.n) * free
+    # V_U also carries values on the constrained dofs: the fine tangent reads them as they are, the state transfer masks them
+    # on every coarser level, and only with them does a transfer that forgets the mask compute something else
+    held = 2e-3 * h * rng.standard_normal(m.n) * ~free
+    return 0.6 * s + noise + held, 0.4 * s - 0.5 * noise
+
+
+def case_reference(name, u_total, m, **kw):
+    c = CASES[name]
+    args = dict(coarsest=c.get("coarsest", 4), dense=c.get("dense", 1), nq0=c.get("nq0"), fold0=c.get("fold0", False), alpha1=A1)
+    args.update(kw)
+    return Reference(m, u_total, **args)
