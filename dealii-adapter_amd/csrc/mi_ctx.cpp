@@ -459,6 +459,28 @@ namespace mi_detail
     return f;
   }
 
+  // the gather that follows a one-launch product into the cells' slots (f: the product's arguments, with x and y): the
+  // smoother's three-term step on the owned nodes straight from the slots, the residual y = b - K x on them, y = K x with
+  // the partials of dotv . y, or y = K x alone.  lattice: as gather_lattice_mode says (lattice meshes: the slots' positions
+  // by arithmetic, the gathers over the owned nodes in node tiles -- "mf_gather_lattice"); false: through the slot tables
+  static void enqueue_slot_gather(const mi_ctx *c, const mi::MfParams &f, const ChebFusion *cheb, const double *dotv, double *partials,
+                                  const bool lattice)
+  {
+    const int              gmode = lattice ? gather_lattice_mode(c) : 0;
+    const mi::SlotLattice *sl    = gmode ? &c->slot_lat : nullptr;
+    const bool             tiles = gmode >= 2;
+    const int64_t          ndofs = int64_t(c->mesh.nnodes) * 3;
+    if (cheb && cheb->xnext)
+      mi::launch_mf_gather_cheb3(f, cheb->b, cheb->dinv6, cheb->xprev, f.x, cheb->xnext, cheb->c1, cheb->c2, c->own0 / 3, c->own_n / 3,
+                                 c->stream, sl, tiles);
+    else if (cheb)
+      mi::launch_mf_gather_residual(f, cheb->b, f.y, c->own0 / 3, c->own_n / 3, c->stream, sl, tiles);
+    else if (dotv)
+      mi::launch_mf_gather_dot(f, ndofs, dotv, partials, c->grid_gdot, c->own0, c->own_n, c->stream, sl);
+    else
+      mi::launch_mf_gather(f, ndofs, c->stream, sl);
+  }
+
   // y = K x on the owned rows (+ optional fused dot partials); x and y are whole local vectors.
   // part: 0 all rows, 1 interior rows only (no ghost columns: may run while the halo is in flight), 2 boundary rows
   void enqueue_spmv(mi_ctx *c, const double *x, double *y, const double *dotv, double *partials, const int32_t *done,
@@ -480,10 +502,7 @@ namespace mi_detail
         f.yc = c->d_mf_yc, f.dst = c->d_mf_dst, f.slot_base = c->d_mf_slot_base, f.slot_src = c->d_mf_src;
         f.slot_inline = c->slots_layout == 1;
         mi::launch_mf_linear_q3(f, lm.op, int32_t(c->mesh.ncells), c->stream);
-        if (dotv)
-          mi::launch_mf_gather_dot(f, int64_t(c->mesh.nnodes) * 3, dotv, partials, c->grid_gdot, c->own0, c->own_n, c->stream);
-        else
-          mi::launch_mf_gather(f, int64_t(c->mesh.nnodes) * 3, c->stream);
+        enqueue_slot_gather(c, f, nullptr, dotv, partials, false);
         return;
       }
     const int  kind       = element_form(c);
@@ -601,20 +620,7 @@ namespace mi_detail
                 mi::launch_mf_spmv(f, 0, int32_t(c->mesh.ncells), c->stream, t >= 0 ? c0->stamps[size_t(t)].a : nullptr,
                                    t >= 0 ? c0->stamps[size_t(t)].b : nullptr);
               }
-            // (lattice meshes: the slots' positions by arithmetic, the Chebyshev gathers in node tiles -- "mf_gather_lattice")
-            const int                gmode = gather_lattice_mode(c);
-            const mi::SlotLattice   *sl    = gmode ? &c->slot_lat : nullptr;
-            const bool               tw    = gmode >= 2;
-            if (cheb && cheb->xnext) // the smoother's step on the owned nodes, straight from the slots (three-term form)
-              mi::launch_mf_gather_cheb3(f, cheb->b, cheb->dinv6, cheb->xprev, x, cheb->xnext, cheb->c1, cheb->c2, c->own0 / 3,
-                                         c->own_n / 3, c->stream, sl, tw);
-            else if (cheb) // ... with the update vector d, in place / the residual
-              mi::launch_mf_gather_cheb(f, cheb->b, cheb->dinv, cheb->d, const_cast<double *>(x), y, cheb->c1, cheb->c2,
-                                        c->own0 / 3, c->own_n / 3, c->stream, sl, tw);
-            else if (ebe_for_cg) // the CG's q = K p: the slot sum and the partials of p.q in one launch
-              mi::launch_mf_gather_dot(f, int64_t(c->mesh.nnodes) * 3, dotv, partials, c->grid_gdot, c->own0, c->own_n, c->stream, sl);
-            else
-              mi::launch_mf_gather(f, int64_t(c->mesh.nnodes) * 3, c->stream, sl);
+            enqueue_slot_gather(c, f, cheb, dotv, partials, true); // (dotv: this is the CG's q = K p)
           }
         else
         for (int col = 0; col < c->mesh.ncolours; ++col)

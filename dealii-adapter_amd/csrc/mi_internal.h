@@ -43,10 +43,10 @@ namespace mi_detail
     double       *d, *xout;
     double        c1, c2;
     int           blk = 0; // dinv = DxD blocks per node
-    int           inplace = 0; // matrix-free single-launch product only: the gather applies the step itself, x += d in
-                               // place (the product is complete by then); d == null: y = b - K x
-    // ... in three-term form (mf_gather_cheb3): x'' = x' + c1 (x' - xprev) + c2 D^-1 (b - K x') written to xnext (may be
-    // xprev's buffer; xprev == null: zero), D^-1 from its symmetric half
+    int           inplace = 0; // matrix-free single-launch product only: the gather of the product's slots applies the
+                               // epilogue itself (dinv, d and xout are not read).  xnext == null: the residual y = b - K x
+    // xnext: the step in three-term form (mf_gather_cheb3): x'' = x' + c1 (x' - xprev) + c2 D^-1 (b - K x') written to xnext
+    // (may be xprev's buffer; xprev == null: zero), D^-1 from its symmetric half
     const double *dinv6 = nullptr, *xprev = nullptr;
     double       *xnext = nullptr;
   };

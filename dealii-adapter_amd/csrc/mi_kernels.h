@@ -363,7 +363,7 @@ namespace mi
   // writes those records from u + du
   void launch_mf_spmv27(const MfParams &p, int32_t cell_count, hipStream_t s, hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr);
   void launch_mf_records27(const MfParams &p, const double *u, const double *du, double *rec27, int32_t cell_count, hipStream_t s);
-  // (sl with ncol > 0, all four gathers: the lattice form -- slot positions by arithmetic, see SlotLattice)
+  // (sl with ncol > 0, all four gathers: the lattice source -- slot positions by arithmetic, see SlotLattice)
   void launch_mf_gather(const MfParams &p, int64_t ndofs, hipStream_t s, const SlotLattice *sl = nullptr);
   // ... with the partials of dotv . y over the owned dofs (fixed grid): the CG's product on the matrix-free fine level
   void launch_mf_gather_dot(const MfParams &p, int64_t ndofs, const double *dotv, double *partials, int grid, int64_t own0,
@@ -397,13 +397,13 @@ namespace mi
                               int64_t ndofs, hipStream_t s);
   void launch_mf_diag_gather(const double *slots6, const int32_t *slot_base, const int32_t *slot_src, const uint8_t *cmask,
                              const int32_t *diagpos, double *blk, double *dinv, double *dinv_blk, double *sym6, int64_t nnodes, hipStream_t s);
-  // gather fused with the smoother's Chebyshev step (d != null: x += d in place) or residual (d == null: yres = b - K x)
+  // gather fused with the smoother's three-term Chebyshev step (xnext = x'' on the owned nodes), or with the residual
+  // (yres = b - K x on the owned nodes); tiles: the lattice source in node tiles (the node range is whole planes)
   void launch_mf_gather_cheb3(const MfParams &p, const double *b, const double *dinv6, const double *xprev, const double *xcur,
                               double *xnext, double c1, double c2, int64_t node0, int64_t nnodes, hipStream_t s,
                               const SlotLattice *sl = nullptr, bool tiles = false);
-  void launch_mf_gather_cheb(const MfParams &p, const double *b, const double *dinv, double *d, double *xio, double *yres,
-                             double c1, double c2, int64_t node0, int64_t nnodes, hipStream_t s, const SlotLattice *sl = nullptr,
-                             bool tiles = false);
+  void launch_mf_gather_residual(const MfParams &p, const double *b, double *yres, int64_t node0, int64_t nnodes, hipStream_t s,
+                                 const SlotLattice *sl = nullptr, bool tiles = false);
   // coarsest multigrid level: dense inverse of the level's sliced-ELL matrix (n <= 96, -1 otherwise) and its application
   int  launch_dense_inverse_from_sell(int dim, const SellParams &p, int n, double *out, hipStream_t s);
   void launch_dense_apply(const double *inv, const double *b, double *x, int n, hipStream_t s);

@@ -2894,157 +2894,7 @@ namespace mi
     return s;
   }
 
-  // y = sum of the cells' contributions, node by node in slot order (= processing order of the cells: the order of the
-  // colour-by-colour update); constrained rows: diag(K) x from the assembled tangent.  One thread per DOF.
-  __global__ __launch_bounds__(256) void mf_gather(MfParams prm, int64_t ndofs)
-  {
-    const int64_t g = int64_t(blockIdx.x) * 256 + threadIdx.x;
-    if (g >= ndofs)
-      return;
-    const int64_t n = g / 3;
-    const int     c = int(g - n * 3);
-    if ((prm.cmask[n] >> c) & 1)
-      {
-        const int32_t dp = prm.diagpos[n]; // -1: ghost node of a slab (its y is never read)
-        prm.y[g]         = dp >= 0 ? prm.vals[int64_t(dp) * 9 + c * 4] * prm.x[g] : 0.0;
-        return;
-      }
-    const int32_t b0 = prm.slot_base[n], b1 = prm.slot_base[n + 1];
-    prm.y[g] = mf_slot_sum(prm, b0, b1, c);
-  }
-
-  // the same sum fused with its consumer in the multigrid smoother: q = (K x) from the slots, then the Chebyshev step
-  // with the 3x3 block-Jacobi diagonal, d = c1 d + c2 D^-1 (b - q), x += d (in place: the product is complete), or,
-  // with d == null, the residual y = b - q.  One thread per DOF of the nodes [node0, node0 + nnodes), 64 nodes per block.
-  __global__ __launch_bounds__(192) void mf_gather_cheb(MfParams prm, const double *__restrict__ b,
-                                                        const double *__restrict__ dinv, double *d, double *xio, double *yres,
-                                                        double c1, double c2, int64_t node0, int64_t nnodes)
-  {
-    __shared__ double s_res[192];
-    const int     ld = threadIdx.x;
-    const int64_t nl = int64_t(blockIdx.x) * 64 + ld / 3;
-    const bool    in = nl < nnodes;
-    const int64_t n  = node0 + nl;
-    const int     c  = ld % 3;
-    const int64_t g  = n * 3 + c;
-    double        res = 0.0;
-    if (in)
-      {
-        double q;
-        if ((prm.cmask[n] >> c) & 1)
-          q = prm.vals[int64_t(prm.diagpos[n]) * 9 + c * 4] * prm.x[g];
-        else
-          {
-            const int32_t b0 = prm.slot_base[n], b1 = prm.slot_base[n + 1];
-            q                = mf_slot_sum(prm, b0, b1, c);
-          }
-        res = b[g] - q;
-      }
-    if (!d)
-      {
-        if (in)
-          yres[g] = res;
-        return;
-      }
-    s_res[ld] = res;
-    __syncthreads();
-    if (!in)
-      return;
-    const int    r0 = (ld / 3) * 3;
-    const double a0 = dinv[g * 3], a1 = dinv[g * 3 + 1], a2 = dinv[g * 3 + 2];
-    double       s  = 0.0;
-    s += a0 * s_res[r0];
-    s += a1 * s_res[r0 + 1];
-    s += a2 * s_res[r0 + 2];
-    const double dn = (c1 != 0.0 ? c1 * d[g] : 0.0) + c2 * s;
-    d[g]            = dn;
-    xio[g]          = xio[g] + dn;
-  }
-
-  // the same step in three-term form with the symmetric half of D^-1 (round 3): x'' = x' + c1 (x' - x) + c2 D^-1 (b - q)
-  // reads x' (the product's operand), x (the iterate before; null: zero) and writes x'' over x -- two reads and a write
-  // of 40 MB vectors instead of d and x read and written, 48 instead of 72 bytes of D^-1 per node: 380 instead of 460 MB
-  // per step of the smoother at 5 M dofs.  The caller swaps the two x buffers.
-  __global__ __launch_bounds__(192) void mf_gather_cheb3(MfParams prm, const double *__restrict__ b,
-                                                         const double *__restrict__ dinv6, const double *xprev,
-                                                         const double *__restrict__ xcur, double *xnext, double c1, double c2,
-                                                         int64_t node0, int64_t nnodes)
-  {
-    __shared__ double s_res[192];
-    const int     ld = threadIdx.x;
-    const int64_t nl = int64_t(blockIdx.x) * 64 + ld / 3;
-    const bool    in = nl < nnodes;
-    const int64_t n  = node0 + nl;
-    const int     c  = ld % 3;
-    const int64_t g  = n * 3 + c;
-    double        res = 0.0, xc = 0.0, xp = 0.0, a0 = 0.0, a1 = 0.0, a2 = 0.0;
-    if (in)
-      {
-        // row c of the symmetric block (xx yy zz xy xz yz)
-        const double *q6 = dinv6 + n * 6;
-        a0               = q6[c == 0 ? 0 : (c == 1 ? 3 : 4)];
-        a1               = q6[c == 0 ? 3 : (c == 1 ? 1 : 5)];
-        a2               = q6[c == 0 ? 4 : (c == 1 ? 5 : 2)];
-        xc               = xcur[g];
-        xp               = (c1 != 0.0 && xprev) ? xprev[g] : 0.0;
-        double q;
-        if ((prm.cmask[n] >> c) & 1)
-          q = prm.vals[int64_t(prm.diagpos[n]) * 9 + c * 4] * xc;
-        else
-          {
-            const int32_t b0 = prm.slot_base[n], b1 = prm.slot_base[n + 1];
-            q                = mf_slot_sum(prm, b0, b1, c);
-          }
-        res = b[g] - q;
-      }
-    s_res[ld] = res;
-    __syncthreads();
-    if (!in)
-      return;
-    const int r0 = (ld / 3) * 3;
-    double    s  = 0.0;
-    s += a0 * s_res[r0];
-    s += a1 * s_res[r0 + 1];
-    s += a2 * s_res[r0 + 2];
-    const double dn = (c1 != 0.0 ? c1 * (xc - xp) : 0.0) + c2 * s;
-    xnext[g]        = xc + dn;
-  }
-
-  // y = sum of the slots as mf_gather, with the partials of dotv . y over the owned dofs [own0, own0 + own_n) in the same
-  // launch: the CG's q = K p and p.q on the matrix-free fine level (round 6).  Fixed grid (grid-stride over the dofs, as
-  // dot_partials): the partials -- one per workgroup -- and their sum do not depend on the launch.
-  __global__ __launch_bounds__(256) void mf_gather_dot(MfParams prm, int64_t ndofs, const double *__restrict__ dotv,
-                                                       double *partials, int64_t own0, int64_t own_n)
-  {
-    __shared__ double s_red[4];
-    double            acc = 0.0;
-    const int64_t     per = ((ndofs + gridDim.x - 1) / gridDim.x + 255) / 256 * 256;
-    const int64_t     g0 = int64_t(blockIdx.x) * per, g1 = imin64(ndofs, g0 + per);
-    for (int64_t g = g0 + threadIdx.x; g < g1; g += 256)
-      {
-        const int64_t n = g / 3;
-        const int     c = int(g - n * 3);
-        double        s;
-        if ((prm.cmask[n] >> c) & 1)
-          {
-            const int32_t dp = prm.diagpos[n];
-            s                = dp >= 0 ? prm.vals[int64_t(dp) * 9 + c * 4] * prm.x[g] : 0.0;
-          }
-        else
-          {
-            const int32_t b0 = prm.slot_base[n], b1 = prm.slot_base[n + 1];
-            s                = mf_slot_sum(prm, b0, b1, c);
-          }
-        prm.y[g] = s;
-        if (g >= own0 && g < own0 + own_n)
-          acc = fma(dotv[g], s, acc);
-      }
-    acc = block_sum<256>(acc, s_red);
-    if (threadIdx.x == 0)
-      partials[blockIdx.x] = acc;
-  }
-
-  // ---- the same four gathers on lattice meshes with cell-major slots (SlotLattice, mi_kernels.h): a node's contributions
+  // ---- the same sum on lattice meshes with cell-major slots (SlotLattice, mi_kernels.h): a node's contributions
   // are found by arithmetic on its coordinates instead of through slot_base -> slot_src -> value.  Nothing depends on a
   // loaded index any more, so cmask, the vector operands and the (one to eight) contributing slots go out as ONE batch of
   // loads; the sum runs over the same values in the same order (ascending parity triple = ascending position), so every
@@ -3070,65 +2920,103 @@ namespace mi
     return s;
   }
 
-  __global__ __launch_bounds__(256) void mf_gather_lat(MfParams prm, SlotLattice sl, int64_t ndofs)
+  // ---- the slot gathers.  What a gather reads its slots through, first in its argument block: the slot tables of MfParams
+  // (any mesh, any slot layout) or, LAT, the lattice arithmetic as well
+  template <bool LAT>
+  struct MfSlots
   {
-    const int64_t g = int64_t(blockIdx.x) * 256 + threadIdx.x;
-    if (g >= ndofs)
-      return;
-    const int64_t n = g / 3;
-    const int     c = int(g - n * 3);
-    int32_t       i, j, k, slot[8];
-    double        v[8];
-    slot_lattice_ijk(sl, uint32_t(n), i, j, k);
-    slot_lattice_slots(sl, i, j, k, slot);
-    const uint8_t cm = prm.cmask[n];
-    mf_slot_load_lattice(prm, slot, c, v);
-    double s = mf_slot_add_lattice(slot, v);
-    if ((cm >> c) & 1)
-      {
-        const int32_t dp = prm.diagpos[n]; // -1: ghost node of a slab (its y is never read)
-        s                = dp >= 0 ? prm.vals[int64_t(dp) * 9 + c * 4] * prm.x[g] : 0.0;
-      }
-    prm.y[g] = s;
-  }
+    static constexpr bool lattice = false;
+    MfParams              prm;
+  };
+  template <>
+  struct MfSlots<true>
+  {
+    static constexpr bool lattice = true;
+    MfParams              prm;
+    SlotLattice           sl;
+  };
+  // q = the product at (node n, component c) from the slots, in two phases, with src, prm = src.prm, n, c and (LAT) the node's
+  // i, j, k in scope.  Text expanded in place, once per scope: the statement order decides the schedule
+  // (profiles/mf_shared_point/README.md), and a gather puts the loads of its own operands between the phases -- on the lattice
+  // source they leave in one batch with the mask and the slots.
+  //   MF_SLOTS_BEGIN: lattice source: the slot positions, the mask.  (Table source: nothing; its row is decided in the sum.)
+  //   MF_SLOTS_SUM:   the contributions in processing order -- table source: of an unconstrained row only; lattice source: read
+  //   regardless.  A constrained row is diag(K)_cc x_c, xv_, from the assembled tangent (xv_ is evaluated for such a row alone).
+  //   GHOSTS_: the gather runs over all local dofs and meets diagpos -1, a ghost node of a slab (its y is never read); the
+  //   gathers over owned nodes never do and do not test for it.
+#define MF_SLOTS_BEGIN(LAT_)                       \
+  int32_t slot[8];                                 \
+  double  v[8];                                    \
+  uint8_t cm = 0;                                  \
+  if constexpr (LAT_)                              \
+    {                                              \
+      slot_lattice_slots(src.sl, i, j, k, slot);   \
+      cm = prm.cmask[n];                           \
+    }
+#define MF_SLOTS_SUM(LAT_, GHOSTS_, q_, xv_)                                                        \
+  if constexpr (LAT_)                                                                               \
+    {                                                                                               \
+      mf_slot_load_lattice(prm, slot, c, v);                                                        \
+      q_ = mf_slot_add_lattice(slot, v);                                                            \
+    }                                                                                               \
+  if (((LAT_ ? cm : prm.cmask[n]) >> c) & 1)                                                        \
+    {                                                                                               \
+      const int32_t dp = prm.diagpos[n];                                                            \
+      q_               = (!(GHOSTS_) || dp >= 0) ? prm.vals[int64_t(dp) * 9 + c * 4] * (xv_) : 0.0; \
+    }                                                                                               \
+  else if constexpr (!(LAT_))                                                                       \
+    {                                                                                               \
+      const int32_t b0 = prm.slot_base[n], b1 = prm.slot_base[n + 1];                               \
+      q_               = mf_slot_sum(prm, b0, b1, c);                                               \
+    }
 
-  __global__ __launch_bounds__(256) void mf_gather_dot_lat(MfParams prm, SlotLattice sl, int64_t ndofs,
-                                                           const double *__restrict__ dotv, double *partials, int64_t own0,
-                                                           int64_t own_n)
+  // y = sum of the cells' contributions, node by node in slot order (= processing order of the cells: the order of the
+  // colour-by-colour update); constrained rows: diag(K) x from the assembled tangent.  One thread per DOF.
+  // DOT: with the partials of dotv . y over the owned dofs [own0, own0 + own_n) in the same launch: the CG's q = K p and p.q
+  // on the matrix-free fine level (round 6).  Fixed grid (grid-stride over the dofs, as dot_partials): the partials -- one
+  // per workgroup -- and their sum do not depend on the launch.
+  template <bool LAT, bool DOT>
+  __global__ __launch_bounds__(256) void mf_gather(MfSlots<LAT> src, int64_t ndofs, const double *__restrict__ dotv, double *partials,
+                                                   int64_t own0, int64_t own_n)
   {
-    __shared__ double s_red[4];
-    double            acc = 0.0;
-    const int64_t     per = ((ndofs + gridDim.x - 1) / gridDim.x + 255) / 256 * 256;
-    const int64_t     g0 = int64_t(blockIdx.x) * per, g1 = imin64(ndofs, g0 + per);
+    const MfParams &prm = src.prm;
+    double          acc = 0.0;
+    int64_t         g0 = int64_t(blockIdx.x) * 256, g1 = ndofs;
+    if constexpr (DOT)
+      {
+        const int64_t per = ((ndofs + gridDim.x - 1) / gridDim.x + 255) / 256 * 256;
+        g0 = int64_t(blockIdx.x) * per, g1 = imin64(ndofs, g0 + per);
+      }
     for (int64_t g = g0 + threadIdx.x; g < g1; g += 256)
       {
         const int64_t n = g / 3;
         const int     c = int(g - n * 3);
-        int32_t       i, j, k, slot[8];
-        double        v[8];
-        slot_lattice_ijk(sl, uint32_t(n), i, j, k);
-        slot_lattice_slots(sl, i, j, k, slot);
-        const uint8_t cm   = prm.cmask[n];
-        const bool    own  = g >= own0 && g < own0 + own_n;
-        const double  dv   = own ? dotv[g] : 0.0;
-        mf_slot_load_lattice(prm, slot, c, v);
-        double s = mf_slot_add_lattice(slot, v);
-        if ((cm >> c) & 1)
-          {
-            const int32_t dp = prm.diagpos[n];
-            s                = dp >= 0 ? prm.vals[int64_t(dp) * 9 + c * 4] * prm.x[g] : 0.0;
-          }
+        int32_t       i, j, k;
+        if constexpr (LAT)
+          slot_lattice_ijk(src.sl, uint32_t(n), i, j, k);
+        MF_SLOTS_BEGIN(LAT)
+        const auto   own = [&] { return g >= own0 && g < own0 + own_n; };
+        // (the lattice source's batch; the table source loads its operand behind the sum's dependent loads, as it always has)
+        const double dv = (LAT && DOT && own()) ? dotv[g] : 0.0;
+        double       s;
+        MF_SLOTS_SUM(LAT, true, s, prm.x[g])
         prm.y[g] = s;
-        if (own)
-          acc = fma(dv, s, acc);
+        if constexpr (!DOT)
+          break; // (one thread per dof)
+        if (own())
+          acc = fma(LAT ? dv : dotv[g], s, acc);
       }
-    acc = block_sum<256>(acc, s_red);
-    if (threadIdx.x == 0)
-      partials[blockIdx.x] = acc;
+    if constexpr (DOT)
+      {
+        __shared__ double s_red[4];
+        acc = block_sum<256>(acc, s_red);
+        if (threadIdx.x == 0)
+          partials[blockIdx.x] = acc;
+      }
   }
 
-  // Which node a thread of the two Chebyshev gathers takes.  W == 0: 64 consecutive nodes of [node0, node0 + nnodes) per
-  // workgroup, as the table form.  W > 0 (node tiles; the range is whole planes of the last direction): a workgroup of
+  // Which node a thread of the two gathers over the owned nodes takes.  W == 0: 64 consecutive nodes of [node0, node0 + nnodes)
+  // per workgroup (either slot source).  W > 0 (node tiles; the range is whole planes of the last direction): a workgroup of
   // 4 x W x 3 threads owns the 2 x 2 node lines (j in {2J, 2J+1}, k in {2K, 2K+1}) of one row of cells and walks a segment of
   // MF_TILE_SEG nodes of them along x, W nodes of each line per step.  A cell's 648-byte run of slots holds nine 72-byte pieces,
   // one per node line, and a 128-byte line of memory holds pieces of two or three of them: with one node line per workgroup
@@ -3144,10 +3032,12 @@ namespace mi
     static constexpr int NT = W ? 12 * W : 192;
     int32_t j = 0, k = 0, x0 = 0, xi = 0;
     bool    line_in = false;
-    __device__ __forceinline__ MfGatherMap(const SlotLattice &sl, const int m, const int64_t node0, const int64_t nnodes)
+    template <class SRC>
+    __device__ __forceinline__ MfGatherMap(const SRC &src, const int m, const int64_t node0, const int64_t nnodes)
     {
       if constexpr (W > 0)
         {
+          const SlotLattice &sl = src.sl;
           const int32_t k0 = int32_t(slot_lattice_div(uint32_t(node0), sl.magic_nn01));
           const int32_t k1 = k0 + int32_t(slot_lattice_div(uint32_t(nnodes), sl.magic_nn01));
           const int     line = m / W;
@@ -3159,12 +3049,14 @@ namespace mi
         }
     }
     static __device__ __forceinline__ int steps() { return W ? MF_TILE_SEG / W : 1; }
-    // node of step st: false where the thread has none
-    __device__ __forceinline__ bool node(const SlotLattice &sl, const int st, const int m, const int64_t node0, const int64_t nnodes,
+    // node of step st: false where the thread has none.  i, jj, kk: its coordinates, for the lattice source alone
+    template <class SRC>
+    __device__ __forceinline__ bool node(const SRC &src, const int st, const int m, const int64_t node0, const int64_t nnodes,
                                          int64_t &n, int32_t &i, int32_t &jj, int32_t &kk) const
     {
       if constexpr (W > 0)
         {
+          const SlotLattice &sl = src.sl;
           i  = x0 + st * W + xi;
           jj = j, kk = k;
           const bool in = line_in && i < sl.nn0;
@@ -3175,102 +3067,51 @@ namespace mi
         {
           const int64_t nl = int64_t(blockIdx.x) * 64 + m;
           const bool    in = nl < nnodes;
-          n                = in ? node0 + nl : node0;
-          slot_lattice_ijk(sl, uint32_t(n), i, jj, kk);
+          n                = (in || !SRC::lattice) ? node0 + nl : node0; // (the coordinates are taken of a node that exists)
+          if constexpr (SRC::lattice)
+            slot_lattice_ijk(src.sl, uint32_t(n), i, jj, kk);
           return in;
         }
     }
     // (uniform) whether step st + 1 has nodes
-    __device__ __forceinline__ bool more(const SlotLattice &sl, const int st) const
+    template <class SRC>
+    __device__ __forceinline__ bool more(const SRC &src, const int st) const
     {
-      return W > 0 && st + 1 < steps() && x0 + (st + 1) * W < sl.nn0;
+      if constexpr (W > 0)
+        return st + 1 < steps() && x0 + (st + 1) * W < src.sl.nn0;
+      else
+        return false;
     }
   };
 
-  template <int W>
-  __global__ __launch_bounds__(MfGatherMap<W>::NT) void mf_gather_cheb_lat(MfParams prm, SlotLattice sl, const double *__restrict__ b,
-                                                                          const double *__restrict__ dinv, double *d, double *xio,
-                                                                          double *yres, double c1, double c2, int64_t node0,
-                                                                          int64_t nnodes)
+  // the same sum fused with its consumer in the multigrid smoother: q = (K x') from the slots, then the Chebyshev step with
+  // the 3x3 block-Jacobi diagonal in three-term form, with the symmetric half of D^-1 (round 3):
+  // x'' = x' + c1 (x' - x) + c2 D^-1 (b - q) reads x' (the product's operand), x (the iterate before; null: zero) and writes
+  // x'' over x -- two reads and a write of 40 MB vectors instead of an update vector d and x read and written, 48 instead of
+  // 72 bytes of D^-1 per node: 380 instead of 460 MB per step of the smoother at 5 M dofs.  The caller swaps the two x
+  // buffers.  One thread per DOF of the owned nodes [node0, node0 + nnodes), mapped by MfGatherMap<W>.
+  template <bool LAT, int W>
+  __global__ __launch_bounds__(MfGatherMap<W>::NT) void mf_gather_cheb3(MfSlots<LAT> src, const double *__restrict__ b,
+                                                                       const double *__restrict__ dinv6, const double *xprev,
+                                                                       const double *__restrict__ xcur, double *xnext, double c1,
+                                                                       double c2, int64_t node0, int64_t nnodes)
   {
+    static_assert(LAT || W == 0, "node tiles are a form of the lattice source");
     constexpr int NT = MfGatherMap<W>::NT;
-    __shared__ double s_res[2][NT]; // (two buffers: a step's writes never meet the reads of the step before)
+    __shared__ double s_res[W ? 2 : 1][NT]; // (two buffers: a step's writes never meet the reads of the step before)
+    const MfParams      &prm = src.prm;
     const int            ld = threadIdx.x, c = ld % 3, m = ld / 3;
-    const MfGatherMap<W> map(sl, m, node0, nnodes);
+    const MfGatherMap<W> map(src, m, node0, nnodes);
     for (int st = 0;; ++st)
       {
-        int64_t    n;
-        int32_t    i, j, k, slot[8];
-        double     v[8];
-        const bool in = map.node(sl, st, m, node0, nnodes, n, i, j, k);
-        const int64_t g = n * 3 + c;
-        double     res = 0.0, a0 = 0.0, a1 = 0.0, a2 = 0.0, dold = 0.0, xold = 0.0;
+        int64_t       n;
+        int32_t       i, j, k;
+        const bool    in = map.node(src, st, m, node0, nnodes, n, i, j, k);
+        const int64_t g  = n * 3 + c;
+        double        res = 0.0, xc = 0.0, xp = 0.0, a0 = 0.0, a1 = 0.0, a2 = 0.0;
         if (in)
           {
-            slot_lattice_slots(sl, i, j, k, slot);
-            const uint8_t cm = prm.cmask[n];
-            const double  bv = b[g];
-            if (d)
-              {
-                a0 = dinv[g * 3], a1 = dinv[g * 3 + 1], a2 = dinv[g * 3 + 2];
-                dold = c1 != 0.0 ? d[g] : 0.0;
-                xold = xio[g];
-              }
-            mf_slot_load_lattice(prm, slot, c, v);
-            double q = mf_slot_add_lattice(slot, v);
-            if ((cm >> c) & 1)
-              q = prm.vals[int64_t(prm.diagpos[n]) * 9 + c * 4] * prm.x[g];
-            res = bv - q;
-          }
-        if (!d)
-          {
-            if (in)
-              yres[g] = res;
-          }
-        else
-          {
-            double *sr = s_res[st & 1];
-            sr[ld]     = res;
-            __syncthreads();
-            if (in)
-              {
-                const int r0 = (ld / 3) * 3;
-                double    s  = 0.0;
-                s += a0 * sr[r0];
-                s += a1 * sr[r0 + 1];
-                s += a2 * sr[r0 + 2];
-                const double dn = (c1 != 0.0 ? c1 * dold : 0.0) + c2 * s;
-                d[g]            = dn;
-                xio[g]          = xold + dn;
-              }
-          }
-        if (!map.more(sl, st))
-          break;
-      }
-  }
-
-  template <int W>
-  __global__ __launch_bounds__(MfGatherMap<W>::NT) void mf_gather_cheb3_lat(MfParams prm, SlotLattice sl, const double *__restrict__ b,
-                                                                           const double *__restrict__ dinv6, const double *xprev,
-                                                                           const double *__restrict__ xcur, double *xnext,
-                                                                           double c1, double c2, int64_t node0, int64_t nnodes)
-  {
-    constexpr int NT = MfGatherMap<W>::NT;
-    __shared__ double s_res[2][NT];
-    const int            ld = threadIdx.x, c = ld % 3, m = ld / 3;
-    const MfGatherMap<W> map(sl, m, node0, nnodes);
-    for (int st = 0;; ++st)
-      {
-        int64_t    n;
-        int32_t    i, j, k, slot[8];
-        double     v[8];
-        const bool in = map.node(sl, st, m, node0, nnodes, n, i, j, k);
-        const int64_t g = n * 3 + c;
-        double     res = 0.0, xc = 0.0, xp = 0.0, a0 = 0.0, a1 = 0.0, a2 = 0.0;
-        if (in)
-          {
-            slot_lattice_slots(sl, i, j, k, slot);
-            const uint8_t cm = prm.cmask[n];
+            MF_SLOTS_BEGIN(LAT)
             // row c of the symmetric block (xx yy zz xy xz yz)
             const double *q6 = dinv6 + n * 6;
             a0               = q6[c == 0 ? 0 : (c == 1 ? 3 : 4)];
@@ -3278,14 +3119,12 @@ namespace mi
             a2               = q6[c == 0 ? 4 : (c == 1 ? 5 : 2)];
             xc               = xcur[g];
             xp               = (c1 != 0.0 && xprev) ? xprev[g] : 0.0;
-            const double bv  = b[g];
-            mf_slot_load_lattice(prm, slot, c, v);
-            double q = mf_slot_add_lattice(slot, v);
-            if ((cm >> c) & 1)
-              q = prm.vals[int64_t(prm.diagpos[n]) * 9 + c * 4] * xc;
-            res = bv - q;
+            const double bv  = LAT ? b[g] : 0.0; // (the lattice source's batch; the table source: behind its sum, as in mf_gather)
+            double       q;
+            MF_SLOTS_SUM(LAT, false, q, xc)
+            res = (LAT ? bv : b[g]) - q;
           }
-        double *sr = s_res[st & 1];
+        double *sr = s_res[st & (W ? 1 : 0)];
         sr[ld]     = res;
         __syncthreads();
         if (in)
@@ -3298,10 +3137,40 @@ namespace mi
             const double dn = (c1 != 0.0 ? c1 * (xc - xp) : 0.0) + c2 * s;
             xnext[g]        = xc + dn;
           }
-        if (!map.more(sl, st))
+        if (!map.more(src, st))
           break;
       }
   }
+
+  // ... and with the residual: yres = b - q on the owned nodes, on the same maps
+  template <bool LAT, int W>
+  __global__ __launch_bounds__(MfGatherMap<W>::NT) void mf_gather_residual(MfSlots<LAT> src, const double *__restrict__ b, double *yres,
+                                                                          int64_t node0, int64_t nnodes)
+  {
+    static_assert(LAT || W == 0, "node tiles are a form of the lattice source");
+    const MfParams      &prm = src.prm;
+    const int            ld = threadIdx.x, c = ld % 3, m = ld / 3;
+    const MfGatherMap<W> map(src, m, node0, nnodes);
+    for (int st = 0;; ++st)
+      {
+        int64_t    n;
+        int32_t    i, j, k;
+        const bool in = map.node(src, st, m, node0, nnodes, n, i, j, k);
+        if (in)
+          {
+            const int64_t g = n * 3 + c;
+            MF_SLOTS_BEGIN(LAT)
+            const double bv = LAT ? b[g] : 0.0; // (the lattice source's batch; the table source: behind its sum, as in mf_gather)
+            double       q;
+            MF_SLOTS_SUM(LAT, false, q, prm.x[g])
+            yres[g] = (LAT ? bv : b[g]) - q;
+          }
+        if (!map.more(src, st))
+          break;
+      }
+  }
+#undef MF_SLOTS_BEGIN
+#undef MF_SLOTS_SUM
 
   // ------------------------------------------------------------------ matrix-free fine level: the diagonal blocks (round 6)
   // With the fine level matrix-free end to end (tuning "fine_level" 1) nothing multiplies the assembled fine tangent any
@@ -7483,20 +7352,20 @@ namespace mi
     const int64_t k0 = node0 / sl.nn01, k1 = k0 + nnodes / sl.nn01;
     return dim3(unsigned((sl.nn0 + MF_TILE_SEG - 1) / MF_TILE_SEG), unsigned(sl.nc[1] + 1), unsigned(((k1 - 1) >> 1) - (k0 >> 1) + 1));
   }
-  // sl (with ncol > 0): the lattice form; tiles: in node tiles (the caller has checked that the range is whole planes)
-  void launch_mf_gather_cheb(const MfParams &p, const double *b, const double *dinv, double *d, double *xio, double *yres,
-                             double c1, double c2, int64_t node0, int64_t nnodes, hipStream_t s, const SlotLattice *sl, bool tiles)
+  // sl (with ncol > 0): the lattice source; tiles: in node tiles (the caller has checked that the range is whole planes)
+  void launch_mf_gather_residual(const MfParams &p, const double *b, double *yres, int64_t node0, int64_t nnodes, hipStream_t s,
+                                 const SlotLattice *sl, bool tiles)
   {
     if (nnodes <= 0)
       return;
     if (sl && sl->ncol > 0 && tiles)
-      hipLaunchKernelGGL(mf_gather_cheb_lat<MF_TILE_W>, mf_tile_grid(*sl, node0, nnodes), dim3(MfGatherMap<MF_TILE_W>::NT), 0, s, p,
-                         *sl, b, dinv, d, xio, yres, c1, c2, node0, nnodes);
+      hipLaunchKernelGGL((mf_gather_residual<true, MF_TILE_W>), mf_tile_grid(*sl, node0, nnodes), dim3(MfGatherMap<MF_TILE_W>::NT), 0,
+                         s, MfSlots<true>{p, *sl}, b, yres, node0, nnodes);
     else if (sl && sl->ncol > 0)
-      hipLaunchKernelGGL(mf_gather_cheb_lat<0>, dim3(int((nnodes + 63) / 64)), dim3(192), 0, s, p, *sl, b, dinv, d, xio, yres, c1, c2,
+      hipLaunchKernelGGL((mf_gather_residual<true, 0>), dim3(int((nnodes + 63) / 64)), dim3(192), 0, s, MfSlots<true>{p, *sl}, b, yres,
                          node0, nnodes);
     else
-      hipLaunchKernelGGL(mf_gather_cheb, dim3(int((nnodes + 63) / 64)), dim3(192), 0, s, p, b, dinv, d, xio, yres, c1, c2,
+      hipLaunchKernelGGL((mf_gather_residual<false, 0>), dim3(int((nnodes + 63) / 64)), dim3(192), 0, s, MfSlots<false>{p}, b, yres,
                          node0, nnodes);
   }
   void launch_mf_gather_cheb3(const MfParams &p, const double *b, const double *dinv6, const double *xprev, const double *xcur,
@@ -7506,29 +7375,34 @@ namespace mi
     if (nnodes <= 0)
       return;
     if (sl && sl->ncol > 0 && tiles)
-      hipLaunchKernelGGL(mf_gather_cheb3_lat<MF_TILE_W>, mf_tile_grid(*sl, node0, nnodes), dim3(MfGatherMap<MF_TILE_W>::NT), 0, s, p,
-                         *sl, b, dinv6, xprev, xcur, xnext, c1, c2, node0, nnodes);
+      hipLaunchKernelGGL((mf_gather_cheb3<true, MF_TILE_W>), mf_tile_grid(*sl, node0, nnodes), dim3(MfGatherMap<MF_TILE_W>::NT), 0, s,
+                         MfSlots<true>{p, *sl}, b, dinv6, xprev, xcur, xnext, c1, c2, node0, nnodes);
     else if (sl && sl->ncol > 0)
-      hipLaunchKernelGGL(mf_gather_cheb3_lat<0>, dim3(int((nnodes + 63) / 64)), dim3(192), 0, s, p, *sl, b, dinv6, xprev, xcur, xnext,
-                         c1, c2, node0, nnodes);
+      hipLaunchKernelGGL((mf_gather_cheb3<true, 0>), dim3(int((nnodes + 63) / 64)), dim3(192), 0, s, MfSlots<true>{p, *sl}, b, dinv6,
+                         xprev, xcur, xnext, c1, c2, node0, nnodes);
     else
-      hipLaunchKernelGGL(mf_gather_cheb3, dim3(int((nnodes + 63) / 64)), dim3(192), 0, s, p, b, dinv6, xprev, xcur, xnext, c1, c2,
-                         node0, nnodes);
+      hipLaunchKernelGGL((mf_gather_cheb3<false, 0>), dim3(int((nnodes + 63) / 64)), dim3(192), 0, s, MfSlots<false>{p}, b, dinv6,
+                         xprev, xcur, xnext, c1, c2, node0, nnodes);
   }
   void launch_mf_gather(const MfParams &p, int64_t ndofs, hipStream_t s, const SlotLattice *sl)
   {
+    const double *no_dotv     = nullptr;
+    double       *no_partials = nullptr;
     if (sl && sl->ncol > 0)
-      hipLaunchKernelGGL(mf_gather_lat, dim3(int((ndofs + 255) / 256)), dim3(256), 0, s, p, *sl, ndofs);
+      hipLaunchKernelGGL((mf_gather<true, false>), dim3(int((ndofs + 255) / 256)), dim3(256), 0, s, MfSlots<true>{p, *sl}, ndofs,
+                         no_dotv, no_partials, int64_t(0), int64_t(0));
     else
-      hipLaunchKernelGGL(mf_gather, dim3(int((ndofs + 255) / 256)), dim3(256), 0, s, p, ndofs);
+      hipLaunchKernelGGL((mf_gather<false, false>), dim3(int((ndofs + 255) / 256)), dim3(256), 0, s, MfSlots<false>{p}, ndofs, no_dotv,
+                         no_partials, int64_t(0), int64_t(0));
   }
   void launch_mf_gather_dot(const MfParams &p, int64_t ndofs, const double *dotv, double *partials, int grid, int64_t own0,
                             int64_t own_n, hipStream_t s, const SlotLattice *sl)
   {
     if (sl && sl->ncol > 0)
-      hipLaunchKernelGGL(mf_gather_dot_lat, dim3(grid), dim3(256), 0, s, p, *sl, ndofs, dotv, partials, own0, own_n);
+      hipLaunchKernelGGL((mf_gather<true, true>), dim3(grid), dim3(256), 0, s, MfSlots<true>{p, *sl}, ndofs, dotv, partials, own0,
+                         own_n);
     else
-      hipLaunchKernelGGL(mf_gather_dot, dim3(grid), dim3(256), 0, s, p, ndofs, dotv, partials, own0, own_n);
+      hipLaunchKernelGGL((mf_gather<false, true>), dim3(grid), dim3(256), 0, s, MfSlots<false>{p}, ndofs, dotv, partials, own0, own_n);
   }
   void launch_point_pass_slots(const AsmParams &p, hipStream_t s)
   {

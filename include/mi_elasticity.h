@@ -432,7 +432,7 @@ int mi_set_profiling(mi_ctx *ctx, int enable);
  *  mg_scale_lmax_percent 10..400                   tests: spoil the eigenvalue estimates once                           -
  *
  * Further switches of the experiments build only (read at creation; diagnostics): MI_MG_NU, MI_MG_NU_COARSE, MI_MG_RATIO, MI_MG_KIND,
- * MI_MG_BLOCK, MI_MG_THREE_TERM, MI_MG_COARSEST, MI_MG_DENSE, MI_MG_FACTOR, MI_MG_SAFETY, MI_MG_POWER_ITS,
+ * MI_MG_BLOCK, MI_MG_COARSEST, MI_MG_DENSE, MI_MG_FACTOR, MI_MG_SAFETY, MI_MG_POWER_ITS,
  * MI_MG_COARSE_DEGREE, MI_MG_COARSE_RATIO, MI_MG_FUSE_MAX_NODES, MI_MG_VERBOSE (multigrid parameters);
  * MI_MF_XCD (XCD-aware cell order of mf_spmv), MI_ASM_CELL_LATTICE, MI_ASM_STAMPS / MI_MF_STAMPS / MI_MF_DBG (phase stamps
  * and timing-only ablations of the two element kernels). */

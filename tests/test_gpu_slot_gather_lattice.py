@@ -1,6 +1,6 @@
 """GPU: the slot gathers with slot positions by arithmetic ("mf_gather_lattice" 1) and in node tiles (2) against the slot tables (0).
 
-On lattice meshes with cell-major slots the four gathers (mf_gather, mf_gather_cheb in both modes, mf_gather_cheb3,
+On lattice meshes with cell-major slots the four gathers (mf_gather, the residual gather, mf_gather_cheb3,
 mf_gather_dot) find a node's contributions from its coordinates instead of through slot_base / slot_src, and the two
 Chebyshev gathers walk 2 x 2 node lines per workgroup.  Neither changes which values are added nor in which order, so every
 result must have the BITS of the table form: numpy.array_equal throughout, no tolerance.  (That the table form itself is the
@@ -10,7 +10,7 @@ Per shape and fine level, modes 1 and 2 against mode 0, each mode in a context o
   1. the smoother-form product of a random x (mf_spmv27 + mf_gather);
   2. the CG-form product of the same x (mf_spmv + mf_gather; on "fine_level" 1 this is the CG's operator);
   3. one Newmark step under the multigrid preconditioner from a random small state: the smoother runs mf_gather_cheb3 and
-     mf_gather_cheb's residual mode, the CG of "fine_level" 1 runs mf_gather_dot (its p.q decides every step length, so equal
+     the residual gather, the CG of "fine_level" 1 runs mf_gather_dot (its p.q decides every step length, so equal
      iterates mean equal partial sums).  Displacement, velocity, acceleration, Newton and CG iteration counts.
 "mf_gather_lattice_active" must report the mode that was set.
 
