@@ -139,6 +139,13 @@ def lib():
         L.mi_linear_get_diagonal.argtypes = [vp, dp]
         for f in ("mi_linear_setup", "mi_linear_step", "mi_linear_matrix_get_csr", "mi_linear_apply", "mi_linear_get_diagonal"):
             getattr(L, f).restype = C.c_int
+        L.mi_linear_get_diagonal_blocks.argtypes = [vp, dp]
+        L.mi_linear_mg_n_levels.argtypes = [vp]
+        L.mi_linear_mg_level_describe.argtypes = [vp, C.c_int, C.POINTER(MgLevelDesc)]
+        L.mi_linear_mg_level_context.argtypes = [vp, C.c_int, C.POINTER(vp)]
+        for f in ("mi_linear_get_diagonal_blocks", "mi_linear_mg_n_levels", "mi_linear_mg_level_describe",
+                  "mi_linear_mg_level_context"):
+            getattr(L, f).restype = C.c_int
         L.mi_set_profiling.argtypes = [vp, C.c_int]
         L.mi_get_timings.argtypes = [vp, C.POINTER(Timings)]
         L.mi_partition_describe.restype = C.c_int
@@ -257,6 +264,13 @@ class LevelView:
 
     def diagonal_blocks(self):
         return Context.diagonal_blocks(self)
+
+    # a level of the linear model's hierarchy (mi_linear_mg_level_context)
+    def linear_csr(self, which):
+        return Context.linear_csr(self, which)
+
+    def linear_diagonal_blocks(self):
+        return Context.linear_diagonal_blocks(self)
 
 
 class Context:
@@ -448,13 +462,30 @@ class Context:
     def mg_level_describe(self, level):
         d = MgLevelDesc()
         self._chk(lib().mi_mg_level_describe(self.h, level, C.byref(d)))
-        return dict(degree=d.degree, reps=tuple(d.reps)[:self.dim], n_dofs=d.n_dofs, lmax=d.lmax,
-                    interval_ratio=d.interval_ratio, smoother_degree=d.smoother_degree, exact_solve=d.exact_solve,
-                    distributed=d.distributed)
+        return self._level_desc(d)
 
     def mg_level_context(self, level):
         h = C.c_void_p()
         self._chk(lib().mi_mg_level_context(self.h, level, C.byref(h)))
+        return LevelView(self, h)
+
+    def _level_desc(self, d):
+        return dict(degree=d.degree, reps=tuple(d.reps)[:self.dim], n_dofs=d.n_dofs, lmax=d.lmax,
+                    interval_ratio=d.interval_ratio, smoother_degree=d.smoother_degree, exact_solve=d.exact_solve,
+                    distributed=d.distributed)
+
+    # ---- the linear model's own hierarchy (tuning key "linear_precond" 1), complete after linear_setup
+    def linear_mg_n_levels(self):
+        return lib().mi_linear_mg_n_levels(self.h)
+
+    def linear_mg_level_describe(self, level):
+        d = MgLevelDesc()
+        self._chk(lib().mi_linear_mg_level_describe(self.h, level, C.byref(d)))
+        return self._level_desc(d)
+
+    def linear_mg_level_context(self, level):
+        h = C.c_void_p()
+        self._chk(lib().mi_linear_mg_level_context(self.h, level, C.byref(h)))
         return LevelView(self, h)
 
     # ---- linear model (mi_linear_setup / mi_linear_step); the operators follow the tuning key "linear_operator"
@@ -469,7 +500,7 @@ class Context:
         return its.value, res.value
 
     def linear_apply(self, which, x):
-        """y = K x (0), M x (1), A x (2) through the device kernels of the current set-up"""
+        """y = K x (0), M x (1), A x (2) through the device kernels of the current set-up; 3: one V-cycle of its multigrid"""
         x = np.ascontiguousarray(x, dtype=np.float64)
         y = np.zeros_like(x)
         self._chk(lib().mi_linear_apply(self.h, which, _dp(x), _dp(y)))
@@ -490,6 +521,12 @@ class Context:
         d = np.zeros(self.n)
         self._chk(lib().mi_linear_get_diagonal(self.h, _dp(d)))
         return d
+
+    def linear_diagonal_blocks(self):
+        """[n_nodes, dim, dim]: the node blocks of the stepping matrix in use (the smoother's D under "linear_precond" 1)"""
+        b = np.zeros((self.nnodes, self.dim, self.dim))
+        self._chk(lib().mi_linear_get_diagonal_blocks(self.h, _dp(b)))
+        return b
 
     def set_profiling(self, on=True):
         self._chk(lib().mi_set_profiling(self.h, int(on)))

@@ -431,6 +431,8 @@ namespace mi_detail
 
   bool mf_gather_fusable(const mi_ctx *c)
   {
+    if (c->active_linear_mf) // the matrix-free linear model: every product is one launch + a slot gather (3D: D^-1 has its halves)
+      return true;
     return element_form(c) == 2 && c->ebe == 2 && c->mf_slots && c->d_mf_yc && c->precond_storage == 64 &&
            !c->active_sell_vals && c->d_dinv_blk;
   }
@@ -491,7 +493,8 @@ namespace mi_detail
     // (opt-in A/B "cg_operator" 1: the CG's own product as well, with p.q by a separate reduction -- then the
     // sliced-ELL copy of the tangent is never made)
     // matrix-free linear model: (c_K K + c_M M) x into the cells' slots, then the slot sum -- with the partials of dotv . y
-    // for the CG's q = A p; rows of constrained dofs: diag(A) x (one slab: no parts)
+    // for the CG's q = A p; rows of constrained dofs: diag(A) x (one slab: no parts).  cheb (the model's multigrid smoother and
+    // the V-cycle's residual, always in the gather's own form): the slot sum takes the step or forms b - A x
     if (c->active_linear_mf)
       {
         if (part == 1)
@@ -502,7 +505,7 @@ namespace mi_detail
         f.yc = c->d_mf_yc, f.dst = c->d_mf_dst, f.slot_base = c->d_mf_slot_base, f.slot_src = c->d_mf_src;
         f.slot_inline = c->slots_layout == 1;
         mi::launch_mf_linear_q3(f, lm.op, int32_t(c->mesh.ncells), c->stream);
-        enqueue_slot_gather(c, f, nullptr, dotv, partials, false);
+        enqueue_slot_gather(c, f, cheb, dotv, partials, false);
         return;
       }
     const int  kind       = element_form(c);
@@ -1446,7 +1449,7 @@ namespace mi_detail
       use_mg = use_mg && mg_active(m);
     if (use_mg)
       {
-        if (c0->mg_stale && (c0->mg_force || !c0->mg_lag))
+        if (!c0->mg_linear && c0->mg_stale && (c0->mg_force || !c0->mg_lag)) // (the linear model's hierarchy is never refreshed)
           {
             if ((rc = mg_update(T)))
               return rc;
@@ -3206,6 +3209,13 @@ int mi_set_tuning(mi_ctx *c, const char *key, int value)
           m->linear_operator = value;
           continue;
         }
+      if (k == "linear_precond" && (value == 0 || value == 1))
+        {
+          if (value == 1 && c->team->size != 1) // (before any member changes)
+            return fail(c, MI_EINVAL, "\"linear_precond\" 1: the linear model's multigrid exists on an undecomposed mesh only");
+          m->linear_precond = value;
+          continue;
+        }
       if (k == "fine_level" && (value == 0 || value == 1))
         {
           if (m->linear_mf)
@@ -3391,6 +3401,10 @@ int mi_get_tuning(mi_ctx *c, const char *key, int *value)
     *value = m->linear_operator;
   else if (k == "linear_operator_active") // what the current linear set-up runs (0 without one)
     *value = (m->linear && m->linear_mf) ? 1 : 0;
+  else if (k == "linear_precond")
+    *value = m->linear_precond;
+  else if (k == "linear_precond_active") // 1: the solve of the current linear set-up is multigrid-preconditioned (0 without one)
+    *value = mi_linear_mg_n_levels(m) > 1 ? 1 : 0;
   else if (k == "mf_diag_lag")
     *value = m->mf_diag_lag;
   else if (k == "smoother_quadrature")

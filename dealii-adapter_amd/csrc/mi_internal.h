@@ -271,6 +271,12 @@ struct mi_ctx
   // linear_mf: what the current set-up runs.  While it holds the context keeps NO assembled array: d_vals is released too
   int           linear_operator = 0;
   bool          linear_mf       = false;
+  // tuning "linear_precond": 0 the linear model's solve is the Jacobi-PCG | 1 preconditioned by a multigrid V-cycle on a hierarchy
+  // of the (constant) stepping matrix, owned by the LinearModel and built by mi_linear_setup (undecomposed contexts).  Read by
+  // the next mi_linear_setup.  mg_linear: that hierarchy while the model's stepping matrix is selected (linear_select), else
+  // null: the multigrid code then runs on it instead of `mg`, whatever "precond" says; nothing refreshes it
+  int           linear_precond = 0;
+  mi_detail::Multigrid *mg_linear = nullptr;
   const mi_detail::LinearMf *active_linear_mf = nullptr;
   std::vector<double> h_iface;   // host copy of the last interface values (linear model: consistent loading)
   mi_detail::LinearModel *linear = nullptr;
@@ -346,6 +352,16 @@ namespace mi_detail
   void mg_reset_estimates(Team &T); // eigenvalue estimates of all levels from scratch at the next operator update
   void mg_scale_estimates(Team &T, double f); // tests: spoil the current estimates // build the level hierarchy of a slab (once)
   void mg_destroy(mi_ctx *c);
+  void mg_free(Multigrid *mg); // a hierarchy with its level contexts, transfers and workspaces
+  // the linear model's hierarchy ("linear_precond" 1): the shape of mg_setup; level 0 = c with its stepping matrix selected and the
+  // inverse node blocks given (full and, 3D, symmetric halves); levels >= 1 set up as linear models of their own meshes
+  // (linear_setup_level) with the stepping matrix selected for good; dense inverse and eigenvalue estimates once
+  int  mg_setup_linear(mi_ctx *c, double theta, const double *dinv_blk, const double *dinv_sym6, Multigrid **out);
+  int  mg_n_levels(const Multigrid *mg);
+  int  mg_describe(mi_ctx *c, const Multigrid &mg, int level, mi_mg_level_desc *out);
+  mi_ctx *mg_level_ctx(const Multigrid &mg, int level);
+  int  linear_setup_level(mi_ctx *lc, double theta); // mi_linear.cpp
+  void linear_select(mi_ctx *m, int which);          // mi_linear.cpp
   int  mg_update(Team &T);  // re-assemble the coarse operators for the current state (team-wide)
   int  mg_distributed_levels(const mi_ctx *c);
   int  mg_apply(Team &T);   // W_Z = V-cycle(W_R) on every slab of the team (team-wide, collective)

@@ -390,6 +390,9 @@ namespace mi
                            hipEvent_t ev_stop = nullptr);
   void launch_mf_linear_diag_q3(const MfParams &p, const MfLinearOp &op, int32_t cell_count, double *blk, double *dinv, int64_t ndofs,
                                 hipStream_t s);
+  // "linear_precond" 1: the nodes' whole 3 x 3 blocks of that operator, every cell's symmetric halves into slots6 [ncells * 64][6]
+  // (slot = the product's); launch_mf_diag_gather sums them, applies the constraint rule and inverts
+  void launch_mf_linear_diag_blk_q3(const MfParams &p, const MfLinearOp &op, int32_t cell_count, double *slots6, hipStream_t s);
   // the matrix-free fine level's point pass over ALL cells in one launch (assemble_q2sf<true> with the residual into slots:
   // AsmParams::res_slots / slot_dst; cell_begin = 0, cell_count = all) and the sum of the slots into system_rhs
   void launch_point_pass_slots(const AsmParams &p, hipStream_t s);

@@ -4512,8 +4512,12 @@ namespace mi
   //   A_(a,c)(a,c) = sum_q JxW (theta^2 dt^2 ((lambda + mu) g_a[c]^2 + mu g_a . g_a) + rho N_a^2),   g_a = Jinv^T grad_xi N_a.
   // One wave per cell, lane = node a = (k*4+j)*4+i, a loop over the 64 points; written for clarity.  Nothing is dropped on the
   // diagonal (a constrained dof keeps its own: MatrixTools::apply_boundary_values, :426-451).
-  template <bool BOX>
-  __global__ __launch_bounds__(64 * MFQ3S_WPB) void mf_linear_diag_q3(MfParams prm, MfLinearOp op)
+  // BLK ("linear_precond" 1: the block-Jacobi D of the multigrid smoother): the node's whole 3 x 3 block
+  //   A_(a,c)(a,d) = sum_q JxW (theta^2 dt^2 ((lambda + mu) g_a[c] g_a[d] + delta_cd mu g_a . g_a) + delta_cd rho N_a^2)
+  // as its symmetric half xx yy zz xy xz yz into slots6 [nslots][6] (the layout of mf_diag_q3; mf_diag_gather sums them).  The
+  // three diagonal entries are the expressions of the scalar form.
+  template <bool BOX, bool BLK>
+  __global__ __launch_bounds__(64 * MFQ3S_WPB) void mf_linear_diag_q3(MfParams prm, MfLinearOp op, double *__restrict__ slots6)
   {
     const int     t    = threadIdx.x & 63;
     const int64_t cell = int64_t(blockIdx.x) * MFQ3S_WPB + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -4522,6 +4526,7 @@ namespace mi
     const int     ia[3] = {t & 3, (t >> 2) & 3, t >> 4};
     const double *tab   = prm.tab_q3s;
     double        d[3]  = {0.0, 0.0, 0.0};
+    double        o[3]  = {0.0, 0.0, 0.0}; // BLK: xy xz yz
     for (int q = 0; q < MFQ3S_NQ; ++q)
       {
         const int qi[3] = {q & 3, (q >> 2) & 3, q >> 4};
@@ -4542,11 +4547,30 @@ namespace mi
 #pragma unroll
         for (int c = 0; c < 3; ++c)
           d[c] += w * (op.c_K * ((op.lambda + op.mu) * g[c] * g[c] + op.mu * gg) + op.c_M * op.rho * n * n);
+        if constexpr (BLK)
+          {
+            const double wl = w * op.c_K * (op.lambda + op.mu);
+            o[0] += wl * g[0] * g[1];
+            o[1] += wl * g[0] * g[2];
+            o[2] += wl * g[1] * g[2];
+          }
       }
     const int64_t slot = prm.slot_inline ? cell * MFQ3S_NPC + t : int64_t(prm.dst[cell * MFQ3S_NPC + t]);
+    if constexpr (BLK)
+      {
 #pragma unroll
-    for (int c = 0; c < 3; ++c)
-      prm.yc[slot * 3 + c] = d[c];
+        for (int c = 0; c < 3; ++c)
+          {
+            slots6[slot * 6 + c]     = d[c];
+            slots6[slot * 6 + 3 + c] = o[c];
+          }
+      }
+    else
+      {
+#pragma unroll
+        for (int c = 0; c < 3; ++c)
+          prm.yc[slot * 3 + c] = d[c];
+      }
   }
 
   // ... summed per node in slot order (= processing order of the cells) into the diagonal entries of the node's block
@@ -7520,9 +7544,18 @@ namespace mi
       return;
     MfParams q = p;
     q.count    = cell_count;
-    auto *kern = q.cellbox ? mf_linear_diag_q3<true> : mf_linear_diag_q3<false>;
-    hipLaunchKernelGGL(kern, dim3((cell_count + MFQ3S_WPB - 1) / MFQ3S_WPB), dim3(64 * MFQ3S_WPB), 0, s, q, op);
+    auto *kern = q.cellbox ? mf_linear_diag_q3<true, false> : mf_linear_diag_q3<false, false>;
+    hipLaunchKernelGGL(kern, dim3((cell_count + MFQ3S_WPB - 1) / MFQ3S_WPB), dim3(64 * MFQ3S_WPB), 0, s, q, op, (double *)nullptr);
     hipLaunchKernelGGL(mf_linear_diag_gather, dim3(int((ndofs + 255) / 256)), dim3(256), 0, s, q, blk, dinv, ndofs);
+  }
+  void launch_mf_linear_diag_blk_q3(const MfParams &p, const MfLinearOp &op, int32_t cell_count, double *slots6, hipStream_t s)
+  {
+    if (cell_count <= 0)
+      return;
+    MfParams q = p;
+    q.count    = cell_count;
+    auto *kern = q.cellbox ? mf_linear_diag_q3<true, true> : mf_linear_diag_q3<false, true>;
+    hipLaunchKernelGGL(kern, dim3((cell_count + MFQ3S_WPB - 1) / MFQ3S_WPB), dim3(64 * MFQ3S_WPB), 0, s, q, op, slots6);
   }
   void launch_mf_diag_gather(const double *slots6, const int32_t *slot_base, const int32_t *slot_src, const uint8_t *cmask,
                              const int32_t *diagpos, double *blk, double *dinv, double *dinv_blk, double *sym6, int64_t nnodes, hipStream_t s)

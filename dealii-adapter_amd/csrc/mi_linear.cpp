@@ -10,7 +10,12 @@
 // Tuning "linear_operator" 1 (3D Q3, one slab): nothing is assembled.  K, M and the stepping matrix are one kernel
 // (mf_linear_q3: (c_K K + c_M M) x on the model's own 4 x 4 x 4 rule, one wave per cell) + the slot gathers; the set-up forms
 // the diagonal of the stepping matrix (mf_linear_diag_q3) and the body-force vector as M (b, b, ...), and releases the
-// nonlinear tangent array.  The per-step path is the same; the solve is the Jacobi-PCG whatever "solver_type" says.
+// nonlinear tangent array.  The per-step path is the same; the solve is the PCG whatever "solver_type" says.
+//
+// Tuning "linear_precond" 1 (one slab): the PCG is preconditioned by a geometric multigrid V-cycle on a hierarchy of the
+// stepping matrix that the model owns (mg_setup_linear): built once per set-up, never refreshed, independent of "precond" and
+// of the tangent's hierarchy.  Level 0 is the context with the stepping matrix selected, in either operator form; its
+// block-Jacobi D is the model's (the node blocks of d_A, or mf_linear_diag_q3<., true> + mf_diag_gather without a matrix).
 #include <cmath>
 #include <cstring>
 #include <map>
@@ -33,6 +38,11 @@ namespace mi_detail
     double  *d_diag = nullptr, *d_tab4 = nullptr;
     int32_t *d_diagpos_mf = nullptr;
     uint8_t *d_nomask = nullptr; // [nnodes] zeros: the constraint mask of K and M (no row replaced)
+    // "linear_precond" 1: the hierarchy of the stepping matrix, the inverse node blocks of level 0 (full, and in 3D their
+    // symmetric halves), the iterations of the previous step's solve (what cg_run may enqueue without polling)
+    Multigrid *mg = nullptr;
+    double    *d_dinv_blk = nullptr, *d_dinv_sym6 = nullptr;
+    int        last_its = 0;
     // consistent-load operator on the interface nodes (scalar CSR over interface slots), :458-521
     std::vector<int32_t> B_rowptr, B_col;
     std::vector<double>  B_val;
@@ -42,8 +52,10 @@ namespace mi_detail
   {
     if (!c->linear)
       return;
+    mg_free(c->linear->mg);
+    c->mg_linear = nullptr;
     for (double *p : {c->linear->d_K, c->linear->d_M, c->linear->d_A, c->linear->d_dinvA, c->linear->d_body, c->linear->d_diag,
-                      c->linear->d_tab4})
+                      c->linear->d_tab4, c->linear->d_dinv_blk, c->linear->d_dinv_sym6})
       if (p)
         hipFree(p);
     if (c->linear->d_diagpos_mf)
@@ -109,7 +121,25 @@ static int linear_setup_matrix_free(mi_ctx *c, LinearModel &L, const mi::Tables1
   mi::MfParams f = mf_params(c);
   f.tab_q3s = L.d_tab4, f.yc = c->d_mf_yc, f.dst = c->d_mf_dst, f.slot_base = c->d_mf_slot_base, f.slot_src = c->d_mf_src;
   f.slot_inline = c->slots_layout == 1;
-  mi::launch_mf_linear_diag_q3(f, L.op[2].op, int32_t(m.ncells), L.d_diag, L.d_dinvA, c->n, c->stream);
+  if (c->linear_precond == 1)
+    {
+      // the nodes' whole blocks of the stepping matrix, cell by cell into slots of six, summed in slot order.  The gather's
+      // constraint rule (row and column of a constrained dof dropped, |diagonal contribution| kept) is the model's: the
+      // diagonal contributions are sums of squares, so nothing changes sign.  Out: the blocks, 1 / diagonal, D^-1 in both forms
+      double *d_slots6 = nullptr;
+      HIPCHK(c, hipMalloc((void **)&d_slots6, size_t(m.ncells) * 64 * 6 * sizeof(double)));
+      HIPCHK(c, hipMalloc((void **)&L.d_dinv_blk, nn * 9 * sizeof(double)));
+      HIPCHK(c, hipMalloc((void **)&L.d_dinv_sym6, nn * 6 * sizeof(double)));
+      mi::launch_mf_linear_diag_blk_q3(f, L.op[2].op, int32_t(m.ncells), d_slots6, c->stream);
+      mi::launch_mf_diag_gather(d_slots6, c->d_mf_slot_base, c->d_mf_src, c->d_cmask, L.d_diagpos_mf, L.d_diag, L.d_dinvA, L.d_dinv_blk,
+                                L.d_dinv_sym6, m.nnodes, c->stream);
+      const hipError_t e1 = hipGetLastError(), e2 = hipStreamSynchronize(c->stream);
+      hipFree(d_slots6);
+      HIPCHK(c, e1);
+      HIPCHK(c, e2);
+    }
+  else
+    mi::launch_mf_linear_diag_q3(f, L.op[2].op, int32_t(m.ncells), L.d_diag, L.d_dinvA, c->n, c->stream);
   HIPCHK(c, hipGetLastError());
   if (L.body_force_enabled)
     {
@@ -299,13 +329,21 @@ static int linear_setup_member(mi_ctx *c, double theta)
   return MI_OK;
 }
 
-// which operator the next products of a slab apply: 0 K, 1 M, 2 the stepping matrix; -1 none (back to the tangent)
-static void linear_select(mi_ctx *m, int which)
+// the model's multigrid ("linear_precond" 1, one slab): the inverse node blocks of level 0 where a matrix is assembled (the
+// matrix-free set-up has formed them), then the hierarchy
+static int linear_setup_multigrid(mi_ctx *c, double theta)
 {
-  LinearModel &L      = *m->linear;
-  m->active_sell_vals = (which < 0 || L.mf) ? nullptr : which == 0 ? L.d_K : which == 1 ? L.d_M : L.d_A;
-  m->active_linear_mf = (which < 0 || !L.mf) ? nullptr : &L.op[which];
-  m->active_dinv      = which == 2 ? L.d_dinvA : nullptr;
+  LinearModel &L = *c->linear;
+  if (!L.mf)
+    {
+      const size_t nn = size_t(c->mesh.nnodes), DD = size_t(c->dim) * c->dim;
+      HIPCHK(c, hipMalloc((void **)&L.d_dinv_blk, nn * DD * sizeof(double)));
+      if (c->dim == 3)
+        HIPCHK(c, hipMalloc((void **)&L.d_dinv_sym6, nn * 6 * sizeof(double)));
+      mi::launch_extract_dinv_blk(c->dim, L.d_A, c->d_diagpos, L.d_dinv_blk, L.d_dinv_sym6, c->mesh.nnodes, c->stream);
+      HIPCHK(c, hipGetLastError());
+    }
+  return mg_setup_linear(c, theta, L.d_dinv_blk, L.d_dinv_sym6, &L.mg);
 }
 
 int mi_linear_setup(mi_ctx *c, double theta)
@@ -319,6 +357,8 @@ int mi_linear_setup(mi_ctx *c, double theta)
       if (rc)
         return m == c ? rc : fail(c, rc, "%s", m->err.c_str());
     }
+  if (c->linear_precond == 1 && c->team->size == 1)
+    return linear_setup_multigrid(c, theta);
   return MI_OK;
 }
 
@@ -419,7 +459,15 @@ int mi_linear_step(mi_ctx *c, int data_consistent, double abs_tol, int64_t max_i
         *res = 0.0;
     }
   if (!rc && !direct)
-    rc = cg_run(c0, MI_L_VELOCITY, MI_L_SYSTEM_RHS, -abs_tol, max_it, its, res);
+    {
+      // (multigrid: the iterations of the previous step's solve may be enqueued without polling -- the same iterates)
+      LinearModel &Lm = *c0->linear;
+      int          n_its = 0;
+      rc = cg_run(c0, MI_L_VELOCITY, MI_L_SYSTEM_RHS, -abs_tol, max_it, &n_its, res, false, false, Lm.mg ? Lm.last_its : 0);
+      Lm.last_its = rc == MI_OK ? n_its : 0;
+      if (its)
+        *its = n_its;
+    }
   for (mi_ctx *m : T.members)
     linear_select(m, -1);
   if (rc)
@@ -466,18 +514,33 @@ int mi_linear_matrix_get_csr(mi_ctx *c, int which, int64_t *rowptr, int32_t *col
 // arrays or mf_linear_q3 + mf_gather.  The product is timed as MI_T_SPMV (device stamps) when profiling is on.
 int mi_linear_apply(mi_ctx *c, int which, const double *x_host, double *y_host)
 {
-  if (!c->linear || which < 0 || which > 2 || !x_host || !y_host)
+  if (!c->linear || which < 0 || which > 3 || !x_host || !y_host)
     return fail(c, MI_EINVAL, "linear model not set up, bad operator id or null argument");
   if (team_size(c) != 1)
     return fail(c, MI_EINVAL, "mi_linear_apply is only available on an undecomposed mesh");
+  if (which == 3 && !c->linear->mg)
+    return fail(c, MI_EINVAL, "mi_linear_apply: the linear set-up has no multigrid hierarchy (\"linear_precond\" 1 and mi_linear_setup)");
   HIPCHK(c, hipSetDevice(c->device));
   HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (which == 3) // y = B x: one V-cycle, as the solve applies it to its residual
+    {
+      HIPCHK(c, hipMemcpy(c->work(W_R), x_host, size_t(c->n) * sizeof(double), hipMemcpyHostToDevice));
+      linear_select(c, 2);
+      const int rc = mg_apply(*c->team);
+      linear_select(c, -1);
+      if (rc)
+        return rc;
+      HIPCHK(c, hipStreamSynchronize(c->stream));
+      HIPCHK(c, hipMemcpy(y_host, c->work(W_Z), size_t(c->n) * sizeof(double), hipMemcpyDeviceToHost));
+      return MI_OK;
+    }
   HIPCHK(c, hipMemcpy(c->work(W_P), x_host, size_t(c->n) * sizeof(double), hipMemcpyHostToDevice));
+  const bool level = c->active_sell_vals && c->active_sell_vals == c->linear->d_A; // a borrowed multigrid level keeps its selection
   linear_select(c, which);
   const int t = tic(c, MI_T_SPMV);
   enqueue_spmv(c, c->work(W_P), c->work(W_Q), nullptr, nullptr, nullptr);
   toc(c, t);
-  linear_select(c, -1);
+  linear_select(c, level ? 2 : -1);
   HIPCHK(c, hipGetLastError());
   HIPCHK(c, hipStreamSynchronize(c->stream));
   HIPCHK(c, hipMemcpy(y_host, c->work(W_Q), size_t(c->n) * sizeof(double), hipMemcpyDeviceToHost));
@@ -517,4 +580,90 @@ int mi_linear_get_diagonal(mi_ctx *c, double *diag_host)
   return MI_OK;
 }
 
+// the node blocks of the stepping matrix in use, [nnodes][dim][dim]: what the block-Jacobi smoother of "linear_precond" 1 inverts
+// -- out of the assembled array, or as mf_linear_diag_q3 + the gather formed them (diagonal entries alone with the key at 0)
+int mi_linear_get_diagonal_blocks(mi_ctx *c, double *blocks)
+{
+  if (!c->linear || !blocks)
+    return fail(c, MI_EINVAL, "linear model not set up or null argument");
+  if (team_size(c) != 1)
+    return fail(c, MI_EINVAL, "mi_linear_get_diagonal_blocks is only available on an undecomposed mesh");
+  const LinearModel &L   = *c->linear;
+  const size_t       cnt = size_t(c->mesh.nnodes) * c->dim * c->dim;
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (L.mf)
+    {
+      HIPCHK(c, hipMemcpy(blocks, L.d_diag, cnt * sizeof(double), hipMemcpyDeviceToHost));
+      return MI_OK;
+    }
+  double *tmp = nullptr;
+  HIPCHK(c, hipMalloc((void **)&tmp, cnt * sizeof(double)));
+  mi::launch_gather_diag_blocks(c->dim, L.d_A, c->d_diagpos, tmp, c->mesh.nnodes, c->stream);
+  const hipError_t e1 = hipStreamSynchronize(c->stream);
+  const hipError_t e2 = hipMemcpy(blocks, tmp, cnt * sizeof(double), hipMemcpyDeviceToHost);
+  hipFree(tmp);
+  HIPCHK(c, e1);
+  HIPCHK(c, e2);
+  return MI_OK;
+}
+
+// ---- read-only view of the model's hierarchy (the contracts of mi_mg_n_levels, mi_mg_level_describe, mi_mg_level_context)
+int mi_linear_mg_n_levels(const mi_ctx *c)
+{
+  return c->linear ? mg_n_levels(c->linear->mg) : 0;
+}
+
+int mi_linear_mg_level_describe(mi_ctx *c, int level, mi_mg_level_desc *out)
+{
+  if (!out)
+    return fail(c, MI_EINVAL, "mi_linear_mg_level_describe: null argument");
+  const int nl = mi_linear_mg_n_levels(c);
+  if (level < 0 || level >= nl)
+    return fail(c, MI_EINVAL, "mi_linear_mg_level_describe: level %d of %d (\"linear_precond\" 1 and mi_linear_setup)", level, nl);
+  return mg_describe(c, *c->linear->mg, level, out);
+}
+
+int mi_linear_mg_level_context(mi_ctx *c, int level, mi_ctx **borrowed)
+{
+  if (!borrowed)
+    return fail(c, MI_EINVAL, "mi_linear_mg_level_context: null argument");
+  *borrowed    = nullptr;
+  const int nl = mi_linear_mg_n_levels(c);
+  if (level < 0 || level >= nl)
+    return fail(c, MI_EINVAL, "mi_linear_mg_level_context: level %d of %d (\"linear_precond\" 1 and mi_linear_setup)", level, nl);
+  *borrowed = mg_level_ctx(*c->linear->mg, level);
+  return MI_OK;
+}
+
 } // extern "C"
+
+// which operator the next products of a slab apply: 0 K, 1 M, 2 the stepping matrix; -1 none (back to the tangent).  With the
+// stepping matrix its hierarchy becomes the active one, where the model has one
+void mi_detail::linear_select(mi_ctx *m, int which)
+{
+  LinearModel &L      = *m->linear;
+  m->active_sell_vals = (which < 0 || L.mf) ? nullptr : which == 0 ? L.d_K : which == 1 ? L.d_M : L.d_A;
+  m->active_linear_mf = (which < 0 || !L.mf) ? nullptr : &L.op[which];
+  m->active_dinv      = which == 2 ? L.d_dinvA : nullptr;
+  m->mg_linear        = which == 2 ? L.mg : nullptr;
+}
+
+// a level >= 1 of the model's hierarchy: the assembled linear model of the level's own mesh, the stepping matrix selected for
+// good, its inverse node blocks where the level context keeps those of its tangent (it never assembles one)
+int mi_detail::linear_setup_level(mi_ctx *lc, double theta)
+{
+  lc->linear_operator = 0;
+  if (const int rc = linear_setup_member(lc, theta))
+    return rc;
+  linear_select(lc, 2);
+  const size_t nn = size_t(lc->mesh.nnodes), DD = size_t(lc->dim) * lc->dim;
+  if (!lc->d_dinv_blk)
+    HIPCHK(lc, hipMalloc((void **)&lc->d_dinv_blk, nn * DD * sizeof(double)));
+  if (!lc->d_dinv_sym6 && lc->dim == 3)
+    HIPCHK(lc, hipMalloc((void **)&lc->d_dinv_sym6, nn * 6 * sizeof(double)));
+  mi::launch_extract_dinv_blk(lc->dim, lc->linear->d_A, lc->d_diagpos, lc->d_dinv_blk, lc->d_dinv_sym6, lc->mesh.nnodes, lc->stream);
+  HIPCHK(lc, hipGetLastError());
+  return MI_OK;
+}
+

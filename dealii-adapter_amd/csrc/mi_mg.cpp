@@ -47,6 +47,11 @@ namespace mi_detail
     // and its first x buffer IS W_Z, so a V-cycle neither copies its input nor (unless an odd number of fused steps
     // left the result in the second buffer) its output
     double *b_ext = nullptr, *x_ext = nullptr;
+    // the block-Jacobi D^-1 of the level: the level context's own (the tangent's), or -- level 0 of the linear model's hierarchy --
+    // the model's arrays for its stepping matrix (borrowed)
+    const double *dinv_blk_ext = nullptr, *dinv_sym6_ext = nullptr;
+    const double *dinv_blk() const { return dinv_blk_ext ? dinv_blk_ext : ctx->d_dinv_blk; }
+    const double *dinv_sym6() const { return dinv_blk_ext ? dinv_sym6_ext : ctx->d_dinv_sym6; }
     double *x_first() const { return x_ext ? x_ext : ws + ctx->n; }
     double *b() const { return b_ext ? b_ext : ws; }
     double *x() const { return x_swapped ? ws + 6 * ctx->n : x_first(); }
@@ -96,9 +101,16 @@ namespace mi_detail
                                   // view (mi_mg_level_describe) answers only then
   };
 
+  // the hierarchy a V-cycle, a smoother or an eigenvalue estimate runs on: the tangent's, or the linear model's while its
+  // stepping matrix is selected (mi_ctx::mg_linear)
+  static inline Multigrid &hier(const mi_ctx *m)
+  {
+    return m->mg_linear ? *m->mg_linear : *m->mg;
+  }
+
   static inline bool is_dist(const Team &T, size_t l)
   {
-    return T.size > 1 && l < T.members[0]->mg->n_dist;
+    return T.size > 1 && l < hier(T.members[0]).n_dist;
   }
 
   int mg_distributed_levels(const mi_ctx *c)
@@ -108,6 +120,8 @@ namespace mi_detail
 
   bool mg_active(const mi_ctx *c)
   {
+    if (c->mg_linear) // the linear model's solve on its own hierarchy: "precond" and `mg` are not involved
+      return c->mg_linear->levels.size() > 1;
     return c->precond == 1 && c->mg && c->mg->levels.size() > 1 && !c->active_sell_vals && !c->active_linear_mf;
   }
 
@@ -319,13 +333,13 @@ namespace mi_detail
       int       rc = MI_OK;
       if (is_dist(T, l))
         rc = team_spmv(
-          T, [l](mi_ctx *m) { return m->mg->levels[l].ctx; }, x_of, [l](mi_ctx *m) { return m->mg->levels[l].q(); },
+          T, [l](mi_ctx *m) { return hier(m).levels[l].ctx; }, x_of, [l](mi_ctx *m) { return hier(m).levels[l].q(); },
           nullptr, true, cheb, ghosts_current);
       else
         for (size_t k = 0; k < T.members.size(); ++k)
           {
             mi_ctx  *m = T.members[k];
-            MgLevel &L = m->mg->levels[l];
+            MgLevel &L = hier(m).levels[l];
             enqueue_spmv(L.ctx, x_of(m), L.q(), nullptr, nullptr, nullptr, 0, true, cheb ? &cheb[k] : nullptr);
           }
       toc(T.members[0], t);
@@ -370,18 +384,18 @@ namespace mi_detail
     int krylov_lmax(Team &T, size_t l, int steps, double *ritz_max)
     {
       mi_ctx    *c0   = T.members[0];
-      Multigrid &mg0  = *c0->mg;
+      Multigrid &mg0  = hier(c0);
       const bool dist = is_dist(T, l);
       int        rc;
-      auto vec_r = [l](mi_ctx *m) { return m->mg->levels[l].r(); };
-      auto vec_p = [l](mi_ctx *m) { MgLevel &L = m->mg->levels[l]; return L.ws + 6 * L.ctx->n; };
+      auto vec_r = [l](mi_ctx *m) { return hier(m).levels[l].r(); };
+      auto vec_p = [l](mi_ctx *m) { MgLevel &L = hier(m).levels[l]; return L.ws + 6 * L.ctx->n; };
       auto precondition = [&]() { // z (in d) = D^-1 r
         for (mi_ctx *m : T.members)
           {
-            MgLevel &L = m->mg->levels[l];
+            MgLevel &L = hier(m).levels[l];
             mi_ctx  *c = L.ctx;
             if (mg0.block)
-              mi::launch_blk_apply(c->dim, L.d(), L.r(), c->d_dinv_blk, c->mesh.nnodes, c->stream);
+              mi::launch_blk_apply(c->dim, L.d(), L.r(), L.dinv_blk(), c->mesh.nnodes, c->stream);
             else
               mi::launch_vec_scale_mul(L.d(), L.r(), c->work(W_DINV), 1.0, c->n, c->stream);
           }
@@ -389,7 +403,7 @@ namespace mi_detail
       auto dot = [&](const std::function<double *(mi_ctx *)> &a, const std::function<double *(mi_ctx *)> &b, double *out) -> int {
         for (mi_ctx *m : T.members)
           {
-            mi_ctx *c = m->mg->levels[l].ctx;
+            mi_ctx *c = hier(m).levels[l].ctx;
             mi::launch_dot_partials(a(m) + c->own0, b(m) + c->own0, c->own_n, m->part(5), m->grid_vec, c->stream);
             mi::launch_finish_sum(m->part(5), m->grid_vec, m->d_sc + 14, c->stream);
           }
@@ -401,17 +415,17 @@ namespace mi_detail
         *out = c0->h_pinned[0];
         return MI_OK;
       };
-      auto vec_z = [l](mi_ctx *m) { return m->mg->levels[l].d(); };
-      auto vec_q = [l](mi_ctx *m) { return m->mg->levels[l].q(); };
+      auto vec_z = [l](mi_ctx *m) { return hier(m).levels[l].d(); };
+      auto vec_q = [l](mi_ctx *m) { return hier(m).levels[l].q(); };
       for (mi_ctx *m : T.members) // r = the start vector, p = z = D^-1 r
         {
-          MgLevel &L = m->mg->levels[l];
+          MgLevel &L = hier(m).levels[l];
           HIPCHK(m, hipMemcpyAsync(L.r(), L.ev(), size_t(L.ctx->n) * sizeof(double), hipMemcpyDeviceToDevice, L.ctx->stream));
         }
       precondition();
       for (mi_ctx *m : T.members)
         {
-          MgLevel &L = m->mg->levels[l];
+          MgLevel &L = hier(m).levels[l];
           HIPCHK(m, hipMemcpyAsync(vec_p(m), L.d(), size_t(L.ctx->n) * sizeof(double), hipMemcpyDeviceToDevice, L.ctx->stream));
         }
       double rz = 0.0;
@@ -432,7 +446,7 @@ namespace mi_detail
           const double alpha = rz / pq;
           for (mi_ctx *m : T.members)
             {
-              MgLevel &L = m->mg->levels[l];
+              MgLevel &L = hier(m).levels[l];
               mi::launch_vec_lincomb2(L.r(), 1.0, L.r(), -alpha, L.q(), L.ctx->n, L.ctx->stream); // r -= alpha q
             }
           precondition();
@@ -447,7 +461,7 @@ namespace mi_detail
             break;
           for (mi_ctx *m : T.members)
             {
-              MgLevel &L = m->mg->levels[l];
+              MgLevel &L = hier(m).levels[l];
               mi::launch_vec_lincomb2(vec_p(m), 1.0, L.d(), beta, vec_p(m), L.ctx->n, L.ctx->stream); // p = z + beta p
             }
           alpha_prev = alpha, beta_prev = beta, rz = rz_new;
@@ -465,12 +479,12 @@ namespace mi_detail
     int estimate_lmax(Team &T, size_t l)
     {
       mi_ctx    *c0  = T.members[0];
-      Multigrid &mg0 = *c0->mg;
+      Multigrid &mg0 = hier(c0);
       const bool dist = is_dist(T, l);
       int        its  = mg0.power_its_update;
       for (mi_ctx *m : T.members)
         {
-          MgLevel      &L = m->mg->levels[l];
+          MgLevel      &L = hier(m).levels[l];
           mi_ctx       *c = L.ctx;
           const int64_t n = c->n;
           if (!L.ev_ready)
@@ -490,7 +504,7 @@ namespace mi_detail
         }
       double lam = 0.0;
       int    rc;
-      auto   ev_of = [l](mi_ctx *m) { return m->mg->levels[l].ev(); };
+      auto   ev_of = [l](mi_ctx *m) { return hier(m).levels[l].ev(); };
       // The estimate |D^-1 A v|_D of a v with |v|_D = 1 grows monotonically towards lambda_max and never passes it: D^-1 A is
       // self-adjoint in the inner product of D, not in the Euclidean one, where |D^-1 A v|_2 is bounded by the 2-norm of
       // D^-1 A only -- up to 6 % above lambda_max where the blocks of D differ from node to node, and an estimate that had
@@ -524,10 +538,10 @@ namespace mi_detail
             return rc;
           for (mi_ctx *m : T.members)
             {
-              MgLevel &L = m->mg->levels[l];
+              MgLevel &L = hier(m).levels[l];
               mi_ctx  *c = L.ctx;
               if (mg0.block)
-                mi::launch_blk_apply(c->dim, L.d(), L.q(), c->d_dinv_blk, c->mesh.nnodes, c->stream);
+                mi::launch_blk_apply(c->dim, L.d(), L.q(), L.dinv_blk(), c->mesh.nnodes, c->stream);
               else
                 mi::launch_vec_scale_mul(L.d(), L.q(), c->work(W_DINV), 1.0, c->n, c->stream); // w = D^-1 A v
               // |w|_D^2 = w . q over the owned dofs of the level -> scalar slot 14 of the slab
@@ -560,7 +574,7 @@ namespace mi_detail
           prev = nw;
           for (mi_ctx *m : T.members)
             {
-              MgLevel &L = m->mg->levels[l];
+              MgLevel &L = hier(m).levels[l];
               mi::launch_vec_scale_mul(L.ev(), L.d(), nullptr, 1.0 / nw, L.ctx->n, L.ctx->stream);
             }
         }
@@ -569,11 +583,11 @@ namespace mi_detail
       // from the previous eigenvector each).  It is never given back: a power estimate that grows between two refreshes may
       // have left its plateau or may follow a tangent that stiffens -- the two cannot be told apart, and an interval a
       // little too long costs an iteration where one too short costs the positive definiteness of the cycle
-      MgLevel     &Lc    = c0->mg->levels[l];
+      MgLevel     &Lc    = hier(c0).levels[l];
       const double boost = first ? std::max(1.0, lam > 0.0 ? ritz / lam : 1.0) : std::max(1.0, Lc.lam_boost);
       for (mi_ctx *m : T.members)
         {
-          MgLevel &L  = m->mg->levels[l];
+          MgLevel &L  = hier(m).levels[l];
           L.lam_power = lam;
           L.lam_boost = boost;
           L.lmax      = lam * boost * mg0.lmax_safety;
@@ -634,13 +648,13 @@ namespace mi_detail
     return MI_OK;
   }
 
-  void mg_destroy(mi_ctx *c)
+  void mg_free(Multigrid *mg)
   {
-    if (!c->mg)
+    if (!mg)
       return;
-    for (size_t l = 0; l < c->mg->levels.size(); ++l)
+    for (size_t l = 0; l < mg->levels.size(); ++l)
       {
-        MgLevel &L = c->mg->levels[l];
+        MgLevel &L = mg->levels[l];
         for (void *p : L.to_coarse.dev)
           hipFree(p);
         if (L.ws)
@@ -650,15 +664,18 @@ namespace mi_detail
         if (l > 0 && L.team)
           destroy_team(L.team); // destroys the level context; the stream is shared and stays
       }
-    delete c->mg;
+    delete mg;
+  }
+
+  void mg_destroy(mi_ctx *c)
+  {
+    mg_free(c->mg);
     c->mg = nullptr;
   }
 
-  int mg_setup(mi_ctx *c)
+  // the parameters of a hierarchy of context c: the defaults of Multigrid, the experiment hooks, the context's tuning keys
+  static void mg_configure(const mi_ctx *c, Multigrid *mg)
   {
-    mg_destroy(c);
-    Multigrid *mg = new Multigrid;
-    c->mg         = mg;
     if (const char *e = mi::exp_env("MI_MG_NU"))
       mg->nu = std::max(1, atoi(e));
     if (const char *e = mi::exp_env("MI_MG_NU_COARSE"))
@@ -699,6 +716,12 @@ namespace mi_detail
       mg->coarsest_reps = int(c->mg_coarsest);
     if (c->mg_dense >= 0)
       mg->dense = int(c->mg_dense);
+  }
+
+  // the shape of a hierarchy over context c (its level 0): level contexts, workspaces, transfers, the coarsest level's dense
+  // inverse (storage).  No operator yet.  On failure the levels built so far stay in *mg for the caller to free
+  static int mg_build_levels(mi_ctx *c, Multigrid *mg)
+  {
     MgLevel L0;
     L0.ctx = c;
     mg->levels.push_back(L0);
@@ -831,11 +854,99 @@ namespace mi_detail
         MgLevel &L = mg->levels.back();
         HIPCHK(c, hipMalloc((void **)&L.dense_inv, size_t(L.ctx->n) * size_t(L.ctx->n) * sizeof(double)));
       }
+    return MI_OK;
+  }
+
+  int mg_setup(mi_ctx *c)
+  {
+    mg_destroy(c);
+    Multigrid *mg = new Multigrid;
+    c->mg         = mg;
+    mg_configure(c, mg);
+    if (const int rc = mg_build_levels(c, mg))
+      return rc;
     if (mg->block)
       for (MgLevel &L : mg->levels)
         L.ctx->want_dinv_blk = true; // filled by the next assembly of the level
     c->mg_stale = true;
     return MI_OK;
+  }
+
+  // what the levels of the active hierarchy solve or smooth with, from the operators they hold now: the coarsest level's dense
+  // inverse, the eigenvalue estimates of the others
+  static int mg_level_solvers(Team &T)
+  {
+    mi_ctx      *c0 = T.members[0];
+    const size_t nl = hier(c0).levels.size();
+    for (size_t l = 0; l < nl; ++l)
+      {
+        if (l + 1 == nl && hier(c0).levels[l].dense_inv) // exact coarse solve: invert the level matrix instead
+          {
+            for (mi_ctx *m : T.members)
+              {
+                MgLevel &L = hier(m).levels[l];
+                mi::SellParams sp = sell_params(L.ctx, nullptr, nullptr, nullptr, nullptr, nullptr);
+                if (mi::launch_dense_inverse_from_sell(L.ctx->dim, sp, int(L.ctx->n), L.dense_inv, L.ctx->stream))
+                  return fail(c0, MI_EINVAL, "multigrid: coarsest level too large for the dense solve");
+              }
+            continue;
+          }
+        if (const int rc = estimate_lmax(T, l))
+          return rc;
+      }
+    return MI_OK;
+  }
+
+  // The linear model's hierarchy.  The stepping matrix A = M + theta^2 dt^2 K is constant, so everything is built here, once:
+  // the levels' operators (every level >= 1 assembles the linear model of its own, unperturbed mesh), their block-Jacobi D, the
+  // dense inverse and the first eigenvalue estimates.  Nothing refreshes it; "mg_lag", "mg_refresh_every" and the refresh
+  // counter belong to the tangent's hierarchy.
+  int mg_setup_linear(mi_ctx *c, double theta, const double *dinv_blk, const double *dinv_sym6, Multigrid **out)
+  {
+    *out          = nullptr;
+    Multigrid *mg = new Multigrid;
+    mg_configure(c, mg);
+    int rc = mg_build_levels(c, mg);
+    if (!rc && mg->levels.size() < 2) // a mesh that is its own coarsest level: nothing to cycle over, the solve stays Jacobi
+      {
+        mg_free(mg);
+        return MI_OK;
+      }
+    mg->levels[0].dinv_blk_ext  = dinv_blk;
+    mg->levels[0].dinv_sym6_ext = dinv_sym6;
+    for (size_t l = 1; l < mg->levels.size() && !rc; ++l)
+      {
+        mi_ctx *lc = mg->levels[l].ctx;
+        if ((rc = linear_setup_level(lc, theta)))
+          fail(c, rc, "linear multigrid level %d: %s", int(l), lc->err.c_str());
+      }
+    if (!rc)
+      {
+        linear_select(c, 2); // level 0's products are the model's stepping matrix ...
+        c->mg_linear = mg;   // ... and the estimates run on this hierarchy (the model does not own it yet)
+        rc           = mg_level_solvers(*c->team);
+        linear_select(c, -1);
+        if (!rc && hipStreamSynchronize(c->stream) != hipSuccess)
+          rc = fail(c, MI_EHIP, "linear multigrid set-up failed on the device");
+      }
+    if (rc)
+      {
+        mg_free(mg);
+        return rc;
+      }
+    mg->built = true;
+    *out      = mg;
+    return MI_OK;
+  }
+
+  int mg_n_levels(const Multigrid *mg)
+  {
+    return mg ? int(mg->levels.size()) : 0;
+  }
+
+  mi_ctx *mg_level_ctx(const Multigrid &mg, int level)
+  {
+    return level >= 0 && size_t(level) < mg.levels.size() ? mg.levels[size_t(level)].ctx : nullptr;
   }
 
   // coarse operators for the current state: u_total interpolated down the hierarchy (level 1 summed over the
@@ -858,7 +969,7 @@ namespace mi_detail
     for (mi_ctx *m : T.members)
       {
         // u_total = u + du of the slab (all local nodes: the ghost copies are kept consistent)
-        MgLevel &L0 = m->mg->levels[0];
+        MgLevel &L0 = hier(m).levels[0];
         HIPCHK(m, hipMemcpyAsync(L0.x(), m->vec(MI_V_TOTAL_DISPLACEMENT), size_t(m->n) * sizeof(double),
                                  hipMemcpyDeviceToDevice, m->stream));
         mi::launch_vec_add(L0.x(), m->vec(MI_V_SOLUTION_DELTA), m->n, m->stream);
@@ -877,42 +988,28 @@ namespace mi_detail
           }
         if (is_dist(T, l - 1) && !is_dist(T, l) &&
             (rc = team_allreduce_vectors(
-               T, [l](mi_ctx *m) { return m->mg->levels[l].ctx->vec(MI_V_TOTAL_DISPLACEMENT); },
+               T, [l](mi_ctx *m) { return hier(m).levels[l].ctx->vec(MI_V_TOTAL_DISPLACEMENT); },
                size_t(c0->mg->levels[l].ctx->n))))
           return rc;
         if (is_dist(T, l) && l >= c0->mg->n_aligned)
           {
             // induced cuts: a node was served by the slab that owns its left source plane -- possibly on one of that slab's
             // ghost planes; to the owner, then to every ghost copy
-            auto u_of   = [l](mi_ctx *m) { return m->mg->levels[l].ctx->vec(MI_V_TOTAL_DISPLACEMENT); };
-            auto ctx_of = [l](mi_ctx *m) { return m->mg->levels[l].ctx; };
+            auto u_of   = [l](mi_ctx *m) { return hier(m).levels[l].ctx->vec(MI_V_TOTAL_DISPLACEMENT); };
+            auto ctx_of = [l](mi_ctx *m) { return hier(m).levels[l].ctx; };
             if ((rc = team_halo_accumulate(T, u_of, ctx_of)) || (rc = team_halo(T, u_of, ctx_of)))
               return rc;
           }
         for (mi_ctx *m : T.members)
           {
-            MgLevel &C = m->mg->levels[l];
+            MgLevel &C = hier(m).levels[l];
             if ((rc = enqueue_assembly(C.ctx)))
               return fail(c0, rc, "multigrid level %d: %s", int(l), C.ctx->err.c_str());
           }
       }
     HIPCHK(c0, hipGetLastError());
-    for (size_t l = 0; l < nl; ++l)
-      {
-        if (l + 1 == nl && c0->mg->levels[l].dense_inv) // exact coarse solve: invert the level matrix instead
-          {
-            for (mi_ctx *m : T.members)
-              {
-                MgLevel &L = m->mg->levels[l];
-                mi::SellParams sp = sell_params(L.ctx, nullptr, nullptr, nullptr, nullptr, nullptr);
-                if (mi::launch_dense_inverse_from_sell(L.ctx->dim, sp, int(L.ctx->n), L.dense_inv, L.ctx->stream))
-                  return fail(c0, MI_EINVAL, "multigrid: coarsest level too large for the dense solve");
-              }
-            continue;
-          }
-        if ((rc = estimate_lmax(T, l)))
-          return rc;
-      }
+    if ((rc = mg_level_solvers(T)))
+      return rc;
     for (mi_ctx *m : T.members)
       {
         m->mg_stale  = false;
@@ -931,14 +1028,14 @@ namespace mi_detail
     // whether level l runs its smoother steps and residual as fused products (see Multigrid::fuse)
     bool fuse_level(Team &T, size_t l)
     {
-      const Multigrid &mg0 = *T.members[0]->mg;
+      const Multigrid &mg0 = hier(T.members[0]);
       if (mg0.fuse == 0)
         return false;
       for (mi_ctx *m : T.members)
         {
-          const mi_ctx *lc = m->mg->levels[l].ctx;
-          if (lc->mf_fine) // no assembled rows to fuse an epilogue into (the matrix-free gather takes the step instead)
-            return false;
+          const mi_ctx *lc = hier(m).levels[l].ctx;
+          if ((lc->mf_fine && !lc->active_sell_vals) || lc->active_linear_mf) // no assembled rows to fuse an epilogue into (the
+            return false;                                                     // matrix-free gather takes the step instead)
           if (lc->spmv_variant != 3 || (mg0.fuse == 1 && lc->mesh.nnodes > mg0.fuse_max_nodes))
             return false;
         }
@@ -951,10 +1048,10 @@ namespace mi_detail
     // first_done: the first step of a zero start (x = d = c2 D^-1 b) was taken by the restriction that produced b
     int chebyshev(Team &T, size_t l, int k, double ratio, bool zero_start, bool ghosts_current = false, bool first_done = false)
     {
-      const double b = T.members[0]->mg->levels[l].lmax, a = b / ratio;
+      const double b = hier(T.members[0]).levels[l].lmax, a = b / ratio;
       const double theta = 0.5 * (b + a), delta = 0.5 * (b - a), sigma = theta / delta;
       double       rho_old = 1.0 / sigma;
-      auto         x_of    = [l](mi_ctx *m) { return m->mg->levels[l].x(); };
+      auto         x_of    = [l](mi_ctx *m) { return hier(m).levels[l].x(); };
       int          rc;
       for (int j = 0; j < k; ++j)
         {
@@ -976,9 +1073,9 @@ namespace mi_detail
             }
           // level 0 with the single-launch matrix-free product and the symmetric halves of D^-1: the gather of the product
           // applies this step itself, in three-term form
-          bool mf_fused = !skip_spmv && l == 0 && T.members[0]->mg->block;
+          bool mf_fused = !skip_spmv && l == 0 && hier(T.members[0]).block;
           for (mi_ctx *m : T.members)
-            mf_fused = mf_fused && mf_gather_fusable(m) && m->mg->levels[l].ctx->d_dinv_sym6;
+            mf_fused = mf_fused && mf_gather_fusable(m) && hier(m).levels[l].dinv_sym6();
           if (mf_fused)
             {
               // x'' over the buffer of the iterate before (zero after the first step of a zero start), then the two x buffers
@@ -986,9 +1083,9 @@ namespace mi_detail
               std::vector<ChebFusion> cf;
               for (mi_ctx *m : T.members)
                 {
-                  MgLevel   &L = m->mg->levels[l];
+                  MgLevel   &L = hier(m).levels[l];
                   ChebFusion f{L.b(), nullptr, nullptr, nullptr, c1, c2, 1, 1};
-                  f.dinv6 = L.ctx->d_dinv_sym6;
+                  f.dinv6 = L.dinv_sym6();
                   f.xprev = (j == 1 && zero_start) ? nullptr : L.x_other();
                   f.xnext = L.x_other();
                   cf.push_back(f);
@@ -996,7 +1093,7 @@ namespace mi_detail
               if ((rc = level_spmv(T, l, x_of, cf.data(), first && ghosts_current)))
                 return rc;
               for (mi_ctx *m : T.members)
-                m->mg->levels[l].x_swapped = !m->mg->levels[l].x_swapped;
+                hier(m).levels[l].x_swapped = !hier(m).levels[l].x_swapped;
               continue;
             }
           bool fused = !skip_spmv && fuse_level(T, l);
@@ -1006,26 +1103,26 @@ namespace mi_detail
               std::vector<ChebFusion> cf;
               for (mi_ctx *m : T.members)
                 {
-                  MgLevel &L = m->mg->levels[l];
-                  if (m->mg->block)
-                    cf.push_back(ChebFusion{L.b(), L.ctx->d_dinv_blk, L.d(), L.x_other(), c1, c2, 1});
+                  MgLevel &L = hier(m).levels[l];
+                  if (hier(m).block)
+                    cf.push_back(ChebFusion{L.b(), L.dinv_blk(), L.d(), L.x_other(), c1, c2, 1});
                   else
                     cf.push_back(ChebFusion{L.b(), L.ctx->work(W_DINV), L.d(), L.x_other(), c1, c2, 0});
                 }
               if ((rc = level_spmv(T, l, x_of, cf.data(), first && ghosts_current)))
                 return rc;
               for (mi_ctx *m : T.members)
-                m->mg->levels[l].x_swapped = !m->mg->levels[l].x_swapped;
+                hier(m).levels[l].x_swapped = !hier(m).levels[l].x_swapped;
               continue;
             }
           if (!skip_spmv && (rc = level_spmv(T, l, x_of, nullptr, first && ghosts_current)))
             return rc;
           for (mi_ctx *m : T.members)
             {
-              MgLevel      &L  = m->mg->levels[l];
+              MgLevel      &L  = hier(m).levels[l];
               const int64_t o0 = L.ctx->own0, on = L.ctx->own_n;
-              if (m->mg->block)
-                mi::launch_cheb_step_blk(L.ctx->dim, L.x(), L.d(), L.b(), skip_spmv ? nullptr : L.q(), L.ctx->d_dinv_blk,
+              if (hier(m).block)
+                mi::launch_cheb_step_blk(L.ctx->dim, L.x(), L.d(), L.b(), skip_spmv ? nullptr : L.q(), L.dinv_blk(),
                                          c1, c2, o0 / L.ctx->dim, on / L.ctx->dim, L.ctx->stream);
               else
                 mi::launch_cheb_step(L.x() + o0, L.d() + o0, L.b() + o0, skip_spmv ? nullptr : L.q() + o0,
@@ -1055,16 +1152,16 @@ namespace mi_detail
     int chebyshev4(Team &T, size_t l, int k, bool zero_start)
     {
       k = std::min(k, 6);
-      const double  rho  = T.members[0]->mg->levels[l].lmax;
+      const double  rho  = hier(T.members[0]).levels[l].lmax;
       const double *beta = cheb4_betas(k);
-      auto          x_of = [l](mi_ctx *m) { return m->mg->levels[l].x(); };
-      auto          d_of = [l](mi_ctx *m) { return m->mg->levels[l].d(); };
+      auto          x_of = [l](mi_ctx *m) { return hier(m).levels[l].x(); };
+      auto          d_of = [l](mi_ctx *m) { return hier(m).levels[l].d(); };
       int           rc;
       if (!zero_start && (rc = level_spmv(T, l, x_of)))
         return rc;
       for (mi_ctx *m : T.members)
         {
-          MgLevel      &L  = m->mg->levels[l];
+          MgLevel      &L  = hier(m).levels[l];
           const int64_t o0 = L.ctx->own0, on = L.ctx->own_n;
           mi::launch_cheb4_start(L.x() + o0, L.d() + o0, L.r() + o0, L.b() + o0, zero_start ? nullptr : L.q() + o0,
                                  L.ctx->work(W_DINV) + o0, 4.0 / (3.0 * rho), on, L.ctx->stream);
@@ -1077,7 +1174,7 @@ namespace mi_detail
           const double ca = (2.0 * i - 1.0) / (2.0 * i + 3.0), cb = (8.0 * i + 4.0) / ((2.0 * i + 3.0) * rho);
           for (mi_ctx *m : T.members)
             {
-              MgLevel      &L  = m->mg->levels[l];
+              MgLevel      &L  = hier(m).levels[l];
               const int64_t o0 = L.ctx->own0, on = L.ctx->own_n;
               mi::launch_cheb4_step(L.x() + o0, L.d() + o0, L.r() + o0, last ? nullptr : L.q() + o0,
                                     L.ctx->work(W_DINV) + o0, beta[i - 1], ca, cb, on, L.ctx->stream);
@@ -1088,7 +1185,7 @@ namespace mi_detail
 
     int smooth(Team &T, size_t l, int k, bool zero_start, bool ghosts_current = false, bool first_done = false)
     {
-      Multigrid &mg0 = *T.members[0]->mg;
+      Multigrid &mg0 = hier(T.members[0]);
       return mg0.kind == 4 ? chebyshev4(T, l, k, zero_start) :
                              chebyshev(T, l, k, mg0.smooth_ratio, zero_start, ghosts_current, first_done);
     }
@@ -1097,7 +1194,7 @@ namespace mi_detail
     int vcycle(Team &T, size_t l, bool first_done = false)
     {
       mi_ctx      *c0  = T.members[0];
-      Multigrid   &mg0 = *c0->mg;
+      Multigrid   &mg0 = hier(c0);
       const size_t nl  = mg0.levels.size();
       int          rc;
       if (l + 1 == nl)
@@ -1106,7 +1203,7 @@ namespace mi_detail
             return chebyshev(T, l, mg0.coarse_degree, mg0.coarse_ratio, true);
           for (mi_ctx *m : T.members)
             {
-              MgLevel &L = m->mg->levels[l];
+              MgLevel &L = hier(m).levels[l];
               mi::launch_dense_apply(L.dense_inv, L.b(), L.x(), int(L.ctx->n), L.ctx->stream);
             }
           return MI_OK;
@@ -1116,11 +1213,11 @@ namespace mi_detail
       const int  nu     = (l == 0) ? mg0.nu : ((l == 1 && mg0.nu_level1 > 0) ? mg0.nu_level1 : mg0.nu_coarse);
       if ((rc = smooth(T, l, nu, true, false, first_done)))
         return rc;
-      auto x_of   = [l](mi_ctx *m) { return m->mg->levels[l].x(); };
-      auto q_of   = [l](mi_ctx *m) { return m->mg->levels[l].q(); };
-      auto ctx_l  = [l](mi_ctx *m) { return m->mg->levels[l].ctx; };
-      auto ctx_c  = [l](mi_ctx *m) { return m->mg->levels[l + 1].ctx; };
-      auto xc_of  = [l](mi_ctx *m) { return m->mg->levels[l + 1].x(); };
+      auto x_of   = [l](mi_ctx *m) { return hier(m).levels[l].x(); };
+      auto q_of   = [l](mi_ctx *m) { return hier(m).levels[l].q(); };
+      auto ctx_l  = [l](mi_ctx *m) { return hier(m).levels[l].ctx; };
+      auto ctx_c  = [l](mi_ctx *m) { return hier(m).levels[l + 1].ctx; };
+      auto xc_of  = [l](mi_ctx *m) { return hier(m).levels[l + 1].x(); };
       bool mf_fused = l == 0;
       for (mi_ctx *m : T.members)
         mf_fused = mf_fused && mf_gather_fusable(m);
@@ -1128,7 +1225,7 @@ namespace mi_detail
         {
           std::vector<ChebFusion> cf; // the gather of the matrix-free product writes q = b - A x on the owned rows
           for (mi_ctx *m : T.members)
-            cf.push_back(ChebFusion{m->mg->levels[l].b(), nullptr, nullptr, nullptr, 0.0, 0.0, 0, 1});
+            cf.push_back(ChebFusion{hier(m).levels[l].b(), nullptr, nullptr, nullptr, 0.0, 0.0, 0, 1});
           if ((rc = level_spmv(T, l, x_of, cf.data())))
             return rc;
         }
@@ -1136,7 +1233,7 @@ namespace mi_detail
         {
           std::vector<ChebFusion> cf; // residual mode of the fused epilogue: q = b - A x on the owned rows
           for (mi_ctx *m : T.members)
-            cf.push_back(ChebFusion{m->mg->levels[l].b(), nullptr, nullptr, nullptr, 0.0, 0.0});
+            cf.push_back(ChebFusion{hier(m).levels[l].b(), nullptr, nullptr, nullptr, 0.0, 0.0});
           if ((rc = level_spmv(T, l, x_of, cf.data())))
             return rc;
         }
@@ -1146,7 +1243,7 @@ namespace mi_detail
             return rc;
           for (mi_ctx *m : T.members)
             {
-              MgLevel &L = m->mg->levels[l];
+              MgLevel &L = hier(m).levels[l];
               mi::launch_vec_residual(L.q() + L.ctx->own0, L.b() + L.ctx->own0, L.q() + L.ctx->own0, L.ctx->own_n,
                                       L.ctx->stream); // q = b - A x (owned)
             }
@@ -1161,18 +1258,18 @@ namespace mi_detail
       bool fuse_first = mg0.restrict_fuse && mg0.kind == 1 && mg0.block && l + 2 < nl && !(dist_l && !dist_c) && !induced_c;
       for (mi_ctx *m : T.members)
         {
-          const MgLevel &C = m->mg->levels[l + 1];
-          fuse_first = fuse_first && C.ctx->dim == 3 && C.ctx->d_dinv_blk && C.lmax > 0.0 &&
-                       L_restrict_lists_fit(m->mg->levels[l].to_coarse.restrict_);
+          const MgLevel &C = hier(m).levels[l + 1];
+          fuse_first = fuse_first && C.ctx->dim == 3 && C.dinv_blk() && C.lmax > 0.0 &&
+                       L_restrict_lists_fit(hier(m).levels[l].to_coarse.restrict_);
         }
       for (mi_ctx *m : T.members)
         {
-          MgLevel &L = m->mg->levels[l], &C = m->mg->levels[l + 1];
+          MgLevel &L = hier(m).levels[l], &C = hier(m).levels[l + 1];
           if (fuse_first)
             {
               const double bb = C.lmax, aa = bb / mg0.smooth_ratio, theta = 0.5 * (bb + aa);
               mi::launch_lattice_restrict_first_step(L.ctx->dim, L.to_coarse.restrict_, C.b(), L.q(), C.ctx->d_cmask, C.x(), C.d(),
-                                                     C.ctx->d_dinv_blk, 1.0 / theta, C.ctx->own0 / C.ctx->dim,
+                                                     C.dinv_blk(), 1.0 / theta, C.ctx->own0 / C.ctx->dim,
                                                      C.ctx->own_n / C.ctx->dim, L.ctx->stream);
             }
           else
@@ -1180,10 +1277,10 @@ namespace mi_detail
         }
       if (dist_l && !dist_c &&
           (rc = team_allreduce_vectors(
-             T, [l](mi_ctx *m) { return m->mg->levels[l + 1].b(); }, size_t(mg0.levels[l + 1].ctx->n))))
+             T, [l](mi_ctx *m) { return hier(m).levels[l + 1].b(); }, size_t(mg0.levels[l + 1].ctx->n))))
         return rc;
       // induced cuts: every slab has restricted its OWNED planes; what landed on a coarse ghost plane belongs to a neighbour
-      if (induced_c && (rc = team_halo_accumulate(T, [l](mi_ctx *m) { return m->mg->levels[l + 1].b(); }, ctx_c)))
+      if (induced_c && (rc = team_halo_accumulate(T, [l](mi_ctx *m) { return hier(m).levels[l + 1].b(); }, ctx_c)))
         return rc;
       if ((rc = vcycle(T, l + 1, fuse_first)))
         return rc;
@@ -1191,7 +1288,7 @@ namespace mi_detail
         return rc;
       for (mi_ctx *m : T.members)
         {
-          MgLevel &L = m->mg->levels[l], &C = m->mg->levels[l + 1];
+          MgLevel &L = hier(m).levels[l], &C = hier(m).levels[l + 1];
           mi::launch_lattice_interp(L.ctx->dim, true, L.to_coarse.prolong, L.x(), C.x(), L.ctx->d_cmask, L.ctx->stream);
         }
       // The first product of the post-smoother needs no halo exchange (round 4): the residual product above exchanged the
@@ -1209,27 +1306,27 @@ namespace mi_detail
   {
     for (mi_ctx *m : T.members)
       {
-        MgLevel &L0 = m->mg->levels[0];
+        MgLevel &L0 = hier(m).levels[0];
         L0.b_ext    = m->work(W_R);
         L0.x_ext    = m->work(W_Z);
       }
     {
       // the three-term smoother steps change the roles of level 0's two x buffers 2 nu - 1 times per cycle: start in the
       // buffer from which the last step lands in W_Z
-      Multigrid &mg0   = *T.members[0]->mg;
+      Multigrid &mg0   = hier(T.members[0]);
       bool       three = mg0.block && mg0.kind == 1;
       for (mi_ctx *m : T.members)
-        three = three && mf_gather_fusable(m) && m->d_dinv_sym6;
+        three = three && mf_gather_fusable(m) && hier(m).levels[0].dinv_sym6();
       if (three)
         for (mi_ctx *m : T.members)
-          m->mg->levels[0].x_swapped = ((2 * mg0.nu - 1) & 1) != 0;
+          hier(m).levels[0].x_swapped = ((2 * mg0.nu - 1) & 1) != 0;
     }
     int rc = vcycle(T, 0);
     if (rc)
       return rc;
     for (mi_ctx *m : T.members)
-      if (m->mg->levels[0].x() != m->work(W_Z))
-        HIPCHK(m, hipMemcpyAsync(m->work(W_Z), m->mg->levels[0].x(), size_t(m->n) * sizeof(double), hipMemcpyDeviceToDevice,
+      if (hier(m).levels[0].x() != m->work(W_Z))
+        HIPCHK(m, hipMemcpyAsync(m->work(W_Z), hier(m).levels[0].x(), size_t(m->n) * sizeof(double), hipMemcpyDeviceToDevice,
                                  m->stream));
     HIPCHK(T.members[0], hipGetLastError());
     return MI_OK;
@@ -1268,9 +1365,14 @@ int mi_mg_level_describe(mi_ctx *c, int level, mi_mg_level_desc *out)
     return fail(c, MI_EINVAL, "mi_mg_level_describe: null argument");
   if (int e = mg_view_check(c, level, "mi_mg_level_describe"))
     return e;
+  return mg_describe(c, *c->team->members[0]->mg, level, out);
+}
+
+// what a level of hierarchy mg of context c is and runs (mi_mg_level_describe, mi_linear_mg_level_describe)
+int mi_detail::mg_describe(mi_ctx *c, const Multigrid &mg, int level, mi_mg_level_desc *out)
+{
   Team            &T  = *c->team;
   const mi_ctx    *c0 = T.members[0];
-  const Multigrid &mg = *c0->mg;
   const size_t     l = size_t(level), nl = mg.levels.size();
   const MgLevel   &L  = mg.levels[l];
   const bool       last = l + 1 == nl && nl > 1;
@@ -1286,7 +1388,7 @@ int mi_mg_level_describe(mi_ctx *c, int level, mi_mg_level_desc *out)
       out->n_dofs *= int64_t(L.ctx->degree) * md.reps[d] + 1;
     }
   out->exact_solve = last && L.dense_inv ? 1 : 0;
-  out->distributed = is_dist(T, l) ? 1 : 0;
+  out->distributed = T.size > 1 && l < mg.n_dist ? 1 : 0;
   if (!out->exact_solve)
     {
       out->lmax            = L.lmax;

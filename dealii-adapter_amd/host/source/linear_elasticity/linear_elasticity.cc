@@ -100,12 +100,21 @@ namespace Linear_Elasticity
     if (const char *f = std::getenv("MI_LINEAR_OPERATOR"))
       if (std::atoi(f) != 0 && mi_set_tuning(device->ctx(), "linear_operator", 1) != MI_OK)
         std::cout << "MI_LINEAR_OPERATOR ignored: " << mi_last_error(device->ctx()) << std::endl;
+    // MI_LINEAR_PRECOND=1: the solve preconditioned by the linear model's multigrid V-cycle (one rank), handed on as the tuning key
+    // "linear_precond" in the same way.  Refused on a team: said once, the run is Jacobi-PCG
+    if (const char *f = std::getenv("MI_LINEAR_PRECOND"))
+      if (std::atoi(f) != 0 && mi_set_tuning(device->ctx(), "linear_precond", 1) != MI_OK)
+        std::cout << "MI_LINEAR_PRECOND ignored: " << mi_last_error(device->ctx()) << std::endl;
     device->check(mi_linear_setup(device->ctx(), parameters.theta), "mi_linear_setup");
     {
-      int mf = 0;
+      int mf = 0, mg = 0;
       device->check(mi_get_tuning(device->ctx(), "linear_operator_active", &mf), "mi_get_tuning");
       if (mf)
         std::cout << "Linear operators: matrix-free (K, M and the stepping matrix on mf_linear_q3, nothing assembled)" << std::endl;
+      device->check(mi_get_tuning(device->ctx(), "linear_precond_active", &mg), "mi_get_tuning");
+      if (mg)
+        std::cout << "Linear solver: CG preconditioned by a multigrid V-cycle of " << mi_linear_mg_n_levels(device->ctx())
+                  << " levels" << std::endl;
     }
 
     std::cout << "Triangulation:"

@@ -199,17 +199,25 @@ enum
  * boundary values of :426-451 eliminated; consistent-load operator of :458-521; body-force vector (:358-373) */
 int mi_linear_setup(mi_ctx *ctx, double theta);
 /* one pass of the time loop body (:676-684): assemble_rhs (:378-454, data_consistent: 1 "Stress" face integral,
- * 0 "Force" nodal forces), solve (:525-575; Jacobi-PCG, absolute tolerance, warm start from the previous
- * velocity), update_displacement (:579-586) */
+ * 0 "Force" nodal forces), solve (:525-575; Jacobi-PCG -- multigrid-PCG with "linear_precond" 1 --, absolute tolerance, warm
+ * start from the previous velocity), update_displacement (:579-586) */
 int mi_linear_step(mi_ctx *ctx, int data_consistent, double abs_tol, int64_t max_it, int *its, double *res);
 /* K (0), M (1) or the constrained stepping matrix (2) as scalar CSR, for parity tests */
 int mi_linear_matrix_get_csr(mi_ctx *ctx, int which, int64_t *rowptr, int32_t *col, double *val);
 /* y = K x (0), M x (1) or A x (2) through the device kernels the current set-up runs, in either mode of "linear_operator"
  * (host arrays of n_dofs; undecomposed mesh).  A: constrained columns dropped, row of a constrained dof = diag(A) x.  K, M:
- * unconstrained, as assembled.  With profiling on, the product alone is timed under MI_T_SPMV. */
+ * unconstrained, as assembled.  With profiling on, the product alone is timed under MI_T_SPMV.
+ * 3: y = B x, one multigrid V-cycle of the current set-up ("linear_precond" 1) as the solve applies it to its residual;
+ * MI_EINVAL where the set-up has no hierarchy. */
 int mi_linear_apply(mi_ctx *ctx, int which, const double *x_host, double *y_host);
 /* the Jacobi diagonal of the stepping matrix the PCG of mi_linear_step uses (n_dofs; undecomposed mesh) */
 int mi_linear_get_diagonal(mi_ctx *ctx, double *diag_host);
+/* the dim x dim node blocks of the stepping matrix in use (host array [n_nodes][dim * dim], row-major; undecomposed mesh):
+ * with "linear_precond" 1 the D whose inverse the block-Jacobi smoother multiplies with, in either mode of "linear_operator",
+ * under the model's constraint rule (row and column of a constrained dof zero inside the block, its diagonal entry kept).
+ * On a borrowed level context (mi_linear_mg_level_context) the level's.  A matrix-free set-up with "linear_precond" 0 forms
+ * the diagonal entries alone. */
+int mi_linear_get_diagonal_blocks(mi_ctx *ctx, double *blocks);
 
 /* per-vector device snapshots: what `old_state_data[i] = *state_variables[i]` (adapter.h:457-460) and its
  * inverse (:481-482) become when VectorType is a handle to a device-resident vector */
@@ -278,6 +286,14 @@ int mi_mg_level_describe(mi_ctx *ctx, int level, mi_mg_level_desc *out);
  * mi_set_tuning / mi_vec_set, and it dies with the next rebuild of the hierarchy ("precond", "fine_level", "mg_coarsest",
  * "mg_dense", "mg_dist_nodes") and with mi_ctx_destroy(ctx). */
 int mi_mg_level_context(mi_ctx *ctx, int level, mi_ctx **borrowed);
+/* The linear model's own multigrid hierarchy ("linear_precond" 1), read-only, with the contracts of mi_mg_n_levels,
+ * mi_mg_level_describe and mi_mg_level_context (which keep describing the tangent's hierarchy alone).  It is built by
+ * mi_linear_setup and complete when that returns: 0 levels / MI_EINVAL without one.  A borrowed level context answers
+ * mi_n_dofs, mi_n_nodes, mi_nnz, mi_get_constrained, mi_linear_matrix_get_csr (2: the level's stepping matrix) and
+ * mi_linear_get_diagonal_blocks; level 0 is `ctx` itself.  It dies with the next mi_linear_setup and with mi_ctx_destroy(ctx). */
+int mi_linear_mg_n_levels(const mi_ctx *ctx);
+int mi_linear_mg_level_describe(mi_ctx *ctx, int level, mi_mg_level_desc *out);
+int mi_linear_mg_level_context(mi_ctx *ctx, int level, mi_ctx **borrowed);
 
 /* per-kernel-class device timings from HIP events on the context's stream */
 enum
@@ -353,6 +369,18 @@ int mi_set_profiling(mi_ctx *ctx, int enable);
  *                                                  the PCG route there; "fine_level" cannot change meanwhile.  Same
  *                                                  operators up to rounding.  Read-back "linear_operator_active": what the
  *                                                  current linear set-up runs (0 without one)
+ *  linear_precond       0 | 1                      linear model: the solve of mi_linear_step is the Jacobi-PCG | the PCG   -
+ *                                                  preconditioned by a geometric multigrid V-cycle on a hierarchy of the
+ *                                                  (constant) stepping matrix that the model owns: the shape rules of the
+ *                                                  tangent's ("mg_coarsest", "mg_dense"; nu 3 / 2 over ratio 20), every level
+ *                                                  >= 1 the assembled linear model of its own unperturbed mesh, level 0 the
+ *                                                  context in either mode of "linear_operator" (matrix-free: the smoother
+ *                                                  steps and the residual in the slot gathers, D from mf_linear_diag_q3's
+ *                                                  block form).  Built once by the next mi_linear_setup, never refreshed;
+ *                                                  independent of "precond" and of the tangent's hierarchy.  Undecomposed
+ *                                                  contexts only (a team: MI_EINVAL, the key stays 0).  "solver_type" 1
+ *                                                  keeps precedence where the band solver applies.  Read-back
+ *                                                  "linear_precond_active": what the current linear set-up runs
  *  mf_diag_lag          0 | 1                      "fine_level" 1: diagonal blocks (smoother's D, Jacobi diagonal) at     -
  *                                                  every tangent | at the first tangent of a time step, kept over its
  *                                                  Newton iterations (what bench.py and the executable set)
