@@ -429,6 +429,14 @@ namespace mi_detail
            element_form(c) == 2 && c->mf_slots && c->d_mf_yc && !c->active_sell_vals;
   }
 
+  // the next assembly of a Q3 matrix-free level runs mf_point_pass_q3 + residual_gather instead of the generic residual pass
+  // and mf_records_q3 ("point_pass_q3" 1).  The one test for it: enqueue_assembly's dispatch and the "point_pass_q3_active"
+  // query both read it.  The records, the slots and their tables exist exactly while the Q3 level does.
+  bool assembly_runs_point_pass_q3(const mi_ctx *c)
+  {
+    return c->point_pass_q3 == 1 && c->mf_fine && c->d_qrec_q3 && c->d_mf_yc && c->d_mf_dst && c->d_mf_slot_base;
+  }
+
   bool mf_gather_fusable(const mi_ctx *c)
   {
     if (c->active_linear_mf) // the matrix-free linear model: every product is one launch + a slot gather (3D: D^-1 has its halves)
@@ -900,9 +908,11 @@ namespace mi_detail
   int enqueue_assembly(mi_ctx *c, bool residual_only)
   {
     // tangent_matrix = 0 (:1054) is implied: the first cell that touches a block stores instead of adding
-    // (system_rhs = 0, :1055 -- except where residual_gather writes every entry of it: the one-launch point pass, 3D Q2)
+    // (system_rhs = 0, :1055 -- except where residual_gather writes every entry of it: the one-launch point pass of 3D Q2,
+    // and of 3D Q3 under "point_pass_q3" 1)
     const bool one_launch = c->mf_fine && c->mf_point_slots && c->d_mf_yc && !c->d_qrec_q3;
-    if (!one_launch)
+    const bool pass_q3    = assembly_runs_point_pass_q3(c); // ... and the Q3 level's own point pass ("point_pass_q3" 1)
+    if (!one_launch && !pass_q3)
       HIPCHK(c, hipMemsetAsync(c->vec(MI_V_SYSTEM_RHS), 0, size_t(c->n) * sizeof(double), c->stream));
     HIPCHK(c, hipMemsetAsync(c->d_sc + SC_INVERTED, 0, sizeof(double), c->stream));
     mi::AsmParams p  = asm_params(c);
@@ -934,11 +944,24 @@ namespace mi_detail
         mi::launch_residual_gather(c->d_mf_yc, c->d_mf_slot_base, c->d_mf_src, c->d_cmask, c->vec(MI_V_SYSTEM_RHS),
                                    int64_t(c->mesh.nnodes) * 3, c->stream);
       }
+    if (pass_q3) // Q3 level: residual (and, in a tangent pass, the records) of all cells in one launch, then the same sum
+      {
+        mi::MfParams f = mf_params(c);
+        f.yc = c->d_mf_yc, f.dst = c->d_mf_dst, f.slot_inline = c->slots_layout == 1;
+        mi::MfPointPass pp{};
+        pp.u = c->vec(MI_V_TOTAL_DISPLACEMENT), pp.du = c->vec(MI_V_SOLUTION_DELTA), pp.acc = p.acc;
+        for (int d = 0; d < 3; ++d)
+          pp.body[d] = p.body[d];
+        pp.rho = p.rho, pp.rec = residual_only ? nullptr : c->d_qrec_q3, pp.inverted = p.inverted;
+        mi::launch_mf_point_pass_q3(f, pp, int32_t(c->mesh.ncells), c->stream);
+        mi::launch_residual_gather(c->d_mf_yc, c->d_mf_slot_base, c->d_mf_src, c->d_cmask, c->vec(MI_V_SYSTEM_RHS),
+                                   int64_t(c->mesh.nnodes) * 3, c->stream);
+      }
     for (int col = 0; col < c->mesh.ncolours; ++col)
       {
         p.cell_begin = c->mesh.colour_begin[col];
         p.cell_count = int32_t(c->mesh.colour_begin[col + 1] - c->mesh.colour_begin[col]);
-        if (!one_launch && mi::launch_assemble_cells(c->dim, c->degree, p, c->stream))
+        if (!one_launch && !pass_q3 && mi::launch_assemble_cells(c->dim, c->degree, p, c->stream))
           return fail(c, MI_EINVAL, "no assembly kernel for dim=%d degree=%d", c->dim, c->degree);
         const int fb = int(c->mesh.iface_colour_begin[col]);
         const int fc = int(c->mesh.iface_colour_begin[col + 1]) - fb;
@@ -966,7 +989,8 @@ namespace mi_detail
                                 int32_t(c->mesh.ncells), c->stream);
         c->qrec27_valid = true;
       }
-    if (c->d_qrec_q3) // Q3 fine level: F, J^(-2/3), 1/J at the 125 points of the assembly's rule, from the state of the residual
+    if (c->d_qrec_q3 && !pass_q3) // Q3 fine level: F, J^(-2/3), 1/J at the 125 points of the assembly's rule, from the state of the
+                                  // residual (the point pass wrote them itself)
       mi::launch_mf_records_q3(mf_params(c), c->vec(MI_V_TOTAL_DISPLACEMENT), c->vec(MI_V_SOLUTION_DELTA), c->d_qrec_q3,
                                int32_t(c->mesh.ncells), c->stream);
     c->qrec_q3s_valid = false;
@@ -3193,6 +3217,11 @@ int mi_set_tuning(mi_ctx *c, const char *key, int value)
           m->mf_point_slots = value;
           continue;
         }
+      if (k == "point_pass_q3" && (value == 0 || value == 1)) // Q3 matrix-free level: assembly in one sum-factorised launch (1) |
+        {                                                     // generic residual pass + mf_records_q3 (0); elsewhere: remembered
+          m->point_pass_q3 = value;
+          continue;
+        }
       if (k == "mf_diag_lag" && (value == 0 || value == 1))
         {
           m->mf_diag_lag   = value;
@@ -3411,6 +3440,10 @@ int mi_get_tuning(mi_ctx *c, const char *key, int *value)
     *value = m->smoother_points;
   else if (k == "smoother_quadrature_active") // 3: the smoother's fine-level products run on the 27-point records of the current tangent
     *value = smoother_runs_q27(m) ? 3 : 4;
+  else if (k == "point_pass_q3")
+    *value = m->point_pass_q3;
+  else if (k == "point_pass_q3_active") // 1: the next assembly of this context runs mf_point_pass_q3 + residual_gather
+    *value = assembly_runs_point_pass_q3(m) ? 1 : 0;
   else if (k == "smoother_quadrature_q3")
     *value = m->smoother_points_q3;
   else if (k == "smoother_quadrature_q3_active") // 4: the next smoother product runs mf_spmv_q3s; 5: a Q3 matrix-free level on mf_spmv_q3; 0: neither

@@ -203,7 +203,7 @@ struct mi_ctx
   // mf_spmv; d_vals is released.  Same results as the assembled level [REF nonlinear_elasticity.cc:1044-1087, 1153-1191].
   // 3D Q3 (one slab): the same level on mf_spmv_q3.  The residual pass is the generic element kernel's (assemble_cells with
   // residual_only, the assembled path's bits); the records come after it from u + du (mf_records_q3, 125 points: d_qrec_q3),
-  // the diagonal blocks from mf_diag_q3.  "smoother_quadrature", "smoother_precision" 32 and "mf_slots_cell_major" have no
+  // the diagonal blocks from mf_diag_q3 ("point_pass_q3" 1: residual and records from one launch, below).  "smoother_quadrature", "smoother_precision" 32 and "mf_slots_cell_major" have no
   // effect there: the slots are cell-major, and the smoother multiplies with the CG's 125-point product unless
   // "smoother_quadrature_q3" is 4.
   int       mf_fine = 0;
@@ -218,6 +218,12 @@ struct mi_ctx
   double   *d_qrec_q3s = nullptr; // [ncells][MF_NREC][64]
   double   *d_tab_q3s  = nullptr; // 1D tables of the 4-point rule for Q3
   bool      qrec_q3s_valid = false; // d_qrec_q3s belongs to the current tangent (cleared by every change of the key)
+  // tuning "point_pass_q3" 1 (3D Q3 matrix-free level; default 0: the generic residual pass colour by colour + mf_records_q3):
+  // an assembly of the level is ONE launch of mf_point_pass_q3 over all cells -- the residual into the product's slots, in a
+  // tangent pass the records as well -- and residual_gather, as the 3D Q2 level has it ("mf_point_slots").  The residual then
+  // agrees with the generic pass to rounding, not bitwise.  The key is remembered on any context and has an effect only
+  // while the Q3 level exists (assembly_runs_point_pass_q3)
+  int       point_pass_q3 = 0;
   // "mf_diag_lag" 1 (what bench.py and the executable set beside "fine_level" 1): the diagonal blocks -- the smoother's D,
   // the Jacobi diagonal -- are formed at the FIRST tangent of a time step and kept over its Newton iterations, as the coarse
   // operators are ("mg_lag"); a preconditioner-side policy: the operator (records) and the residual are always current

@@ -219,6 +219,15 @@ namespace mi
     int32_t         sel_n, sel_begin[9], sel_pos0[8];
   };
 
+  // what the Q3 level's point pass (mf_point_pass_q3) takes beside MfParams: the state, the mass term's constants, its outputs
+  struct MfPointPass
+  {
+    const double *u, *du, *acc; // total displacement, solution delta, acceleration
+    double        body[3], rho;
+    double       *rec;          // [ncells][MF_NREC][MF_Q3_QS] the records to write; null: the residual-only pass, which touches none
+    double       *inverted;     // as AsmParams::inverted
+  };
+
   // matrix-free operator of the linear model on 3D Q3 cells (see mf_linear_q3): y = (c_K K + c_M M) x
   struct MfLinearOp
   {
@@ -378,6 +387,10 @@ namespace mi
   void launch_mf_records_q3(const MfParams &p, const double *u, const double *du, double *rec, int32_t cell_count, hipStream_t s);
   void launch_mf_spmv_q3(const MfParams &p, int32_t cell_count, hipStream_t s, hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr);
   void launch_mf_diag_q3(const MfParams &p, double *slots6, int32_t cell_count, hipStream_t s);
+  // ... the level's point pass in one launch ("point_pass_q3" 1; see mf_point_pass_q3): the residual of every cell into its slots
+  // (MfParams::yc / dst / slot_inline, the product's), from u + du and the acceleration; with pp.rec set, the records of
+  // launch_mf_records_q3 into it as well (null: the residual-only pass).  launch_residual_gather then sums the slots into system_rhs
+  void launch_mf_point_pass_q3(const MfParams &p, const MfPointPass &pp, int32_t cell_count, hipStream_t s);
   // ... the multigrid smoother's operator on the element's full-order rule, 4 x 4 x 4 points (see mf_spmv_q3s): records
   // [ncells][MF_NREC][64] of its own (MfParams::qrec_q3s, written by mf_records_q3s from u + du with the fold rule of
   // mf_records27), the rule's 1D tables MfParams::tab_q3s; one wave per cell, the results into the same cell-major slots

@@ -2358,7 +2358,7 @@ namespace mi
 
   // ------------------------------------------------------------------ matrix-free kernels: what they share
   // One definition each of what the three families -- 64-point Q2 (mf_spmv, mf_diag), 27-point smoother (mf_records27,
-  // mf_spmv27), Q3 (mf_records_q3, mf_spmv_q3, mf_diag_q3; mf_records_q3s, mf_spmv_q3s) -- do at a quadrature point:
+  // mf_spmv27), Q3 (mf_records_q3, mf_spmv_q3, mf_point_pass_q3, mf_diag_q3; mf_records_q3s, mf_spmv_q3s) -- do at a quadrature point:
   // mf_geometry, MF_M, MF_POINT_ALGEBRA / MF_POINT_SM, MF_RECORD_TAIL here; MF_DIAG_POINT, MF_DIAG_ACCUMULATE at mf_diag.
   // The sum-factorisation passes, the LDS layouts and the lane mappings stay with the kernels.  The geometry is a function; the tensor algebra is text expanded in
   // place, so that every kernel hands the optimiser its statements in the order it always did (its register allocation
@@ -3769,7 +3769,7 @@ namespace mi
   // The product of mf_spmv for cubic elements: 64 nodes per cell, the assembly's 125 points (qf_cell(5), 5 per direction).
   // One workgroup of 128 threads = one cell; a thread owns one quadrature point (threads 125-127 mirror point 124 and store
   // nothing).  Records [cell][MF_NREC][MFQ3_QS] (F[9], J^(-2/3), 1/J, padded to 128 points), written by mf_records_q3 from
-  // u + du after the residual pass.  Sum factorisation one direction at a time (4 nodes <-> 5 points); in the passes that
+  // u + du after the residual pass (or by mf_point_pass_q3 with the residual, "point_pass_q3" 1).  Sum factorisation one direction at a time (4 nodes <-> 5 points); in the passes that
   // contract towards or away from the nodes a thread owns one line and produces all outputs along the contracted direction,
   // so the 1D tables are uniform (scalar) operands:
   //   E1  item (c,k,j):   x-line -> A_S / A_D [c,k,j][qx]                              48 items, 40 multiply-adds
@@ -3859,87 +3859,12 @@ namespace mi
     __syncthreads(); // B is consumed
   }
 
-  // F, J^(-2/3), 1/J at the 125 points from u + du (the state the Q3 tangent is linearised at), one workgroup per cell
-  template <bool BOX>
-  __global__ __launch_bounds__(MFQ3_NT, BOX ? 4 : 2) void mf_records_q3(MfParams prm, const double *__restrict__ u, const double *__restrict__ du,
-                                                              double *__restrict__ rec)
+  // I3 + I2 + I1 + store: Q in R0 (12 numbers per point: Q[(i*4+l)][q], the value term in rows 3, 7, 11; the caller's barrier
+  // stands behind their writes) -> the cell's 192 results in its slots.  C goes to R1, E to R0 over Q.  Shared by mf_spmv_q3
+  // and mf_point_pass_q3, as mfq3s_integrate is by the 64-point pair.
+  __device__ __forceinline__ void mfq3_integrate(const MfParams &prm, double *__restrict__ R0, double *__restrict__ R1, const int t,
+                                                 const int64_t cell)
   {
-    __shared__ double R0[MFQ3_R0], R1[MFQ3_R1], sT[40];
-    const int     t    = threadIdx.x, it = t < MFQ3_NQ ? t : MFQ3_NQ - 1;
-    const int64_t cell = blockIdx.x;
-    if (t < 40)
-      sT[t] = prm.tab1d[t];
-    if (t < MFQ3_NPC)
-      {
-        const int32_t node = prm.conn[cell * MFQ3_NPC + t];
-#pragma unroll
-        for (int c = 0; c < 3; ++c)
-          R1[c * MFQ3_NPC + t] = u[int64_t(node) * 3 + c] + du[int64_t(node) * 3 + c]; // get_total_solution, :580-588
-      }
-    __syncthreads();
-    double H[3][3], V[3];
-    mfq3_gradients(prm.tab1d, sT, R0, R1, t, it, H, V);
-    const int qz = it / 25, qy = (it - 25 * qz) / 5, qx = it - 25 * qz - 5 * qy;
-    double    Ji[9], detJ;
-    mf_geometry<BOX>(prm, cell, prm.tab1d + MFQ3_TX, qx, qy, qz, Ji, detJ);
-    // (det F <= 0 is reported by the residual pass at these same points, nonlinear_elasticity.cc:935)
-    MF_RECORD_TAIL(false, t < MFQ3_NQ, rec + cell * int64_t(MF_NREC * MFQ3_QS) + t, MFQ3_QS)
-  }
-
-  template <bool BOX>
-  __global__ __launch_bounds__(MFQ3_NT, 4) void mf_spmv_q3(MfParams prm)
-  {
-    __shared__ double R0[MFQ3_R0], R1[MFQ3_R1], sT[40];
-    const int     t    = threadIdx.x, it = t < MFQ3_NQ ? t : MFQ3_NQ - 1;
-    const int64_t cell = blockIdx.x;
-    if (t < 40)
-      sT[t] = prm.tab1d[t];
-    // gather x (constrained entries masked)
-    if (t < MFQ3_NPC)
-      {
-        const int32_t node = prm.conn[cell * MFQ3_NPC + t];
-        const int     cm   = prm.cmask[node];
-#pragma unroll
-        for (int c = 0; c < 3; ++c)
-          R1[c * MFQ3_NPC + t] = ((cm >> c) & 1) ? 0.0 : prm.x[int64_t(node) * 3 + c];
-      }
-    // this thread's record: consumed after the gradient passes
-    double rec[MF_NREC];
-    {
-      const double *__restrict__ rp = prm.qrec + cell * int64_t(MF_NREC * MFQ3_QS) + it;
-#pragma unroll
-      for (int f = 0; f < MF_NREC; ++f)
-        rec[f] = __builtin_nontemporal_load(&rp[f * MFQ3_QS]);
-    }
-    __syncthreads();
-    double H[3][3], V[3];
-    mfq3_gradients(prm.tab1d, sT, R0, R1, t, it, H, V);
-    // ---- point stage: Q = JxW S M^T (MF_POINT_ALGEBRA), 12 numbers per point into R0: Q[(i*4+l)][q]
-    {
-      const int qz = it / 25, qy = (it - 25 * qz) / 5, qx = it - 25 * qz - 5 * qy;
-      const double wq = prm.tab1d[MFQ3_TW + qx] * prm.tab1d[MFQ3_TW + qy] * prm.tab1d[MFQ3_TW + qz];
-      double       Finv[9], tau[6], tiso[6], cII, cS, Ji[9], detJ, M[9];
-      neo_hooke_from_F<3>(rec, det3x3(rec), rec[9], rec[10], prm.mu, prm.kappa, Finv, tau, tiso, cII, cS);
-      mf_geometry<BOX>(prm, cell, prm.tab1d + MFQ3_TX, qx, qy, qz, Ji, detJ);
-      MF_M(BOX, i_, j_)
-      const double w = detJ * wq, wcII = w * cII, cs2 = 0.5 * cS;
-      MF_POINT_ALGEBRA(double)
-      const double wm       = prm.mass * w;
-#pragma unroll
-      for (int i = 0; i < 3; ++i)
-        {
-          double Sm[3];
-#pragma unroll
-          for (int j = 0; j < 3; ++j)
-              Sm[j] = MF_POINT_SM(double, i, j);
-          // (threads 125-127 write the padding entries 125-127 of every row, which nobody reads)
-#pragma unroll
-          for (int l = 0; l < 3; ++l)
-            R0[(i * 4 + l) * MFQ3_QS + t] = MF_POINT_Q(Sm, l);
-          R0[(i * 4 + 3) * MFQ3_QS + t] = wm * V[i];
-        }
-    }
-    __syncthreads();
     double S[5][4], D[5][4]; // uniform: scalar registers
 #pragma unroll
     for (int q = 0; q < 5; ++q)
@@ -4033,6 +3958,208 @@ namespace mi
             prm.yc[slot * 3 + c] = yv;
           }
       }
+  }
+
+  // F, J^(-2/3), 1/J at the 125 points from u + du (the state the Q3 tangent is linearised at), one workgroup per cell
+  template <bool BOX>
+  __global__ __launch_bounds__(MFQ3_NT, BOX ? 4 : 2) void mf_records_q3(MfParams prm, const double *__restrict__ u, const double *__restrict__ du,
+                                                              double *__restrict__ rec)
+  {
+    __shared__ double R0[MFQ3_R0], R1[MFQ3_R1], sT[40];
+    const int     t    = threadIdx.x, it = t < MFQ3_NQ ? t : MFQ3_NQ - 1;
+    const int64_t cell = blockIdx.x;
+    if (t < 40)
+      sT[t] = prm.tab1d[t];
+    if (t < MFQ3_NPC)
+      {
+        const int32_t node = prm.conn[cell * MFQ3_NPC + t];
+#pragma unroll
+        for (int c = 0; c < 3; ++c)
+          R1[c * MFQ3_NPC + t] = u[int64_t(node) * 3 + c] + du[int64_t(node) * 3 + c]; // get_total_solution, :580-588
+      }
+    __syncthreads();
+    double H[3][3], V[3];
+    mfq3_gradients(prm.tab1d, sT, R0, R1, t, it, H, V);
+    const int qz = it / 25, qy = (it - 25 * qz) / 5, qx = it - 25 * qz - 5 * qy;
+    double    Ji[9], detJ;
+    mf_geometry<BOX>(prm, cell, prm.tab1d + MFQ3_TX, qx, qy, qz, Ji, detJ);
+    // (det F <= 0 is reported by the residual pass at these same points, nonlinear_elasticity.cc:935)
+    MF_RECORD_TAIL(false, t < MFQ3_NQ, rec + cell * int64_t(MF_NREC * MFQ3_QS) + t, MFQ3_QS)
+  }
+
+  template <bool BOX>
+  __global__ __launch_bounds__(MFQ3_NT, 4) void mf_spmv_q3(MfParams prm)
+  {
+    __shared__ double R0[MFQ3_R0], R1[MFQ3_R1], sT[40];
+    const int     t    = threadIdx.x, it = t < MFQ3_NQ ? t : MFQ3_NQ - 1;
+    const int64_t cell = blockIdx.x;
+    if (t < 40)
+      sT[t] = prm.tab1d[t];
+    // gather x (constrained entries masked)
+    if (t < MFQ3_NPC)
+      {
+        const int32_t node = prm.conn[cell * MFQ3_NPC + t];
+        const int     cm   = prm.cmask[node];
+#pragma unroll
+        for (int c = 0; c < 3; ++c)
+          R1[c * MFQ3_NPC + t] = ((cm >> c) & 1) ? 0.0 : prm.x[int64_t(node) * 3 + c];
+      }
+    // this thread's record: consumed after the gradient passes
+    double rec[MF_NREC];
+    {
+      const double *__restrict__ rp = prm.qrec + cell * int64_t(MF_NREC * MFQ3_QS) + it;
+#pragma unroll
+      for (int f = 0; f < MF_NREC; ++f)
+        rec[f] = __builtin_nontemporal_load(&rp[f * MFQ3_QS]);
+    }
+    __syncthreads();
+    double H[3][3], V[3];
+    mfq3_gradients(prm.tab1d, sT, R0, R1, t, it, H, V);
+    // ---- point stage: Q = JxW S M^T (MF_POINT_ALGEBRA), 12 numbers per point into R0: Q[(i*4+l)][q]
+    {
+      const int qz = it / 25, qy = (it - 25 * qz) / 5, qx = it - 25 * qz - 5 * qy;
+      const double wq = prm.tab1d[MFQ3_TW + qx] * prm.tab1d[MFQ3_TW + qy] * prm.tab1d[MFQ3_TW + qz];
+      double       Finv[9], tau[6], tiso[6], cII, cS, Ji[9], detJ, M[9];
+      neo_hooke_from_F<3>(rec, det3x3(rec), rec[9], rec[10], prm.mu, prm.kappa, Finv, tau, tiso, cII, cS);
+      mf_geometry<BOX>(prm, cell, prm.tab1d + MFQ3_TX, qx, qy, qz, Ji, detJ);
+      MF_M(BOX, i_, j_)
+      const double w = detJ * wq, wcII = w * cII, cs2 = 0.5 * cS;
+      MF_POINT_ALGEBRA(double)
+      const double wm       = prm.mass * w;
+#pragma unroll
+      for (int i = 0; i < 3; ++i)
+        {
+          double Sm[3];
+#pragma unroll
+          for (int j = 0; j < 3; ++j)
+              Sm[j] = MF_POINT_SM(double, i, j);
+          // (threads 125-127 write the padding entries 125-127 of every row, which nobody reads)
+#pragma unroll
+          for (int l = 0; l < 3; ++l)
+            R0[(i * 4 + l) * MFQ3_QS + t] = MF_POINT_Q(Sm, l);
+          R0[(i * 4 + 3) * MFQ3_QS + t] = wm * V[i];
+        }
+    }
+    __syncthreads();
+    mfq3_integrate(prm, R0, R1, t, cell);
+  }
+
+  // The level's point pass ("point_pass_q3" 1): records and residual of ALL cells in one launch, in the shape of mf_spmv_q3 --
+  // E1-E3 on u + du (unmasked: the residual is formed at the full state), the point stage of the RESIDUAL, I3-I1 into the
+  // cell's slots; residual_gather then sums them per node in processing order, as for the 3D Q2 level (assemble_q2sf<true>
+  // with res_slots).  Point stage: F from H and the cell's geometry (MF_RECORD_TAIL: the record's own statements, so the
+  // record is mf_records_q3's), det F <= 0 reported as the generic pass does at these same points (nonlinear_elasticity.cc:935),
+  // neo_hooke_from_F, M = Jinv F^-1, w = detJ wq;  Q = w tau M^T  (the generic kernel's tau g_a with g_a = M^T grad_xi N_a: tau
+  // itself, so a stress-free state gives exact zeros) into the three gradient rows,  rho w (acc - body)  into the value row.
+  // The mass term needs values only: acc - body is gathered per node (a nodal constant interpolates to itself) and taken
+  // through a value-only E1-E3 by the second wave in the part of R0 that mfq3_gradients leaves alone --
+  //   X' [c*64 + a] at 480, A'_S [c,k,j][qx] at 672, B'_SS [c,k][qy][qx] at 912 (ends at 1212 of MFQ3_R0 = 1536)
+  // -- before the gradient passes, so the LDS is mf_spmv_q3's; the value at the point waits in the thread's own column of
+  // Q's rows 4-6 (512 - 896: over X' and A').  Residual only (mi_assemble_residual): pp.rec is null and no record is touched.
+  // That is a uniform run-time branch around the eleven stores, not a second instance: as a template parameter the two
+  // instances came out with residuals that differed in the last bit on box cells (the compiler fuses multiply-adds by the
+  // number of uses a product has, and the stored F adds uses), and mi_assemble_residual has to return mi_assemble's bits.
+  // Launch bounds: on boxes the kernel needs 129 registers (F stays live for the record beside the material's operands), so
+  // it is built for 3 waves per SIMD like the general instance; at 4 it spilled to scratch.
+  constexpr int MFQ3_VX = 480, MFQ3_VA = 672, MFQ3_VB = 912, MFQ3_VM = 4 * MFQ3_QS;
+  static_assert(MFQ3_VX >= 2 * 240 && MFQ3_VB + 300 <= MFQ3_R0, "the value pass lies behind A and inside R0");
+  static_assert(MFQ3_VM >= MFQ3_VX && MFQ3_VM + 3 * MFQ3_QS <= MFQ3_VB, "the point values lie over X' and A' and below B'");
+  template <bool BOX>
+  __global__ __launch_bounds__(MFQ3_NT, BOX ? 3 : 2) void mf_point_pass_q3(MfParams prm, MfPointPass pp)
+  {
+    __shared__ double R0[MFQ3_R0], R1[MFQ3_R1], sT[40];
+    const int     t    = threadIdx.x, it = t < MFQ3_NQ ? t : MFQ3_NQ - 1;
+    const int     tv   = t - MFQ3_NPC; // the second wave's item in the value pass
+    const int64_t cell = blockIdx.x;
+    if (t < 40)
+      sT[t] = prm.tab1d[t];
+    // gather u + du (first wave) and acc - body (second wave)
+    {
+      const int     a    = t & (MFQ3_NPC - 1);
+      const int32_t node = prm.conn[cell * MFQ3_NPC + a];
+      if (t < MFQ3_NPC)
+        {
+#pragma unroll
+          for (int c = 0; c < 3; ++c)
+            R1[c * MFQ3_NPC + a] = pp.u[int64_t(node) * 3 + c] + pp.du[int64_t(node) * 3 + c]; // get_total_solution, :580-588
+        }
+      else
+        {
+#pragma unroll
+          for (int c = 0; c < 3; ++c)
+            R0[MFQ3_VX + c * MFQ3_NPC + a] = pp.acc[int64_t(node) * 3 + c] - pp.body[c];
+        }
+    }
+    __syncthreads();
+    {
+      double S[5][4]; // uniform: scalar registers
+#pragma unroll
+      for (int q = 0; q < 5; ++q)
+#pragma unroll
+        for (int a = 0; a < 4; ++a)
+          S[q][a] = prm.tab1d[q * 4 + a];
+      if (tv >= 0 && tv < 48) // E1': line (c,k,j) = tv
+        {
+          const double x0 = R0[MFQ3_VX + tv * 4], x1 = R0[MFQ3_VX + tv * 4 + 1], x2 = R0[MFQ3_VX + tv * 4 + 2], x3 = R0[MFQ3_VX + tv * 4 + 3];
+#pragma unroll
+          for (int qx = 0; qx < 5; ++qx)
+            R0[MFQ3_VA + tv * 5 + qx] = S[qx][0] * x0 + S[qx][1] * x1 + S[qx][2] * x2 + S[qx][3] * x3;
+        }
+      __syncthreads();
+      if (tv >= 0 && tv < 60) // E2': item (c,k,qx): tv = ck * 5 + qx
+        {
+          const int ck = tv / 5, qx = tv - 5 * ck;
+          double    as[4];
+#pragma unroll
+          for (int j = 0; j < 4; ++j)
+            as[j] = R0[MFQ3_VA + (ck * 4 + j) * 5 + qx];
+#pragma unroll
+          for (int qy = 0; qy < 5; ++qy)
+            R0[MFQ3_VB + ck * 25 + qy * 5 + qx] = S[qy][0] * as[0] + S[qy][1] * as[1] + S[qy][2] * as[2] + S[qy][3] * as[3];
+        }
+      __syncthreads();
+      const int qz = it / 25, q25 = it - 25 * qz; // E3': item = point
+#pragma unroll
+      for (int c = 0; c < 3; ++c)
+        {
+          double vm = 0.0;
+#pragma unroll
+          for (int k = 0; k < 4; ++k)
+            vm = fma(sT[qz * 4 + k], R0[MFQ3_VB + (c * 4 + k) * 25 + q25], vm);
+          R0[MFQ3_VM + c * MFQ3_QS + t] = vm; // (over X' and A', both consumed: no register held across the gradient passes)
+        }
+    }
+    double H[3][3], V[3];
+    mfq3_gradients(prm.tab1d, sT, R0, R1, t, it, H, V); // (writes R0 below MFQ3_VX only; its barriers stand behind E3')
+    // ---- point stage: Q = JxW tau M^T, 12 numbers per point into R0: Q[(i*4+l)][q]
+    {
+      const int    qz = it / 25, qy = (it - 25 * qz) / 5, qx = it - 25 * qz - 5 * qy;
+      const double wq = prm.tab1d[MFQ3_TW + qx] * prm.tab1d[MFQ3_TW + qy] * prm.tab1d[MFQ3_TW + qz];
+      double       Ji[9], detJ;
+      mf_geometry<BOX>(prm, cell, prm.tab1d + MFQ3_TX, qx, qy, qz, Ji, detJ);
+      // (the record at `it`, stored by every thread: threads 125-127 repeat point 124's values)
+      MF_RECORD_TAIL(false, pp.rec != nullptr, pp.rec + cell * int64_t(MF_NREC * MFQ3_QS) + it, MFQ3_QS)
+      if (!(J > 0.0)) // inverted element (nonlinear_elasticity.cc:935 asserts det F > 0)
+        *pp.inverted = 1.0;
+      double Finv[9], tau[6], tiso[6], cII, cS, M[9];
+      neo_hooke_from_F<3>(F, J, Jm, rJ, prm.mu, prm.kappa, Finv, tau, tiso, cII, cS);
+      MF_M(BOX, i_, j_)
+      const double w       = detJ * wq; // JxW of the reference configuration
+      const double T[3][3] = {{tau[0], tau[3], tau[4]}, {tau[3], tau[1], tau[5]}, {tau[4], tau[5], tau[2]}};
+      // acc - body at the point: this thread's own column of rows 4-6, read before any row of the column is written
+      const double vm[3] = {R0[MFQ3_VM + t], R0[MFQ3_VM + MFQ3_QS + t], R0[MFQ3_VM + 2 * MFQ3_QS + t]};
+#pragma unroll
+      for (int i = 0; i < 3; ++i)
+        {
+          // (threads 125-127 write the padding entries 125-127 of every row, which nobody reads)
+#pragma unroll
+          for (int l = 0; l < 3; ++l)
+            R0[(i * 4 + l) * MFQ3_QS + t] = w * fma(T[i][2], M[l * 3 + 2], fma(T[i][1], M[l * 3 + 1], T[i][0] * M[l * 3]));
+          R0[(i * 4 + 3) * MFQ3_QS + t] = pp.rho * w * vm[i];
+        }
+    }
+    __syncthreads();
+    mfq3_integrate(prm, R0, R1, t, cell);
   }
 
   // the nodes' 3x3 diagonal blocks from the Q3 records, into the cells' slots [nslots][6] (as mf_diag).  Stage 1, thread =
@@ -7494,6 +7621,13 @@ namespace mi
       hipExtLaunchKernelGGL(kern, dim3(cell_count), dim3(MFQ3_NT), 0, s, ev_start, ev_stop, 0, p);
     else
       hipLaunchKernelGGL(kern, dim3(cell_count), dim3(MFQ3_NT), 0, s, p);
+  }
+  void launch_mf_point_pass_q3(const MfParams &p, const MfPointPass &pp, int32_t cell_count, hipStream_t s)
+  {
+    if (cell_count <= 0)
+      return;
+    auto *kern = p.cellbox ? mf_point_pass_q3<true> : mf_point_pass_q3<false>;
+    hipLaunchKernelGGL(kern, dim3(cell_count), dim3(MFQ3_NT), 0, s, p, pp);
   }
   void launch_mf_diag_q3(const MfParams &p, double *slots6, int32_t cell_count, hipStream_t s)
   {

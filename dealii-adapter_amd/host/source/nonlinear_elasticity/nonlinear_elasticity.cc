@@ -211,6 +211,10 @@ namespace Nonlinear_Elasticity
       if (const char *f = std::getenv("MI_SMOOTHER_QUADRATURE_Q3"))
         if (mi_set_tuning(device->ctx(), "smoother_quadrature_q3", std::atoi(f)) != MI_OK)
           std::cout << "MI_SMOOTHER_QUADRATURE_Q3 ignored: " << mi_last_error(device->ctx()) << std::endl;
+      // 1: an assembly of a 3D Q3 matrix-free level is one sum-factorised launch, records and residual (0: the generic residual pass)
+      if (const char *f = std::getenv("MI_POINT_PASS_Q3"))
+        if (mi_set_tuning(device->ctx(), "point_pass_q3", std::atoi(f)) != MI_OK)
+          std::cout << "MI_POINT_PASS_Q3 ignored: " << mi_last_error(device->ctx()) << std::endl;
     }
 
     std::cout << "Triangulation:"

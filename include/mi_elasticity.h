@@ -390,6 +390,15 @@ int mi_set_profiling(mi_ctx *ctx, int enable);
  *                                                  (as mf_spmv) | the trilinear map inverted at every point
  *  mf_point_slots       1 | 0                      "fine_level" 1: the point pass (records + residual) over all cells in  -
  *                                                  one launch, residual through the product's slots | eight colour launches
+ *  point_pass_q3        0 | 1                      3D Q3 matrix-free level ("fine_level" 1): an assembly forms the         MI_POINT_PASS_Q3
+ *                                                  residual with the generic element kernel colour by colour and then the
+ *                                                  records (mf_records_q3) | records and residual of all cells in ONE
+ *                                                  sum-factorised launch (mf_point_pass_q3, the shape of mf_spmv_q3) into
+ *                                                  the product's slots + residual_gather; mi_assemble_residual runs the
+ *                                                  same kernel without the record stores.  Same residual up to rounding.
+ *                                                  Elsewhere accepted, remembered, no effect; either order with
+ *                                                  "fine_level".  Read-back "point_pass_q3_active": 1 = the next assembly
+ *                                                  of this context runs that kernel, else 0
  *  smoother_operator    2 | 1 | 0                  fine-level products of the smoother on 3D Q2 slabs > 100 k nodes:    MI_EBE
  *                                                  matrix-free from the assembly's point records | stored element
  *                                                  tangents | assembled matrix
