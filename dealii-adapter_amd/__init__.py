@@ -72,6 +72,10 @@ class MgLevelDesc(C.Structure):
                 ("distributed", C.c_int32), ("reserved", C.c_int32)]
 
 
+class EnergyInfo(C.Structure):
+    _fields_ = [("strain", C.c_double), ("kinetic", C.c_double), ("body", C.c_double), ("reserved", C.c_double)]
+
+
 class MiError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("mi_elasticity error %d: %s" % (code, msg))
@@ -145,6 +149,9 @@ def lib():
         L.mi_linear_mg_level_context.argtypes = [vp, C.c_int, C.POINTER(vp)]
         for f in ("mi_linear_get_diagonal_blocks", "mi_linear_mg_n_levels", "mi_linear_mg_level_describe",
                   "mi_linear_mg_level_context"):
+            getattr(L, f).restype = C.c_int
+        for f in ("mi_energy", "mi_linear_energy"):
+            getattr(L, f).argtypes = [vp, C.POINTER(EnergyInfo)]
             getattr(L, f).restype = C.c_int
         L.mi_set_profiling.argtypes = [vp, C.c_int]
         L.mi_get_timings.argtypes = [vp, C.POINTER(Timings)]
@@ -428,6 +435,12 @@ class Context:
         self._chk(lib().mi_comm_broadcast(self.h, _dp(v), v.size))
         return v
 
+    def energy(self):
+        """strain energy, kinetic energy and body-force potential of the committed state (V_U, V_V) of the nonlinear model"""
+        e = EnergyInfo()
+        self._chk(lib().mi_energy(self.h, C.byref(e)))
+        return dict(strain=e.strain, kinetic=e.kinetic, body=e.body)
+
     def state_save(self):
         self._chk(lib().mi_state_save(self.h))
 
@@ -498,6 +511,12 @@ class Context:
         self._chk(lib().mi_linear_step(self.h, int(data_consistent), abs_tol, self.n * 10 if max_it is None else max_it,
                                        C.byref(its), C.byref(res)))
         return its.value, res.value
+
+    def linear_energy(self):
+        """1/2 u.K u, 1/2 v.M v and -u.f_body of the linear model, through the products of the current set-up"""
+        e = EnergyInfo()
+        self._chk(lib().mi_linear_energy(self.h, C.byref(e)))
+        return dict(strain=e.strain, kinetic=e.kinetic, body=e.body)
 
     def linear_apply(self, which, x):
         """y = K x (0), M x (1), A x (2) through the device kernels of the current set-up; 3: one V-cycle of its multigrid"""

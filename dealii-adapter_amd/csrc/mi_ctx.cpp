@@ -44,7 +44,8 @@ namespace mi_detail
     SC_NORM_RHS = 8,
     SC_NORM_UPD = 9,
     SC_TOT = 10, // [rr, rz, pq, bb] all-reduced totals of the distributed CG
-    SC_START = 14 // [h.b, h.Ah] of a predicted start vector (cg_run, scale_start)
+    SC_START = 14, // [h.b, h.Ah] of a predicted start vector (cg_run, scale_start)
+    SC_ENERGY = 16 // [strain, kinetic, body, inverted] of mi_energy / mi_linear_energy: one all-reduce
   };
 
   int team_size(const mi_ctx *c)
@@ -1174,10 +1175,16 @@ namespace mi_detail
   }
 
   // the geometry class of the local cells: when every one is an axis-parallel box, d_cellbox = 1/h and the volume per cell
+  static int make_cellbox(mi_ctx *c, double **dst);
   int upload_cellbox(mi_ctx *c)
   {
     if (c->d_cellbox)
       return MI_OK;
+    return make_cellbox(c, &c->d_cellbox);
+  }
+  // ... into *dst (left null unless every local cell is an axis-parallel box)
+  static int make_cellbox(mi_ctx *c, double **dst)
+  {
     bool box = c->dim == 3;
     for (int64_t e = 0; e < c->mesh.ncells && box; ++e)
       {
@@ -1198,8 +1205,75 @@ namespace mi_detail
             cb[size_t(e) * 4 + 2] = 1.0 / hz;
             cb[size_t(e) * 4 + 3] = hx * hy * hz;
           }
-        return upload(c, &c->d_cellbox, cb);
+        return upload(c, dst, cb);
       }
+    return MI_OK;
+  }
+
+  // ---- energy diagnostics ------------------------------------------------------------------------------------
+  // the cells' buffer and, on 3D contexts that keep no cell boxes, boxes of the call's own (first use)
+  static int energy_prepare(mi_ctx *c)
+  {
+    const size_t nc = size_t(c->mesh.ncells);
+    if (!c->d_energy)
+      HIPCHK(c, hipMalloc((void **)&c->d_energy, (nc + nc / 1024 + 1) * 3 * sizeof(double)));
+    if (!c->d_cellbox && !c->energy_box_checked)
+      {
+        if (int rc = make_cellbox(c, &c->d_energy_box))
+          return rc;
+        c->energy_box_checked = true;
+      }
+    return MI_OK;
+  }
+
+  // strain energy, kinetic energy and body-force potential of one slab's owned cells into its scalars [SC_ENERGY, +3), the
+  // inverted flag into SC_ENERGY + 3 (enqueued; energy_finish sums over the team and reads back)
+  static int enqueue_energy(mi_ctx *c)
+  {
+    if (int rc = energy_prepare(c))
+      return rc;
+    HIPCHK(c, hipMemsetAsync(c->d_sc + SC_ENERGY, 0, 4 * sizeof(double), c->stream));
+    mi::MfParams f = mf_params(c);
+    if (!f.cellbox)
+      f.cellbox = c->d_energy_box;
+    mi::EnergyParams e{};
+    e.conn = c->d_conn, e.cverts = c->d_cverts, e.tab1d = c->d_tab;
+    e.u = c->vec(MI_V_TOTAL_DISPLACEMENT), e.v = c->vec(MI_V_VELOCITY);
+    e.mu = c->mat.mu, e.kappa = c->kappa, e.rho = c->mat.rho;
+    for (int d = 0; d < 3; ++d)
+      e.body[d] = c->mat.body_force[d];
+    e.cell_e   = c->d_energy;
+    e.inverted = c->d_sc + SC_ENERGY + 3;
+    // owned cell layers [z0, z1) of the slab's local box: the ghost layer above them starts at this node
+    e.own_node_end = int32_t(c->slab.plane_nodes * int64_t(c->degree) * (c->slab.z1 - c->slab.z0));
+    // (experiments build: the generic kernel on 3D Q2 / Q3 as well, the cross-check of the two sum-factorised forms)
+    static const bool generic = mi::exp_env("MI_ENERGY_GENERIC") && atoi(mi::exp_env("MI_ENERGY_GENERIC")) != 0;
+    if (mi::launch_energy(c->dim, c->degree, f, e, int32_t(c->mesh.ncells), generic, c->stream))
+      return fail(c, MI_EINVAL, "no energy kernel for dim=%d degree=%d", c->dim, c->degree);
+    mi::launch_energy_sum(c->d_energy, c->mesh.ncells, c->d_energy + size_t(c->mesh.ncells) * 3, c->d_sc + SC_ENERGY, c->stream);
+    HIPCHK(c, hipGetLastError());
+    return MI_OK;
+  }
+
+  double *energy_scalars(mi_ctx *c) { return c->d_sc + SC_ENERGY; }
+
+  // the slabs' four scalars in ONE all-reduce (team_allreduce, as team_masked_norm), then to the host.  The call is a
+  // diagnostic: the counter of scalar all-reduces stays where it was
+  int energy_finish(Team &T, mi_energy_info *out, double *inverted)
+  {
+    mi_ctx       *c0 = T.members[0];
+    const int64_t n0 = T.n_scalar_allreduce;
+    int           rc = team_allreduce(T, SC_ENERGY, 4);
+    T.n_scalar_allreduce = n0;
+    if (rc)
+      return rc;
+    HIPCHK(c0, hipGetLastError());
+    HIPCHK(c0, hipMemcpyAsync(c0->h_pinned, c0->d_sc + SC_ENERGY, 4 * sizeof(double), hipMemcpyDeviceToHost, c0->stream));
+    if ((rc = sync(c0)))
+      return rc;
+    out->strain = c0->h_pinned[0], out->kinetic = c0->h_pinned[1], out->body = c0->h_pinned[2], out->reserved = 0.0;
+    if (inverted)
+      *inverted = c0->h_pinned[3];
     return MI_OK;
   }
 
@@ -1831,7 +1905,7 @@ namespace mi_detail
                     c->d_qrec27, c->d_tab27, c->d_qrec_q3, c->d_qrec_q3s, c->d_tab_q3s, c->d_diag_blk, c->d_diag_slots, c->d_diagpos_mf, c->d_face_slots, c->d_fn_ids, c->d_fn_start, c->d_fn_src,
                     c->d_pred[0][0], c->d_pred[0][1], c->d_pred[1][0], c->d_pred[1][1], c->d_pred[2][0], c->d_pred[2][1], c->d_pred[3][0], c->d_pred[3][1],
                     c->d_pred_saved[0][0], c->d_pred_saved[0][1], c->d_pred_saved[1][0], c->d_pred_saved[1][1], c->d_pred_saved[2][0],
-                    c->d_pred_saved[2][1], c->d_pred_saved[3][0], c->d_pred_saved[3][1]};
+                    c->d_pred_saved[2][1], c->d_pred_saved[3][0], c->d_pred_saved[3][1], c->d_energy, c->d_energy_box};
     for (void *p : ptrs)
       if (p)
         hipFree(p);
@@ -1995,7 +2069,7 @@ namespace mi_detail
     HIPCHK(c, hipMalloc((void **)&c->d_work, size_t(W_COUNT) * size_t(c->n) * sizeof(double)));
     HIPCHK(c, hipMalloc((void **)&c->d_saved, size_t(6) * size_t(c->n) * sizeof(double)));
     HIPCHK(c, hipMalloc((void **)&c->d_part, size_t(8) * MAX_PART * sizeof(double)));
-    HIPCHK(c, hipMalloc((void **)&c->d_sc, 16 * sizeof(double)));
+    HIPCHK(c, hipMalloc((void **)&c->d_sc, 20 * sizeof(double)));
     HIPCHK(c, hipMalloc((void **)&c->d_flags, 4 * sizeof(int32_t)));
     const size_t nif = std::max<size_t>(m.iface_nodes.size(), 1) * size_t(c->dim);
     HIPCHK(c, hipMalloc((void **)&c->d_iface_buf, nif * sizeof(double)));
@@ -2564,6 +2638,26 @@ int mi_assemble(mi_ctx *c, double *res_norm)
 int mi_assemble_residual(mi_ctx *c, double *res_norm)
 {
   return assemble_impl(c, true, res_norm);
+}
+
+// Strain energy, kinetic energy and body-force potential of the committed state (MI_V_TOTAL_DISPLACEMENT, MI_V_VELOCITY).
+// Needs no matrix, record or hierarchy and changes none: every mode of a context, every slab of a team (each sums the cells
+// it owns; one all-reduce of the three sums and the inverted flag); no timing slot, no counter
+int mi_energy(mi_ctx *c, mi_energy_info *out)
+{
+  if (!c || !out)
+    return c ? fail(c, MI_EINVAL, "mi_energy: null argument") : MI_EINVAL;
+  HIPCHK(c, hipSetDevice(c->device));
+  Team &T = *c->team;
+  for (mi_ctx *m : T.members)
+    if (const int rc = enqueue_energy(m))
+      return m == c ? rc : fail(c, rc, "%s", m->err.c_str());
+  double    inverted = 0;
+  const int rc       = energy_finish(T, out, &inverted);
+  if (rc == MI_OK && inverted > 0.0) // ln J has no value there; the same error as an assembly of this state gives
+    return fail(c, MI_EINVAL, "inverted element: det F <= 0 at a quadrature point (the displacement has folded a cell; the "
+                              "reference asserts det F > 0, nonlinear_elasticity.cc:935)");
+  return rc;
 }
 
 int mi_comm_info(const mi_ctx *c, int *team_size, int *rccl_ranks)

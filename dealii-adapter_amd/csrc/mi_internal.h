@@ -245,6 +245,11 @@ struct mi_ctx
   int32_t  *d_band_perm = nullptr;
   int       band_hbw = 0;
   int       solver_direct = 0; // tuning "solver_type" 1: mi_newmark_step / mi_linear_step solve with the banded Cholesky
+  // energy diagnostics (mi_energy), allocated on first use: the cells' three numbers [ncells][3] + the partial sums behind them;
+  // [ncells][4] cell boxes of its own where the context has none (d_cellbox switches assemble_q2sf's geometry, and the call
+  // must not change what a later assembly computes)
+  double   *d_energy = nullptr, *d_energy_box = nullptr;
+  bool      energy_box_checked = false;
   uint16_t *d_off   = nullptr;
   uint8_t  *d_cmask = nullptr;
   double   *h_pinned = nullptr; // pinned host scratch (scalars, flags, interface buffer)
@@ -344,6 +349,10 @@ namespace mi_detail
   void linear_destroy(mi_ctx *c);
   int  build_slot_tables(mi_ctx *c);
   int  upload_cellbox(mi_ctx *c);
+  // energy diagnostics: a slab's four scalars [strain, kinetic, body, inverted flag] on the device; their sum over the team
+  // in one all-reduce and the read-back (mi_energy, mi_linear_energy)
+  double *energy_scalars(mi_ctx *c);
+  int     energy_finish(Team &T, mi_energy_info *out, double *inverted);
   // matrix-free linear model: slot tables, slots and cell boxes where absent, the tangent array released / allocated again
   int  linear_mf_prepare(mi_ctx *c);
   int  linear_mf_leave(mi_ctx *c);

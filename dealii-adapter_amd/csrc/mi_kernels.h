@@ -228,6 +228,21 @@ namespace mi
     double       *inverted;     // as AsmParams::inverted
   };
 
+  // energy diagnostics (see energy_q3 / energy_q2 / energy_cells): the state, the material, where the cells' three numbers go.
+  // The two sum-factorised forms take mesh tables, 1D tables and geometry from MfParams; energy_cells from here
+  struct EnergyParams
+  {
+    const int32_t *conn;   // [ncells][npc] colour-sorted
+    const double  *cverts; // [ncells][2^dim][dim]
+    const double  *tab1d;  // the assembly's tables (AsmParams::tab1d)
+    const double  *u, *v;  // total displacement (committed state), velocity
+    double         mu, kappa, rho;
+    double         body[3];
+    double        *cell_e;   // [ncells][3] strain, kinetic, body-force potential of every cell
+    double        *inverted; // as AsmParams::inverted (a slot of its own)
+    int32_t        own_node_end; // a cell whose first node is this or a later one belongs to the slab's ghost layer: zeros
+  };
+
   // matrix-free operator of the linear model on 3D Q3 cells (see mf_linear_q3): y = (c_K K + c_M M) x
   struct MfLinearOp
   {
@@ -391,6 +406,12 @@ namespace mi
   // (MfParams::yc / dst / slot_inline, the product's), from u + du and the acceleration; with pp.rec set, the records of
   // launch_mf_records_q3 into it as well (null: the residual-only pass).  launch_residual_gather then sums the slots into system_rhs
   void launch_mf_point_pass_q3(const MfParams &p, const MfPointPass &pp, int32_t cell_count, hipStream_t s);
+  // energy diagnostics: every cell's strain energy, kinetic energy and body-force potential into e.cell_e, by the kernel of
+  // (dim, degree) -- energy_q3, energy_q2 (p.conn, p.tab1d, p.cverts / p.cellbox) or energy_cells; generic: energy_cells on
+  // 3D Q2 / Q3 too (cross-check).  -1: no kernel for the element.  launch_energy_sum: the cells' numbers in a fixed order into
+  // out[3]; scratch holds 3 doubles per 1024 cells
+  int  launch_energy(int dim, int degree, const MfParams &p, const EnergyParams &e, int32_t cell_count, bool generic, hipStream_t s);
+  void launch_energy_sum(const double *cell_e, int64_t ncells, double *scratch, double *out, hipStream_t s);
   // ... the multigrid smoother's operator on the element's full-order rule, 4 x 4 x 4 points (see mf_spmv_q3s): records
   // [ncells][MF_NREC][64] of its own (MfParams::qrec_q3s, written by mf_records_q3s from u + du with the fold rule of
   // mf_records27), the rule's 1D tables MfParams::tab_q3s; one wave per cell, the results into the same cell-major slots

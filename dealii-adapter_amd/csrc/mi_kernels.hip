@@ -4559,6 +4559,376 @@ namespace mi
     MI_WAVE_SYNC();
     mfq3s_integrate(prm, S, D, R, t, ti, cell);
   }
+  // ------------------------------------------------------------------ energy diagnostics (mi_energy)
+  // Three numbers per cell, [cell][3] of EnergyParams::cell_e, from the committed state u and the velocity v:
+  //   strain   sum_q Psi(F(u)) JxW,  Psi = kappa/4 (J^2 - 1 - 2 ln J) + mu/2 (J^(-2/d) tr(F F^T) - d)
+  //            (get_Psi, compressible_neo_hook_material.h:30-35, 62-72) on the assembly's rule qf_cell (nonlinear_elasticity.cc:74)
+  //   kinetic  sum_q 1/2 rho |v_h|^2 JxW
+  //   body     sum_q -rho b . u_h JxW
+  // The forward half of the residual pass and a reduction: no slots, no back-contraction, no record.  A cell of a slab's ghost
+  // layer (first node at or behind own_node_end) stores zeros; a point with det F <= 0 raises *inverted and adds no Psi (ln J
+  // has no value there).  The sums are in a fixed order -- the wave's reduction network, then the waves in ascending order
+  // through LDS -- so a call repeats bit by bit; energy_sum adds the cells in a fixed order too.  Three forms, chosen by
+  // launch_energy as the assembly chooses its kernel: energy_q3 (3D Q3, the shape of mf_point_pass_q3 up to the point stage),
+  // energy_q2 (3D Q2, the forward half of mf_spmv), energy_cells (every other element; plain loops over the cell's nodes).
+  template <int DIM>
+  __device__ __forceinline__ void energy_point(const double *F, const double J, const double Jm, const double *uq, const double *vq,
+                                               const double w, const EnergyParams &ep, double e[3])
+  {
+    double ff = 0.0; // tr(F F^T) over the DIM x DIM part
+#pragma unroll
+    for (int i = 0; i < DIM; ++i)
+#pragma unroll
+      for (int j = 0; j < DIM; ++j)
+        ff = fma(F[i * 3 + j], F[i * 3 + j], ff);
+    const double psi = 0.25 * ep.kappa * (J * J - 1.0 - 2.0 * log(J)) + 0.5 * ep.mu * (Jm * ff - double(DIM));
+    double       vv = 0.0, bu = 0.0;
+#pragma unroll
+    for (int i = 0; i < DIM; ++i)
+      {
+        vv = fma(vq[i], vq[i], vv);
+        bu = fma(ep.body[i], uq[i], bu);
+      }
+    e[0] = J > 0.0 ? w * psi : 0.0;
+    e[1] = 0.5 * ep.rho * w * vv;
+    e[2] = -(ep.rho * w * bu);
+  }
+
+  // 3D Q3: 128 threads per cell, thread = point of the 5 x 5 x 5 rule (threads 125-127 contribute exact zeros).  The first wave
+  // gathers u, the second v; v's values come through the value-only passes E1'-E3' of mf_point_pass_q3 (same LDS places), u's
+  // gradients and values from mfq3_gradients; geometry from mf_geometry, F, J, J^(-2/3) from the record's own statements.
+  // Launch bounds: the general instance holds the trilinear map's 24 vertices beside H and the record's statements; built for
+  // 4 waves per SIMD it spilled 8 registers to scratch, at 3 it needs none (boxes: 110 registers, 4 waves).
+  template <bool BOX>
+  __global__ __launch_bounds__(MFQ3_NT, BOX ? 4 : 3) void energy_q3(MfParams prm, EnergyParams ep)
+  {
+    __shared__ double R0[MFQ3_R0], R1[MFQ3_R1], sT[40], sW[3];
+    const int     t    = threadIdx.x, it = t < MFQ3_NQ ? t : MFQ3_NQ - 1;
+    const int     tv   = t - MFQ3_NPC; // the second wave's item in the value pass
+    const int64_t cell = blockIdx.x;
+    if (prm.conn[cell * MFQ3_NPC] >= ep.own_node_end) // ghost layer of a slab: counted by the slab that owns it
+      {
+        if (t < 3)
+          ep.cell_e[cell * 3 + t] = 0.0;
+        return;
+      }
+    if (t < 40)
+      sT[t] = prm.tab1d[t];
+    {
+      const int     a    = t & (MFQ3_NPC - 1);
+      const int32_t node = prm.conn[cell * MFQ3_NPC + a];
+      if (t < MFQ3_NPC)
+        {
+#pragma unroll
+          for (int c = 0; c < 3; ++c)
+            R1[c * MFQ3_NPC + a] = ep.u[int64_t(node) * 3 + c];
+        }
+      else
+        {
+#pragma unroll
+          for (int c = 0; c < 3; ++c)
+            R0[MFQ3_VX + c * MFQ3_NPC + a] = ep.v[int64_t(node) * 3 + c];
+        }
+    }
+    __syncthreads();
+    {
+      double S[5][4]; // uniform: scalar registers
+#pragma unroll
+      for (int q = 0; q < 5; ++q)
+#pragma unroll
+        for (int a = 0; a < 4; ++a)
+          S[q][a] = prm.tab1d[q * 4 + a];
+      if (tv >= 0 && tv < 48) // E1': line (c,k,j) = tv
+        {
+          const double x0 = R0[MFQ3_VX + tv * 4], x1 = R0[MFQ3_VX + tv * 4 + 1], x2 = R0[MFQ3_VX + tv * 4 + 2], x3 = R0[MFQ3_VX + tv * 4 + 3];
+#pragma unroll
+          for (int qx = 0; qx < 5; ++qx)
+            R0[MFQ3_VA + tv * 5 + qx] = S[qx][0] * x0 + S[qx][1] * x1 + S[qx][2] * x2 + S[qx][3] * x3;
+        }
+      __syncthreads();
+      if (tv >= 0 && tv < 60) // E2': item (c,k,qx): tv = ck * 5 + qx
+        {
+          const int ck = tv / 5, qx = tv - 5 * ck;
+          double    as[4];
+#pragma unroll
+          for (int j = 0; j < 4; ++j)
+            as[j] = R0[MFQ3_VA + (ck * 4 + j) * 5 + qx];
+#pragma unroll
+          for (int qy = 0; qy < 5; ++qy)
+            R0[MFQ3_VB + ck * 25 + qy * 5 + qx] = S[qy][0] * as[0] + S[qy][1] * as[1] + S[qy][2] * as[2] + S[qy][3] * as[3];
+        }
+      __syncthreads();
+      const int qz = it / 25, q25 = it - 25 * qz; // E3': item = point
+#pragma unroll
+      for (int c = 0; c < 3; ++c)
+        {
+          double vm = 0.0;
+#pragma unroll
+          for (int k = 0; k < 4; ++k)
+            vm = fma(sT[qz * 4 + k], R0[MFQ3_VB + (c * 4 + k) * 25 + q25], vm);
+          R0[MFQ3_VM + c * MFQ3_QS + t] = vm; // (over X' and A', both consumed; read back by this thread alone)
+        }
+    }
+    double H[3][3], V[3];
+    mfq3_gradients(prm.tab1d, sT, R0, R1, t, it, H, V); // (writes R0 below MFQ3_VX only; its barriers stand behind E3')
+    double e[3];
+    {
+      const int    qz = it / 25, qy = (it - 25 * qz) / 5, qx = it - 25 * qz - 5 * qy;
+      const double wq = prm.tab1d[MFQ3_TW + qx] * prm.tab1d[MFQ3_TW + qy] * prm.tab1d[MFQ3_TW + qz];
+      double       Ji[9], detJ;
+      mf_geometry<BOX>(prm, cell, prm.tab1d + MFQ3_TX, qx, qy, qz, Ji, detJ);
+      MF_RECORD_TAIL(false, false, static_cast<double *>(nullptr), MFQ3_QS)
+      if (!(J > 0.0)) // inverted element (nonlinear_elasticity.cc:935 asserts det F > 0)
+        *ep.inverted = 1.0;
+      const double vq[3] = {R0[MFQ3_VM + t], R0[MFQ3_VM + MFQ3_QS + t], R0[MFQ3_VM + 2 * MFQ3_QS + t]};
+      energy_point<3>(F, J, Jm, V, vq, detJ * wq, ep, e);
+      (void)rJ;
+    }
+#pragma unroll
+    for (int k = 0; k < 3; ++k)
+      e[k] = wave_sum_lane63(t < MFQ3_NQ ? e[k] : 0.0);
+    if (t == MFQ3_NT - 1) // lane 63 of the second wave
+      sW[0] = e[0], sW[1] = e[1], sW[2] = e[2];
+    __syncthreads();
+    if (t == 63)
+      {
+        double *__restrict__ o = ep.cell_e + cell * 3;
+        o[0] = e[0] + sW[0], o[1] = e[1] + sW[1], o[2] = e[2] + sW[2];
+      }
+  }
+
+  // 3D Q2: one wave per cell, lane = point of the 4 x 4 x 4 rule -- the gather and the contractions E12, E3 of mf_spmv on u
+  // (unmasked: the energy belongs to the full state), the value-only half of them on v
+  template <bool BOX>
+  __global__ __launch_bounds__(64, 4) void energy_q2(MfParams prm, EnergyParams ep)
+  {
+    constexpr int NPC = 27, PS = 20, PW = 9 * PS;
+    __shared__ double sX[3 * NPC], sXv[3 * NPC], sB[3 * PW], sBv[PW];
+    const int     lane = threadIdx.x;
+    const int64_t cell = blockIdx.x;
+    if (prm.conn[cell * NPC] >= ep.own_node_end) // ghost layer of a slab
+      {
+        if (lane < 3)
+          ep.cell_e[cell * 3 + lane] = 0.0;
+        return;
+      }
+    if (lane < NPC)
+      {
+        const int32_t node = prm.conn[cell * NPC + lane];
+#pragma unroll
+        for (int c = 0; c < 3; ++c)
+          {
+            sX[c * NPC + lane]  = ep.u[int64_t(node) * 3 + c];
+            sXv[c * NPC + lane] = ep.v[int64_t(node) * 3 + c];
+          }
+      }
+    // 1D tables: S[q][a] = N_a(x_q), D[q][a] = N_a'(x_q) (uniform -> scalar registers)
+    double S[4][3], D[4][3];
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+#pragma unroll
+      for (int a = 0; a < 3; ++a)
+        {
+          S[q][a] = prm.tab1d[q * 3 + a];
+          D[q][a] = prm.tab1d[12 + q * 3 + a];
+        }
+    const int qz = lane >> 4, q16 = lane & 15;
+    double    Sz[3], Dz[3], Sx[3], Dx[3]; // this lane's rows of the tables: qz for E3, qx = lane & 3 for E12
+#pragma unroll
+    for (int k = 0; k < 3; ++k)
+      {
+        Sz[k] = prm.tab1d[qz * 3 + k];
+        Dz[k] = prm.tab1d[12 + qz * 3 + k];
+        Sx[k] = prm.tab1d[(lane & 3) * 3 + k];
+        Dx[k] = prm.tab1d[12 + (lane & 3) * 3 + k];
+      }
+    const double wq = prm.tab1d[24 + (lane & 3)] * prm.tab1d[24 + ((lane >> 2) & 3)] * prm.tab1d[24 + qz];
+    __syncthreads();
+    // ---- E12: lane = (c*3+k)*4 + qx contracts i, then j: B_DS / B_SD / B_SS [c*3+k][qy][qx] of u, B_SS of v
+    const int pck = lane >> 2, pqx = lane & 3;
+    if (lane < 36)
+      {
+        double as[3], ad[3], av[3];
+#pragma unroll
+        for (int j = 0; j < 3; ++j)
+          {
+            const double x0 = sX[pck * 9 + j * 3], x1 = sX[pck * 9 + j * 3 + 1], x2 = sX[pck * 9 + j * 3 + 2];
+            const double v0 = sXv[pck * 9 + j * 3], v1 = sXv[pck * 9 + j * 3 + 1], v2 = sXv[pck * 9 + j * 3 + 2];
+            as[j] = Sx[0] * x0 + Sx[1] * x1 + Sx[2] * x2;
+            ad[j] = Dx[0] * x0 + Dx[1] * x1 + Dx[2] * x2;
+            av[j] = Sx[0] * v0 + Sx[1] * v1 + Sx[2] * v2;
+          }
+#pragma unroll
+        for (int qy = 0; qy < 4; ++qy)
+          {
+            const int o    = pck * PS + qy * 4 + pqx;
+            sB[o]          = S[qy][0] * ad[0] + S[qy][1] * ad[1] + S[qy][2] * ad[2]; // d/dx
+            sB[o + PW]     = D[qy][0] * as[0] + D[qy][1] * as[1] + D[qy][2] * as[2]; // d/dy
+            sB[o + 2 * PW] = S[qy][0] * as[0] + S[qy][1] * as[1] + S[qy][2] * as[2]; // value / d/dz
+            sBv[o]         = S[qy][0] * av[0] + S[qy][1] * av[1] + S[qy][2] * av[2];
+          }
+      }
+    __syncthreads();
+    // ---- E3: contract k.  lane = quadrature point; H[c][l] = d u_c / d xi_l, V[c] = u_c, Vv[c] = v_c
+    double H[3][3], V[3], Vv[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+      {
+        H[c][0] = H[c][1] = H[c][2] = V[c] = Vv[c] = 0.0;
+#pragma unroll
+        for (int k = 0; k < 3; ++k)
+          {
+            const int    o   = (c * 3 + k) * PS + q16;
+            const double bds = sB[o], bsd = sB[o + PW], bss = sB[o + 2 * PW];
+            H[c][0] = fma(Sz[k], bds, H[c][0]);
+            H[c][1] = fma(Sz[k], bsd, H[c][1]);
+            H[c][2] = fma(Dz[k], bss, H[c][2]);
+            V[c]    = fma(Sz[k], bss, V[c]);
+            Vv[c]   = fma(Sz[k], sBv[o], Vv[c]);
+          }
+      }
+    double e[3];
+    {
+      double Ji[9], detJ;
+      mf_geometry<BOX>(prm, cell, prm.tab1d + 28, lane & 3, (lane >> 2) & 3, qz, Ji, detJ);
+      MF_RECORD_TAIL(false, false, static_cast<double *>(nullptr), 64)
+      if (!(J > 0.0)) // inverted element (nonlinear_elasticity.cc:935 asserts det F > 0)
+        *ep.inverted = 1.0;
+      energy_point<3>(F, J, Jm, V, Vv, detJ * wq, ep, e);
+      (void)rJ;
+    }
+#pragma unroll
+    for (int k = 0; k < 3; ++k)
+      e[k] = wave_sum_lane63(e[k]);
+    if (lane == 63)
+      {
+        double *__restrict__ o = ep.cell_e + cell * 3;
+        o[0] = e[0], o[1] = e[1], o[2] = e[2];
+      }
+  }
+
+  // every other element (2D p = 1..4, 3D p = 1, 4 -- the reference's small geometries) and the cross-check of the two forms
+  // above: one workgroup per cell, thread = quadrature point, plain loops over the cell's nodes as in phase A of assemble_cells
+  template <int DIM, int P, int NT>
+  __global__ __launch_bounds__(NT) void energy_cells(EnergyParams ep)
+  {
+    using E = Elem<DIM, P>;
+    constexpr int NPC = E::NPC, NQ = E::NQ, NQ1 = E::NQ1, NP1 = E::NP1, NV = E::NV;
+    static_assert(NQ <= NT && NT % 64 == 0, "one thread per quadrature point, whole waves");
+    __shared__ double s_N1[NQ1 * NP1], s_dN1[NQ1 * NP1], s_qw[NQ1], s_qx[NQ1];
+    __shared__ double s_u[NPC * DIM], s_v[NPC * DIM], s_verts[NV * DIM], s_red[NT / 64];
+    const int     tid  = threadIdx.x;
+    const int64_t cell = blockIdx.x;
+    if (ep.conn[cell * NPC] >= ep.own_node_end) // ghost layer of a slab
+      {
+        if (tid < 3)
+          ep.cell_e[cell * 3 + tid] = 0.0;
+        return;
+      }
+    for (int i = tid; i < NQ1 * NP1; i += NT)
+      {
+        s_N1[i]  = ep.tab1d[i];
+        s_dN1[i] = ep.tab1d[NQ1 * NP1 + i];
+      }
+    if (tid < NQ1)
+      {
+        s_qw[tid] = ep.tab1d[2 * NQ1 * NP1 + tid];
+        s_qx[tid] = ep.tab1d[2 * NQ1 * NP1 + NQ1 + tid];
+      }
+    if (tid < NV * DIM)
+      s_verts[tid] = ep.cverts[cell * (NV * DIM) + tid];
+    for (int i = tid; i < NPC * DIM; i += NT)
+      {
+        const int     a = i / DIM, c = i - a * DIM;
+        const int64_t g = int64_t(ep.conn[cell * NPC + a]) * DIM + c;
+        s_u[i]          = ep.u[g];
+        s_v[i]          = ep.v[g];
+      }
+    __syncthreads();
+    double e[3] = {0.0, 0.0, 0.0};
+    if (tid < NQ)
+      {
+        const int q = tid;
+        double    gxi[9], uq[3] = {0.0, 0.0, 0.0}, vq[3] = {0.0, 0.0, 0.0};
+#pragma unroll
+        for (int k = 0; k < 9; ++k)
+          gxi[k] = 0.0;
+        for (int a = 0; a < NPC; ++a)
+          {
+            double N, dN[3];
+            shape_at_qp<DIM, P>(s_N1, s_dN1, q, a, N, dN);
+#pragma unroll
+            for (int i = 0; i < DIM; ++i)
+              {
+                const double ui = s_u[a * DIM + i];
+#pragma unroll
+                for (int j = 0; j < DIM; ++j)
+                  gxi[i * 3 + j] = fma(ui, dN[j], gxi[i * 3 + j]);
+                uq[i] = fma(ui, N, uq[i]);
+                vq[i] = fma(s_v[a * DIM + i], N, vq[i]);
+              }
+          }
+        double    xi[3] = {0.0, 0.0, 0.0}, wq = 1.0;
+        const int qi[3] = {q % NQ1, (q / NQ1) % NQ1, (DIM == 3) ? q / (NQ1 * NQ1) : 0};
+#pragma unroll
+        for (int d = 0; d < DIM; ++d)
+          {
+            xi[d] = s_qx[qi[d]];
+            wq *= s_qw[qi[d]];
+          }
+        double Jm[9], Ji[9];
+        q1_jacobian<DIM>(s_verts, xi, Jm);
+        const double detJ = det3x3(Jm);
+        inv3x3(Jm, detJ, Ji);
+        double F[9]; // I + grad_xi u Jinv, embedded in 3 x 3
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+#pragma unroll
+          for (int j = 0; j < 3; ++j)
+            F[i * 3 + j] = (i < DIM && j < DIM) ? gxi[i * 3 + 0] * Ji[0 * 3 + j] + gxi[i * 3 + 1] * Ji[1 * 3 + j] +
+                                                    (DIM == 3 ? gxi[i * 3 + 2] * Ji[2 * 3 + j] : 0.0) :
+                                                  0.0;
+        F[0] += 1.0, F[4] += 1.0, F[8] += 1.0;
+        const double J = det3x3(F);
+        if (!(J > 0.0)) // inverted element (nonlinear_elasticity.cc:935 asserts det F > 0)
+          *ep.inverted = 1.0;
+        const double Jd = (DIM == 3) ? 1.0 / (cbrt(J) * cbrt(J)) : 1.0 / J; // J^(-2/d)
+        energy_point<DIM>(F, J, Jd, uq, vq, detJ * wq, ep, e);
+      }
+#pragma unroll
+    for (int k = 0; k < 3; ++k)
+      e[k] = block_sum<NT>(e[k], s_red);
+    if (tid == 0)
+      {
+        double *__restrict__ o = ep.cell_e + cell * 3;
+        o[0] = e[0], o[1] = e[1], o[2] = e[2];
+      }
+  }
+
+  // the cells' numbers summed in a fixed order: workgroup b adds the items [b chunk, (b + 1) chunk) of in[n][3] into
+  // out[b][3] (thread-strided, then block_sum) -- once over the cells, once over the workgroups' sums; no atomics
+  __global__ __launch_bounds__(256) void energy_sum(const double *__restrict__ in, const int64_t n, const int64_t chunk,
+                                                    double *__restrict__ out)
+  {
+    __shared__ double s_red[4];
+    const int64_t i0 = blockIdx.x * chunk, i1 = imin64(n, i0 + chunk);
+    double        s[3] = {0.0, 0.0, 0.0};
+    for (int64_t i = i0 + threadIdx.x; i < i1; i += 256)
+      {
+        s[0] += in[i * 3];
+        s[1] += in[i * 3 + 1];
+        s[2] += in[i * 3 + 2];
+      }
+#pragma unroll
+    for (int k = 0; k < 3; ++k)
+      s[k] = block_sum<256>(s[k], s_red);
+    if (threadIdx.x == 0)
+      {
+        out[blockIdx.x * 3]     = s[0];
+        out[blockIdx.x * 3 + 1] = s[1];
+        out[blockIdx.x * 3 + 2] = s[2];
+      }
+  }
   // (the last matrix-free kernel: the shared text ends here)
 #undef MF_RECORD_TAIL
 #undef MF_M
@@ -7628,6 +7998,51 @@ namespace mi
       return;
     auto *kern = p.cellbox ? mf_point_pass_q3<true> : mf_point_pass_q3<false>;
     hipLaunchKernelGGL(kern, dim3(cell_count), dim3(MFQ3_NT), 0, s, p, pp);
+  }
+  int launch_energy(int dim, int degree, const MfParams &p, const EnergyParams &e, int32_t cell_count, bool generic, hipStream_t s)
+  {
+    if (cell_count <= 0)
+      return 0;
+    if (dim == 3 && degree == 3 && !generic)
+      {
+        auto *kern = p.cellbox ? energy_q3<true> : energy_q3<false>;
+        hipLaunchKernelGGL(kern, dim3(cell_count), dim3(MFQ3_NT), 0, s, p, e);
+        return 0;
+      }
+    if (dim == 3 && degree == 2 && !generic)
+      {
+        auto *kern = p.cellbox ? energy_q2<true> : energy_q2<false>;
+        hipLaunchKernelGGL(kern, dim3(cell_count), dim3(64), 0, s, p, e);
+        return 0;
+      }
+#define MI_EN(D_, P_, NT_)                                                                                          \
+  if (dim == D_ && degree == P_)                                                                                    \
+    {                                                                                                               \
+      hipLaunchKernelGGL((energy_cells<D_, P_, NT_>), dim3(cell_count), dim3(NT_), 0, s, e);                        \
+      return 0;                                                                                                     \
+    }
+    MI_EN(3, 1, 64)
+    MI_EN(3, 2, 64)
+    MI_EN(3, 3, 128)
+    MI_EN(3, 4, 256)
+    MI_EN(2, 1, 64)
+    MI_EN(2, 2, 64)
+    MI_EN(2, 3, 64)
+    MI_EN(2, 4, 64)
+#undef MI_EN
+    return -1;
+  }
+  void launch_energy_sum(const double *cell_e, int64_t ncells, double *scratch, double *out, hipStream_t s)
+  {
+    const int64_t chunk = 1024;
+    const int     nblk  = int((ncells + chunk - 1) / chunk);
+    if (nblk <= 1)
+      {
+        hipLaunchKernelGGL(energy_sum, dim3(1), dim3(256), 0, s, cell_e, ncells, ncells, out);
+        return;
+      }
+    hipLaunchKernelGGL(energy_sum, dim3(nblk), dim3(256), 0, s, cell_e, ncells, chunk, scratch);
+    hipLaunchKernelGGL(energy_sum, dim3(1), dim3(256), 0, s, scratch, int64_t(nblk), int64_t(nblk), out);
   }
   void launch_mf_diag_q3(const MfParams &p, double *slots6, int32_t cell_count, hipStream_t s)
   {

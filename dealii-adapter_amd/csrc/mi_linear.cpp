@@ -478,6 +478,56 @@ int mi_linear_step(mi_ctx *c, int data_consistent, double abs_tol, int64_t max_i
   return sync(c0);
 }
 
+// 1/2 u . (K u), 1/2 v . (M v), -u . f_body: two products of the current set-up with the dot product fused (their partials
+// count per workgroup of the product: the slot gather's or the sliced-ELL launch's, as in cg_run), one reduction of the
+// body-force vector, the three sums in one all-reduce.  No new point kernel
+int mi_linear_energy(mi_ctx *c, mi_energy_info *out)
+{
+  if (!c || !out)
+    return c ? fail(c, MI_EINVAL, "mi_linear_energy: null argument") : MI_EINVAL;
+  if (!c->linear)
+    return fail(c, MI_EINVAL, "mi_linear_setup has not been called");
+  HIPCHK(c, hipSetDevice(c->device));
+  Team &T    = *c->team;
+  auto  self = [](mi_ctx *m) { return m; };
+  int   rc   = MI_OK;
+  for (int w = 0; w < 2 && !rc; ++w) // K on the displacement, M on the velocity
+    {
+      const int               vid = w == 0 ? MI_L_DISPLACEMENT : MI_L_VELOCITY;
+      std::vector<SpmvFusion> fu;
+      for (mi_ctx *m : T.members)
+        {
+          linear_select(m, w);
+          fu.push_back(SpmvFusion{m->vec(vid), m->part(5 + w), nullptr});
+        }
+      rc = team_spmv(T, self, [vid](mi_ctx *m) { return m->vec(vid); }, [](mi_ctx *m) { return m->work(W_Q); }, fu.data());
+      for (mi_ctx *m : T.members)
+        {
+          const int np = m->linear->mf ? m->grid_gdot : m->grid_spmv;
+          mi::launch_finish_sum(m->part(5 + w), np, energy_scalars(m) + w, m->stream);
+          linear_select(m, -1);
+        }
+    }
+  if (rc)
+    return rc;
+  for (mi_ctx *m : T.members)
+    {
+      double *sc = energy_scalars(m);
+      HIPCHK(m, hipMemsetAsync(sc + 2, 0, 2 * sizeof(double), m->stream));
+      if (m->linear->body_force_enabled)
+        {
+          mi::launch_dot_partials(m->vec(MI_L_DISPLACEMENT) + m->own0, m->linear->d_body + m->own0, m->own_n, m->part(7), m->grid_vec,
+                                  m->stream);
+          mi::launch_finish_sum(m->part(7), m->grid_vec, sc + 2, m->stream);
+        }
+    }
+  HIPCHK(c, hipGetLastError());
+  if ((rc = energy_finish(T, out, nullptr)))
+    return rc;
+  out->strain *= 0.5, out->kinetic *= 0.5, out->body = -out->body;
+  return MI_OK;
+}
+
 int mi_linear_matrix_get_csr(mi_ctx *c, int which, int64_t *rowptr, int32_t *col, double *val)
 {
   if (!c->linear || which < 0 || which > 2)

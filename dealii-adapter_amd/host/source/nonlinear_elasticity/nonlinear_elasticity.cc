@@ -369,6 +369,9 @@ namespace Nonlinear_Elasticity
   template <int dim>
   void Solid<dim>::log_step_json() const
   {
+    // what the structure holds after the step (collective: every rank asks, rank 0 writes)
+    mi_energy_info energy{};
+    device->check(mi_energy(device->ctx(), &energy), "mi_energy");
     if (mi::host_rank() > 0)
       return;
     std::ofstream out(parameters.output_folder + "/steps.jsonl", std::ios::app);
@@ -377,7 +380,8 @@ namespace Nonlinear_Elasticity
     out << std::setprecision(17) << "{\"timestep\": " << time.get_timestep() << ", \"time\": " << time.current()
         << ", \"newton_iterations\": " << last_newton_iterations << ", \"linear_iterations\": " << last_lin_iterations
         << ", \"residual_abs\": " << error_residual.u << ", \"update_abs\": " << error_update.u
-        << ", \"n_dofs\": " << mi_n_dofs(device->ctx()) << "}\n";
+        << ", \"n_dofs\": " << mi_n_dofs(device->ctx()) << ", \"strain_energy\": " << energy.strain
+        << ", \"kinetic_energy\": " << energy.kinetic << ", \"body_potential\": " << energy.body << "}\n";
   }
 
   // :1215-1254: solution-XXX.vtk with index timestep / output_interval

@@ -183,6 +183,30 @@ int mi_newmark_step(mi_ctx *ctx, const mi_solver_desc *s, mi_step_info *info);
 int mi_state_save(mi_ctx *ctx);
 int mi_state_restore(mi_ctx *ctx);
 
+/* ---- energy diagnostics ------------------------------------------------------------------ */
+/* What the structure holds, summed on the device.  The reference has the stored-energy function (get_Psi) but never
+ * integrates it; a caller logs these per step to watch drift, an unstable coupling, or whether a run has settled.
+ * NOT a term: the work of the interface traction.  With the reference's pull-back at the cell point (nonlinear_elasticity.cc:
+ * 825-827) that load has no potential; a caller who wants a balance accumulates f_ext . delta u itself. */
+typedef struct
+{
+  double strain;   /* nonlinear: sum over cells and points of Psi(F(u)) JxW, Psi = get_Psi = kappa/4 (J^2 - 1 - 2 ln J) +
+                      mu/2 (J^(-2/dim) tr(F F^T) - dim) (compressible_neo_hook_material.h:30-35, 62-72), rule qf_cell =
+                      QGauss(p+2) (nonlinear_elasticity.cc:74); linear: 1/2 u^T K u                                     */
+  double kinetic;  /* 1/2 rho int |v_h|^2 on the model's own rule = 1/2 v^T M v with the consistent mass the model
+                      itself uses (nonlinear: QGauss(p+2); linear: the M of linear_elasticity.cc:248-374, QGauss(p+1))  */
+  double body;     /* potential of the body force: -rho int b . u_h  (linear: -u . body-force vector of :358-373)       */
+  double reserved; /* 0 */
+} mi_energy_info;
+/* Nonlinear model, COMMITTED state: reads MI_V_TOTAL_DISPLACEMENT and MI_V_VELOCITY alone -- not + MI_V_SOLUTION_DELTA:
+ * after mi_newmark_finish_step the delta is already folded into u; inside a step the numbers are those of the last
+ * finished step.  Modifies no vector, record, matrix, hierarchy, counter or timing, and needs no matrix: every (dim, degree)
+ * an assembly supports, "fine_level" 0 and 1, after a "linear_operator" 1 set-up has released the tangent array, single,
+ * emulated and RCCL teams (collective: every rank calls and receives the same numbers; each slab sums the cells it owns).
+ * Bitwise repeatable (per-cell sums, then a fixed-order reduction; no floating-point atomics).  A point with det F <= 0:
+ * MI_EINVAL "inverted element" as from mi_assemble, since ln J has no value there. */
+int mi_energy(mi_ctx *ctx, mi_energy_info *out);
+
 /* ---- linear model: ElastoDynamics (source/linear_elasticity/linear_elasticity.cc) -------------------------- */
 /* state vectors of the linear model live in the same slots as the nonlinear ones */
 enum
@@ -202,6 +226,11 @@ int mi_linear_setup(mi_ctx *ctx, double theta);
  * 0 "Force" nodal forces), solve (:525-575; Jacobi-PCG -- multigrid-PCG with "linear_precond" 1 --, absolute tolerance, warm
  * start from the previous velocity), update_displacement (:579-586) */
 int mi_linear_step(mi_ctx *ctx, int data_consistent, double abs_tol, int64_t max_it, int *its, double *res);
+/* energies of the linear model after mi_linear_setup (MI_EINVAL without one): 1/2 u . (K u), 1/2 v . (M v) and -u . f_body with
+ * u = MI_L_DISPLACEMENT, v = MI_L_VELOCITY, through the products the current set-up runs -- the sliced-ELL product on the
+ * assembled K and M, or mf_linear_q3 + the slot gather ("linear_operator" 1), each with the dot product fused.  Runs
+ * wherever mi_linear_step runs, teams included (collective).  Overwrites the solver's work vectors, no state vector. */
+int mi_linear_energy(mi_ctx *ctx, mi_energy_info *out);
 /* K (0), M (1) or the constrained stepping matrix (2) as scalar CSR, for parity tests */
 int mi_linear_matrix_get_csr(mi_ctx *ctx, int which, int64_t *rowptr, int32_t *col, double *val);
 /* y = K x (0), M x (1) or A x (2) through the device kernels the current set-up runs, in either mode of "linear_operator"
@@ -472,7 +501,8 @@ int mi_set_profiling(mi_ctx *ctx, int enable);
  * MI_MG_BLOCK, MI_MG_COARSEST, MI_MG_DENSE, MI_MG_FACTOR, MI_MG_SAFETY, MI_MG_POWER_ITS,
  * MI_MG_COARSE_DEGREE, MI_MG_COARSE_RATIO, MI_MG_FUSE_MAX_NODES, MI_MG_VERBOSE (multigrid parameters);
  * MI_MF_XCD (XCD-aware cell order of mf_spmv), MI_ASM_CELL_LATTICE, MI_ASM_STAMPS / MI_MF_STAMPS / MI_MF_DBG (phase stamps
- * and timing-only ablations of the two element kernels). */
+ * and timing-only ablations of the two element kernels), MI_ENERGY_GENERIC (mi_energy through the generic kernel on 3D Q2 / Q3
+ * too: the cross-check of tools/energy_generic_check.py). */
 int mi_set_tuning(mi_ctx *ctx, const char *key, int value);
 /* Read back.  Counters since the last mi_reset_timings (what a solve costs in latency-bound events; counted on one slab
  * as well, where the collectives themselves are no-ops): "count_scalar_allreduce", "count_scalar_allreduce_cg" (those inside
