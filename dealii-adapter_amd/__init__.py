@@ -272,6 +272,10 @@ class LevelView:
     def diagonal_blocks(self):
         return Context.diagonal_blocks(self)
 
+    def get_tuning(self, key):
+        """read-backs of the level's own context ("spmv_lds_launches", "spmv_split_launches": the kernel its products run)"""
+        return Context.get_tuning(self, key)
+
     # a level of the linear model's hierarchy (mi_linear_mg_level_context)
     def linear_csr(self, which):
         return Context.linear_csr(self, which)

@@ -3578,6 +3578,19 @@ int mi_get_tuning(mi_ctx *c, const char *key, int *value)
     *value = m->precond;
   else if (k == "spmv_variant")
     *value = m->spmv_variant;
+  else if (k == "spmv_lds_launches" || k == "spmv_split_launches")
+    {
+      // launches of one sliced-ELL product of this context: the interior and the boundary launch of every slab that have a
+      // slice, by the kernel enqueue_spmv gives them (split_int / split_bnd).  Answers on a borrowed level context too.
+      const bool want_split = k == "spmv_split_launches";
+      int        n          = 0;
+      for (const mi_ctx *s : c->team->members)
+        {
+          const int64_t nin = s->mesh.sell_nslices_interior, nbd = s->mesh.sell_nslices - nin;
+          n += (nin > 0 && s->split_int == want_split) + (nbd > 0 && s->split_bnd == want_split);
+        }
+      *value = n;
+    }
   else if (k == "count_scalar_allreduce")
     *value = int(c->team->n_scalar_allreduce);
   else if (k == "count_scalar_allreduce_cg")

@@ -481,7 +481,11 @@ int mi_set_profiling(mi_ctx *ctx, int enable);
  *                                                  through the unassembled form | streaming calibration kernels
  *  sell_icol            1 | 0                      column indices generated from the rows' column boxes | read          MI_SELL_ICOL
  *  sell_unroll, spmv_grid, xcd_remap               launch shape of the sliced-ELL product (MI_SELL_SPLIT=0: never the   MI_SELL_UNROLL
- *                                                  one-workgroup-per-slice kernel on short launches)
+ *                                                  one-workgroup-per-slice kernel on short launches).  Read-backs
+ *                                                  "spmv_lds_launches" / "spmv_split_launches": how many launches of one
+ *                                                  sliced-ELL product of the context (interior and boundary rows of every
+ *                                                  slab, those with a slice) run sell_spmv / sell_spmv_split; no setter;
+ *                                                  answered on a borrowed multigrid level context too
  *  cg_fused_dot         1 | 0                      p.q partials in the product's epilogue | separate reduction          MI_CG_FUSED_DOT
  *  small_cg             1 | 0                      matrices <= 1 MiB: whole Jacobi-PCG in one launch | three launches   MI_SMALL_CG
  *                                                  per iteration
@@ -511,7 +515,8 @@ int mi_set_tuning(mi_ctx *ctx, const char *key, int value);
  * are matrix-free / use the stored element tangents, 0: the assembled matrix), "precond", "spmv_variant",
  * "mf_single_launch", "cell_lattice", "mg_refresh_every", "cg_speculate", "halo_skip", "cut_axis" (1 / 2 / 3: the slabs
  * are cut along x / y / z, 0: not decomposed), "cg_single_reduction_active", "mg_distributed_levels" (multigrid levels cut
- * into slabs; 0 on one slab). */
+ * into slabs; 0 on one slab), "spmv_lds_launches" / "spmv_split_launches" (launches of one sliced-ELL product on
+ * sell_spmv / sell_spmv_split; read-only). */
 int mi_get_tuning(mi_ctx *ctx, const char *key, int *value);
 int mi_reset_timings(mi_ctx *ctx);
 int mi_get_timings(mi_ctx *ctx, mi_timings *out);

@@ -350,6 +350,16 @@ CASES = {
     "q2_4416_induced": dict(dim=3, p=2, reps=(4, 4, 16), kind="cube", roles=ROLES_A, slabs=2, cut_axis=3,
                             keys=[("mg_dist_nodes", 0)]),
 }
+# Mid-size cases, a table of their own (CASES and what was measured on it stay what they are): the smallest meshes of their
+# kind with more than 10,240 nodes, i.e. more than 160 slices of 64 rows, above which a product of level 0 leaves
+# sell_spmv_split for sell_spmv (tests/test_gpu_sell_lds_product.py); vertices moved by 5 % of the cell size.
+# e_ref of these cases, float64 against long double cycle as for E_REF (tests/test_mirror_multigrid.py): q1_3d 6.22e-16,
+# q2_11 9.04e-16, 2d_q4 8.16e-16 -- within E_REF, so the tolerance of the GPU tests is the one of CASES.
+MID_CASES = {
+    "q1_3d": dict(dim=3, p=1, reps=(22, 21, 21), kind="perturbed", roles=ROLES_A),
+    "q2_11": dict(dim=3, p=2, reps=(11, 11, 11), kind="perturbed", roles=ROLES_A),
+    "2d_q4": dict(dim=2, p=4, reps=(26, 25), kind="perturbed", roles=ROLES_2D),
+}
 
 
 def geometry(kind, dim, reps, seed):
@@ -358,6 +368,9 @@ def geometry(kind, dim, reps, seed):
     lo = (0.0,) * dim
     if kind == "cube":
         return lo, tuple(0.1 * reps), None
+    if kind == "perturbed":  # cells of 0.1, every vertex moved by 5 % of that (standard deviation)
+        nverts = int(np.prod(reps + 1))
+        return lo, tuple(0.1 * reps), 0.05 * 0.1 * np.random.default_rng(seed).standard_normal((nverts, dim))
     h = np.array([0.13, 0.1, 0.07])[:dim]
     hi = tuple(h * reps)
     rng = np.random.default_rng(seed)
@@ -370,8 +383,12 @@ def geometry(kind, dim, reps, seed):
     return lo, hi, 0.08 * h.min() * rng.standard_normal((len(vid), dim))
 
 
+def case(name):
+    return CASES[name] if name in CASES else MID_CASES[name]
+
+
 def case_mesh(name):
-    c = CASES[name]
+    c = case(name)
     lo, hi, perturb = geometry(c["kind"], c["dim"], c["reps"], seed=sum(c["reps"]))
     return Mi.Mesh(c["dim"], c["p"], c["reps"], lo, hi, c["roles"], perturb=perturb), lo, hi, perturb
 
@@ -407,7 +424,7 @@ def case_state(m, seed, amplitude=0.25):
 
 
 def case_reference(name, u_total, m, **kw):
-    c = CASES[name]
+    c = case(name)
     args = dict(coarsest=c.get("coarsest", 4), dense=c.get("dense", 1), nq0=c.get("nq0"), fold0=c.get("fold0", False), alpha1=A1)
     args.update(kw)
     return Reference(m, u_total, **args)

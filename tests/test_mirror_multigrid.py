@@ -9,7 +9,11 @@
   * with an exact coarsest level and many smoother steps on a two-level hierarchy, B_ref A approaches the identity
     (|B A x - x| / |x| = 0.18, 1.3e-3, 2.0e-12 for nu = 2, 8, 30);
   * e_ref, the relmax between the float64 and the long double cycle on a random right-hand side, for every case of the GPU
-    table.  Measured worst: 8.98e-16 (case q2_4416_induced); mg_reference.E_REF = 1.0e-15 is what the GPU tolerance rests on.
+    table.  Measured worst: 8.98e-16 (case q2_4416_induced); mg_reference.E_REF = 1.0e-15 is what the GPU tolerance rests on;
+  * the same for the mid-size cases mg_reference.MID_CASES (level 0 above 10,240 nodes, tests/test_gpu_sell_lds_product.py),
+    whose shapes are written by hand too.  Measured: q1_3d 6.22e-16, q2_11 9.04e-16, 2d_q4 8.16e-16 -- within E_REF, so
+    these cases take the GPU tolerance of the others.  A case builds its hierarchy in 4 to 30 s and runs the long double
+    cycle in under a second.
 """
 import os
 import sys
@@ -54,6 +58,23 @@ def test_hierarchy_shapes_equal_the_hand_written_lists():
     # the hierarchy-rebuild test's shapes of case 1
     assert [l["reps"] for l in R.hierarchy(3, 2, (6, 5, 4), 2, 1)] == [(6, 5, 4), (6, 5, 4), (3, 3, 2), (2, 2, 2)]
     assert [(l["exact"], l["nu"]) for l in R.hierarchy(3, 2, (6, 5, 4), 4, 0)] == [(0, 3), (0, 2), (0, 12)]
+
+
+MID_SHAPES = {
+    "q1_3d": [(1, (22, 21, 21), 33396, 0), (1, (11, 11, 11), 5184, 0), (1, (6, 6, 6), 1029, 0), (1, (3, 3, 3), 192, 1)],
+    "q2_11": [(2, (11, 11, 11), 36501, 0), (1, (11, 11, 11), 5184, 0), (1, (6, 6, 6), 1029, 0), (1, (3, 3, 3), 192, 1)],
+    "2d_q4": [(4, (26, 25), 21210, 0), (1, (26, 25), 1404, 0), (1, (13, 13), 392, 0), (1, (7, 7), 128, 0), (1, (4, 4), 50, 1)],
+}
+
+
+def test_mid_case_shapes_equal_the_hand_written_lists():
+    assert sorted(MID_SHAPES) == sorted(R.MID_CASES) and not set(R.MID_CASES) & set(R.CASES)
+    for name, c in R.MID_CASES.items():
+        h = R.hierarchy(c["dim"], c["p"], c["reps"])
+        assert [(l["degree"], l["reps"], l["n_dofs"], l["exact"]) for l in h] == MID_SHAPES[name], name
+        assert h[0]["n_dofs"] // c["dim"] > 160 * 64  # more than SELL_SPLIT_MAX_SLICES slices of 64 rows on level 0
+        lo, hi, perturb = R.geometry(c["kind"], c["dim"], c["reps"], seed=sum(c["reps"]))
+        assert np.allclose(hi, 0.1 * np.array(c["reps"])) and 0.004 < perturb.std() < 0.006  # 5 % of the cell size
 
 
 SMALL = [(3, 2, (3, 2, 2), R.ROLES_A), (3, 1, (5, 4, 3), R.ROLES_B), (2, 2, (6, 4), R.ROLES_2D)]
@@ -137,20 +158,32 @@ def test_two_level_cycle_with_many_smoother_steps_approaches_the_inverse():
     assert err[0] > err[1] > err[2] and err[2] < 1e-6
 
 
+def _e_ref(name):
+    m = R.case_mesh(name)[0]
+    u, du = R.case_state(m, seed=len(name))
+    ref = R.case_reference(name, u + du, m)
+    lmax = ref.true_lmax()
+    r = np.random.default_rng(5).standard_normal(m.n) * ~m.constrained
+    z, zl = ref.vcycle(r, lmax), ref.vcycle(r, lmax, np.longdouble)
+    e = float(np.abs(z - zl).max() / np.abs(zl).max())
+    print("e_ref %-20s %.2e" % (name, e))
+    return e
+
+
 def test_reference_rounding_on_the_gpu_cases():
     """e_ref per case of the GPU table: float64 against long double cycle, random right-hand side, true lmax x 1.15"""
     assert np.finfo(np.longdouble).eps < 1e-18
     worst = 0.0
     for name in R.CASES:
-        m = R.case_mesh(name)[0]
-        u, du = R.case_state(m, seed=len(name))
-        ref = R.case_reference(name, u + du, m)
-        lmax = ref.true_lmax()
-        r = np.random.default_rng(5).standard_normal(m.n) * ~m.constrained
-        z, zl = ref.vcycle(r, lmax), ref.vcycle(r, lmax, np.longdouble)
-        e = float(np.abs(z - zl).max() / np.abs(zl).max())
-        print("e_ref %-20s %.2e" % (name, e))
+        e = _e_ref(name)
         assert e <= R.E_REF, (name, e)  # (each on its own: a NaN fails)
         worst = max(worst, e)
     print("worst e_ref %.3e" % worst)
     assert worst <= R.E_REF
+
+
+@pytest.mark.parametrize("name", sorted(R.MID_CASES))
+def test_reference_rounding_on_the_mid_cases(name):
+    """the same on a mid-size case: within E_REF, so the GPU tolerance of the small cases holds for it"""
+    assert np.finfo(np.longdouble).eps < 1e-18
+    assert _e_ref(name) <= R.E_REF
