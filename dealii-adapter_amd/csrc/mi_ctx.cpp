@@ -420,6 +420,29 @@ namespace mi_detail
            !(c->smoother_precision == 32 && c->qrec32_valid);
   }
 
+  // the smoother's fine-level products run mf_spmv<..., float>: fp32 arithmetic on the fp32 records of the current tangent
+  // (opt-in "smoother_precision" 32).  The one test for it: enqueue_spmv hands the fp32 records to the launch exactly where
+  // this holds (with the call's own condition: a smoother product), and the "smoother_precision_active" query reads it.  The
+  // records must belong to the current tangent (assemble_q2sf alone writes them: 3D Q2); the launch must have the production
+  // shape for which the float instantiation exists (one launch into cell-major slots, box cells, lattice ids); and the
+  // smoother's products must reach the element form at all, as for smoother_runs_q27.
+  bool smoother_runs_f32(const mi_ctx *c)
+  {
+    return c->smoother_precision == 32 && c->qrec32_valid && c->d_qrec32 && !c->d_qrec_q3 && element_form(c) == 2 &&
+           c->mf_slots && c->d_mf_yc && c->d_cellbox && c->lat.ncol > 0 && !c->active_sell_vals && !c->active_linear_mf &&
+           (c->mf_fine || (c->ebe != 0 && c->precond_storage == 64));
+  }
+
+  // the smoother's products of this context multiply with the fp32-rounded copy of the assembled values ("precond_storage" 32).
+  // The one test for it: enqueue_spmv's sliced-ELL branch (with the call's own condition: a smoother product) and the
+  // "precond_storage_levels" query both read it.  A matrix-free fine level has no assembled values (and refuses the key);
+  // the linear model's operators stay fp64.
+  bool smoother_reads_vals32(const mi_ctx *c)
+  {
+    return c->precond_storage == 32 && c->d_sell_vals32 && !c->active_sell_vals && !c->active_linear_mf && !c->mf_fine &&
+           (c->spmv_variant == 3 || c->spmv_variant == 4);
+  }
+
   // the smoother's fine-level products of a Q3 matrix-free level run mf_spmv_q3s on the 64-point records of the current
   // tangent ("smoother_quadrature_q3" 4).  The one test for it, as smoother_runs_q27 is for Q2: enqueue_spmv's dispatch (with
   // the call's own condition: a smoother product) and the "smoother_quadrature_q3_active" query both read it.  The rest of it is
@@ -546,7 +569,7 @@ namespace mi_detail
         f.qrec    = q3 ? c->d_qrec_q3 : c->d_qrec;
         // opt-in "smoother_precision" 32: the SMOOTHER's products in fp32 arithmetic on fp32 records (residuals, start-vector
         // products and mi_spmv keep the fp64 form)
-        f.qrec32  = (smoother && c->smoother_precision == 32 && c->qrec32_valid) ? c->d_qrec32 : nullptr;
+        f.qrec32  = (smoother && smoother_runs_f32(c)) ? c->d_qrec32 : nullptr;
         f.vals    = c->mf_fine ? c->d_diag_blk : c->d_vals;      // (diagonal entries of constrained dofs)
         f.diagpos = c->mf_fine ? c->d_diagpos_mf : c->d_diagpos;
         f.x       = x;
@@ -654,7 +677,7 @@ namespace mi_detail
       {
         refresh_vals32(c);
         mi::SellParams p   = sell_params(c, x, y, dotv, partials, done);
-        if (smoother && c->precond_storage == 32 && c->d_sell_vals32 && !c->active_sell_vals)
+        if (smoother && smoother_reads_vals32(c))
           p.vals32 = c->d_sell_vals32;
         if (cheb)
           {
@@ -3564,6 +3587,12 @@ int mi_get_tuning(mi_ctx *c, const char *key, int *value)
     *value = m->cg_speculate;
   else if (k == "smoother_precision")
     *value = m->smoother_precision;
+  else if (k == "smoother_precision_active") // 32: the next smoother product of level 0 runs the float instantiation of mf_spmv
+    *value = smoother_runs_f32(m) ? 32 : 64;
+  else if (k == "precond_storage") // of the context asked: a borrowed level context answers for itself
+    *value = c->precond_storage;
+  else if (k == "precond_storage_levels") // levels (level 0 included) whose cycle products multiply with the fp32 copy; slab 0's
+    *value = mg_storage_levels(m);
   else if (k == "cg_single_reduction")
     *value = m->cg_single_reduction;
   else if (k == "mg_distributed_levels") // levels of the multigrid hierarchy that are cut into slabs (0: no hierarchy)

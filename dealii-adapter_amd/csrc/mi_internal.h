@@ -394,6 +394,8 @@ namespace mi_detail
                 const ChebFusion *cheb = nullptr, // cheb: one entry per member
                 bool ghosts_current = false);     // the ghost planes of x are up to date: no exchange (Team::halo_skip)
   int mg_set_storage(mi_ctx *c, int bits); // mi_mg.cpp: forwards to the level contexts
+  int mg_storage_levels(const mi_ctx *c);  // mi_mg.cpp: levels of the hierarchy whose cycle products read the fp32 copy
+  bool smoother_reads_vals32(const mi_ctx *c); // mi_ctx.cpp: the smoother's products of c multiply with the fp32-rounded values
   int mg_set_fuse(mi_ctx *c, int fuse);
   int mg_set_restrict_fuse(mi_ctx *c, int on);
   int team_allreduce_vectors(Team &T, const std::function<double *(mi_ctx *)> &vec, size_t n);

@@ -630,6 +630,16 @@ namespace mi_detail
     return MI_OK;
   }
 
+  // how many levels of c's hierarchy, level 0 included, multiply their cycle products with the fp32 copy (0 without a hierarchy)
+  int mg_storage_levels(const mi_ctx *c)
+  {
+    int n = 0;
+    if (c->mg)
+      for (const MgLevel &L : c->mg->levels)
+        n += smoother_reads_vals32(L.ctx) ? 1 : 0;
+    return n;
+  }
+
   // 0 never fuse the smoother update into the product, 1 on the latency-bound levels (default), 2 on every level
   int mg_set_fuse(mi_ctx *c, int fuse)
   {
@@ -865,6 +875,12 @@ namespace mi_detail
     mg_configure(c, mg);
     if (const int rc = mg_build_levels(c, mg))
       return rc;
+    // the new levels take the fine context's smoother storage ("precond_storage" set before "precond" 1, or before a shape key
+    // rebuilt the hierarchy, used to leave them on fp64 beside an fp32 level 0): fp32 array allocated, copy marked stale.  Here
+    // and not in mg_build_levels: the linear model's hierarchy shares that function and keeps fp64 values by design
+    if (c->precond_storage != 64)
+      if (const int rc = mg_set_storage(c, c->precond_storage))
+        return rc;
     if (mg->block)
       for (MgLevel &L : mg->levels)
         L.ctx->want_dinv_blk = true; // filled by the next assembly of the level

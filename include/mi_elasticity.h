@@ -436,8 +436,17 @@ int mi_set_profiling(mi_ctx *ctx, int enable);
  *  cg_r0_operator       1 | 0                      A h of a predicted start vector h ("cg_warm_start" 2 / 3) by the     -
  *                                                  matrix-free product where the point records exist | assembled
  *  precond_storage      64 | 32                    smoother multiplies with the fp64 matrices | an fp32-rounded copy    -
- *                                                  (opt-in; arithmetic, CG product, residuals stay fp64)
- *  mf_single_launch     1 | 0                      matrix-free product: one launch + gather | eight colour launches     MI_MF_SINGLE_LAUNCH
+ *                                                  (opt-in; arithmetic, the CG's product and residual stay fp64; every
+ *                                                  product of a V-cycle -- smoother steps, the cycle's residual, the
+ *                                                  eigenvalue estimates -- reads the copy, D^-1 and the coarsest level's
+ *                                                  inverse come from the fp64 values).  Levels built later -- "precond" 1
+ *                                                  after the key, a hierarchy rebuilt by a shape key -- take the setting.
+ *                                                  Read-backs, no setters: "precond_storage" = the setting of the context
+ *                                                  asked (a borrowed multigrid level context answers for itself);
+ *                                                  "precond_storage_levels" = how many levels of the hierarchy, level 0
+ *                                                  included, multiply their cycle products with the fp32 copy (0 without
+ *                                                  a hierarchy or with 64; on a team: slab 0's)
+ *  mf_single_launch    1 | 0                      matrix-free product: one launch + gather | eight colour launches     MI_MF_SINGLE_LAUNCH
  *  cell_lattice         1 | 0                      mf_spmv: node ids of a cell by lattice arithmetic | from conn        MI_CELL_LATTICE
  *  element_tangents     2 | 1                      tests: keep point records / element tangents whatever the size       -
  *  DECOMPOSITION
@@ -464,7 +473,10 @@ int mi_set_profiling(mi_ctx *ctx, int enable);
  *                                                  of the next smoother product on such a level, 0 elsewhere
  *  smoother_precision   64 | 32                    the smoother's matrix-free fine-level products in fp64 | in fp32      -
  *                                                  arithmetic on fp32 point records (opt-in; everything else stays fp64;
- *                                                  takes effect with the next tangent assembly)
+ *                                                  takes effect with the next tangent assembly).  Read-back, no setter:
+ *                                                  "smoother_precision_active" = 32 if the next smoother product of level 0
+ *                                                  runs the float instantiation of mf_spmv (fp32 records of the current
+ *                                                  tangent; one launch, box cells, lattice ids, cell-major slots), else 64
  *  cg_single_reduction  -1 | 0 | 1                multigrid-PCG with ONE all-reduce per iteration (r.z, z.Az, ||r||^2;      MI_CG_SINGLE_REDUCTION
  *                                                  Chronopoulos-Gear form): on teams of several slabs | never | always
  *  cg_speculate_margin  0 | 1..16                  expected iterations of a solve left to polled ones (0: two)          -
@@ -516,7 +528,8 @@ int mi_set_tuning(mi_ctx *ctx, const char *key, int value);
  * "mf_single_launch", "cell_lattice", "mg_refresh_every", "cg_speculate", "halo_skip", "cut_axis" (1 / 2 / 3: the slabs
  * are cut along x / y / z, 0: not decomposed), "cg_single_reduction_active", "mg_distributed_levels" (multigrid levels cut
  * into slabs; 0 on one slab), "spmv_lds_launches" / "spmv_split_launches" (launches of one sliced-ELL product on
- * sell_spmv / sell_spmv_split; read-only). */
+ * sell_spmv / sell_spmv_split; read-only), "precond_storage", "precond_storage_levels" and "smoother_precision_active"
+ * (what the fp32 opt-ins of the preconditioner do now; read-only, described with their keys above). */
 int mi_get_tuning(mi_ctx *ctx, const char *key, int *value);
 int mi_reset_timings(mi_ctx *ctx);
 int mi_get_timings(mi_ctx *ctx, mi_timings *out);

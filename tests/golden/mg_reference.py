@@ -18,6 +18,18 @@ by 12 steps over [lmax / 60, lmax].  lmax per level is an argument: the one scal
 Precision: every product of the cycle runs in the dtype of the call (float64 or np.longdouble).  Level matrices are cast up
 and multiplied with np.add.at; block inverses, the Cholesky factor of the coarsest level and the transfers are written in
 plain array arithmetic, because LAPACK and scipy's sparse kernels exist in double only.
+
+The fp32 opt-ins of the preconditioner (levels(), vcycle() and lambda_true() take them; the defaults are the fp64 cycle, bit
+for bit what it was):
+  storage=32 ("precond_storage" 32).  In the library every product of a cycle -- smoother steps, the cycle's residual, the
+    eigenvalue estimates -- goes through level_spmv with smoother = true and reads the fp32-rounded copy of the level's values
+    (d_sell_vals32) in fp64 arithmetic; D^-1 (extract_dinv_blk) and the coarsest level's dense inverse
+    (launch_dense_inverse_from_sell) read the fp64 values.  So _Level.mult multiplies with astype(float32).astype(dtype) of the
+    product matrix, and dinv / dense() keep the unrounded A.  product_matrices: one CSR per level to round instead of A --
+    the device's own exports, so that both sides round the same bits (a value that differs in the last fp64 bit may round to
+    the other fp32 neighbour).  lambda_true(l, storage=32) is the largest eigenvalue of D^-1 A_32.
+  product0="f32" / "f32r" ("smoother_precision" 32).  Level 0 multiplies in an emulation of fp32 arithmetic, in two
+    accumulation orders; no attempt at the kernel's own arithmetic: E32 below is a measured distance, not an equality.
 """
 import numpy as np
 import scipy.sparse as sp
@@ -183,19 +195,40 @@ def spd_inverse(A):
 
 
 class _Level:
-    """one level in one dtype: the matrix as COO arrays, D^-1 as node blocks"""
+    """one level in one dtype: the matrix as COO arrays, D^-1 as node blocks.  product: the matrix that mult() multiplies
+    with (None: A itself); storage 32: its values rounded to float32 and cast back, the arithmetic stays in dtype.  dense()
+    -- what the coarsest level inverts -- is A at full precision whatever the product reads.  f32: None, or 0 / 1 = mult()
+    emulates a product in fp32 arithmetic: values and operand cast to float32, accumulated in float32 with np.add.at in the
+    stored order of the entries (0) or in the reverse of it (1), result cast back"""
 
-    def __init__(self, A, Dinv, dim, dtype):
+    def __init__(self, A, Dinv, dim, dtype, product=None, storage=64, f32=None):
         coo = A.tocoo()
         self.n, self.dim = A.shape[0], dim
         self.rows, self.cols, self.vals = coo.row, coo.col, coo.data.astype(dtype)
         self.Dinv = Dinv.astype(dtype)
         self.dtype = dtype
         self.inverse = None
+        self.f32 = f32
+        if product is None and storage == 64:
+            self.prows, self.pcols, self.pvals = self.rows, self.cols, self.vals
+        else:
+            assert storage in (64, 32)
+            pc = coo if product is None else product.tocoo()
+            assert pc.shape == A.shape
+            data = pc.data.astype(np.float32).astype(dtype) if storage == 32 else pc.data.astype(dtype)
+            self.prows, self.pcols, self.pvals = pc.row, pc.col, data
+        if f32 is not None:
+            order = slice(None) if f32 == 0 else slice(None, None, -1)
+            self.prows, self.pcols = self.prows[order], self.pcols[order]
+            self.pvals = self.pvals[order].astype(np.float32)
 
     def mult(self, x):
+        if self.f32 is not None:
+            y = np.zeros(self.n, np.float32)
+            np.add.at(y, self.prows, self.pvals * x.astype(np.float32)[self.pcols])
+            return y.astype(self.dtype)
         y = np.zeros(self.n, self.dtype)
-        np.add.at(y, self.rows, self.vals * x[self.cols])
+        np.add.at(y, self.prows, self.pvals * x[self.pcols])
         return y
 
     def dinv(self, r):
@@ -271,10 +304,15 @@ class Reference:
             self.D.append(node_blocks(Ac, dim))
         self._cache = {}
 
-    def lambda_true(self, l):
-        """largest eigenvalue of D^-1 A on level l"""
+    def lambda_true(self, l, storage=64, product_matrices=None):
+        """largest eigenvalue of D^-1 A on level l; storage 32: of D^-1 A_32, A_32 = the product matrix of the level
+        (product_matrices[l], or A) with fp32-rounded values, D from the unrounded A as ever"""
         import scipy.sparse.linalg as spla
         A, D, dim = self.A[l], self.D[l], self.dim
+        if product_matrices is not None:
+            A = product_matrices[l].tocsr()
+        if storage == 32:
+            A = sp.csr_matrix((A.data.astype(np.float32).astype(np.float64), A.indices, A.indptr), shape=A.shape)
         w, V = np.linalg.eigh(D)  # D^-1/2 by blocks
         Dmh = np.einsum("nij,nj,nkj->nik", V, 1 / np.sqrt(w), V)
         S = sp.bsr_matrix((Dmh, np.arange(len(Dmh)), np.arange(len(Dmh) + 1)), shape=A.shape).tocsr()
@@ -285,21 +323,35 @@ class Reference:
         v0 = np.random.default_rng(0).standard_normal(A.shape[0])  # (a seeded start vector: the same digits in every run)
         return float(spla.eigsh(B, k=1, which="LA", tol=1e-12, v0=v0, return_eigenvectors=False)[0])
 
-    def levels(self, dtype):
-        if dtype not in self._cache:
-            Ls = [_Level(A, invert_blocks(D.astype(dtype)), self.dim, dtype) for A, D in zip(self.A, self.D)]
+    def levels(self, dtype, storage=64, product_matrices=None, product0=None):
+        """(levels, transfers) in one dtype.  storage 32: every product of the cycle multiplies with fp32-rounded values;
+        product_matrices: one CSR matrix per level that the products read in place of A (D^-1 and the dense inverse keep
+        coming from A); product0 "f32" / "f32r": level 0 multiplies in the fp32 emulation, stored / reverse order"""
+        if dtype in self._cache and storage == 64 and product_matrices is None and product0 is None:
+            return self._cache[dtype][:2]
+        key = (dtype, storage, None if product_matrices is None else tuple(id(P) for P in product_matrices), product0)
+        if key not in self._cache:
+            base = self._cache.get(dtype)
+            f32 = {None: None, "f32": 0, "f32r": 1}[product0]
+            Ls = []
+            for l, (A, D) in enumerate(zip(self.A, self.D)):
+                Dinv = base[0][l].Dinv if base else invert_blocks(D.astype(dtype))
+                P = None if product_matrices is None else product_matrices[l]
+                Ls.append(_Level(A, Dinv, self.dim, dtype, P, storage, f32 if l == 0 else None))
             if self.shape[-1]["exact"]:
-                Ls[-1].inverse = spd_inverse(Ls[-1].dense())
-            Ts = []
-            for t in self.T:
-                Ts.append(Transfer(self.dim, t.nf, t.nc, ~t.free_f, ~t.free_c, dtype))
-            self._cache[dtype] = (Ls, Ts)
-        return self._cache[dtype]
+                Ls[-1].inverse = base[0][-1].inverse if base else spd_inverse(Ls[-1].dense())
+            Ts = base[1] if base else [Transfer(self.dim, t.nf, t.nc, ~t.free_f, ~t.free_c, dtype) for t in self.T]
+            # (the entry keeps product_matrices alive: an id in the key is never that of another list's matrix)
+            self._cache[key] = (Ls, Ts, product_matrices)
+            if key == (dtype, 64, None, None):
+                self._cache[dtype] = self._cache[key]
+        return self._cache[key][:2]
 
-    def vcycle(self, r, lmax, dtype=np.float64, nu=None, l=0):
+    def vcycle(self, r, lmax, dtype=np.float64, nu=None, l=0, storage=64, product_matrices=None, product0=None):
         """B r: one V-cycle on the right-hand side r; lmax[l] per smoothed level (ignored on an exact one);
-        nu: override of the smoother steps of every level but an inexact coarsest one (tests of the reference itself)"""
-        Ls, Ts = self.levels(dtype)
+        nu: override of the smoother steps of every level but an inexact coarsest one (tests of the reference itself);
+        storage, product_matrices, product0: as for levels()"""
+        Ls, Ts = self.levels(dtype, storage, product_matrices, product0)
         L, sh = Ls[l], self.shape[l]
         b = np.asarray(r).astype(dtype)
         if l + 1 == len(Ls) and len(Ls) > 1:
@@ -309,7 +361,7 @@ class Reference:
         k = sh["nu"] if nu is None else nu
         x = chebyshev(L, b, None, k, lmax[l], sh["ratio"])
         res = b - L.mult(x)
-        xc = self.vcycle(Ts[l].restrict(res), lmax, dtype, nu, l + 1)
+        xc = self.vcycle(Ts[l].restrict(res), lmax, dtype, nu, l + 1, storage, product_matrices, product0)
         x = x + Ts[l].prolong(xc)
         return chebyshev(L, b, x, k, lmax[l], sh["ratio"])
 
@@ -360,6 +412,28 @@ MID_CASES = {
     "q2_11": dict(dim=3, p=2, reps=(11, 11, 11), kind="perturbed", roles=ROLES_A),
     "2d_q4": dict(dim=2, p=4, reps=(26, 25), kind="perturbed", roles=ROLES_2D),
 }
+# The fp32 opt-ins of the preconditioner (tests/test_gpu_multigrid_fp32.py), a table of their own again.  One new mesh: 3D Q3
+# with the fine level assembled.  Both opt-ins make the fine level's smoother multiply with the assembly-rule operator, so
+# every reference of these tests is built by assembled_reference(), whatever rule the case's own keys select under fp64.
+FP32_CASES = {
+    "q3_532_assembled": dict(dim=3, p=3, reps=(5, 3, 2), kind="cube", roles=ROLES_A),
+}
+# "precond_storage" 32: fp64 arithmetic on fp32-rounded values (modelled exactly: Reference.vcycle(storage=32)).  Its own
+# rounding, float64 against long double cycle as for E_REF, lies within E_REF on every case (measured worst 8.9e-16 on
+# q2_4412_3slabs_z, tests/test_mirror_multigrid.py), so the GPU tolerance is the one of the fp64 tests.
+STORAGE_CASES = ["q2_654", "q1_987", "2d_q4_64", "q3_532_assembled", "q2_753_mf27", "q2_4412_3slabs_z", "q2_11"]
+# "smoother_precision" 32: fp32 arithmetic on fp32 point records, on level 0 only.  Not reproducible in numpy; E32 is the
+# worst relmax between the fp64 reference cycle and the cycle whose level-0 products run in the fp32 emulation of
+# _Level.mult, over these cases, three right-hand sides and both accumulation orders, measured and asserted by
+# tests/test_mirror_multigrid.py.  TOL32 = 16 x E32 rounded up to a power of ten, never above 1e-4: the kernel
+# rounds point records and sums in a sum-factorised order, the emulation rounds matrix entries and sums in row order.
+PRECISION_CASES = ["q2_543_mf_fine", "q2_654", "q2_4412_3slabs_z"]
+E32 = 6.0e-7  # measured 5.74e-7 (q2_654, unit vector, reverse order), rounded up in the second digit; TOL32 = 1e-5
+
+
+def tol32():
+    import math
+    return min(1e-4, 10.0 ** math.ceil(math.log10(16 * E32)))
 
 
 def geometry(kind, dim, reps, seed):
@@ -384,7 +458,7 @@ def geometry(kind, dim, reps, seed):
 
 
 def case(name):
-    return CASES[name] if name in CASES else MID_CASES[name]
+    return CASES[name] if name in CASES else MID_CASES[name] if name in MID_CASES else FP32_CASES[name]
 
 
 def case_mesh(name):
@@ -428,3 +502,25 @@ def case_reference(name, u_total, m, **kw):
     args = dict(coarsest=c.get("coarsest", 4), dense=c.get("dense", 1), nq0=c.get("nq0"), fold0=c.get("fold0", False), alpha1=A1)
     args.update(kw)
     return Reference(m, u_total, **args)
+
+
+def assembled_reference(name, u_total, m, **kw):
+    """the reference of a case with the assembly-rule operator on the fine level, whatever its keys select: what both fp32
+    opt-ins of the preconditioner multiply with"""
+    return case_reference(name, u_total, m, nq0=None, fold0=False, **kw)
+
+
+def second_increment(m, du):
+    """V_DELTA of the second tangent in the tests that re-assemble at a changed state (the one of the lagged-operators test)"""
+    return 0.55 * du + 1e-5 * np.random.default_rng(2).standard_normal(m.n) * ~m.constrained
+
+
+def cpu_rhs_set(m, seed=5):
+    """three right-hand sides without a device: white noise, a smooth field, a unit vector next to the clamped face"""
+    free = ~m.constrained
+    node = 1
+    for d in range(1, m.dim):
+        node += int(np.prod(m.nn[:d]))
+    e = np.zeros(m.n)
+    e[node * m.dim] = 1.0
+    return [("random", np.random.default_rng(seed).standard_normal(m.n) * free), ("smooth", shear(m.coords) * free), ("unit", e)]

@@ -110,8 +110,9 @@ def jacobi(A, dtype=np.float64):
     return lambda r: dinv * r
 
 
-def vcycle(ref, lmax, dtype=np.float64):
-    return lambda r: ref.vcycle(r, lmax, dtype)
+def vcycle(ref, lmax, dtype=np.float64, **kw):
+    """kw: storage / product_matrices of mg_reference.Reference.vcycle (the fp32-stored preconditioner)"""
+    return lambda r: ref.vcycle(r, lmax, dtype, **kw)
 
 
 def margin(rn_k, tol_abs, e_r):

@@ -43,8 +43,8 @@ one; c2 = rho / delta in chebyshev -- (c) in all 21; no cmask_tgt in lattice_int
 operators of an unmasked state have other eigenvalues), (b) states in 5, (c) in one; level-1 state from V_U alone in
 mg_update -- (b) states in 15, (c) in 5, (a) in one.
 
-Out of scope: "precond_storage" 32 and "smoother_precision" 32 (an fp32 reference is a separate piece of work) and the
-fourth-kind smoother (experiments build only).
+"precond_storage" 32 and "smoother_precision" 32 are held to their own references in tests/test_gpu_multigrid_fp32.py.  Out of
+scope: the fourth-kind smoother (experiments build only).
 """
 import functools
 import math
@@ -90,7 +90,7 @@ def _reference(name, variant=""):
 
 
 def _context(name, extra_keys=()):
-    c = R.CASES[name]
+    c = R.case(name)
     m, lo, hi, perturb, u, du = _inputs(name)
     G = M.Context(dim=c["dim"], degree=c["p"], reps=c["reps"], lo=lo, hi=hi, face_role=c["roles"], perturb=perturb,
                   slabs=c.get("slabs", 1), cut_axis=c.get("cut_axis", 0))
@@ -132,8 +132,10 @@ def _check_rule(G, name):
         assert c.get("nq0") is None
 
 
-def _check_shape_and_estimates(G, ref, distributed=None, bounds="first"):
-    """(a); returns lmax per level.  bounds "first": both bounds, for first estimates (power value and Ritz value both lie
+def _check_shape_and_estimates(G, ref, distributed=None, bounds="first", lambda_true=None, slack=None):
+    """(a); returns lmax per level.  lambda_true: the eigenvalue of a level where it is not ref.lambda_true (the fp32-stored
+    matrices of tests/test_gpu_multigrid_fp32.py); slack: {level: relative width} by which both bounds of a level whose
+    products run in fp32 arithmetic are widened (same file; no other level, and none here).  bounds "first": both bounds, for first estimates (power value and Ritz value both lie
     below lambda_true, times the safety factor 1.15); "refresh": the lower bound alone -- a refresh continues the power
     iteration and keeps, as a factor, what the Krylov estimate added to the FIRST power value (estimate_lmax: "never given
     back"), so its product may pass 1.15 lambda_true by design; None: no bound (estimates of an older operator)"""
@@ -149,10 +151,11 @@ def _check_shape_and_estimates(G, ref, distributed=None, bounds="first"):
         if sh["exact"]:
             assert d["lmax"] == 0.0
         elif bounds:
-            lam = ref.lambda_true(l)
+            lam = (lambda_true or ref.lambda_true)(l)
+            w = (slack or {}).get(l, 0.0)
             print("level %d: lmax / lambda_true = %.6f" % (l, d["lmax"] / lam))
-            assert lam <= d["lmax"], (l, lam, d["lmax"])
-            assert bounds == "refresh" or d["lmax"] <= 1.15 * lam * (1 + 1e-10), (l, lam, d["lmax"])
+            assert lam * (1 - w) <= d["lmax"], (l, lam, d["lmax"])
+            assert bounds == "refresh" or d["lmax"] <= 1.15 * lam * (1 + 1e-10) * (1 + w), (l, lam, d["lmax"])
         lmax.append(d["lmax"])
     return lmax
 

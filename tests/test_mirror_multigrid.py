@@ -13,8 +13,14 @@
   * the same for the mid-size cases mg_reference.MID_CASES (level 0 above 10,240 nodes, tests/test_gpu_sell_lds_product.py),
     whose shapes are written by hand too.  Measured: q1_3d 6.22e-16, q2_11 9.04e-16, 2d_q4 8.16e-16 -- within E_REF, so
     these cases take the GPU tolerance of the others.  A case builds its hierarchy in 4 to 30 s and runs the long double
-    cycle in under a second.
+    cycle in under a second;
+  * the fp32 opt-ins of the preconditioner (tests/test_gpu_multigrid_fp32.py), on mg_reference.STORAGE_CASES / PRECISION_CASES:
+    the storage-32 cycle's own rounding is within E_REF (worst 8.9e-16) and it lies 4.9e-8 .. 1.3e-7 from the storage-64
+    cycle; the fp32 emulation of the level-0 products lies at most 5.74e-7 from the fp64 cycle (mg_reference.E32 = 6.0e-7,
+    TOL32 = 1e-5); the cycles of the two states that the GPU sequences assemble at lie at least 5.6e-3 apart.
 """
+import functools
+import math
 import os
 import sys
 
@@ -187,3 +193,85 @@ def test_reference_rounding_on_the_mid_cases(name):
     """the same on a mid-size case: within E_REF, so the GPU tolerance of the small cases holds for it"""
     assert np.finfo(np.longdouble).eps < 1e-18
     assert _e_ref(name) <= R.E_REF
+
+
+# ------------------------------------------------------------------ the fp32 opt-ins of the preconditioner
+TOL_GPU = min(1e-10, 10.0 ** math.ceil(math.log10(64 * R.E_REF)))  # TOL of tests/test_gpu_multigrid_reference.py
+
+
+def _relmax(a, b):
+    return float(np.abs(a - b).max() / np.abs(b).max())
+
+
+@functools.lru_cache(maxsize=None)
+def _assembled(name, second=False):
+    """(mesh, reference with the assembly-rule fine operator, true lmax x 1.15) of a case at its state / at its second state"""
+    m = R.case_mesh(name)[0]
+    u, du = R.case_state(m, seed=len(name))
+    if second:
+        du = R.second_increment(m, du)
+    ref = R.assembled_reference(name, u + du, m)
+    return m, ref, ref.true_lmax()
+
+
+@pytest.mark.parametrize("name", R.STORAGE_CASES)
+def test_storage32_reference_rounding_and_distance(name):
+    """"precond_storage" 32 in the reference: fp64 arithmetic on fp32-rounded product matrices (here the mirror's own,
+    rounded: no device).  Its rounding, float64 against long double cycle, is within E_REF, so the GPU tolerance stays 1e-13;
+    and the key is visible: the storage-32 cycle lies at least 1e3 tolerances from the storage-64 one.
+    Measured e_ref / distance: q2_654 4.9e-16 / 6.9e-8, q1_987 4.1e-16 / 4.9e-8, 2d_q4_64 7.4e-16 / 1.3e-7, q3_532_assembled
+    6.6e-16 / 7.9e-8, q2_753_mf27 5.9e-16 / 9.3e-8, q2_4412_3slabs_z 8.9e-16 / 1.2e-7, q2_11 8.2e-16 / 1.1e-7."""
+    assert np.finfo(np.longdouble).eps < 1e-18
+    m, ref, lmax = _assembled(name)
+    r = np.random.default_rng(5).standard_normal(m.n) * ~m.constrained
+    z32, z32l = ref.vcycle(r, lmax, storage=32), ref.vcycle(r, lmax, np.longdouble, storage=32)
+    e = _relmax(z32, z32l)
+    d = _relmax(z32, ref.vcycle(r, lmax))
+    print("storage 32 %-20s e_ref %.2e  distance to storage 64 %.2e" % (name, e, d))
+    assert e <= R.E_REF, (name, e)
+    assert d >= 1e3 * TOL_GPU, (name, d)
+    # D^-1 and the dense inverse stay fp64: rounding them too gives another cycle
+    Ls = ref.levels(np.float64, 32)[0]
+    assert Ls[0].Dinv.astype(np.float32).astype(np.float64).tolist() != Ls[0].Dinv.tolist()
+    assert np.array_equal(Ls[-1].dense(), ref.levels(np.float64)[0][-1].dense())
+    # product_matrices: the same matrices handed in are the same cycle, to the bit
+    assert np.array_equal(ref.vcycle(r, lmax, storage=32, product_matrices=[A.copy() for A in ref.A]), z32)
+    # the eigenvalue the estimate is bounded by moves with the values
+    l = len(ref.shape) - 2
+    lam, lam32 = ref.lambda_true(l), ref.lambda_true(l, storage=32)
+    print("level %d lambda_true %.12f, storage 32 %.12f" % (l, lam, lam32))
+    assert lam32 != lam and abs(lam32 - lam) < 1e-6 * lam
+
+
+@pytest.mark.parametrize("name", R.PRECISION_CASES)
+def test_fp32_emulation_distance_is_within_E32(name):
+    """"smoother_precision" 32: the fp64 reference cycle against the cycle whose level-0 products run in the fp32 emulation,
+    three right-hand sides, both accumulation orders.  Measured worst: q2_543_mf_fine 4.80e-7, q2_654 5.74e-7,
+    q2_4412_3slabs_z 4.84e-7 (all figures 1.4e-7 .. 5.7e-7); mg_reference.E32 is what the GPU tolerance rests on."""
+    m, ref, lmax = _assembled(name)
+    worst = 0.0
+    for what, r in R.cpu_rhs_set(m):
+        z = ref.vcycle(r, lmax)
+        za, zb = ref.vcycle(r, lmax, product0="f32"), ref.vcycle(r, lmax, product0="f32r")
+        assert not np.array_equal(za, zb)  # two orders of one sum: two roundings
+        for order, zz in (("stored", za), ("reverse", zb)):
+            e = _relmax(zz, z)
+            print("fp32 emulation %-18s %-7s %-7s relmax %.2e" % (name, what, order, e))
+            assert 1e-10 < e <= R.E32, (name, what, order, e)
+            worst = max(worst, e)
+    print("worst fp32 emulation distance %-18s %.2e (E32 %.1e, TOL32 %.0e)" % (name, worst, R.E32, R.tol32()))
+    assert R.tol32() <= 1e-4 and 16 * R.E32 <= R.tol32() < 160 * R.E32
+
+
+@pytest.mark.parametrize("name", ["q2_543_mf_fine", "q2_654"])
+def test_cycle_of_the_other_tangent_is_far_from_the_tolerance(name):
+    """the tests that re-assemble at a changed state tell fresh from stale: the reference cycles at the two states lie at
+    least 100 x TOL32 (and so far more than 100 x the storage tolerance) apart.  Measured, smallest of three
+    right-hand sides: q2_543_mf_fine 6.4e-3, q2_654 5.6e-3 (the unit vector; 1.2e-2 .. 2.7e-2 on the others)."""
+    m, ref, lmax = _assembled(name)
+    _, ref2, lmax2 = _assembled(name, second=True)
+    for what, r in R.cpu_rhs_set(m):
+        d = _relmax(ref2.vcycle(r, lmax2), ref.vcycle(r, lmax))
+        d_op = _relmax(ref2.vcycle(r, lmax), ref.vcycle(r, lmax))  # (the same lmax: the operators alone)
+        print("second state %-18s %-7s relmax %.2e (same lmax: %.2e)" % (name, what, d, d_op))
+        assert d >= 100 * R.tol32() and d_op >= 100 * R.tol32(), (name, what, d, d_op)
