@@ -17,6 +17,7 @@ HEADER = os.path.join(ROOT, "include", "mi_elasticity.h")
 
 MI_OK, MI_EINVAL, MI_EHIP, MI_ENOCONV_LIN, MI_ENOCONV_NR, MI_ECOMM = 0, -1, -2, -3, -4, -5
 FACE_FREE, FACE_CLAMPED, FACE_INTERFACE, FACE_ZCLAMP = 0, 1, 7, 8
+STRESS_NEOHOOKE, STRESS_LINEAR = 0, 1  # mi_stress_field's models
 (V_U, V_U_OLD, V_V, V_V_OLD, V_A, V_A_OLD, V_STRESS, V_DELTA, V_NEWTON, V_RHS) = range(10)
 (T_ASSEMBLE_CELLS, T_ASSEMBLE_TOTAL, T_SPMV, T_CG_VECTOR, T_CG_TOTAL, T_NEWMARK, T_STEP, T_ASSEMBLE_DIAG, T_ASSEMBLE_RESIDUAL,
  T_SPMV_PRECOND, T_EBE_LAUNCH, T_COUNT) = range(12)
@@ -153,6 +154,8 @@ def lib():
         for f in ("mi_energy", "mi_linear_energy"):
             getattr(L, f).argtypes = [vp, C.POINTER(EnergyInfo)]
             getattr(L, f).restype = C.c_int
+        L.mi_stress_field.argtypes = [vp, C.c_int, dp, dp, dp]
+        L.mi_stress_field.restype = C.c_int
         L.mi_set_profiling.argtypes = [vp, C.c_int]
         L.mi_get_timings.argtypes = [vp, C.POINTER(Timings)]
         L.mi_partition_describe.restype = C.c_int
@@ -444,6 +447,15 @@ class Context:
         e = EnergyInfo()
         self._chk(lib().mi_energy(self.h, C.byref(e)))
         return dict(strain=e.strain, kinetic=e.kinetic, body=e.body)
+
+    def stress_field(self, model=STRESS_NEOHOOKE):
+        """(sigma[n_nodes, ncomp], von_mises[n_nodes], weight[n_nodes]) of the committed state V_U: the lumped L2 projection of
+        the Cauchy stress (STRESS_NEOHOOKE) or of lambda tr(eps) I + 2 mu eps (STRESS_LINEAR) onto the nodes; components
+        xx, yy, zz, xy, xz, yz in 3D, xx, yy, xy in 2D"""
+        ncomp = self.dim * (self.dim + 1) // 2
+        sigma, vm, w = np.zeros((self.nnodes, ncomp)), np.zeros(self.nnodes), np.zeros(self.nnodes)
+        self._chk(lib().mi_stress_field(self.h, model, _dp(sigma), _dp(vm), _dp(w)))
+        return sigma, vm, w
 
     def state_save(self):
         self._chk(lib().mi_state_save(self.h))

@@ -1235,11 +1235,8 @@ namespace mi_detail
 
   // ---- energy diagnostics ------------------------------------------------------------------------------------
   // the cells' buffer and, on 3D contexts that keep no cell boxes, boxes of the call's own (first use)
-  static int energy_prepare(mi_ctx *c)
+  static int energy_box_prepare(mi_ctx *c)
   {
-    const size_t nc = size_t(c->mesh.ncells);
-    if (!c->d_energy)
-      HIPCHK(c, hipMalloc((void **)&c->d_energy, (nc + nc / 1024 + 1) * 3 * sizeof(double)));
     if (!c->d_cellbox && !c->energy_box_checked)
       {
         if (int rc = make_cellbox(c, &c->d_energy_box))
@@ -1247,6 +1244,13 @@ namespace mi_detail
         c->energy_box_checked = true;
       }
     return MI_OK;
+  }
+  static int energy_prepare(mi_ctx *c)
+  {
+    const size_t nc = size_t(c->mesh.ncells);
+    if (!c->d_energy)
+      HIPCHK(c, hipMalloc((void **)&c->d_energy, (nc + nc / 1024 + 1) * 3 * sizeof(double)));
+    return energy_box_prepare(c);
   }
 
   // strain energy, kinetic energy and body-force potential of one slab's owned cells into its scalars [SC_ENERGY, +3), the
@@ -1297,6 +1301,51 @@ namespace mi_detail
     out->strain = c0->h_pinned[0], out->kinetic = c0->h_pinned[1], out->body = c0->h_pinned[2], out->reserved = 0.0;
     if (inverted)
       *inverted = c0->h_pinned[3];
+    return MI_OK;
+  }
+
+  // ---- nodal stress recovery (mi_stress_field) -----------------------------------------------------------------
+  // One slab's lumped projection, enqueued: the accumulator zeroed, the local cells colour by colour (ghost layer included:
+  // like the residual pass on system_rhs, that completes every OWNED node -- the nodes of the slab's first plane, owned by the
+  // slab below, and of the ghost planes stay partial and are never read), then stress_finish.  d_stress: [nnodes][8] accumulator,
+  // behind it sigma [nnodes][ncomp], von Mises [nnodes], weight [nnodes]; allocated on first use, as the linear model's tables
+  static int enqueue_stress(mi_ctx *c, int model)
+  {
+    const size_t nn = size_t(c->mesh.nnodes), ncomp = size_t(c->dim * (c->dim + 1) / 2);
+    if (!c->d_stress)
+      HIPCHK(c, hipMalloc((void **)&c->d_stress, nn * (8 + ncomp + 2) * sizeof(double)));
+    if (model == MI_STRESS_LINEAR && !c->d_stress_tab)
+      {
+        mi::Tables1D t;
+        t.build(c->degree, c->degree + 1); // quad_order = degree + 1, linear_elasticity.cc:61
+        if (int rc = upload(c, &c->d_stress_tab, t.packed()))
+          return rc;
+      }
+    if (int rc = energy_box_prepare(c))
+      return rc;
+    HIPCHK(c, hipMemsetAsync(c->d_stress, 0, nn * 8 * sizeof(double), c->stream));
+    HIPCHK(c, hipMemsetAsync(c->d_sc + SC_ENERGY + 3, 0, sizeof(double), c->stream)); // (mi_energy's flag: it zeroes it itself)
+    mi::MfParams f = mf_params(c);
+    if (!f.cellbox)
+      f.cellbox = c->d_energy_box;
+    mi::StressParams sp{};
+    sp.conn = c->d_conn, sp.cverts = c->d_cverts, sp.tab = model == MI_STRESS_LINEAR ? c->d_stress_tab : c->d_tab;
+    sp.u  = c->vec(MI_V_TOTAL_DISPLACEMENT);
+    sp.mu = c->mat.mu, sp.kappa = c->kappa, sp.lambda = 2 * c->mat.mu * c->mat.nu / (1 - 2 * c->mat.nu); // parameters.cc:189
+    sp.acc      = c->d_stress;
+    sp.inverted = c->d_sc + SC_ENERGY + 3;
+    // (experiments build: the generic kernel on 3D Q2 / Q3 as well, the cross-check of the two sum-factorised forms)
+    static const bool generic = mi::exp_env("MI_STRESS_GENERIC") && atoi(mi::exp_env("MI_STRESS_GENERIC")) != 0;
+    for (int col = 0; col < c->mesh.ncolours; ++col)
+      {
+        sp.cell_begin = c->mesh.colour_begin[col];
+        sp.cell_count = int32_t(c->mesh.colour_begin[col + 1] - c->mesh.colour_begin[col]);
+        if (mi::launch_stress(c->dim, c->degree, model, f, sp, generic, c->stream))
+          return fail(c, MI_EINVAL, "no stress kernel for dim=%d degree=%d", c->dim, c->degree);
+      }
+    double *out = c->d_stress + nn * 8;
+    mi::launch_stress_finish(c->dim, c->d_stress, int64_t(nn), out, out + nn * ncomp, out + nn * (ncomp + 1), c->stream);
+    HIPCHK(c, hipGetLastError());
     return MI_OK;
   }
 
@@ -1928,7 +1977,8 @@ namespace mi_detail
                     c->d_qrec27, c->d_tab27, c->d_qrec_q3, c->d_qrec_q3s, c->d_tab_q3s, c->d_diag_blk, c->d_diag_slots, c->d_diagpos_mf, c->d_face_slots, c->d_fn_ids, c->d_fn_start, c->d_fn_src,
                     c->d_pred[0][0], c->d_pred[0][1], c->d_pred[1][0], c->d_pred[1][1], c->d_pred[2][0], c->d_pred[2][1], c->d_pred[3][0], c->d_pred[3][1],
                     c->d_pred_saved[0][0], c->d_pred_saved[0][1], c->d_pred_saved[1][0], c->d_pred_saved[1][1], c->d_pred_saved[2][0],
-                    c->d_pred_saved[2][1], c->d_pred_saved[3][0], c->d_pred_saved[3][1], c->d_energy, c->d_energy_box};
+                    c->d_pred_saved[2][1], c->d_pred_saved[3][0], c->d_pred_saved[3][1], c->d_energy, c->d_energy_box,
+                    c->d_stress, c->d_stress_tab};
     for (void *p : ptrs)
       if (p)
         hipFree(p);
@@ -2681,6 +2731,64 @@ int mi_energy(mi_ctx *c, mi_energy_info *out)
     return fail(c, MI_EINVAL, "inverted element: det F <= 0 at a quadrature point (the displacement has folded a cell; the "
                               "reference asserts det F > 0, nonlinear_elasticity.cc:935)");
   return rc;
+}
+
+// Nodal stress field of the committed state (MI_V_TOTAL_DISPLACEMENT): the lumped L2 projection of the Cauchy stress (model 0)
+// or of the linear model's stress (model 1) onto all nodes, its von Mises stress and the lumped weights, as global arrays in
+// the reference's node order.  Needs no matrix, record or hierarchy and changes none; every slab computes its local cells and
+// hands over its owned nodes (as mi_get_diagonal_blocks: one process only); no timing slot, no counter
+int mi_stress_field(mi_ctx *c, int model, double *sigma, double *von_mises, double *weight)
+{
+  if (!c)
+    return MI_EINVAL;
+  if (!sigma)
+    return fail(c, MI_EINVAL, "mi_stress_field: null argument");
+  if (model != MI_STRESS_NEOHOOKE && model != MI_STRESS_LINEAR)
+    return fail(c, MI_EINVAL, "mi_stress_field: model %d (0: neo-Hookean Cauchy stress, 1: linear stress)", model);
+  Team &T = *c->team;
+  if (T.nccl)
+    return fail(c, MI_EINVAL, "mi_stress_field: one process only (single or emulated slabs)");
+  HIPCHK(c, hipSetDevice(c->device));
+  for (mi_ctx *m : T.members)
+    if (const int rc = enqueue_stress(m, model))
+      return m == c ? rc : fail(c, rc, "%s", m->err.c_str());
+  const size_t        ncomp = size_t(c->dim * (c->dim + 1) / 2);
+  double              inverted = 0.0;
+  std::vector<double> h;
+  for (mi_ctx *m : T.members)
+    {
+      const size_t nn = size_t(m->mesh.nnodes);
+      double       flag = 0.0;
+      HIPCHK(m, hipStreamSynchronize(m->stream));
+      HIPCHK(m, hipMemcpy(&flag, m->d_sc + SC_ENERGY + 3, sizeof(double), hipMemcpyDeviceToHost));
+      inverted += flag;
+      const double *res = m->d_stress + nn * 8;
+      if (T.size == 1 && T.i2e.empty()) // one context in the reference's node order: straight into the caller's arrays
+        {
+          HIPCHK(m, hipMemcpy(sigma, res, nn * ncomp * sizeof(double), hipMemcpyDeviceToHost));
+          if (von_mises)
+            HIPCHK(m, hipMemcpy(von_mises, res + nn * ncomp, nn * sizeof(double), hipMemcpyDeviceToHost));
+          if (weight)
+            HIPCHK(m, hipMemcpy(weight, res + nn * (ncomp + 1), nn * sizeof(double), hipMemcpyDeviceToHost));
+          break;
+        }
+      h.resize(nn * (ncomp + 2));
+      HIPCHK(m, hipMemcpy(h.data(), res, h.size() * sizeof(double), hipMemcpyDeviceToHost));
+      for (int64_t ln = m->slab.own_begin; ln < m->slab.own_end; ++ln)
+        {
+          const size_t g = size_t(T.ext_node(ln + m->slab.node_offset));
+          for (size_t k = 0; k < ncomp; ++k)
+            sigma[g * ncomp + k] = h[size_t(ln) * ncomp + k];
+          if (von_mises)
+            von_mises[g] = h[nn * ncomp + size_t(ln)];
+          if (weight)
+            weight[g] = h[nn * (ncomp + 1) + size_t(ln)];
+        }
+    }
+  if (inverted > 0.0) // the Cauchy stress has no meaning there; the same error as an assembly of this state gives
+    return fail(c, MI_EINVAL, "inverted element: det F <= 0 at a quadrature point (the displacement has folded a cell; the "
+                              "reference asserts det F > 0, nonlinear_elasticity.cc:935)");
+  return MI_OK;
 }
 
 int mi_comm_info(const mi_ctx *c, int *team_size, int *rccl_ranks)

@@ -250,6 +250,9 @@ struct mi_ctx
   // must not change what a later assembly computes)
   double   *d_energy = nullptr, *d_energy_box = nullptr;
   bool      energy_box_checked = false;
+  // nodal stress recovery (mi_stress_field), allocated on first use: the accumulator [nnodes][8] with the results behind it
+  // (sigma, von Mises, weight); the 1D tables of the linear model's rule QGauss(p + 1) (model MI_STRESS_LINEAR)
+  double   *d_stress = nullptr, *d_stress_tab = nullptr;
   uint16_t *d_off   = nullptr;
   uint8_t  *d_cmask = nullptr;
   double   *h_pinned = nullptr; // pinned host scratch (scalars, flags, interface buffer)

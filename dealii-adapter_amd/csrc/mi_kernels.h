@@ -243,6 +243,21 @@ namespace mi
     int32_t        own_node_end; // a cell whose first node is this or a later one belongs to the slab's ghost layer: zeros
   };
 
+  // nodal stress recovery (see stress_q2 / stress_q3 / stress_cells): the state, the material, the accumulator, the colour's cells.
+  // The two sum-factorised forms take mesh tables, 1D tables and geometry from MfParams; stress_cells from here
+  struct StressParams
+  {
+    const int32_t *conn;   // [ncells][npc] colour-sorted
+    const double  *cverts; // [ncells][2^dim][dim]
+    const double  *tab;    // the 1D tables of the model's rule: the assembly's (AsmParams::tab1d) or the linear model's (LinAsmParams::tab)
+    const double  *u;      // total displacement (the committed state)
+    double         mu, kappa, lambda;
+    double        *acc;      // [nnodes][8]: sum of N_i w sigma in the order xx yy zz xy xz yz, sum of N_i w, one spare; zeroed by the caller
+    double        *inverted; // as AsmParams::inverted (a slot of its own)
+    int64_t        cell_begin; // the cells of ONE colour: no two of them share a node
+    int32_t        cell_count;
+  };
+
   // matrix-free operator of the linear model on 3D Q3 cells (see mf_linear_q3): y = (c_K K + c_M M) x
   struct MfLinearOp
   {
@@ -412,6 +427,12 @@ namespace mi
   // out[3]; scratch holds 3 doubles per 1024 cells
   int  launch_energy(int dim, int degree, const MfParams &p, const EnergyParams &e, int32_t cell_count, bool generic, hipStream_t s);
   void launch_energy_sum(const double *cell_e, int64_t ncells, double *scratch, double *out, hipStream_t s);
+  // nodal stress recovery: the cells [sp.cell_begin, + sp.cell_count) of one colour add their seven numbers per node to sp.acc,
+  // by the kernel of (dim, degree, model) -- stress_q3, stress_q2 (model 0; p.conn, p.tab1d, p.cverts / p.cellbox) or
+  // stress_cells; generic: stress_cells on 3D Q2 / Q3 too (cross-check).  -1: no kernel for the element.  launch_stress_finish:
+  // sigma[nnodes][dim (dim + 1) / 2] = acc / W, von_mises[nnodes] of that tensor, weight[nnodes] = W
+  int  launch_stress(int dim, int degree, int model, const MfParams &p, const StressParams &sp, bool generic, hipStream_t s);
+  void launch_stress_finish(int dim, const double *acc, int64_t nnodes, double *sigma, double *von_mises, double *weight, hipStream_t s);
   // ... the multigrid smoother's operator on the element's full-order rule, 4 x 4 x 4 points (see mf_spmv_q3s): records
   // [ncells][MF_NREC][64] of its own (MfParams::qrec_q3s, written by mf_records_q3s from u + du with the fold rule of
   // mf_records27), the rule's 1D tables MfParams::tab_q3s; one wave per cell, the results into the same cell-major slots

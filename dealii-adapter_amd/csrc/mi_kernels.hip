@@ -4929,6 +4929,392 @@ namespace mi
         out[blockIdx.x * 3 + 2] = s[2];
       }
   }
+  // ------------------------------------------------------------------ nodal stress recovery (mi_stress_field)
+  // Lumped L2 projection of the stress onto the nodes, in the reference configuration:
+  //   W_i = sum_cells sum_q N_i(q) JxW(q),   sigma_i = (sum_cells sum_q N_i(q) sigma(q) JxW(q)) / W_i
+  // model 0: sigma(q) = tau(F)/J, the Cauchy stress of neo_hooke_from_F at F = I + grad u on the assembly's rule QGauss(p + 2);
+  // model 1: sigma(q) = lambda tr(eps) I + 2 mu eps, eps = sym grad u, on the linear model's rule QGauss(p + 1).
+  // A cell kernel is the forward half of the residual pass up to the point stage and a VALUE-ONLY back-contraction
+  // sum_q N_a(q) (...) of seven fields: w sigma in sym6 order (xx yy zz xy xz yz; 2D: zz, xz, yz stay zero) and w = JxW.
+  // One launch per colour: within a colour no two cells share a node, so a cell adds its numbers to the accumulator
+  // acc[nnodes][8] (sym6, W, one spare) with plain loads and stores; the colours run in order on one stream, so the order of
+  // the sums depends on the mesh alone and a call repeats bit by bit.  No slot table, no atomics.  stress_finish divides by W.
+  // A point with det F <= 0 (model 0) raises *inverted and contributes zeros.
+  // Forms, chosen by launch_stress: stress_q2 (3D Q2, model 0: the forward half of energy_q2 and the transposes of E3, E12 with
+  // the S table alone), stress_q3 (3D Q3, model 0: the shape of energy_q3) and stress_cells (every other element, all of
+  // model 1, and the cross-check of the two).
+  template <int DIM>
+  __device__ __forceinline__ void stress_point(const double *F, const double J, const double Jm, const double rJ, const double w,
+                                               const StressParams &sp, double g[7])
+  {
+    double Finv[9], tau[6], tiso[6], cII, cS;
+    neo_hooke_from_F<DIM>(F, J, Jm, rJ, sp.mu, sp.kappa, Finv, tau, tiso, cII, cS);
+    const bool ok = J > 0.0; // inverted element (nonlinear_elasticity.cc:935 asserts det F > 0)
+    if (!ok)
+      *sp.inverted = 1.0;
+#pragma unroll
+    for (int k = 0; k < 6; ++k)
+      g[k] = ok ? w * tau[k] * rJ : 0.0;
+    g[6] = w;
+    (void)Finv, (void)tiso, (void)cII, (void)cS;
+  }
+
+  // 3D Q2, model 0: one wave per cell, lane = point of the 4 x 4 x 4 rule.  Forward: the gather and E12, E3 of energy_q2 on u
+  // alone.  Backward, through LDS: B3 contracts qz (item = (k, qy, qx), 48 per field), B12 contracts qy and qx (lane = node
+  // (i, j, k), 27 lanes), both with S[q][a] = N_a(x_q).  sG lies over sB (E3 has consumed it, a barrier between).
+  template <bool BOX>
+  __global__ __launch_bounds__(64, 4) void stress_q2(MfParams prm, StressParams sp)
+  {
+    constexpr int NPC = 27, PS = 20, PW = 9 * PS;
+    __shared__ double sX[3 * NPC], sB[3 * PW], sC[7 * 48];
+    double *const sG   = sB; // [7][64]
+    const int     lane = threadIdx.x;
+    const int64_t cell = sp.cell_begin + blockIdx.x;
+    int32_t       node = 0;
+    if (lane < NPC)
+      {
+        node = prm.conn[cell * NPC + lane];
+#pragma unroll
+        for (int c = 0; c < 3; ++c)
+          sX[c * NPC + lane] = sp.u[int64_t(node) * 3 + c];
+      }
+    double S[4][3], D[4][3]; // S[q][a] = N_a(x_q), D[q][a] = N_a'(x_q) (uniform -> scalar registers)
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+#pragma unroll
+      for (int a = 0; a < 3; ++a)
+        {
+          S[q][a] = prm.tab1d[q * 3 + a];
+          D[q][a] = prm.tab1d[12 + q * 3 + a];
+        }
+    const int qz = lane >> 4, q16 = lane & 15;
+    double    Sz[3], Dz[3], Sx[3], Dx[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k)
+      {
+        Sz[k] = prm.tab1d[qz * 3 + k];
+        Dz[k] = prm.tab1d[12 + qz * 3 + k];
+        Sx[k] = prm.tab1d[(lane & 3) * 3 + k];
+        Dx[k] = prm.tab1d[12 + (lane & 3) * 3 + k];
+      }
+    const double wq = prm.tab1d[24 + (lane & 3)] * prm.tab1d[24 + ((lane >> 2) & 3)] * prm.tab1d[24 + qz];
+    __syncthreads();
+    // ---- E12: lane = (c*3+k)*4 + qx contracts i, then j
+    const int pck = lane >> 2, pqx = lane & 3;
+    if (lane < 36)
+      {
+        double as[3], ad[3];
+#pragma unroll
+        for (int j = 0; j < 3; ++j)
+          {
+            const double x0 = sX[pck * 9 + j * 3], x1 = sX[pck * 9 + j * 3 + 1], x2 = sX[pck * 9 + j * 3 + 2];
+            as[j] = Sx[0] * x0 + Sx[1] * x1 + Sx[2] * x2;
+            ad[j] = Dx[0] * x0 + Dx[1] * x1 + Dx[2] * x2;
+          }
+#pragma unroll
+        for (int qy = 0; qy < 4; ++qy)
+          {
+            const int o    = pck * PS + qy * 4 + pqx;
+            sB[o]          = S[qy][0] * ad[0] + S[qy][1] * ad[1] + S[qy][2] * ad[2]; // d/dx
+            sB[o + PW]     = D[qy][0] * as[0] + D[qy][1] * as[1] + D[qy][2] * as[2]; // d/dy
+            sB[o + 2 * PW] = S[qy][0] * as[0] + S[qy][1] * as[1] + S[qy][2] * as[2]; // d/dz
+          }
+      }
+    __syncthreads();
+    // ---- E3: contract k.  lane = quadrature point; H[c][l] = d u_c / d xi_l
+    double H[3][3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+      {
+        H[c][0] = H[c][1] = H[c][2] = 0.0;
+#pragma unroll
+        for (int k = 0; k < 3; ++k)
+          {
+            const int o = (c * 3 + k) * PS + q16;
+            H[c][0]     = fma(Sz[k], sB[o], H[c][0]);
+            H[c][1]     = fma(Sz[k], sB[o + PW], H[c][1]);
+            H[c][2]     = fma(Dz[k], sB[o + 2 * PW], H[c][2]);
+          }
+      }
+    double g[7];
+    {
+      double Ji[9], detJ;
+      mf_geometry<BOX>(prm, cell, prm.tab1d + 28, lane & 3, (lane >> 2) & 3, qz, Ji, detJ);
+      MF_RECORD_TAIL(false, false, static_cast<double *>(nullptr), 64)
+      stress_point<3>(F, J, Jm, rJ, detJ * wq, sp, g);
+    }
+    __syncthreads(); // every lane has read sB: sG may overwrite it
+#pragma unroll
+    for (int f = 0; f < 7; ++f)
+      sG[f * 64 + lane] = g[f];
+    __syncthreads();
+    // ---- B3: item (k, q16), lanes 0..47: C_f[k][q16] = sum_qz S[qz][k] g_f(qz, q16)
+    if (lane < 48)
+      {
+        const int    k  = lane >> 4;
+        const double s0 = prm.tab1d[k], s1 = prm.tab1d[3 + k], s2 = prm.tab1d[6 + k], s3 = prm.tab1d[9 + k];
+#pragma unroll
+        for (int f = 0; f < 7; ++f)
+          sC[f * 48 + lane] = s0 * sG[f * 64 + q16] + s1 * sG[f * 64 + 16 + q16] + s2 * sG[f * 64 + 32 + q16] + s3 * sG[f * 64 + 48 + q16];
+      }
+    __syncthreads();
+    // ---- B12: lane = node (i, j, k): sum_qy S[qy][j] sum_qx S[qx][i] C_f[k][qy][qx], then into the accumulator
+    if (lane < NPC)
+      {
+        const int i = lane % 3, j = (lane / 3) % 3, k = lane / 9;
+        double    si[4], sj[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+          {
+            si[q] = prm.tab1d[q * 3 + i];
+            sj[q] = prm.tab1d[q * 3 + j];
+          }
+        double *__restrict__ o = sp.acc + int64_t(node) * 8;
+#pragma unroll
+        for (int f = 0; f < 7; ++f)
+          {
+            double r = 0.0;
+#pragma unroll
+            for (int qy = 0; qy < 4; ++qy)
+              {
+                const double *c4 = sC + f * 48 + k * 16 + qy * 4;
+                r = fma(sj[qy], si[0] * c4[0] + si[1] * c4[1] + si[2] * c4[2] + si[3] * c4[3], r);
+              }
+            o[f] += r;
+          }
+      }
+  }
+
+  // 3D Q3, model 0: the shape of energy_q3 / mf_point_pass_q3 -- 128 threads per cell, thread = point of the 5 x 5 x 5 rule
+  // (threads 125-127 contribute exact zeros).  Forward: the gather and mfq3_gradients on u.  Backward, value-only, in the LDS
+  // places of the point pass with seven fields where it carries nine:
+  //   g  [f][point]           R0, 7 x MFQ3_QS
+  //   I3' item (f, qy, qx):   contract qz -> C [f,k][qy][qx]     R1, 175 items (two rounds), 700 doubles
+  //   I2' item (f, k, qx):    contract qy -> E [f,k,j][qx]       R0 over g, 140 items (two rounds), 560 doubles
+  //   I1' item (f, k, j):     contract qx -> the line's four nodes, into the accumulator; 112 items
+  // 4 waves per SIMD without spills in both instances (V is not kept, so the general one fits where energy_q3's did not).
+  template <bool BOX>
+  __global__ __launch_bounds__(MFQ3_NT, 4) void stress_q3(MfParams prm, StressParams sp)
+  {
+    __shared__ double  R0[MFQ3_R0], R1[MFQ3_R1], sT[40];
+    __shared__ int32_t sN[MFQ3_NPC];
+    const int     t    = threadIdx.x, it = t < MFQ3_NQ ? t : MFQ3_NQ - 1;
+    const int64_t cell = sp.cell_begin + blockIdx.x;
+    if (t < 40)
+      sT[t] = prm.tab1d[t];
+    if (t < MFQ3_NPC)
+      {
+        const int32_t node = prm.conn[cell * MFQ3_NPC + t];
+        sN[t]              = node;
+#pragma unroll
+        for (int c = 0; c < 3; ++c)
+          R1[c * MFQ3_NPC + t] = sp.u[int64_t(node) * 3 + c];
+      }
+    __syncthreads();
+    double H[3][3], V[3];
+    mfq3_gradients(prm.tab1d, sT, R0, R1, t, it, H, V); // (ends with a barrier: R0 and R1 are free)
+    {
+      const int    qz = it / 25, qy = (it - 25 * qz) / 5, qx = it - 25 * qz - 5 * qy;
+      const double wq = prm.tab1d[MFQ3_TW + qx] * prm.tab1d[MFQ3_TW + qy] * prm.tab1d[MFQ3_TW + qz];
+      double       Ji[9], detJ, g[7];
+      mf_geometry<BOX>(prm, cell, prm.tab1d + MFQ3_TX, qx, qy, qz, Ji, detJ);
+      MF_RECORD_TAIL(false, false, static_cast<double *>(nullptr), MFQ3_QS)
+      stress_point<3>(F, J, Jm, rJ, detJ * wq, sp, g);
+#pragma unroll
+      for (int f = 0; f < 7; ++f)
+        R0[f * MFQ3_QS + t] = t < MFQ3_NQ ? g[f] : 0.0;
+      (void)V;
+    }
+    double S[5][4]; // uniform: scalar registers
+#pragma unroll
+    for (int q = 0; q < 5; ++q)
+#pragma unroll
+      for (int a = 0; a < 4; ++a)
+        S[q][a] = prm.tab1d[q * 4 + a];
+    __syncthreads();
+    for (int item = t; item < 7 * 25; item += MFQ3_NT) // I3'
+      {
+        const int f = item / 25, q25 = item - 25 * f;
+        double    v[5];
+#pragma unroll
+        for (int z = 0; z < 5; ++z)
+          v[z] = R0[f * MFQ3_QS + z * 25 + q25];
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+          R1[(f * 4 + k) * 25 + q25] = S[0][k] * v[0] + S[1][k] * v[1] + S[2][k] * v[2] + S[3][k] * v[3] + S[4][k] * v[4];
+      }
+    __syncthreads();
+    for (int item = t; item < 7 * 4 * 5; item += MFQ3_NT) // I2'
+      {
+        const int fk = item / 5, qx = item - 5 * fk;
+        double    c5[5];
+#pragma unroll
+        for (int qy = 0; qy < 5; ++qy)
+          c5[qy] = R1[fk * 25 + qy * 5 + qx];
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          R0[(fk * 4 + j) * 5 + qx] = S[0][j] * c5[0] + S[1][j] * c5[1] + S[2][j] * c5[2] + S[3][j] * c5[3] + S[4][j] * c5[4];
+      }
+    __syncthreads();
+    if (t < 7 * 16) // I1': line (f, k, j) = t
+      {
+        const int f = t >> 4, kj = t & 15;
+        double    e5[5];
+#pragma unroll
+        for (int qx = 0; qx < 5; ++qx)
+          e5[qx] = R0[t * 5 + qx];
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+          sp.acc[int64_t(sN[kj * 4 + i]) * 8 + f] += S[0][i] * e5[0] + S[1][i] * e5[1] + S[2][i] * e5[2] + S[3][i] * e5[3] + S[4][i] * e5[4];
+      }
+  }
+
+  // every other element (2D p = 1..4, 3D p = 1, 4), all of model 1, and the cross-check of the two forms above: one workgroup per cell,
+  // thread = quadrature point for the point stage (plain loops over the cell's nodes as in energy_cells), thread = node for
+  // the back-contraction (plain loop over the points, in ascending order)
+  template <int DIM, int P, int MODEL, int NT>
+  __global__ __launch_bounds__(NT) void stress_cells(StressParams sp)
+  {
+    constexpr int NP1 = P + 1, NPC = Elem<DIM, P>::NPC, NV = 1 << DIM;
+    constexpr int NQ1 = MODEL == 0 ? P + 2 : P + 1; // qf_cell (nonlinear_elasticity.cc:74) / quad_order (linear_elasticity.cc:61)
+    constexpr int NQ  = DIM == 2 ? NQ1 * NQ1 : NQ1 * NQ1 * NQ1;
+    static_assert(NQ <= NT && NPC <= NT && NT % 64 == 0, "one thread per quadrature point and per node, whole waves");
+    __shared__ double s_N1[NQ1 * NP1], s_dN1[NQ1 * NP1], s_qw[NQ1], s_qx[NQ1];
+    __shared__ double s_u[NPC * DIM], s_verts[NV * DIM], s_g[NQ * 8];
+    const int     tid  = threadIdx.x;
+    const int64_t cell = sp.cell_begin + blockIdx.x;
+    for (int i = tid; i < NQ1 * NP1; i += NT)
+      {
+        s_N1[i]  = sp.tab[i];
+        s_dN1[i] = sp.tab[NQ1 * NP1 + i];
+      }
+    if (tid < NQ1)
+      {
+        s_qw[tid] = sp.tab[2 * NQ1 * NP1 + tid];
+        s_qx[tid] = sp.tab[2 * NQ1 * NP1 + NQ1 + tid];
+      }
+    if (tid < NV * DIM)
+      s_verts[tid] = sp.cverts[cell * (NV * DIM) + tid];
+    for (int i = tid; i < NPC * DIM; i += NT)
+      {
+        const int a = i / DIM, c = i - a * DIM;
+        s_u[i]      = sp.u[int64_t(sp.conn[cell * NPC + a]) * DIM + c];
+      }
+    __syncthreads();
+    if (tid < NQ)
+      {
+        const int q     = tid;
+        const int qi[3] = {q % NQ1, (q / NQ1) % NQ1, (DIM == 3) ? q / (NQ1 * NQ1) : 0};
+        double    gxi[9];
+#pragma unroll
+        for (int k = 0; k < 9; ++k)
+          gxi[k] = 0.0;
+        for (int a = 0; a < NPC; ++a)
+          {
+            const int    ai[3] = {a % NP1, (a / NP1) % NP1, (DIM == 3) ? a / (NP1 * NP1) : 0};
+            const double n0 = s_N1[qi[0] * NP1 + ai[0]], n1 = s_N1[qi[1] * NP1 + ai[1]], n2 = (DIM == 3) ? s_N1[qi[2] * NP1 + ai[2]] : 1.0;
+            const double dN[3] = {s_dN1[qi[0] * NP1 + ai[0]] * n1 * n2, n0 * s_dN1[qi[1] * NP1 + ai[1]] * n2,
+                                  (DIM == 3) ? n0 * n1 * s_dN1[qi[2] * NP1 + ai[2]] : 0.0};
+#pragma unroll
+            for (int i = 0; i < DIM; ++i)
+#pragma unroll
+              for (int j = 0; j < DIM; ++j)
+                gxi[i * 3 + j] = fma(s_u[a * DIM + i], dN[j], gxi[i * 3 + j]);
+          }
+        double xi[3] = {0.0, 0.0, 0.0}, wq = 1.0;
+#pragma unroll
+        for (int d = 0; d < DIM; ++d)
+          {
+            xi[d] = s_qx[qi[d]];
+            wq *= s_qw[qi[d]];
+          }
+        double Jg[9], Ji[9];
+        q1_jacobian<DIM>(s_verts, xi, Jg);
+        const double detJ = det3x3(Jg);
+        inv3x3(Jg, detJ, Ji);
+        double F[9]; // grad u = grad_xi u Jinv, embedded in 3 x 3 (model 0: + I)
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+#pragma unroll
+          for (int j = 0; j < 3; ++j)
+            F[i * 3 + j] = (i < DIM && j < DIM) ? gxi[i * 3 + 0] * Ji[0 * 3 + j] + gxi[i * 3 + 1] * Ji[1 * 3 + j] +
+                                                    (DIM == 3 ? gxi[i * 3 + 2] * Ji[2 * 3 + j] : 0.0) :
+                                                  0.0;
+        const double w = detJ * wq;
+        double       g[7];
+        if constexpr (MODEL == 0)
+          {
+            F[0] += 1.0, F[4] += 1.0, F[8] += 1.0;
+            const double J  = det3x3(F);
+            const double rJ = 1.0 / J, Jm = (DIM == 3) ? 1.0 / (cbrt(J) * cbrt(J)) : rJ; // J^(-2/d)
+            stress_point<DIM>(F, J, Jm, rJ, w, sp, g);
+          }
+        else
+          {
+            const double ltr = sp.lambda * (F[0] + F[4] + F[8]), m2 = 2.0 * sp.mu;
+            g[0] = w * (ltr + m2 * F[0]);
+            g[1] = w * (ltr + m2 * F[4]);
+            g[2] = (DIM == 3) ? w * (ltr + m2 * F[8]) : 0.0;
+            g[3] = w * sp.mu * (F[1] + F[3]);
+            g[4] = w * sp.mu * (F[2] + F[6]);
+            g[5] = w * sp.mu * (F[5] + F[7]);
+            g[6] = w;
+          }
+#pragma unroll
+        for (int f = 0; f < 7; ++f)
+          s_g[q * 8 + f] = g[f];
+      }
+    __syncthreads();
+    if (tid < NPC)
+      {
+        const int a     = tid;
+        const int ai[3] = {a % NP1, (a / NP1) % NP1, (DIM == 3) ? a / (NP1 * NP1) : 0};
+        double    r[7]  = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+        for (int q = 0; q < NQ; ++q)
+          {
+            const int    qj[3] = {q % NQ1, (q / NQ1) % NQ1, (DIM == 3) ? q / (NQ1 * NQ1) : 0};
+            const double N = s_N1[qj[0] * NP1 + ai[0]] * s_N1[qj[1] * NP1 + ai[1]] * ((DIM == 3) ? s_N1[qj[2] * NP1 + ai[2]] : 1.0);
+#pragma unroll
+            for (int f = 0; f < 7; ++f)
+              r[f] = fma(N, s_g[q * 8 + f], r[f]);
+          }
+        double *__restrict__ o = sp.acc + int64_t(sp.conn[cell * NPC + a]) * 8;
+#pragma unroll
+        for (int f = 0; f < 7; ++f)
+          o[f] += r[f];
+      }
+  }
+
+  // one thread per node: sigma = acc / W in the component order xx yy zz xy xz yz (2D: xx yy xy), the von Mises stress of that
+  // NODAL tensor -- 3D sqrt(3/2 s : s), s = sigma - tr(sigma)/3 I; 2D the in-plane form sqrt(sxx^2 - sxx syy + syy^2 + 3 sxy^2)
+  // (the 2D formulation has no sigma_zz) -- and W
+  template <int DIM>
+  __global__ __launch_bounds__(256) void stress_finish(const double *__restrict__ acc, const int64_t nnodes, double *__restrict__ sigma,
+                                                       double *__restrict__ von_mises, double *__restrict__ weight)
+  {
+    const int64_t i = int64_t(blockIdx.x) * 256 + threadIdx.x;
+    if (i >= nnodes)
+      return;
+    const double W = acc[i * 8 + 6];
+    double       s[6];
+#pragma unroll
+    for (int k = 0; k < 6; ++k)
+      s[k] = acc[i * 8 + k] / W;
+    if constexpr (DIM == 3)
+      {
+#pragma unroll
+        for (int k = 0; k < 6; ++k)
+          sigma[i * 6 + k] = s[k];
+        const double m = (s[0] + s[1] + s[2]) / 3.0, d0 = s[0] - m, d1 = s[1] - m, d2 = s[2] - m;
+        von_mises[i]   = sqrt(1.5 * (d0 * d0 + d1 * d1 + d2 * d2 + 2.0 * (s[3] * s[3] + s[4] * s[4] + s[5] * s[5])));
+      }
+    else
+      {
+        sigma[i * 3] = s[0], sigma[i * 3 + 1] = s[1], sigma[i * 3 + 2] = s[3];
+        von_mises[i] = sqrt(s[0] * s[0] - s[0] * s[1] + s[1] * s[1] + 3.0 * s[3] * s[3]);
+      }
+    weight[i] = W;
+  }
   // (the last matrix-free kernel: the shared text ends here)
 #undef MF_RECORD_TAIL
 #undef MF_M
@@ -8043,6 +8429,52 @@ namespace mi
       }
     hipLaunchKernelGGL(energy_sum, dim3(nblk), dim3(256), 0, s, cell_e, ncells, chunk, scratch);
     hipLaunchKernelGGL(energy_sum, dim3(1), dim3(256), 0, s, scratch, int64_t(nblk), int64_t(nblk), out);
+  }
+  int launch_stress(int dim, int degree, int model, const MfParams &p, const StressParams &sp, bool generic, hipStream_t s)
+  {
+    if (sp.cell_count <= 0)
+      return 0;
+    if (dim == 3 && degree == 3 && model == 0 && !generic)
+      {
+        auto *kern = p.cellbox ? stress_q3<true> : stress_q3<false>;
+        hipLaunchKernelGGL(kern, dim3(sp.cell_count), dim3(MFQ3_NT), 0, s, p, sp);
+        return 0;
+      }
+    if (dim == 3 && degree == 2 && model == 0 && !generic)
+      {
+        auto *kern = p.cellbox ? stress_q2<true> : stress_q2<false>;
+        hipLaunchKernelGGL(kern, dim3(sp.cell_count), dim3(64), 0, s, p, sp);
+        return 0;
+      }
+#define MI_ST(D_, P_, NT_)                                                                                          \
+  if (dim == D_ && degree == P_)                                                                                    \
+    {                                                                                                               \
+      if (model == 0)                                                                                               \
+        hipLaunchKernelGGL((stress_cells<D_, P_, 0, NT_>), dim3(sp.cell_count), dim3(NT_), 0, s, sp);               \
+      else                                                                                                          \
+        hipLaunchKernelGGL((stress_cells<D_, P_, 1, NT_>), dim3(sp.cell_count), dim3(NT_), 0, s, sp);               \
+      return 0;                                                                                                     \
+    }
+    MI_ST(3, 1, 64)
+    MI_ST(3, 2, 64)
+    MI_ST(3, 3, 128)
+    MI_ST(3, 4, 256)
+    MI_ST(2, 1, 64)
+    MI_ST(2, 2, 64)
+    MI_ST(2, 3, 64)
+    MI_ST(2, 4, 64)
+#undef MI_ST
+    return -1;
+  }
+  void launch_stress_finish(int dim, const double *acc, int64_t nnodes, double *sigma, double *von_mises, double *weight, hipStream_t s)
+  {
+    if (nnodes <= 0)
+      return;
+    const int grid = int((nnodes + 255) / 256);
+    if (dim == 3)
+      hipLaunchKernelGGL(stress_finish<3>, dim3(grid), dim3(256), 0, s, acc, nnodes, sigma, von_mises, weight);
+    else
+      hipLaunchKernelGGL(stress_finish<2>, dim3(grid), dim3(256), 0, s, acc, nnodes, sigma, von_mises, weight);
   }
   void launch_mf_diag_q3(const MfParams &p, double *slots6, int32_t cell_count, hipStream_t s)
   {

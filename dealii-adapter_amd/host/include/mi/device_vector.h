@@ -83,6 +83,21 @@ namespace mi
     Device &operator=(const Device &) = delete;
 
     mi_ctx *ctx() const { return ctx_; }
+    // nodal stress field of the committed state (mi_stress_field; model MI_STRESS_NEOHOOKE / MI_STRESS_LINEAR): sigma
+    // [n_nodes][dim (dim + 1) / 2] and von Mises [n_nodes] in the reference's node order.  false on an RCCL team, where the
+    // library provides none (one process only); any other failure throws
+    bool stress_field(int model, int dim, std::vector<double> &sigma, std::vector<double> &von_mises) const
+    {
+      int team = 1, rccl = 0;
+      check(mi_comm_info(ctx_, &team, &rccl), "mi_comm_info");
+      if (rccl > 0)
+        return false;
+      const size_t nn = size_t(mi_n_nodes(ctx_));
+      sigma.assign(nn * size_t(dim * (dim + 1) / 2), 0.0);
+      von_mises.assign(nn, 0.0);
+      check(mi_stress_field(ctx_, model, sigma.data(), von_mises.data(), nullptr), "mi_stress_field");
+      return true;
+    }
     void    check(int rc, const char *what) const
     {
       if (rc != MI_OK)

@@ -8,9 +8,14 @@
 // the patch's (p+1)^dim points listed in VTK's Lagrange order, as the reference's `flags.write_higher_order_cells = true`
 // makes DataOut write them (nonlinear_elasticity.cc:1222-1225, linear_elasticity.cc:599; needs ParaView >= 5.5, :1221).
 // higher_order = false: the patch split into p^dim linear sub-cells (types 9 / 12; rounds 1-5), for older readers.
+// stress_model >= 0 (the executables' MI_VTK_STRESS=1): further point data in the same file, stress_xx ... (the dim (dim + 1) / 2
+// unique components: xx yy zz xy xz yz, 2D xx yy xy) and von_mises -- the NODAL values of mi_stress_field (the lumped L2
+// projection of the Cauchy stress, model 0, or of the linear model's stress, model 1) at the patch points, so unlike strain_*
+// they are continuous across cells.  Without it the file is byte for byte what it was.
 #pragma once
 #include <cmath>
 #include <fstream>
+#include <iostream>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -108,12 +113,20 @@ namespace mi
   // team collectives (ncclAllReduce under RCCL), which hang or pair up with the wrong collective when only one rank
   // enters them.  write = false (ranks > 0): take part in the gathers, write nothing.
   inline void write_vtk(const Device &dev, int dim, int p, const int reps[3], const std::string &path, bool write = true,
-                        bool higher_order = true)
+                        bool higher_order = true, int stress_model = -1)
   {
     const int64_t       nn = mi_n_nodes(dev.ctx()), n = mi_n_dofs(dev.ctx());
     std::vector<double> xyz(size_t(nn) * dim), u(size_t(n), 0.0);
     dev.check(mi_get_node_coords(dev.ctx(), xyz.data()), "mi_get_node_coords");
     dev.check(mi_vec_get(dev.ctx(), MI_V_TOTAL_DISPLACEMENT, u.data(), n), "mi_vec_get");
+    std::vector<double> sig, vm;
+    bool                have_stress = false;
+    if (stress_model >= 0)
+      {
+        have_stress = dev.stress_field(stress_model, dim, sig, vm);
+        if (!have_stress && write)
+          std::cout << "\t MI_VTK_STRESS: mi_stress_field runs in one process only, no stress is written on an RCCL team" << std::endl;
+      }
     if (!write)
       return;
     std::ofstream out(path);
@@ -134,7 +147,7 @@ namespace mi
 
     std::vector<double> pts(size_t(ncells) * npc * 3, 0.0), disp(size_t(ncells) * npc * 3, 0.0),
       strain(size_t(ncells) * npc * dim * dim, 0.0);
-    std::vector<int64_t> node((size_t)npc, 0);
+    std::vector<int64_t> node((size_t)npc, 0), pnode(have_stress ? size_t(ncells) * npc : 0, 0); // pnode: the node of every patch point
     for (int64_t c = 0; c < ncells; ++c)
       {
         const int ci[3] = {int(c % rr[0]), int((c / rr[0]) % rr[1]), int(c / (int64_t(rr[0]) * rr[1]))};
@@ -206,6 +219,8 @@ namespace mi
                     gx[i][j] += gu[i][k] * Fi[k][j]; // grad_x u: gradient in the (displaced) output mapping
                 }
             const size_t q = size_t(c) * npc + a;
+            if (have_stress)
+              pnode[q] = node[size_t(a)];
             for (int d = 0; d < dim; ++d)
               {
                 disp[q * 3 + d] = u[size_t(node[size_t(a)]) * dim + d];
@@ -273,5 +288,19 @@ namespace mi
           for (int64_t i = 0; i < npts; ++i)
             out << strain[size_t(i) * dim * dim + d * dim + e] << '\n';
         }
+    if (have_stress)
+      {
+        static const char *const comp3[] = {"xx", "yy", "zz", "xy", "xz", "yz"}, *const comp2[] = {"xx", "yy", "xy"};
+        const int                ncomp   = dim * (dim + 1) / 2;
+        for (int k = 0; k < ncomp; ++k)
+          {
+            out << "SCALARS stress_" << (dim == 3 ? comp3[k] : comp2[k]) << " double 1\nLOOKUP_TABLE default\n";
+            for (int64_t i = 0; i < npts; ++i)
+              out << sig[size_t(pnode[size_t(i)]) * ncomp + k] << '\n';
+          }
+        out << "SCALARS von_mises double 1\nLOOKUP_TABLE default\n";
+        for (int64_t i = 0; i < npts; ++i)
+          out << vm[size_t(pnode[size_t(i)])] << '\n';
+      }
   }
 } // namespace mi

@@ -207,6 +207,33 @@ typedef struct
  * MI_EINVAL "inverted element" as from mi_assemble, since ln J has no value there. */
 int mi_energy(mi_ctx *ctx, mi_energy_info *out);
 
+/* Nodal stress field: what the stress is and where it is largest.  The reference's post-processor stops at the symmetric
+ * gradient (postprocessor.h:61-75); the Kirchhoff stress tau of every residual pass is dropped after its contraction with
+ * grad N.  This is the lumped L2 projection of the stress onto the nodes, in the reference configuration, with N_i the scalar
+ * shape function of node i and the model's own quadrature rule:
+ *     W_i       = sum_cells sum_q N_i(q) JxW(q)                          (lumped weight; sum_i W_i = volume)
+ *     sigma_i   = ( sum_cells sum_q N_i(q) sigma(q) JxW(q) ) / W_i
+ * MI_STRESS_NEOHOOKE: sigma(q) = tau(F)/J, the Cauchy stress of the compressible neo-Hookean material at F = I + grad u
+ *   (compressible_neo_hook_material.h:62-138), u = MI_V_TOTAL_DISPLACEMENT, the COMMITTED state as for mi_energy, on
+ *   qf_cell = QGauss(p+2) (nonlinear_elasticity.cc:74).  A point with det F <= 0: MI_EINVAL "inverted element" as from
+ *   mi_assemble / mi_energy; the context works afterwards (the arrays then hold no result).
+ * MI_STRESS_LINEAR: sigma(q) = lambda tr(eps) I + 2 mu eps, eps = sym grad u, lambda = 2 mu nu / (1 - 2 nu) (parameters.cc:189),
+ *   u = MI_L_DISPLACEMENT (the same slot), on the linear model's QGauss(p+1) (linear_elasticity.cc:61).  Needs no mi_linear_setup.
+ * sigma [n_nodes][ncomp] (required), ncomp = dim (dim + 1) / 2, in the order xx, yy, zz, xy, xz, yz (3D) or xx, yy, xy (2D);
+ * von_mises [n_nodes] and weight [n_nodes] each optional (NULL = not wanted); global arrays in the reference's node order.
+ * All nodes, constrained ones too.  von_mises is formed from the projected NODAL tensor, not projected itself: 3D
+ * sqrt(3/2 s : s), s = sigma - tr(sigma)/3 I; 2D the in-plane form sqrt(sxx^2 - sxx syy + syy^2 + 3 sxy^2), because the
+ * reference's 2D formulation has no sigma_zz.  W_i > 0 on the meshes the library builds (smallest at Q3 / Q4 corner nodes).
+ * Modifies no state vector, record, matrix, hierarchy, counter or timing (scratch of its own is allocated on first use) and
+ * needs no matrix: every (dim, degree) an assembly supports, "fine_level" 0 and 1, after a "linear_operator" 1 set-up has
+ * released the tangent array.  Bitwise repeatable: the cells add to the nodes colour by colour, the colours in order; no
+ * floating-point atomics.  Single contexts and emulated slabs (each slab computes the cells it holds and hands over the
+ * nodes it owns); on an RCCL team MI_EINVAL "one process only", as mi_get_diagonal_blocks.  A bad model, a NULL sigma or a
+ * NULL ctx: MI_EINVAL. */
+#define MI_STRESS_NEOHOOKE 0
+#define MI_STRESS_LINEAR   1
+int mi_stress_field(mi_ctx *ctx, int model, double *sigma, double *von_mises, double *weight);
+
 /* ---- linear model: ElastoDynamics (source/linear_elasticity/linear_elasticity.cc) -------------------------- */
 /* state vectors of the linear model live in the same slots as the nonlinear ones */
 enum
@@ -518,7 +545,8 @@ int mi_set_profiling(mi_ctx *ctx, int enable);
  * MI_MG_COARSE_DEGREE, MI_MG_COARSE_RATIO, MI_MG_FUSE_MAX_NODES, MI_MG_VERBOSE (multigrid parameters);
  * MI_MF_XCD (XCD-aware cell order of mf_spmv), MI_ASM_CELL_LATTICE, MI_ASM_STAMPS / MI_MF_STAMPS / MI_MF_DBG (phase stamps
  * and timing-only ablations of the two element kernels), MI_ENERGY_GENERIC (mi_energy through the generic kernel on 3D Q2 / Q3
- * too: the cross-check of tools/energy_generic_check.py). */
+ * too: the cross-check of tools/energy_generic_check.py), MI_STRESS_GENERIC (mi_stress_field likewise:
+ * tools/stress_generic_check.py). */
 int mi_set_tuning(mi_ctx *ctx, const char *key, int value);
 /* Read back.  Counters since the last mi_reset_timings (what a solve costs in latency-bound events; counted on one slab
  * as well, where the collectives themselves are no-ops): "count_scalar_allreduce", "count_scalar_allreduce_cg" (those inside
