@@ -78,9 +78,10 @@ class EnergyInfo(C.Structure):
 
 
 class MiError(RuntimeError):
-    def __init__(self, code, msg):
+    def __init__(self, code, msg, partial=None):
         super().__init__("mi_elasticity error %d: %s" % (code, msg))
         self.code = code
+        self.partial = partial  # what the call wrote before it gave up (Context.linear_modes on MI_ENOCONV_LIN), else None
 
 
 def build(force=False):
@@ -156,6 +157,12 @@ def lib():
             getattr(L, f).restype = C.c_int
         L.mi_stress_field.argtypes = [vp, C.c_int, dp, dp, dp]
         L.mi_stress_field.restype = C.c_int
+        L.mi_linear_modes.argtypes = [vp, C.c_int, C.c_double, C.c_int, dp, dp, dp, C.POINTER(C.c_int)]
+        L.mi_block_gram.argtypes = [vp, C.c_int64, dp, C.c_int, dp, C.c_int, dp]
+        L.mi_block_combine.argtypes = [vp, C.c_int64, dp, C.c_int, dp, C.c_int, dp]
+        L.mi_dense_sym_eig.argtypes = [C.c_int, dp, dp, dp, dp]
+        for f in ("mi_linear_modes", "mi_block_gram", "mi_block_combine", "mi_dense_sym_eig"):
+            getattr(L, f).restype = C.c_int
         L.mi_set_profiling.argtypes = [vp, C.c_int]
         L.mi_get_timings.argtypes = [vp, C.POINTER(Timings)]
         L.mi_partition_describe.restype = C.c_int
@@ -238,6 +245,33 @@ def comm_unique_id():
     if rc != MI_OK:
         raise MiError(rc, lib().mi_last_error(None).decode())
     return buf.raw
+
+
+def block_gram(ctx, a, b):
+    """a^T b of two tall blocks [n, ma], [n, mb] through the device's block_gram (ma, mb <= 60)"""
+    a, b = np.asfortranarray(a, dtype=np.float64), np.asfortranarray(b, dtype=np.float64)
+    c = np.zeros((a.shape[1], b.shape[1]))
+    ctx._chk(lib().mi_block_gram(ctx.h, a.shape[0], _dp(a), a.shape[1], _dp(b), b.shape[1], _dp(c)))
+    return c
+
+
+def block_combine(ctx, s, coef):
+    """s coef of a tall block [n, ks] and coefficients [ks, my] through the device's block_combine (ks <= 60, my <= 20)"""
+    s, coef = np.asfortranarray(s, dtype=np.float64), np.ascontiguousarray(coef, dtype=np.float64)
+    y = np.zeros((s.shape[0], coef.shape[1]), order="F")
+    ctx._chk(lib().mi_block_combine(ctx.h, s.shape[0], _dp(s), s.shape[1], _dp(coef), coef.shape[1], _dp(y)))
+    return y
+
+
+def dense_sym_eig(A, B):
+    """(w, V) with A V = B V diag(w), V^T B V = I, w ascending: the host's Cholesky + cyclic Jacobi (n <= 64; no device)"""
+    A, B = np.ascontiguousarray(A, dtype=np.float64), np.ascontiguousarray(B, dtype=np.float64)
+    n = A.shape[0]
+    w, V = np.zeros(n), np.zeros((n, n))
+    rc = lib().mi_dense_sym_eig(n, _dp(A), _dp(B), _dp(w), _dp(V))
+    if rc != MI_OK:
+        raise MiError(rc, lib().mi_last_error(None).decode())
+    return w, V.T.copy()  # (eigenvector j is row j of the C array)
 
 
 class LevelView:
@@ -533,6 +567,20 @@ class Context:
         e = EnergyInfo()
         self._chk(lib().mi_linear_energy(self.h, C.byref(e)))
         return dict(strain=e.strain, kinetic=e.kinetic, body=e.body)
+
+    def linear_modes(self, n_modes, tol=1e-8, max_it=1000, want_modes=True):
+        """the n_modes lowest eigenpairs of K phi = lam M phi on the free dofs (mi_linear_modes): dict(lam[n_modes],
+        modes[n_modes, n] or None, residual[n_modes], its).  Not converged within max_it: MiError with code MI_ENOCONV_LIN whose
+        .partial is that dict"""
+        lam, res, its = np.zeros(n_modes), np.zeros(n_modes), C.c_int(0)
+        modes = np.zeros((n_modes, self.n)) if want_modes else None
+        rc = lib().mi_linear_modes(self.h, int(n_modes), float(tol), int(max_it), _dp(lam), _dp(modes) if want_modes else None,
+                                   _dp(res), C.byref(its))
+        out = dict(lam=lam, modes=modes, residual=res, its=its.value)
+        if rc == MI_ENOCONV_LIN:
+            raise MiError(rc, lib().mi_last_error(self.h).decode(), partial=out)
+        self._chk(rc)
+        return out
 
     def linear_apply(self, which, x):
         """y = K x (0), M x (1), A x (2) through the device kernels of the current set-up; 3: one V-cycle of its multigrid"""

@@ -527,4 +527,24 @@ namespace mi
   void launch_vec_add(double *y, const double *x, int64_t n, hipStream_t s);
   void launch_gather_nodes(int dim, const double *v, const int32_t *nodes, int n, double *out, hipStream_t s);
   void launch_scatter_nodes(int dim, double *v, const int32_t *nodes, int n, const double *in, hipStream_t s);
+  // ---- block-vector algebra of the eigensolver (mi_linear_modes): column-major blocks, column j at base + j * ld
+  constexpr int     BLOCK_TILE     = 8;    // block_gram: a workgroup's tile of C, kept in the threads' registers
+  constexpr int64_t BLOCK_CHUNK    = 8192; // rows per workgroup of block_gram and block_residual (= rows per partial)
+  constexpr int     BLOCK_MAX_COLS = 60, BLOCK_MAX_OUT = 20; // widest block; widest output of block_combine
+  inline int64_t    block_chunks(int64_t n) { return (n + BLOCK_CHUNK - 1) / BLOCK_CHUNK; }
+  struct BlockLambda
+  {
+    double v[BLOCK_MAX_OUT];
+  };
+  // c [ma][mb] = a^T b, ma, mb <= BLOCK_MAX_COLS; part: block_chunks(n) * ma * mb doubles.  The grid depends on n, ma, mb alone and
+  // the partials are summed in chunk order: bitwise repeatable
+  void launch_block_gram(const double *a, int ma, int64_t lda, const double *b, int mb, int64_t ldb, int64_t n, double *part,
+                         double *c, hipStream_t s);
+  // y = S coef; coef [ks][my] on the device, ks <= BLOCK_MAX_COLS, my <= BLOCK_MAX_OUT.  y may be columns of S (row-wise in place)
+  void launch_block_combine(const double *S, int ks, int64_t lds, const double *coef, int my, double *y, int64_t ldy, int64_t n,
+                            hipStream_t s);
+  // r_j = kx_j - lam_j mx_j masked, j < m <= BLOCK_MAX_OUT; out [2][m] = |r_j|^2, |mx_j|^2; part: 2 * m * block_chunks(n) doubles
+  void launch_block_residual(int dim, const double *kx, const double *mx, int64_t ld, const BlockLambda &lam, int m,
+                             const uint8_t *cmask, int64_t n, double *r, int64_t ldr, double *part, double *out, hipStream_t s);
+  void launch_block_hash_init(int dim, double *x, int64_t ld, int m, const uint8_t *cmask, int64_t n, hipStream_t s);
 } // namespace mi

@@ -8843,4 +8843,201 @@ namespace mi
     else
       hipLaunchKernelGGL((scatter_nodes<2>), dim3(grid), dim3(256), 0, s, v, nodes, n, in);
   }
+
+  // ------------------------------------------------------------------ block-vector algebra (mi_linear_modes)
+  // Tall-skinny blocks are column-major with a leading dimension: column j of S starts at S + j * ld.  All three kernels stream:
+  // every operand entry is used a handful of times, so rows run along the lanes (coalesced 8-byte loads per column) and the
+  // small matrices live in registers (block_gram), LDS (block_combine) or the kernel arguments (block_residual).
+
+  // C = A^T B.  A workgroup owns BLOCK_CHUNK rows and one BLOCK_TILE x BLOCK_TILE tile of C: a thread keeps the tile in
+  // registers over its rows (16 loads per 64 multiply-adds), the workgroup's sum goes to part[chunk][ma * mb] -- every entry
+  // written by exactly one workgroup, no atomics.  The tile index runs fastest, so the workgroups that read the same rows are in
+  // flight together.  An operand column is read ceil(columns of the other operand / BLOCK_TILE) times.
+  __global__ __launch_bounds__(256) void block_gram(const double *__restrict__ A, int ma, int64_t lda,
+                                                    const double *__restrict__ B, int mb, int64_t ldb, int64_t n,
+                                                    double *__restrict__ part)
+  {
+    constexpr int T = BLOCK_TILE;
+    __shared__ double s_w[4][T * T];
+    const int     tb_n = (mb + T - 1) / T, ntiles = ((ma + T - 1) / T) * tb_n;
+    const int     tile = int(blockIdx.x % unsigned(ntiles));
+    const int64_t chunk = blockIdx.x / unsigned(ntiles);
+    const int     ia0 = (tile / tb_n) * T, jb0 = (tile % tb_n) * T;
+    const int64_t r0 = chunk * BLOCK_CHUNK, r1 = imin64(n, r0 + BLOCK_CHUNK);
+    double        acc[T][T];
+#pragma unroll
+    for (int i = 0; i < T; ++i)
+#pragma unroll
+      for (int j = 0; j < T; ++j)
+        acc[i][j] = 0.0;
+    for (int64_t r = r0 + threadIdx.x; r < r1; r += 256)
+      {
+        double a[T], b[T];
+#pragma unroll
+        for (int i = 0; i < T; ++i)
+          a[i] = ia0 + i < ma ? A[int64_t(ia0 + i) * lda + r] : 0.0;
+#pragma unroll
+        for (int j = 0; j < T; ++j)
+          b[j] = jb0 + j < mb ? B[int64_t(jb0 + j) * ldb + r] : 0.0;
+#pragma unroll
+        for (int i = 0; i < T; ++i)
+#pragma unroll
+          for (int j = 0; j < T; ++j)
+            acc[i][j] = fma(a[i], b[j], acc[i][j]);
+      }
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int i = 0; i < T; ++i)
+#pragma unroll
+      for (int j = 0; j < T; ++j)
+        {
+          const double v = wave_sum_lane63(acc[i][j]);
+          if (lane == 63)
+            s_w[wave][i * T + j] = v;
+        }
+    __syncthreads();
+    if (threadIdx.x < T * T)
+      {
+        const int i = ia0 + int(threadIdx.x) / T, j = jb0 + int(threadIdx.x) % T;
+        if (i < ma && j < mb)
+          part[chunk * (int64_t(ma) * mb) + int64_t(i) * mb + j] =
+            ((s_w[0][threadIdx.x] + s_w[1][threadIdx.x]) + s_w[2][threadIdx.x]) + s_w[3][threadIdx.x];
+      }
+  }
+  // C[e] = sum over the chunks, in chunk order: one thread per entry, the partials of a chunk side by side
+  __global__ __launch_bounds__(256) void block_gram_finish(const double *__restrict__ part, int64_t nchunks, int entries,
+                                                           double *__restrict__ C)
+  {
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    if (e >= entries)
+      return;
+    double s = 0.0;
+    for (int64_t c = 0; c < nchunks; ++c)
+      s += part[c * entries + e];
+    C[e] = s;
+  }
+
+  // Y = S coef, coef [ks][my] row-major in LDS (every lane reads the same word: a broadcast).  A thread owns one row: it holds
+  // the row of S in registers BEFORE it writes its row of Y, and no other thread touches that row -- so Y may be columns of S
+  // itself (S and Y are deliberately not __restrict__).  KS: compile-time bound of ks, so that the row stays in registers.
+  template <int KS>
+  __global__ __launch_bounds__(256) void block_combine(const double *S, int ks, int64_t lds, const double *__restrict__ coef,
+                                                       int my, double *Y, int64_t ldy, int64_t n)
+  {
+    __shared__ double s_c[KS * BLOCK_MAX_OUT];
+    for (int e = threadIdx.x; e < KS * BLOCK_MAX_OUT; e += 256)
+      s_c[e] = e < ks * my ? coef[e] : 0.0;
+    __syncthreads();
+    const int64_t r = int64_t(blockIdx.x) * 256 + threadIdx.x;
+    if (r >= n)
+      return;
+    double s[KS];
+#pragma unroll
+    for (int k = 0; k < KS; ++k)
+      s[k] = k < ks ? S[int64_t(k) * lds + r] : 0.0;
+    for (int j = 0; j < my; ++j)
+      {
+        double y = 0.0;
+#pragma unroll
+        for (int k = 0; k < KS; ++k)
+          if (k < ks)
+            y = fma(s[k], s_c[k * my + j], y);
+        Y[int64_t(j) * ldy + r] = y;
+      }
+  }
+
+  // R_j = KX_j - lambda_j MX_j, zero on constrained dofs, and the partials of |R_j|^2 and |MX_j|^2 of the same pass:
+  // part[0][j][chunk], part[1][j][chunk].  blockIdx.y = column
+  template <int D>
+  __global__ __launch_bounds__(256) void block_residual(const double *__restrict__ KX, const double *__restrict__ MX, int64_t ld,
+                                                        BlockLambda lam, const uint8_t *__restrict__ cmask, int64_t n,
+                                                        double *__restrict__ R, int64_t ldr, double *__restrict__ part)
+  {
+    __shared__ double s_red[4];
+    const int     j = blockIdx.y, m = gridDim.y;
+    const int64_t r0 = int64_t(blockIdx.x) * BLOCK_CHUNK, r1 = imin64(n, r0 + BLOCK_CHUNK);
+    const double  l = lam.v[j];
+    double        sr = 0.0, sm = 0.0;
+    for (int64_t r = r0 + threadIdx.x; r < r1; r += 256)
+      {
+        const int64_t nd = r / D;
+        const double  kx = KX[j * ld + r], mx = MX[j * ld + r];
+        const double  res = ((cmask[nd] >> int(r - nd * D)) & 1) ? 0.0 : fma(-l, mx, kx);
+        R[j * ldr + r] = res;
+        sr = fma(res, res, sr);
+        sm = fma(mx, mx, sm);
+      }
+    sr = block_sum<256>(sr, s_red);
+    sm = block_sum<256>(sm, s_red);
+    if (threadIdx.x == 0)
+      {
+        part[int64_t(j) * gridDim.x + blockIdx.x]     = sr;
+        part[int64_t(m + j) * gridDim.x + blockIdx.x] = sm;
+      }
+  }
+  // out[b] = sum of part[b][0 .. nchunks) in the fixed order of reduce_partials
+  __global__ __launch_bounds__(256) void block_residual_finish(const double *__restrict__ part, int nchunks, double *out)
+  {
+    __shared__ double s_red[4];
+    const double      s = reduce_partials<256>(part + int64_t(blockIdx.x) * nchunks, nchunks, s_red);
+    if (threadIdx.x == 0)
+      out[blockIdx.x] = s;
+  }
+
+  // start block of the eigensolver: a fixed integer hash of (dof, column) mapped to [-1, 1), zero on constrained dofs.  No state
+  template <int D>
+  __global__ __launch_bounds__(256) void block_hash_init(double *X, int64_t ld, const uint8_t *__restrict__ cmask, int64_t n)
+  {
+    const int64_t r = int64_t(blockIdx.x) * 256 + threadIdx.x;
+    if (r >= n)
+      return;
+    const int64_t nd = r / D;
+    uint64_t      h = (uint64_t(r) * 64u + blockIdx.y + 1u) * 0x9E3779B97F4A7C15ull;
+    h ^= h >> 30;
+    h *= 0xBF58476D1CE4E5B9ull;
+    h ^= h >> 27;
+    h *= 0x94D049BB133111EBull;
+    h ^= h >> 31;
+    const double u = double(h >> 11) * (2.0 / 9007199254740992.0) - 1.0;
+    X[int64_t(blockIdx.y) * ld + r] = ((cmask[nd] >> int(r - nd * D)) & 1) ? 0.0 : u;
+  }
+
+  void launch_block_gram(const double *a, int ma, int64_t lda, const double *b, int mb, int64_t ldb, int64_t n, double *part,
+                         double *c, hipStream_t s)
+  {
+    const int64_t nchunks = block_chunks(n);
+    const int     ntiles  = ((ma + BLOCK_TILE - 1) / BLOCK_TILE) * ((mb + BLOCK_TILE - 1) / BLOCK_TILE);
+    hipLaunchKernelGGL(block_gram, dim3(unsigned(nchunks * ntiles)), dim3(256), 0, s, a, ma, lda, b, mb, ldb, n, part);
+    hipLaunchKernelGGL(block_gram_finish, dim3((ma * mb + 255) / 256), dim3(256), 0, s, part, nchunks, ma * mb, c);
+  }
+  void launch_block_combine(const double *S, int ks, int64_t lds, const double *coef, int my, double *y, int64_t ldy, int64_t n,
+                            hipStream_t s)
+  {
+    const dim3 grid(unsigned((n + 255) / 256));
+    if (ks <= 20)
+      hipLaunchKernelGGL((block_combine<20>), grid, dim3(256), 0, s, S, ks, lds, coef, my, y, ldy, n);
+    else if (ks <= 40)
+      hipLaunchKernelGGL((block_combine<40>), grid, dim3(256), 0, s, S, ks, lds, coef, my, y, ldy, n);
+    else
+      hipLaunchKernelGGL((block_combine<BLOCK_MAX_COLS>), grid, dim3(256), 0, s, S, ks, lds, coef, my, y, ldy, n);
+  }
+  void launch_block_residual(int dim, const double *kx, const double *mx, int64_t ld, const BlockLambda &lam, int m,
+                             const uint8_t *cmask, int64_t n, double *r, int64_t ldr, double *part, double *out, hipStream_t s)
+  {
+    const int  nchunks = int(block_chunks(n));
+    const dim3 grid(nchunks, m);
+    if (dim == 3)
+      hipLaunchKernelGGL((block_residual<3>), grid, dim3(256), 0, s, kx, mx, ld, lam, cmask, n, r, ldr, part);
+    else
+      hipLaunchKernelGGL((block_residual<2>), grid, dim3(256), 0, s, kx, mx, ld, lam, cmask, n, r, ldr, part);
+    hipLaunchKernelGGL(block_residual_finish, dim3(2 * m), dim3(256), 0, s, part, nchunks, out);
+  }
+  void launch_block_hash_init(int dim, double *x, int64_t ld, int m, const uint8_t *cmask, int64_t n, hipStream_t s)
+  {
+    const dim3 grid(unsigned((n + 255) / 256), m);
+    if (dim == 3)
+      hipLaunchKernelGGL((block_hash_init<3>), grid, dim3(256), 0, s, x, ld, cmask, n);
+    else
+      hipLaunchKernelGGL((block_hash_init<2>), grid, dim3(256), 0, s, x, ld, cmask, n);
+  }
 } // namespace mi

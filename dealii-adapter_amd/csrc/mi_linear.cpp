@@ -717,3 +717,7 @@ int mi_detail::linear_setup_level(mi_ctx *lc, double theta)
   return MI_OK;
 }
 
+// The modal analysis of the linear model (mi_linear_modes and the block-vector hooks) is compiled with this translation unit:
+// the library is linked from a fixed list of objects in more than one place (the test builds against the RCCL double among
+// them), and the eigensolver is the linear model's.
+#include "mi_modes.cpp"

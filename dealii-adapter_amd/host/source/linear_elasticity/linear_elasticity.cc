@@ -1,6 +1,8 @@
 #include "linear_elasticity.h"
 
+#include <algorithm>
 #include <cmath>
+#include <fstream>
 #include <iomanip>
 #include <iostream>
 #include <sstream>
@@ -116,6 +118,11 @@ namespace Linear_Elasticity
         std::cout << "Linear solver: CG preconditioned by a multigrid V-cycle of " << mi_linear_mg_n_levels(device->ctx())
                   << " levels" << std::endl;
     }
+    // MI_MODES=k: the k lowest vibration modes of the structure before the first step (a switch of this PROGRAM, like the two
+    // above): printed, and written to <Output folder>/modes.json.  A refusal or non-convergence is said and the run goes on
+    if (const char *f = std::getenv("MI_MODES"))
+      if (std::atoi(f) != 0)
+        report_modes(std::atoi(f));
 
     std::cout << "Triangulation:"
               << "\n\t Number of active cells: " << mi_n_cells(device->ctx())
@@ -130,6 +137,48 @@ namespace Linear_Elasticity
     old_stress.bind(*device, MI_L_OLD_STRESS);
     // :238-239
     state_variables = {&old_velocity, &velocity, &old_displacement, &displacement, &old_stress};
+  }
+
+  // lambda, omega = sqrt(lambda) and f = omega / 2 pi of the k lowest modes of K phi = lambda M phi (mi_linear_modes, tol 1e-8, at
+  // most 1000 iterations)
+  template <int dim>
+  void ElastoDynamics<dim>::report_modes(const int k)
+  {
+    const int           n = std::max(k, 1);
+    std::vector<double> lambda(size_t(n), 0.0), residual(size_t(n), 0.0);
+    int                 its = 0;
+    const int           rc  = mi_linear_modes(device->ctx(), k, 1e-8, 1000, lambda.data(), nullptr, residual.data(), &its);
+    if (rc != MI_OK && rc != MI_ENOCONV_LIN)
+      {
+        std::cout << "MI_MODES ignored: " << mi_last_error(device->ctx()) << std::endl;
+        return;
+      }
+    if (rc == MI_ENOCONV_LIN)
+      std::cout << "Vibration modes: " << mi_last_error(device->ctx()) << "; the best pairs follow" << std::endl;
+    if (mi::host_rank() > 0)
+      return;
+    const double two_pi = 2.0 * std::acos(-1.0);
+    auto         hz     = [&](double l) { return std::sqrt(std::max(l, 0.0)) / two_pi; };
+    std::cout << "Vibration modes (" << its << " LOBPCG iterations):" << std::endl;
+    for (int j = 0; j < k; ++j)
+      std::cout << "\t mode " << j + 1 << ": lambda = " << lambda[size_t(j)] << ", omega = " << std::sqrt(std::max(lambda[size_t(j)], 0.0))
+                << " rad/s, frequency = " << hz(lambda[size_t(j)]) << " Hz" << std::endl;
+    std::ofstream out(parameters.output_folder + "/modes.json");
+    if (!out)
+      return;
+    auto list = [&](const char *key, auto value) {
+      out << "\"" << key << "\": [";
+      for (int j = 0; j < k; ++j)
+        out << (j ? ", " : "") << value(j);
+      out << "]";
+    };
+    out << std::setprecision(17) << "{";
+    list("lambda", [&](int j) { return lambda[size_t(j)]; });
+    out << ", ";
+    list("frequency_hz", [&](int j) { return hz(lambda[size_t(j)]); });
+    out << ", ";
+    list("residual", [&](int j) { return residual[size_t(j)]; });
+    out << ", \"iterations\": " << its << ", \"converged\": " << (rc == MI_OK ? "true" : "false") << "}\n";
   }
 
   template <int dim>

@@ -45,6 +45,7 @@ namespace Linear_Elasticity
     void make_grid();
     void setup_system();
     void output_results() const;
+    void report_modes(int k); // MI_MODES=k
 
     const Parameters::AllParameters parameters;
     // linear_elasticity.cc:57, :157-158

@@ -274,6 +274,35 @@ int mi_linear_get_diagonal(mi_ctx *ctx, double *diag_host);
  * On a borrowed level context (mi_linear_mg_level_context) the level's.  A matrix-free set-up with "linear_precond" 0 forms
  * the diagonal entries alone. */
 int mi_linear_get_diagonal_blocks(mi_ctx *ctx, double *blocks);
+/* Modal analysis: the n_modes smallest eigenpairs of  K phi = lambda M phi  on the free dofs of the linear model (phi = 0 on the
+ * dofs mi_get_constrained flags), lambda = omega^2, ascending; frequency f = sqrt(lambda) / 2 pi.
+ *   Needs mi_linear_setup (MI_EINVAL without one) on an undecomposed context: an emulated or RCCL team gives MI_EINVAL, "one slab
+ *   only".  1 <= n_modes <= 16, n_modes + guard <= number of free dofs, tol > 0, max_it >= 1, else MI_EINVAL.  Runs in both forms of
+ *   "linear_operator" and with both values of "linear_precond", 2D and 3D, degrees 1-4.
+ *   Method: LOBPCG on a block of m = n_modes + max(2, n_modes / 4) vectors (the surplus are guard vectors), so 3 m <= 60.  The
+ *   products K x and M x go one vector at a time through the products of the current set-up (the sliced-ELL product or
+ *   mf_linear_q3 + the slot gather), their output zeroed on the constrained dofs.  The preconditioner is what the set-up has for
+ *   the stepping matrix A = M + theta^2 dt^2 K = (theta dt)^2 (K + sigma M), sigma = 1 / (theta dt)^2: the reciprocal diagonal,
+ *   or one multigrid V-cycle with "linear_precond" 1.  The images K S and M S of the search space S = [X W P] are kept, so an
+ *   iteration costs 2 m products and m preconditioner applications; all 9 m^2 scalar products of an iteration are two
+ *   launches of block_gram, the updates six of block_combine.  The Rayleigh-Ritz problem is solved on the host from the device's
+ *   Gram matrices (mi_dense_sym_eig's method); if the Cholesky factor of S^T M S breaks down the iteration is repeated without
+ *   P, and if it breaks down again X is re-orthonormalised in the M-inner product and P restarted.
+ *   Start block: a fixed integer hash of (dof, column), zero on constrained dofs.  There is no random state and no atomic sum:
+ *   two calls return the same bits.
+ *   Stopping: converged when every wanted j has |K x_j - lambda_j M x_j|_2 <= tol max_{k < n_modes} |lambda_k| |M x_j|_2;
+ *   residual[j] is that ratio, evaluated on freshly formed products of the returned pairs.  The scale max |lambda_k| keeps
+ *   rigid-body modes (lambda = 0) meaningful.  Not converged within max_it iterations: MI_ENOCONV_LIN, with the best pairs,
+ *   residual and its still written.
+ *   modes ([n_modes][n_dofs], or NULL): M-orthonormal, exactly zero on constrained dofs, global dof order.
+ *   Convergence speed depends on sigma against the wanted lambda: the preconditioner approximates (K + sigma M)^-1, which is
+ *   the better the smaller sigma is beside lambda.  A context made for modal analysis takes a large time step.  The result
+ *   does not depend on the time step or theta.
+ *   Block storage of 9 m n_dofs doubles (+ the Gram partials) is allocated per call and freed before return.  The call
+ *   overwrites the solver's work vectors, as mi_linear_energy does; it changes no state vector, matrix, hierarchy, tuning key or
+ *   "count_cg_*" counter, and a following mi_linear_step returns the bits it would have returned without the call. */
+int mi_linear_modes(mi_ctx *ctx, int n_modes, double tol, int max_it, double *lambda /* n_modes */,
+                    double *modes /* [n_modes][n_dofs] or NULL */, double *residual /* n_modes or NULL */, int *its /* or NULL */);
 
 /* per-vector device snapshots: what `old_state_data[i] = *state_variables[i]` (adapter.h:457-460) and its
  * inverse (:481-482) become when VectorType is a handle to a device-resident vector */
@@ -307,6 +336,15 @@ int mi_spmv(mi_ctx *ctx, const double *x_host, double *y_host); /* y = K x throu
  * the reference) under the constraint rule of the assembly (nonlinear_elasticity.cc:760-774): out of the assembled tangent or,
  * with "fine_level" 1, as formed from the point records.  One process only (single or emulated slabs). */
 int mi_get_diagonal_blocks(mi_ctx *ctx, double *blocks);
+/* the block-vector kernels of mi_linear_modes on host arrays (any context; blocks column-major: column j of a at a + j n):
+ * c [ma][mb] = a^T b (block_gram; ma, mb <= 60) and y = s coef with coef [ks][my] row-major (block_combine; ks <= 60, my <= 20).
+ * Per-workgroup partials summed in index order, no atomics: bitwise repeatable */
+int mi_block_gram(mi_ctx *ctx, int64_t n, const double *a, int ma, const double *b, int mb, double *c /* [ma][mb] */);
+int mi_block_combine(mi_ctx *ctx, int64_t n, const double *s, int ks, const double *coef /* [ks][my] */, int my, double *y);
+/* host only, no device: A v = w B v for dense symmetric A and symmetric positive definite B, n <= 64 (Cholesky of B + cyclic
+ * Jacobi; the library links no LAPACK).  w ascending, eigenvector j at V + j n, V^T B V = I.  MI_EINVAL where B is not
+ * positive definite */
+int mi_dense_sym_eig(int n, const double *A, const double *B, double *w, double *V);
 
 /* ---- the multigrid hierarchy, read-only (tests) --------------------------------------------
  * What the V-cycle of "spmv_as_smoother" 2 applies: the levels as the last linear solve left them.  Level 0 is the fine
