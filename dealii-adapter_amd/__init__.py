@@ -77,6 +77,11 @@ class EnergyInfo(C.Structure):
     _fields_ = [("strain", C.c_double), ("kinetic", C.c_double), ("body", C.c_double), ("reserved", C.c_double)]
 
 
+class StressErrorInfo(C.Structure):
+    _fields_ = [("error", C.c_double), ("norm", C.c_double), ("relative", C.c_double), ("max_cell_error", C.c_double),
+                ("max_cell", C.c_int64), ("reserved", C.c_int64)]
+
+
 class MiError(RuntimeError):
     def __init__(self, code, msg, partial=None):
         super().__init__("mi_elasticity error %d: %s" % (code, msg))
@@ -157,6 +162,8 @@ def lib():
             getattr(L, f).restype = C.c_int
         L.mi_stress_field.argtypes = [vp, C.c_int, dp, dp, dp]
         L.mi_stress_field.restype = C.c_int
+        L.mi_stress_error.argtypes = [vp, C.c_int, C.POINTER(StressErrorInfo), dp, dp]
+        L.mi_stress_error.restype = C.c_int
         L.mi_linear_modes.argtypes = [vp, C.c_int, C.c_double, C.c_int, dp, dp, dp, C.POINTER(C.c_int)]
         L.mi_block_gram.argtypes = [vp, C.c_int64, dp, C.c_int, dp, C.c_int, dp]
         L.mi_block_combine.argtypes = [vp, C.c_int64, dp, C.c_int, dp, C.c_int, dp]
@@ -490,6 +497,16 @@ class Context:
         sigma, vm, w = np.zeros((self.nnodes, ncomp)), np.zeros(self.nnodes), np.zeros(self.nnodes)
         self._chk(lib().mi_stress_field(self.h, model, _dp(sigma), _dp(vm), _dp(w)))
         return sigma, vm, w
+
+    def stress_error(self, model=STRESS_NEOHOOKE, cells=True):
+        """the Zienkiewicz-Zhu error indicator of stress_field(model): dict(error, norm, relative, max_cell_error, max_cell,
+        eta_cell, norm_cell) -- eta, n, eta / sqrt(n^2 + eta^2), the largest eta_K and its lexicographic cell id, and with
+        cells=True eta_K and n_K of every cell in lexicographic order (x fastest), else None.  An indicator, not a bound"""
+        info = StressErrorInfo()
+        eta, nrm = (np.zeros(self.ncells), np.zeros(self.ncells)) if cells else (None, None)
+        self._chk(lib().mi_stress_error(self.h, model, C.byref(info), _dp(eta) if cells else None, _dp(nrm) if cells else None))
+        return dict(error=info.error, norm=info.norm, relative=info.relative, max_cell_error=info.max_cell_error,
+                    max_cell=int(info.max_cell), eta_cell=eta, norm_cell=nrm)
 
     def state_save(self):
         self._chk(lib().mi_state_save(self.h))

@@ -1349,6 +1349,49 @@ namespace mi_detail
     return MI_OK;
   }
 
+  // ---- stress error indicator (mi_stress_error) --------------------------------------------------------------------
+  // Pass 1 is enqueue_stress as it stands: its nodal sigma stays on the device behind the accumulator.  Pass 2, enqueued behind
+  // it: all cells in one launch (nothing goes to the nodes: no colours), the totals by launch_energy_sum in its fixed order, the
+  // roots in the caller's cell order and the largest.  d_stress_err: cells [ncells][3] | sum scratch [(ncells / 1024 + 1)][3] |
+  // eta_K [ncells] | n_K [ncells] | results: eta^2, n^2, 0, max eta_K, its id.  The inverted flag is enqueue_stress's slot
+  static size_t stress_err_results(const mi_ctx *c)
+  {
+    const size_t nc = size_t(c->mesh.ncells);
+    return (nc + nc / 1024 + 1) * 3 + 2 * nc;
+  }
+  static int enqueue_stress_error(mi_ctx *c, int model)
+  {
+    if (int rc = enqueue_stress(c, model))
+      return rc;
+    const size_t nc = size_t(c->mesh.ncells), nn = size_t(c->mesh.nnodes);
+    if (!c->d_stress_err)
+      HIPCHK(c, hipMalloc((void **)&c->d_stress_err, (stress_err_results(c) + 8) * sizeof(double)));
+    if (!c->d_cell_orig)
+      if (int rc = upload(c, &c->d_cell_orig, c->mesh.cell_orig))
+        return rc;
+    mi::MfParams f = mf_params(c);
+    if (!f.cellbox)
+      f.cellbox = c->d_energy_box;
+    mi::StressErrorParams ep{};
+    ep.conn = c->d_conn, ep.cverts = c->d_cverts, ep.tab = model == MI_STRESS_LINEAR ? c->d_stress_tab : c->d_tab;
+    ep.u     = c->vec(MI_V_TOTAL_DISPLACEMENT);
+    ep.sigma = c->d_stress + nn * 8;
+    ep.mu = c->mat.mu, ep.kappa = c->kappa, ep.lambda = 2 * c->mat.mu * c->mat.nu / (1 - 2 * c->mat.nu);
+    ep.c        = c->dim == 3 ? c->mat.nu / (1 + c->mat.nu) : c->mat.nu; // 2D: the plane-strain compliance of the 2 x 2 formulation
+    ep.inv2mu   = 1.0 / (2 * c->mat.mu);
+    ep.cell_e   = c->d_stress_err;
+    ep.inverted = c->d_sc + SC_ENERGY + 3;
+    // (experiments build: the generic kernel on 3D Q2 / Q3 as well, the cross-check of the two sum-factorised forms)
+    static const bool generic = mi::exp_env("MI_STRESS_ERROR_GENERIC") && atoi(mi::exp_env("MI_STRESS_ERROR_GENERIC")) != 0;
+    if (mi::launch_stress_error(c->dim, c->degree, model, f, ep, int32_t(nc), generic, c->stream))
+      return fail(c, MI_EINVAL, "no stress error kernel for dim=%d degree=%d", c->dim, c->degree);
+    double *scratch = c->d_stress_err + nc * 3, *eta = scratch + (nc / 1024 + 1) * 3, *res = c->d_stress_err + stress_err_results(c);
+    mi::launch_energy_sum(c->d_stress_err, int64_t(nc), scratch, res, c->stream);
+    mi::launch_stress_error_finish(c->d_stress_err, c->d_cell_orig, int64_t(nc), eta, eta + nc, scratch, res + 3, c->stream);
+    HIPCHK(c, hipGetLastError());
+    return MI_OK;
+  }
+
   // the Q3 fine level's records (mf_records_q3), slots and cell geometry
   int alloc_records_q3(mi_ctx *c)
   {
@@ -1978,7 +2021,7 @@ namespace mi_detail
                     c->d_pred[0][0], c->d_pred[0][1], c->d_pred[1][0], c->d_pred[1][1], c->d_pred[2][0], c->d_pred[2][1], c->d_pred[3][0], c->d_pred[3][1],
                     c->d_pred_saved[0][0], c->d_pred_saved[0][1], c->d_pred_saved[1][0], c->d_pred_saved[1][1], c->d_pred_saved[2][0],
                     c->d_pred_saved[2][1], c->d_pred_saved[3][0], c->d_pred_saved[3][1], c->d_energy, c->d_energy_box,
-                    c->d_stress, c->d_stress_tab};
+                    c->d_stress, c->d_stress_tab, c->d_stress_err, c->d_cell_orig};
     for (void *p : ptrs)
       if (p)
         hipFree(p);
@@ -2788,6 +2831,46 @@ int mi_stress_field(mi_ctx *c, int model, double *sigma, double *von_mises, doub
   if (inverted > 0.0) // the Cauchy stress has no meaning there; the same error as an assembly of this state gives
     return fail(c, MI_EINVAL, "inverted element: det F <= 0 at a quadrature point (the displacement has folded a cell; the "
                               "reference asserts det F > 0, nonlinear_elasticity.cc:935)");
+  return MI_OK;
+}
+
+// A posteriori error indicator of that stress field: the Zienkiewicz-Zhu distance between the recovered nodal stress and the
+// elements' raw stress in the complementary energy norm, per cell and in total.  Two passes on the device (enqueue_stress, then
+// enqueue_stress_error), one read-back of five scalars and the flag, the per-cell arrays only where wanted.  Undecomposed
+// contexts only: a slab's first node plane holds a partial sigma*.  No timing slot, no counter
+int mi_stress_error(mi_ctx *c, int model, mi_stress_error_info *out, double *eta_cell, double *norm_cell)
+{
+  if (!c)
+    return MI_EINVAL;
+  if (!out)
+    return fail(c, MI_EINVAL, "mi_stress_error: null argument");
+  if (model != MI_STRESS_NEOHOOKE && model != MI_STRESS_LINEAR)
+    return fail(c, MI_EINVAL, "mi_stress_error: model %d (0: neo-Hookean Cauchy stress, 1: linear stress)", model);
+  if (team_size(c) != 1)
+    return fail(c, MI_EINVAL, "mi_stress_error: one slab only (an undecomposed mesh)");
+  HIPCHK(c, hipSetDevice(c->device));
+  if (const int rc = enqueue_stress_error(c, model))
+    return rc;
+  const size_t  nc  = size_t(c->mesh.ncells);
+  const double *res = c->d_stress_err + stress_err_results(c), *eta = res - 2 * nc;
+  double        h[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipMemcpy(h, res, 5 * sizeof(double), hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(h + 5, c->d_sc + SC_ENERGY + 3, sizeof(double), hipMemcpyDeviceToHost));
+  if (h[5] > 0.0) // the Cauchy stress has no meaning there; the same error as mi_stress_field gives
+    return fail(c, MI_EINVAL, "inverted element: det F <= 0 at a quadrature point (the displacement has folded a cell; the "
+                              "reference asserts det F > 0, nonlinear_elasticity.cc:935)");
+  if (eta_cell)
+    HIPCHK(c, hipMemcpy(eta_cell, eta, nc * sizeof(double), hipMemcpyDeviceToHost));
+  if (norm_cell)
+    HIPCHK(c, hipMemcpy(norm_cell, eta + nc, nc * sizeof(double), hipMemcpyDeviceToHost));
+  const double tot    = h[0] + h[1];
+  out->error          = std::sqrt(h[0]);
+  out->norm           = std::sqrt(h[1]);
+  out->relative       = tot > 0.0 ? std::sqrt(h[0] / tot) : 0.0;
+  out->max_cell_error = h[3];
+  out->max_cell       = int64_t(h[4]);
+  out->reserved       = 0;
   return MI_OK;
 }
 

@@ -253,6 +253,10 @@ struct mi_ctx
   // nodal stress recovery (mi_stress_field), allocated on first use: the accumulator [nnodes][8] with the results behind it
   // (sigma, von Mises, weight); the 1D tables of the linear model's rule QGauss(p + 1) (model MI_STRESS_LINEAR)
   double   *d_stress = nullptr, *d_stress_tab = nullptr;
+  // stress error indicator (mi_stress_error), allocated on first use: the cells' [ncells][3] sums, the scratch of their
+  // fixed-order sum, eta_K and n_K [ncells] each in lexicographic order, eight result scalars; HostMesh::cell_orig on the device
+  double   *d_stress_err = nullptr;
+  int32_t  *d_cell_orig  = nullptr;
   uint16_t *d_off   = nullptr;
   uint8_t  *d_cmask = nullptr;
   double   *h_pinned = nullptr; // pinned host scratch (scalars, flags, interface buffer)

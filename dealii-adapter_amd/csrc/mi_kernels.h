@@ -258,6 +258,21 @@ namespace mi
     int32_t        cell_count;
   };
 
+  // stress error indicator (see stress_error_q2 / stress_error_q3 / stress_error_cells): the state, the recovered nodal stress,
+  // the material, the metric and where the cells' numbers go.  Mesh tables, 1D tables and geometry as StressParams
+  struct StressErrorParams
+  {
+    const int32_t *conn;   // [ncells][npc] colour-sorted
+    const double  *cverts; // [ncells][2^dim][dim]
+    const double  *tab;    // the 1D tables of the model's rule, as StressParams::tab
+    const double  *u;      // total displacement (the committed state)
+    const double  *sigma;  // [nnodes][dim (dim + 1) / 2]: the nodal field of stress_finish (xx yy zz xy xz yz; 2D xx yy xy)
+    double         mu, kappa, lambda;
+    double         c, inv2mu; // m(s) = (s:s - c tr(s)^2) inv2mu: c = nu / (1 + nu) in 3D, nu in 2D; inv2mu = 1 / (2 mu)
+    double        *cell_e;    // [ncells][3]: eta_K^2, n_K^2, 0 (the layout launch_energy_sum adds up)
+    double        *inverted;  // as StressParams::inverted
+  };
+
   // matrix-free operator of the linear model on 3D Q3 cells (see mf_linear_q3): y = (c_K K + c_M M) x
   struct MfLinearOp
   {
@@ -433,6 +448,15 @@ namespace mi
   // sigma[nnodes][dim (dim + 1) / 2] = acc / W, von_mises[nnodes] of that tensor, weight[nnodes] = W
   int  launch_stress(int dim, int degree, int model, const MfParams &p, const StressParams &sp, bool generic, hipStream_t s);
   void launch_stress_finish(int dim, const double *acc, int64_t nnodes, double *sigma, double *von_mises, double *weight, hipStream_t s);
+  // stress error indicator: all cells in one launch store their two sums into ep.cell_e, by the kernel of (dim, degree, model)
+  // -- stress_error_q3, stress_error_q2 (model 0; p.conn, p.tab1d, p.cverts / p.cellbox) or stress_error_cells; generic:
+  // stress_error_cells on 3D Q2 / Q3 too (cross-check).  -1: no kernel for the element.  launch_stress_error_finish:
+  // eta_cell[cell_orig[i]] = sqrt(cell_e[i][0]), norm_cell likewise; max_out[0] the largest eta_K, max_out[1] the smallest
+  // lexicographic id that has it (as a double); scratch holds 2 doubles per 1024 cells (launch_energy_sum's, once that is through)
+  int  launch_stress_error(int dim, int degree, int model, const MfParams &p, const StressErrorParams &ep, int32_t cell_count, bool generic,
+                           hipStream_t s);
+  void launch_stress_error_finish(const double *cell_e, const int32_t *cell_orig, int64_t ncells, double *eta_cell, double *norm_cell,
+                                  double *scratch, double *max_out, hipStream_t s);
   // ... the multigrid smoother's operator on the element's full-order rule, 4 x 4 x 4 points (see mf_spmv_q3s): records
   // [ncells][MF_NREC][64] of its own (MfParams::qrec_q3s, written by mf_records_q3s from u + du with the fold rule of
   // mf_records27), the rule's 1D tables MfParams::tab_q3s; one wave per cell, the results into the same cell-major slots

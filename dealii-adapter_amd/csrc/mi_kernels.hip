@@ -5315,6 +5315,452 @@ namespace mi
       }
     weight[i] = W;
   }
+
+  // ------------------------------------------------------------------ stress error indicator (mi_stress_error)
+  // The Zienkiewicz-Zhu distance between the recovered nodal stress sigma* of mi_stress_field and the raw stress sigma_h of the
+  // elements, in the complementary energy norm, on the model's own rule and in the reference configuration:
+  //   sigma*(q) = sum_a N_a(q) sigma*_a,   e(q) = sigma*(q) - sigma_h(q),   m(s) = (s:s - c tr(s)^2) / (2 mu)
+  //   eta_K^2 = sum_{q in K} m(e(q)) JxW(q),   n_K^2 = sum_{q in K} m(sigma_h(q)) JxW(q)
+  // (c = nu / (1 + nu) in 3D, nu in 2D: StressErrorParams::c.)  The second pass over the cells, behind stress_finish: the forward
+  // half of the stress kernel again, a VALUE-ONLY forward contraction of sigma*'s six fields (three in 2D) with the S table
+  // alone, the point stage, and the two point numbers summed over the cell in a fixed order (as the energy kernels sum their
+  // three).  Nothing goes to the nodes, so all cells run in one launch; a cell stores eta_K^2, n_K^2 and 0 into cell_e[cell][3]
+  // (colour-sorted), launch_energy_sum forms the totals, stress_error_finish the roots in the caller's order and the largest.
+  // A point with det F <= 0 (model 0) raises *inverted and contributes zeros.  Forms, chosen by launch_stress_error as
+  // launch_stress chooses: stress_error_q2, stress_error_q3 (3D, model 0), stress_error_cells (every other element, model 1).
+  template <int DIM>
+  __device__ __forceinline__ bool stress_value(const double *F, const double J, const double Jm, const double rJ, const StressErrorParams &ep,
+                                               double s[6])
+  {
+    double Finv[9], tau[6], tiso[6], cII, cS;
+    neo_hooke_from_F<DIM>(F, J, Jm, rJ, ep.mu, ep.kappa, Finv, tau, tiso, cII, cS);
+    const bool ok = J > 0.0; // inverted element (nonlinear_elasticity.cc:935 asserts det F > 0)
+    if (!ok)
+      *ep.inverted = 1.0;
+#pragma unroll
+    for (int k = 0; k < 6; ++k)
+      s[k] = tau[k] * rJ;
+    (void)Finv, (void)tiso, (void)cII, (void)cS;
+    return ok;
+  }
+  // the two point numbers from the raw stress s and the recovered one r (both xx yy zz xy xz yz; 2D reads xx, yy, xy alone)
+  template <int DIM>
+  __device__ __forceinline__ void stress_error_point(const double s[6], const double r[6], const double w, const bool ok,
+                                                     const StressErrorParams &ep, double e[2])
+  {
+    double dd = 0.0, dt = 0.0, sd = 0.0, st = 0.0, od = 0.0, os = 0.0;
+#pragma unroll
+    for (int k = 0; k < DIM; ++k)
+      {
+        const double d = r[k] - s[k];
+        dd = fma(d, d, dd), dt += d;
+        sd = fma(s[k], s[k], sd), st += s[k];
+      }
+#pragma unroll
+    for (int k = 3; k < (DIM == 3 ? 6 : 4); ++k)
+      {
+        const double d = r[k] - s[k];
+        od = fma(d, d, od);
+        os = fma(s[k], s[k], os);
+      }
+    const double wm = w * ep.inv2mu;
+    e[0] = ok ? wm * (dd + 2.0 * od - ep.c * dt * dt) : 0.0;
+    e[1] = ok ? wm * (sd + 2.0 * os - ep.c * st * st) : 0.0;
+  }
+
+  // 3D Q2, model 0: one wave per cell, lane = point of the 4 x 4 x 4 rule.  The gather of u and E12, E3 of stress_q2 for grad u;
+  // sigma*'s six fields of the 27 nodes go the same way with the S table alone (the transposes of stress_q2's B12 / B3): E12'
+  // item (f, k, qx), 72 items in two rounds, E3' in the point's lane.
+  template <bool BOX>
+  __global__ __launch_bounds__(64, 4) void stress_error_q2(MfParams prm, StressErrorParams ep)
+  {
+    constexpr int NPC = 27, PS = 20, PW = 9 * PS;
+    __shared__ double sX[3 * NPC], sS[6 * NPC], sB[3 * PW], sBs[18 * PS];
+    const int     lane = threadIdx.x;
+    const int64_t cell = blockIdx.x;
+    if (lane < NPC)
+      {
+        const int32_t node = prm.conn[cell * NPC + lane];
+#pragma unroll
+        for (int c = 0; c < 3; ++c)
+          sX[c * NPC + lane] = ep.u[int64_t(node) * 3 + c];
+#pragma unroll
+        for (int f = 0; f < 6; ++f)
+          sS[f * NPC + lane] = ep.sigma[int64_t(node) * 6 + f];
+      }
+    double S[4][3], D[4][3]; // S[q][a] = N_a(x_q), D[q][a] = N_a'(x_q) (uniform -> scalar registers)
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+#pragma unroll
+      for (int a = 0; a < 3; ++a)
+        {
+          S[q][a] = prm.tab1d[q * 3 + a];
+          D[q][a] = prm.tab1d[12 + q * 3 + a];
+        }
+    const int qz = lane >> 4, q16 = lane & 15;
+    double    Sz[3], Dz[3], Sx[3], Dx[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k)
+      {
+        Sz[k] = prm.tab1d[qz * 3 + k];
+        Dz[k] = prm.tab1d[12 + qz * 3 + k];
+        Sx[k] = prm.tab1d[(lane & 3) * 3 + k];
+        Dx[k] = prm.tab1d[12 + (lane & 3) * 3 + k];
+      }
+    const double wq = prm.tab1d[24 + (lane & 3)] * prm.tab1d[24 + ((lane >> 2) & 3)] * prm.tab1d[24 + qz];
+    __syncthreads();
+    // ---- E12: lane = (c*3+k)*4 + qx contracts i, then j
+    const int pck = lane >> 2, pqx = lane & 3;
+    if (lane < 36)
+      {
+        double as[3], ad[3];
+#pragma unroll
+        for (int j = 0; j < 3; ++j)
+          {
+            const double x0 = sX[pck * 9 + j * 3], x1 = sX[pck * 9 + j * 3 + 1], x2 = sX[pck * 9 + j * 3 + 2];
+            as[j] = Sx[0] * x0 + Sx[1] * x1 + Sx[2] * x2;
+            ad[j] = Dx[0] * x0 + Dx[1] * x1 + Dx[2] * x2;
+          }
+#pragma unroll
+        for (int qy = 0; qy < 4; ++qy)
+          {
+            const int o    = pck * PS + qy * 4 + pqx;
+            sB[o]          = S[qy][0] * ad[0] + S[qy][1] * ad[1] + S[qy][2] * ad[2]; // d/dx
+            sB[o + PW]     = D[qy][0] * as[0] + D[qy][1] * as[1] + D[qy][2] * as[2]; // d/dy
+            sB[o + 2 * PW] = S[qy][0] * as[0] + S[qy][1] * as[1] + S[qy][2] * as[2]; // d/dz
+          }
+      }
+    // ---- E12': item = (f*3+k)*4 + qx, values only (item & 3 == lane & 3: this lane's row Sx in both rounds)
+#pragma unroll
+    for (int item = lane; item < 72; item += 64)
+      {
+        const int fk = item >> 2;
+        double    as[3];
+#pragma unroll
+        for (int j = 0; j < 3; ++j)
+          as[j] = Sx[0] * sS[fk * 9 + j * 3] + Sx[1] * sS[fk * 9 + j * 3 + 1] + Sx[2] * sS[fk * 9 + j * 3 + 2];
+#pragma unroll
+        for (int qy = 0; qy < 4; ++qy)
+          sBs[fk * PS + qy * 4 + pqx] = S[qy][0] * as[0] + S[qy][1] * as[1] + S[qy][2] * as[2];
+      }
+    __syncthreads();
+    // ---- E3: contract k.  lane = quadrature point; H[c][l] = d u_c / d xi_l
+    double H[3][3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+      {
+        H[c][0] = H[c][1] = H[c][2] = 0.0;
+#pragma unroll
+        for (int k = 0; k < 3; ++k)
+          {
+            const int o = (c * 3 + k) * PS + q16;
+            H[c][0]     = fma(Sz[k], sB[o], H[c][0]);
+            H[c][1]     = fma(Sz[k], sB[o + PW], H[c][1]);
+            H[c][2]     = fma(Dz[k], sB[o + 2 * PW], H[c][2]);
+          }
+      }
+    double e[2];
+    {
+      double Ji[9], detJ, s[6], r[6];
+      mf_geometry<BOX>(prm, cell, prm.tab1d + 28, lane & 3, (lane >> 2) & 3, qz, Ji, detJ);
+      MF_RECORD_TAIL(false, false, static_cast<double *>(nullptr), 64)
+      const bool ok = stress_value<3>(F, J, Jm, rJ, ep, s);
+      // ---- E3': sigma*(q)
+#pragma unroll
+      for (int f = 0; f < 6; ++f)
+        r[f] = Sz[0] * sBs[(f * 3) * PS + q16] + Sz[1] * sBs[(f * 3 + 1) * PS + q16] + Sz[2] * sBs[(f * 3 + 2) * PS + q16];
+      stress_error_point<3>(s, r, detJ * wq, ok, ep, e);
+    }
+    e[0] = wave_sum_lane63(e[0]);
+    e[1] = wave_sum_lane63(e[1]);
+    if (lane == 63)
+      {
+        double *__restrict__ o = ep.cell_e + cell * 3;
+        o[0] = e[0], o[1] = e[1], o[2] = 0.0;
+      }
+  }
+
+  // 3D Q3, model 0: the shape of stress_q3 / energy_q3 -- 128 threads per cell, thread = point of the 5 x 5 x 5 rule (threads
+  // 125-127 contribute exact zeros).  Both waves gather: u into R1 for mfq3_gradients, sigma*'s six fields (three per wave) into
+  // R0 behind the part the gradients use.  After the point's raw stress, the value-only forward pass of the six fields, laid
+  // over the regions the gradients have consumed:
+  //   X'' [f*64 + a]          R0 at MFQ3_VX, 384 doubles (ends at 864)
+  //   E1'' item (f, k, j):    x-line -> A'' [f,k,j][qx]           R0 at 0, 96 items, 480 doubles
+  //   E2'' item (f, k, qx):   contract j -> B'' [f,k][qy][qx]     R1 at 0, 120 items, 600 doubles
+  //   E3'' item = point:      contract k -> sigma*_f(q)
+  template <bool BOX>
+  __global__ __launch_bounds__(MFQ3_NT, 4) void stress_error_q3(MfParams prm, StressErrorParams ep)
+  {
+    __shared__ double R0[MFQ3_R0], R1[MFQ3_R1], sT[40], sW[2];
+    const int     t    = threadIdx.x, it = t < MFQ3_NQ ? t : MFQ3_NQ - 1;
+    const int64_t cell = blockIdx.x;
+    if (t < 40)
+      sT[t] = prm.tab1d[t];
+    {
+      const int     a = t & (MFQ3_NPC - 1), f0 = (t >> 6) * 3;
+      const int32_t node = prm.conn[cell * MFQ3_NPC + a];
+      if (t < MFQ3_NPC)
+        {
+#pragma unroll
+          for (int c = 0; c < 3; ++c)
+            R1[c * MFQ3_NPC + a] = ep.u[int64_t(node) * 3 + c];
+        }
+#pragma unroll
+      for (int f = 0; f < 3; ++f)
+        R0[MFQ3_VX + (f0 + f) * MFQ3_NPC + a] = ep.sigma[int64_t(node) * 6 + f0 + f];
+    }
+    __syncthreads();
+    double H[3][3], V[3];
+    mfq3_gradients(prm.tab1d, sT, R0, R1, t, it, H, V); // (writes R0 below MFQ3_VX only; ends with a barrier: R0 below it and R1 are free)
+    const int qz = it / 25, q25 = it - 25 * qz;
+    double    s[6], w;
+    bool      ok;
+    {
+      const int    qy = q25 / 5, qx = q25 - 5 * qy;
+      const double wq = prm.tab1d[MFQ3_TW + qx] * prm.tab1d[MFQ3_TW + qy] * prm.tab1d[MFQ3_TW + qz];
+      double       Ji[9], detJ;
+      mf_geometry<BOX>(prm, cell, prm.tab1d + MFQ3_TX, qx, qy, qz, Ji, detJ);
+      MF_RECORD_TAIL(false, false, static_cast<double *>(nullptr), MFQ3_QS)
+      ok = stress_value<3>(F, J, Jm, rJ, ep, s);
+      w  = detJ * wq;
+      (void)V;
+    }
+    {
+      double S[5][4]; // uniform: scalar registers
+#pragma unroll
+      for (int q = 0; q < 5; ++q)
+#pragma unroll
+        for (int a = 0; a < 4; ++a)
+          S[q][a] = prm.tab1d[q * 4 + a];
+      if (t < 96) // E1'': line (f,k,j) = t
+        {
+          const double x0 = R0[MFQ3_VX + t * 4], x1 = R0[MFQ3_VX + t * 4 + 1], x2 = R0[MFQ3_VX + t * 4 + 2], x3 = R0[MFQ3_VX + t * 4 + 3];
+#pragma unroll
+          for (int qx = 0; qx < 5; ++qx)
+            R0[t * 5 + qx] = S[qx][0] * x0 + S[qx][1] * x1 + S[qx][2] * x2 + S[qx][3] * x3;
+        }
+      __syncthreads();
+      if (t < 120) // E2'': item (f,k,qx): t = fk * 5 + qx
+        {
+          const int fk = t / 5, qx = t - 5 * fk;
+          double    as[4];
+#pragma unroll
+          for (int j = 0; j < 4; ++j)
+            as[j] = R0[(fk * 4 + j) * 5 + qx];
+#pragma unroll
+          for (int qy = 0; qy < 5; ++qy)
+            R1[fk * 25 + qy * 5 + qx] = S[qy][0] * as[0] + S[qy][1] * as[1] + S[qy][2] * as[2] + S[qy][3] * as[3];
+        }
+      __syncthreads();
+    }
+    double e[2];
+    {
+      double r[6]; // E3'': sigma*(q)
+#pragma unroll
+      for (int f = 0; f < 6; ++f)
+        {
+          r[f] = 0.0;
+#pragma unroll
+          for (int k = 0; k < 4; ++k)
+            r[f] = fma(sT[qz * 4 + k], R1[(f * 4 + k) * 25 + q25], r[f]);
+        }
+      stress_error_point<3>(s, r, w, ok, ep, e);
+    }
+    e[0] = wave_sum_lane63(t < MFQ3_NQ ? e[0] : 0.0);
+    e[1] = wave_sum_lane63(t < MFQ3_NQ ? e[1] : 0.0);
+    if (t == MFQ3_NT - 1) // lane 63 of the second wave
+      sW[0] = e[0], sW[1] = e[1];
+    __syncthreads();
+    if (t == 63)
+      {
+        double *__restrict__ o = ep.cell_e + cell * 3;
+        o[0] = e[0] + sW[0], o[1] = e[1] + sW[1], o[2] = 0.0;
+      }
+  }
+
+  // every other element (2D p = 1..4, 3D p = 1, 4), all of model 1, and the cross-check of the two forms above: one workgroup per
+  // cell, thread = quadrature point, plain loops over the cell's nodes as in stress_cells -- grad u and sigma*(q) in one loop
+  template <int DIM, int P, int MODEL, int NT>
+  __global__ __launch_bounds__(NT) void stress_error_cells(StressErrorParams ep)
+  {
+    constexpr int NP1 = P + 1, NPC = Elem<DIM, P>::NPC, NV = 1 << DIM, NC = DIM * (DIM + 1) / 2;
+    constexpr int NQ1 = MODEL == 0 ? P + 2 : P + 1; // qf_cell (nonlinear_elasticity.cc:74) / quad_order (linear_elasticity.cc:61)
+    constexpr int NQ  = DIM == 2 ? NQ1 * NQ1 : NQ1 * NQ1 * NQ1;
+    static_assert(NQ <= NT && NT % 64 == 0, "one thread per quadrature point, whole waves");
+    __shared__ double s_N1[NQ1 * NP1], s_dN1[NQ1 * NP1], s_qw[NQ1], s_qx[NQ1];
+    __shared__ double s_u[NPC * DIM], s_sig[NPC * NC], s_verts[NV * DIM], s_red[NT / 64];
+    const int     tid  = threadIdx.x;
+    const int64_t cell = blockIdx.x;
+    for (int i = tid; i < NQ1 * NP1; i += NT)
+      {
+        s_N1[i]  = ep.tab[i];
+        s_dN1[i] = ep.tab[NQ1 * NP1 + i];
+      }
+    if (tid < NQ1)
+      {
+        s_qw[tid] = ep.tab[2 * NQ1 * NP1 + tid];
+        s_qx[tid] = ep.tab[2 * NQ1 * NP1 + NQ1 + tid];
+      }
+    if (tid < NV * DIM)
+      s_verts[tid] = ep.cverts[cell * (NV * DIM) + tid];
+    for (int i = tid; i < NPC * DIM; i += NT)
+      {
+        const int a = i / DIM, c = i - a * DIM;
+        s_u[i]      = ep.u[int64_t(ep.conn[cell * NPC + a]) * DIM + c];
+      }
+    for (int i = tid; i < NPC * NC; i += NT)
+      {
+        const int a = i / NC, f = i - a * NC;
+        s_sig[i]    = ep.sigma[int64_t(ep.conn[cell * NPC + a]) * NC + f];
+      }
+    __syncthreads();
+    double e[2] = {0.0, 0.0};
+    if (tid < NQ)
+      {
+        const int q     = tid;
+        const int qi[3] = {q % NQ1, (q / NQ1) % NQ1, (DIM == 3) ? q / (NQ1 * NQ1) : 0};
+        double    gxi[9], rs[NC];
+#pragma unroll
+        for (int k = 0; k < 9; ++k)
+          gxi[k] = 0.0;
+#pragma unroll
+        for (int k = 0; k < NC; ++k)
+          rs[k] = 0.0;
+        for (int a = 0; a < NPC; ++a)
+          {
+            const int    ai[3] = {a % NP1, (a / NP1) % NP1, (DIM == 3) ? a / (NP1 * NP1) : 0};
+            const double n0 = s_N1[qi[0] * NP1 + ai[0]], n1 = s_N1[qi[1] * NP1 + ai[1]], n2 = (DIM == 3) ? s_N1[qi[2] * NP1 + ai[2]] : 1.0;
+            const double dN[3] = {s_dN1[qi[0] * NP1 + ai[0]] * n1 * n2, n0 * s_dN1[qi[1] * NP1 + ai[1]] * n2,
+                                  (DIM == 3) ? n0 * n1 * s_dN1[qi[2] * NP1 + ai[2]] : 0.0};
+            const double N = n0 * n1 * n2;
+#pragma unroll
+            for (int i = 0; i < DIM; ++i)
+#pragma unroll
+              for (int j = 0; j < DIM; ++j)
+                gxi[i * 3 + j] = fma(s_u[a * DIM + i], dN[j], gxi[i * 3 + j]);
+#pragma unroll
+            for (int k = 0; k < NC; ++k)
+              rs[k] = fma(N, s_sig[a * NC + k], rs[k]);
+          }
+        double xi[3] = {0.0, 0.0, 0.0}, wq = 1.0;
+#pragma unroll
+        for (int d = 0; d < DIM; ++d)
+          {
+            xi[d] = s_qx[qi[d]];
+            wq *= s_qw[qi[d]];
+          }
+        double Jg[9], Ji[9];
+        q1_jacobian<DIM>(s_verts, xi, Jg);
+        const double detJ = det3x3(Jg);
+        inv3x3(Jg, detJ, Ji);
+        double F[9]; // grad u = grad_xi u Jinv, embedded in 3 x 3 (model 0: + I)
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+#pragma unroll
+          for (int j = 0; j < 3; ++j)
+            F[i * 3 + j] = (i < DIM && j < DIM) ? gxi[i * 3 + 0] * Ji[0 * 3 + j] + gxi[i * 3 + 1] * Ji[1 * 3 + j] +
+                                                    (DIM == 3 ? gxi[i * 3 + 2] * Ji[2 * 3 + j] : 0.0) :
+                                                  0.0;
+        double s[6], r[6];
+        bool   ok = true;
+        if constexpr (MODEL == 0)
+          {
+            F[0] += 1.0, F[4] += 1.0, F[8] += 1.0;
+            const double J  = det3x3(F);
+            const double rJ = 1.0 / J, Jm = (DIM == 3) ? 1.0 / (cbrt(J) * cbrt(J)) : rJ; // J^(-2/d)
+            ok              = stress_value<DIM>(F, J, Jm, rJ, ep, s);
+          }
+        else
+          {
+            const double ltr = ep.lambda * (F[0] + F[4] + F[8]), m2 = 2.0 * ep.mu;
+            s[0] = ltr + m2 * F[0];
+            s[1] = ltr + m2 * F[4];
+            s[2] = (DIM == 3) ? ltr + m2 * F[8] : 0.0;
+            s[3] = ep.mu * (F[1] + F[3]);
+            s[4] = ep.mu * (F[2] + F[6]);
+            s[5] = ep.mu * (F[5] + F[7]);
+          }
+        if constexpr (DIM == 3)
+          {
+#pragma unroll
+            for (int k = 0; k < 6; ++k)
+              r[k] = rs[k];
+          }
+        else
+          r[0] = rs[0], r[1] = rs[1], r[2] = 0.0, r[3] = rs[2], r[4] = 0.0, r[5] = 0.0; // the nodal field's xx yy xy
+        stress_error_point<DIM>(s, r, detJ * wq, ok, ep, e);
+      }
+    e[0] = block_sum<NT>(e[0], s_red);
+    e[1] = block_sum<NT>(e[1], s_red);
+    if (tid == 0)
+      {
+        double *__restrict__ o = ep.cell_e + cell * 3;
+        o[0] = e[0], o[1] = e[1], o[2] = 0.0;
+      }
+  }
+
+  // the larger of two (value, id) pairs over the workgroup, the smaller id among equal values: maximum and smallest index do
+  // not depend on the order in which the pairs meet.  Result in s_v[0], s_i[0]
+  __device__ __forceinline__ void block_argmax(const double v, const int64_t id, double *s_v, int64_t *s_i)
+  {
+    const int tid = threadIdx.x;
+    s_v[tid] = v, s_i[tid] = id;
+    __syncthreads();
+    for (int h = 128; h > 0; h >>= 1)
+      {
+        if (tid < h)
+          {
+            const double  v2 = s_v[tid + h];
+            const int64_t i2 = s_i[tid + h];
+            if (v2 > s_v[tid] || (v2 == s_v[tid] && i2 < s_i[tid]))
+              s_v[tid] = v2, s_i[tid] = i2;
+          }
+        __syncthreads();
+      }
+  }
+  // workgroup b takes the colour-sorted cells [b chunk, (b + 1) chunk): eta_K and n_K, the roots of the cell's two sums, into
+  // the caller's lexicographic order (cell_orig: HostMesh::cell_orig), and the largest eta_K of the chunk with the smallest
+  // lexicographic id that has it into part[b][2] (the id as a double: exact below 2^53)
+  __global__ __launch_bounds__(256) void stress_error_finish(const double *__restrict__ cell_e, const int32_t *__restrict__ cell_orig,
+                                                             const int64_t ncells, const int64_t chunk, double *__restrict__ eta_cell,
+                                                             double *__restrict__ norm_cell, double *__restrict__ part)
+  {
+    __shared__ double  s_v[256];
+    __shared__ int64_t s_i[256];
+    const int64_t i0 = blockIdx.x * chunk, i1 = imin64(ncells, i0 + chunk);
+    double        v  = -1.0;
+    int64_t       id = ncells;
+    for (int64_t i = i0 + threadIdx.x; i < i1; i += 256)
+      {
+        const int64_t o = cell_orig[i];
+        const double  e = sqrt(cell_e[i * 3]);
+        eta_cell[o]     = e;
+        norm_cell[o]    = sqrt(cell_e[i * 3 + 1]);
+        if (e > v || (e == v && o < id))
+          v = e, id = o;
+      }
+    block_argmax(v, id, s_v, s_i);
+    if (threadIdx.x == 0)
+      part[blockIdx.x * 2] = s_v[0], part[blockIdx.x * 2 + 1] = double(s_i[0]);
+  }
+  // one workgroup: the same over the n pairs of the chunks, into out[0], out[1]
+  __global__ __launch_bounds__(256) void stress_error_max(const double *__restrict__ part, const int64_t n, double *__restrict__ out)
+  {
+    __shared__ double  s_v[256];
+    __shared__ int64_t s_i[256];
+    double             v  = -1.0;
+    int64_t            id = INT64_MAX;
+    for (int64_t i = threadIdx.x; i < n; i += 256)
+      {
+        const double  e = part[i * 2];
+        const int64_t o = int64_t(part[i * 2 + 1]);
+        if (e > v || (e == v && o < id))
+          v = e, id = o;
+      }
+    block_argmax(v, id, s_v, s_i);
+    if (threadIdx.x == 0)
+      out[0] = s_v[0], out[1] = double(s_i[0]);
+  }
   // (the last matrix-free kernel: the shared text ends here)
 #undef MF_RECORD_TAIL
 #undef MF_M
@@ -8475,6 +8921,53 @@ namespace mi
       hipLaunchKernelGGL(stress_finish<3>, dim3(grid), dim3(256), 0, s, acc, nnodes, sigma, von_mises, weight);
     else
       hipLaunchKernelGGL(stress_finish<2>, dim3(grid), dim3(256), 0, s, acc, nnodes, sigma, von_mises, weight);
+  }
+  int launch_stress_error(int dim, int degree, int model, const MfParams &p, const StressErrorParams &ep, int32_t cell_count, bool generic,
+                          hipStream_t s)
+  {
+    if (cell_count <= 0)
+      return 0;
+    if (dim == 3 && degree == 3 && model == 0 && !generic)
+      {
+        auto *kern = p.cellbox ? stress_error_q3<true> : stress_error_q3<false>;
+        hipLaunchKernelGGL(kern, dim3(cell_count), dim3(MFQ3_NT), 0, s, p, ep);
+        return 0;
+      }
+    if (dim == 3 && degree == 2 && model == 0 && !generic)
+      {
+        auto *kern = p.cellbox ? stress_error_q2<true> : stress_error_q2<false>;
+        hipLaunchKernelGGL(kern, dim3(cell_count), dim3(64), 0, s, p, ep);
+        return 0;
+      }
+#define MI_SE(D_, P_, NT_)                                                                                          \
+  if (dim == D_ && degree == P_)                                                                                    \
+    {                                                                                                               \
+      if (model == 0)                                                                                               \
+        hipLaunchKernelGGL((stress_error_cells<D_, P_, 0, NT_>), dim3(cell_count), dim3(NT_), 0, s, ep);            \
+      else                                                                                                          \
+        hipLaunchKernelGGL((stress_error_cells<D_, P_, 1, NT_>), dim3(cell_count), dim3(NT_), 0, s, ep);            \
+      return 0;                                                                                                     \
+    }
+    MI_SE(3, 1, 64)
+    MI_SE(3, 2, 64)
+    MI_SE(3, 3, 128)
+    MI_SE(3, 4, 256)
+    MI_SE(2, 1, 64)
+    MI_SE(2, 2, 64)
+    MI_SE(2, 3, 64)
+    MI_SE(2, 4, 64)
+#undef MI_SE
+    return -1;
+  }
+  void launch_stress_error_finish(const double *cell_e, const int32_t *cell_orig, int64_t ncells, double *eta_cell, double *norm_cell,
+                                  double *scratch, double *max_out, hipStream_t s)
+  {
+    if (ncells <= 0)
+      return;
+    const int64_t chunk = 1024;
+    const int     nblk  = int((ncells + chunk - 1) / chunk);
+    hipLaunchKernelGGL(stress_error_finish, dim3(nblk), dim3(256), 0, s, cell_e, cell_orig, ncells, chunk, eta_cell, norm_cell, scratch);
+    hipLaunchKernelGGL(stress_error_max, dim3(1), dim3(256), 0, s, scratch, int64_t(nblk), max_out);
   }
   void launch_mf_diag_q3(const MfParams &p, double *slots6, int32_t cell_count, hipStream_t s)
   {

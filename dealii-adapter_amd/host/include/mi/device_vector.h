@@ -98,6 +98,20 @@ namespace mi
       check(mi_stress_field(ctx_, model, sigma.data(), von_mises.data(), nullptr), "mi_stress_field");
       return true;
     }
+    // error indicator of that stress field (mi_stress_error): the totals into info, eta_K [n_cells] in lexicographic cell order
+    // into eta_cell where wanted.  false on a team (emulated slabs or RCCL), where the library provides none (one slab only);
+    // any other failure throws
+    bool stress_error(int model, mi_stress_error_info &info, std::vector<double> *eta_cell = nullptr) const
+    {
+      int team = 1, rccl = 0;
+      check(mi_comm_info(ctx_, &team, &rccl), "mi_comm_info");
+      if (team > 1 || rccl > 0)
+        return false;
+      if (eta_cell)
+        eta_cell->assign(size_t(mi_n_cells(ctx_)), 0.0);
+      check(mi_stress_error(ctx_, model, &info, eta_cell ? eta_cell->data() : nullptr, nullptr), "mi_stress_error");
+      return true;
+    }
     void    check(int rc, const char *what) const
     {
       if (rc != MI_OK)

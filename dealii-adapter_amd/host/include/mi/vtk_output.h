@@ -12,6 +12,9 @@
 // unique components: xx yy zz xy xz yz, 2D xx yy xy) and von_mises -- the NODAL values of mi_stress_field (the lumped L2
 // projection of the Cauchy stress, model 0, or of the linear model's stress, model 1) at the patch points, so unlike strain_*
 // they are continuous across cells.  Without it the file is byte for byte what it was.
+// stress_error_model >= 0 (the executables' MI_VTK_STRESS_ERROR=1): CELL_DATA `stress_error` behind the point data, eta_K of
+// mi_stress_error (the distance between that nodal stress and the elements' raw stress) -- one value per Lagrange cell; with
+// linear sub-cells every sub-cell carries its element's value.  Without it the file is byte for byte what it was.
 #pragma once
 #include <cmath>
 #include <fstream>
@@ -113,7 +116,7 @@ namespace mi
   // team collectives (ncclAllReduce under RCCL), which hang or pair up with the wrong collective when only one rank
   // enters them.  write = false (ranks > 0): take part in the gathers, write nothing.
   inline void write_vtk(const Device &dev, int dim, int p, const int reps[3], const std::string &path, bool write = true,
-                        bool higher_order = true, int stress_model = -1)
+                        bool higher_order = true, int stress_model = -1, int stress_error_model = -1)
   {
     const int64_t       nn = mi_n_nodes(dev.ctx()), n = mi_n_dofs(dev.ctx());
     std::vector<double> xyz(size_t(nn) * dim), u(size_t(n), 0.0);
@@ -126,6 +129,15 @@ namespace mi
         have_stress = dev.stress_field(stress_model, dim, sig, vm);
         if (!have_stress && write)
           std::cout << "\t MI_VTK_STRESS: mi_stress_field runs in one process only, no stress is written on an RCCL team" << std::endl;
+      }
+    std::vector<double> eta_cell;
+    bool                have_error = false;
+    if (stress_error_model >= 0)
+      {
+        mi_stress_error_info info{};
+        have_error = dev.stress_error(stress_error_model, info, &eta_cell);
+        if (!have_error && write)
+          std::cout << "\t MI_VTK_STRESS_ERROR: mi_stress_error runs on one slab only, no stress error is written on a team" << std::endl;
       }
     if (!write)
       return;
@@ -301,6 +313,14 @@ namespace mi
         out << "SCALARS von_mises double 1\nLOOKUP_TABLE default\n";
         for (int64_t i = 0; i < npts; ++i)
           out << vm[size_t(pnode[size_t(i)])] << '\n';
+      }
+    if (have_error)
+      {
+        const int64_t per_cell = higher_order ? 1 : nsub / ncells; // the sub-cells of a patch follow one another
+        out << "CELL_DATA " << ncells * per_cell << "\nSCALARS stress_error double 1\nLOOKUP_TABLE default\n";
+        for (int64_t c = 0; c < ncells; ++c)
+          for (int64_t k = 0; k < per_cell; ++k)
+            out << eta_cell[size_t(c)] << '\n';
       }
   }
 } // namespace mi

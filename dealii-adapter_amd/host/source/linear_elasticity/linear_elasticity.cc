@@ -191,7 +191,8 @@ namespace Linear_Elasticity
     // all ranks: the global views behind the output are gathered by team collectives; rank 0 writes the file
     mi::write_vtk(*device, dim, int(parameters.poly_degree), mesh_desc.reps, parameters.output_folder + "/" + name.str(), mi::host_rank() == 0,
                   !std::getenv("MI_VTK_LINEAR_CELLS"), // higher-order cells as the reference (:1222-1225); the switch: linear sub-cells
-                  std::getenv("MI_VTK_STRESS") && std::atoi(std::getenv("MI_VTK_STRESS")) != 0 ? MI_STRESS_LINEAR : -1); // + nodal stress
+                  std::getenv("MI_VTK_STRESS") && std::atoi(std::getenv("MI_VTK_STRESS")) != 0 ? MI_STRESS_LINEAR : -1, // + nodal stress
+                  std::getenv("MI_VTK_STRESS_ERROR") && std::atoi(std::getenv("MI_VTK_STRESS_ERROR")) != 0 ? MI_STRESS_LINEAR : -1); // + eta_K
     timer.leave_subsection("Output results");
   }
 

@@ -372,6 +372,17 @@ namespace Nonlinear_Elasticity
     // what the structure holds after the step (collective: every rank asks, rank 0 writes)
     mi_energy_info energy{};
     device->check(mi_energy(device->ctx(), &energy), "mi_energy");
+    // MI_STRESS_ERROR=1: the stress error indicator of the step's state as four further keys
+    mi_stress_error_info serr{};
+    bool                 have_serr = false;
+    if (std::getenv("MI_STRESS_ERROR") && std::atoi(std::getenv("MI_STRESS_ERROR")) != 0)
+      {
+        have_serr = device->stress_error(MI_STRESS_NEOHOOKE, serr);
+        static bool told = false; // (one line per run, not per step)
+        if (!have_serr && !told && mi::host_rank() == 0)
+          std::cout << "\t MI_STRESS_ERROR: mi_stress_error runs on one slab only, no stress error is written on a team" << std::endl;
+        told = told || !have_serr;
+      }
     if (mi::host_rank() > 0)
       return;
     std::ofstream out(parameters.output_folder + "/steps.jsonl", std::ios::app);
@@ -381,7 +392,11 @@ namespace Nonlinear_Elasticity
         << ", \"newton_iterations\": " << last_newton_iterations << ", \"linear_iterations\": " << last_lin_iterations
         << ", \"residual_abs\": " << error_residual.u << ", \"update_abs\": " << error_update.u
         << ", \"n_dofs\": " << mi_n_dofs(device->ctx()) << ", \"strain_energy\": " << energy.strain
-        << ", \"kinetic_energy\": " << energy.kinetic << ", \"body_potential\": " << energy.body << "}\n";
+        << ", \"kinetic_energy\": " << energy.kinetic << ", \"body_potential\": " << energy.body;
+    if (have_serr)
+      out << ", \"stress_error\": " << serr.error << ", \"stress_norm\": " << serr.norm << ", \"stress_error_relative\": " << serr.relative
+          << ", \"stress_error_max_cell\": " << serr.max_cell;
+    out << "}\n";
   }
 
   // :1215-1254: solution-XXX.vtk with index timestep / output_interval
@@ -395,7 +410,8 @@ namespace Nonlinear_Elasticity
     // all ranks: the global views behind the output are gathered by team collectives; rank 0 writes the file
     mi::write_vtk(*device, dim, int(degree), mesh_desc.reps, parameters.output_folder + "/" + name.str(), mi::host_rank() == 0,
                   !std::getenv("MI_VTK_LINEAR_CELLS"), // higher-order cells as the reference (:1222-1225); the switch: linear sub-cells
-                  std::getenv("MI_VTK_STRESS") && std::atoi(std::getenv("MI_VTK_STRESS")) != 0 ? MI_STRESS_NEOHOOKE : -1); // + nodal stress
+                  std::getenv("MI_VTK_STRESS") && std::atoi(std::getenv("MI_VTK_STRESS")) != 0 ? MI_STRESS_NEOHOOKE : -1, // + nodal stress
+                  std::getenv("MI_VTK_STRESS_ERROR") && std::atoi(std::getenv("MI_VTK_STRESS_ERROR")) != 0 ? MI_STRESS_NEOHOOKE : -1); // + eta_K
     std::cout << "\t Output written to " << name.str() << " \n" << std::endl;
     timer.leave_subsection("Output results");
   }

@@ -234,6 +234,40 @@ int mi_energy(mi_ctx *ctx, mi_energy_info *out);
 #define MI_STRESS_LINEAR   1
 int mi_stress_field(mi_ctx *ctx, int model, double *sigma, double *von_mises, double *weight);
 
+/* A posteriori stress error indicator: how far to trust that stress on this mesh.  The Zienkiewicz-Zhu distance between the
+ * recovered field sigma* of mi_stress_field(model) and the raw stress sigma_h of the elements, same state, same rule,
+ * reference configuration.  With sigma*(q) = sum_i N_i(q) sigma*_i and e(q) = sigma*(q) - sigma_h(q):
+ *     m(s)    = ( s:s - c tr(s)^2 ) / (2 mu)      s:s counts each off-diagonal entry twice; c = nu / (1 + nu) in 3D and
+ *                                                 c = nu in 2D (the plane-strain compliance of the reference's 2 x 2
+ *                                                 formulation, which has no sigma_zz)
+ *     eta_K^2 = sum_{q in K} m(e(q)) JxW(q)       n_K^2 = sum_{q in K} m(sigma_h(q)) JxW(q)
+ *     eta = sqrt(sum_K eta_K^2)    n = sqrt(sum_K n_K^2)    relative = eta / sqrt(n^2 + eta^2)   (0 where n = eta = 0)
+ * m is the complementary energy density of isotropic linear elasticity, s : C^-1 : s, positive definite for nu < 1/2.  For
+ * MI_STRESS_LINEAR n^2 = u^T K u exactly on the model's rule; for MI_STRESS_NEOHOOKE the same metric is applied to the Cauchy
+ * stress tau(F)/J: a scaling, not the material's own energy.  sigma_h(q) is what mi_stress_field projects (model 0 on
+ * QGauss(p+2), model 1 on QGauss(p+1)).
+ * AN INDICATOR, NOT A GUARANTEED BOUND: on smooth fields eta falls like h^p or faster and eta / true error was measured
+ * between 0.45 and 1.3, but nothing bounds the error from above by eta.
+ * eta_cell, norm_cell [n_cells], each optional (NULL = not wanted): eta_K and n_K (not their squares) in lexicographic cell
+ * order with x fastest, cell (i, j, k) at i + reps[0] (j + reps[1] k).  max_cell is the lexicographic id of the largest
+ * eta_K, the smallest id on ties.
+ * The contract of mi_stress_field: every (dim, degree) an assembly supports, "fine_level" 0 and 1, after a "linear_operator" 1
+ * set-up has released the tangent array, model 1 without mi_linear_setup.  Modifies no state vector, record, matrix,
+ * hierarchy, counter or timing (scratch of its own is allocated on first use).  Bitwise repeatable: fixed-order sums, no
+ * floating-point atomics.  Model 0 with a point of det F <= 0: MI_EINVAL "inverted element"; the context works afterwards.
+ * Undecomposed contexts only: on an emulated or RCCL team MI_EINVAL "one slab only", as mi_linear_modes (a slab's first
+ * node plane holds a partial sigma*, and the exchange of a six-component nodal field is not provided).  A bad model, a NULL
+ * out or a NULL ctx: MI_EINVAL. */
+typedef struct
+{
+  double  error, norm, relative; /* eta, n, eta / sqrt(n^2 + eta^2) */
+  double  max_cell_error;        /* largest eta_K */
+  int64_t max_cell;              /* its lexicographic cell id; the smallest id on ties */
+  int64_t reserved;              /* 0 */
+} mi_stress_error_info;
+int mi_stress_error(mi_ctx *ctx, int model, mi_stress_error_info *out, double *eta_cell /* [n_cells] or NULL */,
+                    double *norm_cell /* [n_cells] or NULL */);
+
 /* ---- linear model: ElastoDynamics (source/linear_elasticity/linear_elasticity.cc) -------------------------- */
 /* state vectors of the linear model live in the same slots as the nonlinear ones */
 enum
@@ -584,7 +618,8 @@ int mi_set_profiling(mi_ctx *ctx, int enable);
  * MI_MF_XCD (XCD-aware cell order of mf_spmv), MI_ASM_CELL_LATTICE, MI_ASM_STAMPS / MI_MF_STAMPS / MI_MF_DBG (phase stamps
  * and timing-only ablations of the two element kernels), MI_ENERGY_GENERIC (mi_energy through the generic kernel on 3D Q2 / Q3
  * too: the cross-check of tools/energy_generic_check.py), MI_STRESS_GENERIC (mi_stress_field likewise:
- * tools/stress_generic_check.py). */
+ * tools/stress_generic_check.py), MI_STRESS_ERROR_GENERIC (the second pass of mi_stress_error likewise:
+ * tools/stress_error_generic_check.py). */
 int mi_set_tuning(mi_ctx *ctx, const char *key, int value);
 /* Read back.  Counters since the last mi_reset_timings (what a solve costs in latency-bound events; counted on one slab
  * as well, where the collectives themselves are no-ops): "count_scalar_allreduce", "count_scalar_allreduce_cg" (those inside
