@@ -1252,6 +1252,30 @@ namespace mi_detail
       HIPCHK(c, hipMalloc((void **)&c->d_energy, (nc + nc / 1024 + 1) * 3 * sizeof(double)));
     return energy_box_prepare(c);
   }
+  // the fields EnergyParams, StressParams and StressErrorParams share, into p: the mesh, the rule's tables (the linear model's:
+  // d_stress_tab, built by enqueue_stress), the committed state, the material and the inverted flag's slot; returns the
+  // sum-factorised kernels' MfParams with the boxes of energy_box_prepare where the context keeps none
+  // the linear model's first Lame parameter (parameters.cc:189): StressParams and StressErrorParams carry it
+  static double lame_lambda(const mi_ctx *c) { return 2 * c->mat.mu * c->mat.nu / (1 - 2 * c->mat.nu); }
+  template <class Params>
+  static mi::MfParams post_params(mi_ctx *c, int model, Params &p)
+  {
+    p.conn = c->d_conn, p.cverts = c->d_cverts, p.tab = model == MI_STRESS_LINEAR ? c->d_stress_tab : c->d_tab;
+    p.u  = c->vec(MI_V_TOTAL_DISPLACEMENT);
+    p.mu = c->mat.mu, p.kappa = c->kappa;
+    p.inverted = c->d_sc + SC_ENERGY + 3;
+    mi::MfParams f = mf_params(c);
+    if (!f.cellbox)
+      f.cellbox = c->d_energy_box;
+    return f;
+  }
+  // experiments build: a variable MI_*_GENERIC that is set and not 0 puts the generic kernel on 3D Q2 / Q3 as well, the
+  // cross-check of the two sum-factorised forms
+  static bool post_generic(const char *var)
+  {
+    const char *e = mi::exp_env(var);
+    return e && atoi(e) != 0;
+  }
 
   // strain energy, kinetic energy and body-force potential of one slab's owned cells into its scalars [SC_ENERGY, +3), the
   // inverted flag into SC_ENERGY + 3 (enqueued; energy_finish sums over the team and reads back)
@@ -1260,21 +1284,15 @@ namespace mi_detail
     if (int rc = energy_prepare(c))
       return rc;
     HIPCHK(c, hipMemsetAsync(c->d_sc + SC_ENERGY, 0, 4 * sizeof(double), c->stream));
-    mi::MfParams f = mf_params(c);
-    if (!f.cellbox)
-      f.cellbox = c->d_energy_box;
-    mi::EnergyParams e{};
-    e.conn = c->d_conn, e.cverts = c->d_cverts, e.tab1d = c->d_tab;
-    e.u = c->vec(MI_V_TOTAL_DISPLACEMENT), e.v = c->vec(MI_V_VELOCITY);
-    e.mu = c->mat.mu, e.kappa = c->kappa, e.rho = c->mat.rho;
+    mi::EnergyParams   e{};
+    const mi::MfParams f = post_params(c, MI_STRESS_NEOHOOKE, e);
+    e.v = c->vec(MI_V_VELOCITY), e.rho = c->mat.rho;
     for (int d = 0; d < 3; ++d)
       e.body[d] = c->mat.body_force[d];
-    e.cell_e   = c->d_energy;
-    e.inverted = c->d_sc + SC_ENERGY + 3;
+    e.cell_e = c->d_energy;
     // owned cell layers [z0, z1) of the slab's local box: the ghost layer above them starts at this node
     e.own_node_end = int32_t(c->slab.plane_nodes * int64_t(c->degree) * (c->slab.z1 - c->slab.z0));
-    // (experiments build: the generic kernel on 3D Q2 / Q3 as well, the cross-check of the two sum-factorised forms)
-    static const bool generic = mi::exp_env("MI_ENERGY_GENERIC") && atoi(mi::exp_env("MI_ENERGY_GENERIC")) != 0;
+    static const bool generic = post_generic("MI_ENERGY_GENERIC");
     if (mi::launch_energy(c->dim, c->degree, f, e, int32_t(c->mesh.ncells), generic, c->stream))
       return fail(c, MI_EINVAL, "no energy kernel for dim=%d degree=%d", c->dim, c->degree);
     mi::launch_energy_sum(c->d_energy, c->mesh.ncells, c->d_energy + size_t(c->mesh.ncells) * 3, c->d_sc + SC_ENERGY, c->stream);
@@ -1325,17 +1343,11 @@ namespace mi_detail
       return rc;
     HIPCHK(c, hipMemsetAsync(c->d_stress, 0, nn * 8 * sizeof(double), c->stream));
     HIPCHK(c, hipMemsetAsync(c->d_sc + SC_ENERGY + 3, 0, sizeof(double), c->stream)); // (mi_energy's flag: it zeroes it itself)
-    mi::MfParams f = mf_params(c);
-    if (!f.cellbox)
-      f.cellbox = c->d_energy_box;
-    mi::StressParams sp{};
-    sp.conn = c->d_conn, sp.cverts = c->d_cverts, sp.tab = model == MI_STRESS_LINEAR ? c->d_stress_tab : c->d_tab;
-    sp.u  = c->vec(MI_V_TOTAL_DISPLACEMENT);
-    sp.mu = c->mat.mu, sp.kappa = c->kappa, sp.lambda = 2 * c->mat.mu * c->mat.nu / (1 - 2 * c->mat.nu); // parameters.cc:189
-    sp.acc      = c->d_stress;
-    sp.inverted = c->d_sc + SC_ENERGY + 3;
-    // (experiments build: the generic kernel on 3D Q2 / Q3 as well, the cross-check of the two sum-factorised forms)
-    static const bool generic = mi::exp_env("MI_STRESS_GENERIC") && atoi(mi::exp_env("MI_STRESS_GENERIC")) != 0;
+    mi::StressParams   sp{};
+    const mi::MfParams f = post_params(c, model, sp);
+    sp.lambda = lame_lambda(c);
+    sp.acc    = c->d_stress;
+    static const bool generic = post_generic("MI_STRESS_GENERIC");
     for (int col = 0; col < c->mesh.ncolours; ++col)
       {
         sp.cell_begin = c->mesh.colour_begin[col];
@@ -1369,20 +1381,14 @@ namespace mi_detail
     if (!c->d_cell_orig)
       if (int rc = upload(c, &c->d_cell_orig, c->mesh.cell_orig))
         return rc;
-    mi::MfParams f = mf_params(c);
-    if (!f.cellbox)
-      f.cellbox = c->d_energy_box;
     mi::StressErrorParams ep{};
-    ep.conn = c->d_conn, ep.cverts = c->d_cverts, ep.tab = model == MI_STRESS_LINEAR ? c->d_stress_tab : c->d_tab;
-    ep.u     = c->vec(MI_V_TOTAL_DISPLACEMENT);
-    ep.sigma = c->d_stress + nn * 8;
-    ep.mu = c->mat.mu, ep.kappa = c->kappa, ep.lambda = 2 * c->mat.mu * c->mat.nu / (1 - 2 * c->mat.nu);
-    ep.c        = c->dim == 3 ? c->mat.nu / (1 + c->mat.nu) : c->mat.nu; // 2D: the plane-strain compliance of the 2 x 2 formulation
-    ep.inv2mu   = 1.0 / (2 * c->mat.mu);
-    ep.cell_e   = c->d_stress_err;
-    ep.inverted = c->d_sc + SC_ENERGY + 3;
-    // (experiments build: the generic kernel on 3D Q2 / Q3 as well, the cross-check of the two sum-factorised forms)
-    static const bool generic = mi::exp_env("MI_STRESS_ERROR_GENERIC") && atoi(mi::exp_env("MI_STRESS_ERROR_GENERIC")) != 0;
+    const mi::MfParams    f = post_params(c, model, ep);
+    ep.lambda = lame_lambda(c);
+    ep.sigma  = c->d_stress + nn * 8;
+    ep.c      = c->dim == 3 ? c->mat.nu / (1 + c->mat.nu) : c->mat.nu; // 2D: the plane-strain compliance of the 2 x 2 formulation
+    ep.inv2mu = 1.0 / (2 * c->mat.mu);
+    ep.cell_e = c->d_stress_err;
+    static const bool generic = post_generic("MI_STRESS_ERROR_GENERIC");
     if (mi::launch_stress_error(c->dim, c->degree, model, f, ep, int32_t(nc), generic, c->stream))
       return fail(c, MI_EINVAL, "no stress error kernel for dim=%d degree=%d", c->dim, c->degree);
     double *scratch = c->d_stress_err + nc * 3, *eta = scratch + (nc / 1024 + 1) * 3, *res = c->d_stress_err + stress_err_results(c);

@@ -234,7 +234,7 @@ namespace mi
   {
     const int32_t *conn;   // [ncells][npc] colour-sorted
     const double  *cverts; // [ncells][2^dim][dim]
-    const double  *tab1d;  // the assembly's tables (AsmParams::tab1d)
+    const double  *tab;    // the assembly's tables (AsmParams::tab1d), as StressParams::tab
     const double  *u, *v;  // total displacement (committed state), velocity
     double         mu, kappa, rho;
     double         body[3];

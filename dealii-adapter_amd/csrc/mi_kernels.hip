@@ -175,16 +175,17 @@ namespace mi
       }
   }
 
-  // unit-cell value and gradient of cell shape function a at cell quadrature point q from the 1D tables
-  template <int DIM, int P>
+  // unit-cell value and gradient of cell shape function a at cell quadrature point q from the 1D tables of a rule with
+  // NQ1 points per direction (the assembly's unless said otherwise)
+  template <int DIM, int P, int NQ1 = Elem<DIM, P>::NQ1>
   __device__ __forceinline__ void shape_at_qp(const double *__restrict__ sN1, const double *__restrict__ sdN1, int q,
                                               int a, double &N, double *dN)
   {
     using E = Elem<DIM, P>;
     int qi[3], ai[3];
-    qi[0] = q % E::NQ1;
-    qi[1] = (q / E::NQ1) % E::NQ1;
-    qi[2] = (DIM == 3) ? q / (E::NQ1 * E::NQ1) : 0;
+    qi[0] = q % NQ1;
+    qi[1] = (q / NQ1) % NQ1;
+    qi[2] = (DIM == 3) ? q / (NQ1 * NQ1) : 0;
     ai[0] = a % E::NP1;
     ai[1] = (a / E::NP1) % E::NP1;
     ai[2] = (DIM == 3) ? a / (E::NP1 * E::NP1) : 0;
@@ -4559,6 +4560,381 @@ namespace mi
     MI_WAVE_SYNC();
     mfq3s_integrate(prm, S, D, R, t, ti, cell);
   }
+  // ------------------------------------------------------------------ forward halves of the post-processing kernels
+  // mi_energy, mi_stress_field and mi_stress_error each run one cell kernel per element family -- 3D Q2 (one wave per cell,
+  // lane = point of the 4 x 4 x 4 rule), 3D Q3 (128 threads per cell, thread = point of the 5 x 5 x 5 rule) and the generic
+  // form (one workgroup per cell, thread = point, plain loops over the cell's nodes).  What the three features share within a
+  // family stands here once: the gather, the contractions to grad_xi u, the value-only contractions of further nodal fields
+  // with the S table alone, the point's kinematics, the cell sums.  The kernels below add their own point stage and epilogue.
+
+  // NF components of one node's entry of a nodal field x[node][STRIDE] into dst[c * NPC] (dst: the node's place in the cell)
+  template <int NF, int NPC, int STRIDE = NF>
+  __device__ __forceinline__ void post_gather(const double *__restrict__ x, const int32_t node, double *dst)
+  {
+#pragma unroll
+    for (int c = 0; c < NF; ++c)
+      dst[c * NPC] = x[int64_t(node) * STRIDE + c];
+  }
+
+  // the kinematics of point (qx, qy, qz) of a 3D tensor rule (1D weights tw[], points tx[]) from H = grad_xi u: geometry from
+  // mf_geometry, F = I + H Jinv, J = det F, J^(-2/3), 1/J from the record's own statements (MF_RECORD_TAIL), w = JxW
+  struct PostPoint
+  {
+    double F[9], J, Jm, rJ, w;
+  };
+  template <bool BOX>
+  __device__ __forceinline__ void post_point(const MfParams &prm, const int64_t cell, const double *tw, const double *tx, const int qx,
+                                             const int qy, const int qz, const double (&H)[3][3], PostPoint &pt)
+  {
+    const double wq = tw[qx] * tw[qy] * tw[qz];
+    double       Ji[9], detJ;
+    mf_geometry<BOX>(prm, cell, tx, qx, qy, qz, Ji, detJ);
+    MF_RECORD_TAIL(false, false, static_cast<double *>(nullptr), 1)
+#pragma unroll
+    for (int k = 0; k < 9; ++k)
+      pt.F[k] = F[k];
+    pt.J = J, pt.Jm = Jm, pt.rJ = rJ, pt.w = detJ * wq;
+  }
+
+  // the Cauchy stress tau(F)/J of neo_hooke_from_F, times w, in sym6 order; a point with det F <= 0 (nonlinear_elasticity.cc:935
+  // asserts det F > 0) raises *inverted, gets zeros and returns false
+  template <int DIM, class Params>
+  __device__ __forceinline__ bool stress_value(const double *F, const double J, const double Jm, const double rJ, const Params &p,
+                                               const double w, double s[6])
+  {
+    double Finv[9], tau[6], tiso[6], cII, cS;
+    neo_hooke_from_F<DIM>(F, J, Jm, rJ, p.mu, p.kappa, Finv, tau, tiso, cII, cS);
+    const bool ok = J > 0.0;
+    if (!ok)
+      *p.inverted = 1.0;
+#pragma unroll
+    for (int k = 0; k < 6; ++k)
+      s[k] = ok ? w * tau[k] * rJ : 0.0;
+    (void)Finv, (void)tiso, (void)cII, (void)cS;
+    return ok;
+  }
+  // the small-strain stress lambda tr(eps) I + 2 mu eps, eps = sym G, of the embedded displacement gradient G, times w
+  template <int DIM>
+  __device__ __forceinline__ void linear_stress(const double *G, const double lambda, const double mu, const double w, double s[6])
+  {
+    const double ltr = lambda * (G[0] + G[4] + G[8]), m2 = 2.0 * mu;
+    s[0] = w * (ltr + m2 * G[0]);
+    s[1] = w * (ltr + m2 * G[4]);
+    s[2] = (DIM == 3) ? w * (ltr + m2 * G[8]) : 0.0;
+    s[3] = w * mu * (G[1] + G[3]);
+    s[4] = w * mu * (G[2] + G[6]);
+    s[5] = w * mu * (G[5] + G[7]);
+  }
+
+  // ---- 3D Q2.  LDS of a cell: the gathered field X[c * 27 + a] and the planes B[(c * 3 + k) * PS + qy * 4 + qx] (PW apart)
+  constexpr int PQ2_NPC = 27, PQ2_PS = 20, PQ2_PW = 9 * PQ2_PS;
+  // value-only forward pass of NF nodal fields through S[q][a] = N_a(x_q) alone, in two halves around the cell's barrier:
+  // E12' item (f, k, qx) contracts i, then j (NF * 12 items; item & 3 == lane & 3: this lane's row Sx in every round) ...
+  template <int NF>
+  __device__ __forceinline__ void postq2_values_e12(const double (&S)[4][3], const double (&Sx)[3], const double *sXf, double *sBf,
+                                                    const int lane)
+  {
+#pragma unroll
+    for (int item = lane; item < NF * 12; item += 64)
+      {
+        const int fk = item >> 2;
+        double    as[3];
+#pragma unroll
+        for (int j = 0; j < 3; ++j)
+          as[j] = Sx[0] * sXf[fk * 9 + j * 3] + Sx[1] * sXf[fk * 9 + j * 3 + 1] + Sx[2] * sXf[fk * 9 + j * 3 + 2];
+#pragma unroll
+        for (int qy = 0; qy < 4; ++qy)
+          sBf[fk * PQ2_PS + qy * 4 + (lane & 3)] = S[qy][0] * as[0] + S[qy][1] * as[1] + S[qy][2] * as[2];
+      }
+  }
+  // ... E3' in the point's lane contracts k: r[f] = the field's value at the point (Sz: the lane's row of S, q16 = lane & 15)
+  // FMA_CHAIN: the sum as the chain fma(Sz[k], ., r) from zero (energy_q2's v, fused into E3 there before) or as the plain sum
+  // of three products (stress_error_q2's sigma*): the compiler contracts the plain sum to fma(Sz2 c, fma(Sz0 a, Sz1 b)), which
+  // rounds another product than the chain does, so each caller keeps the form its results were made with
+  template <int NF, bool FMA_CHAIN>
+  __device__ __forceinline__ void postq2_values_e3(const double (&Sz)[3], const double *sBf, const int q16, double (&r)[NF])
+  {
+#pragma unroll
+    for (int f = 0; f < NF; ++f)
+      {
+        const double b0 = sBf[(f * 3) * PQ2_PS + q16], b1 = sBf[(f * 3 + 1) * PQ2_PS + q16], b2 = sBf[(f * 3 + 2) * PQ2_PS + q16];
+        r[f] = FMA_CHAIN ? fma(Sz[2], b2, fma(Sz[1], b1, fma(Sz[0], b0, 0.0))) : Sz[0] * b0 + Sz[1] * b1 + Sz[2] * b2;
+      }
+  }
+  // The forward half: the gather of u (unmasked: the full state) and, NF > 0, of the nodal field xf[node][NF] into sXf; the
+  // rows of the 1D tables; E12 (lane = (c*3+k)*4 + qx contracts i, then j: B_DS / B_SD / B_SS of u) and E12' of xf; E3 (lane
+  // = point contracts k): H[c][l] = d u_c / d xi_l, V[c] = u_c.  Leaves the lane's node (lanes 0..26) and its row Sz for E3'
+  template <int NF>
+  __device__ __forceinline__ void postq2_forward(const MfParams &prm, const int64_t cell, const double *u, const double *xf, double *sX,
+                                                 double *sXf, double *sB, double *sBf, int32_t &node, double (&H)[3][3], double (&V)[3],
+                                                 double (&Sz)[3])
+  {
+    constexpr int NPC = PQ2_NPC, PS = PQ2_PS, PW = PQ2_PW;
+    const int     lane = threadIdx.x;
+    node               = 0;
+    if (lane < NPC)
+      {
+        node = prm.conn[cell * NPC + lane];
+        post_gather<3, NPC>(u, node, sX + lane);
+        if constexpr (NF > 0)
+          post_gather<NF, NPC>(xf, node, sXf + lane);
+      }
+    // 1D tables: S[q][a] = N_a(x_q), D[q][a] = N_a'(x_q) (uniform -> scalar registers)
+    double S[4][3], D[4][3];
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+#pragma unroll
+      for (int a = 0; a < 3; ++a)
+        {
+          S[q][a] = prm.tab1d[q * 3 + a];
+          D[q][a] = prm.tab1d[12 + q * 3 + a];
+        }
+    const int qz = lane >> 4, q16 = lane & 15;
+    double    Dz[3], Sx[3], Dx[3]; // this lane's rows of the tables: qz for E3, qx = lane & 3 for E12
+#pragma unroll
+    for (int k = 0; k < 3; ++k)
+      {
+        Sz[k] = prm.tab1d[qz * 3 + k];
+        Dz[k] = prm.tab1d[12 + qz * 3 + k];
+        Sx[k] = prm.tab1d[(lane & 3) * 3 + k];
+        Dx[k] = prm.tab1d[12 + (lane & 3) * 3 + k];
+      }
+    __syncthreads();
+    const int pck = lane >> 2, pqx = lane & 3;
+    if (lane < 36) // E12
+      {
+        double as[3], ad[3];
+#pragma unroll
+        for (int j = 0; j < 3; ++j)
+          {
+            const double x0 = sX[pck * 9 + j * 3], x1 = sX[pck * 9 + j * 3 + 1], x2 = sX[pck * 9 + j * 3 + 2];
+            as[j] = Sx[0] * x0 + Sx[1] * x1 + Sx[2] * x2;
+            ad[j] = Dx[0] * x0 + Dx[1] * x1 + Dx[2] * x2;
+          }
+#pragma unroll
+        for (int qy = 0; qy < 4; ++qy)
+          {
+            const int o    = pck * PS + qy * 4 + pqx;
+            sB[o]          = S[qy][0] * ad[0] + S[qy][1] * ad[1] + S[qy][2] * ad[2]; // d/dx
+            sB[o + PW]     = D[qy][0] * as[0] + D[qy][1] * as[1] + D[qy][2] * as[2]; // d/dy
+            sB[o + 2 * PW] = S[qy][0] * as[0] + S[qy][1] * as[1] + S[qy][2] * as[2]; // value / d/dz
+          }
+      }
+    if constexpr (NF > 0)
+      postq2_values_e12<NF>(S, Sx, sXf, sBf, lane);
+    __syncthreads();
+#pragma unroll
+    for (int c = 0; c < 3; ++c) // E3
+      {
+        H[c][0] = H[c][1] = H[c][2] = V[c] = 0.0;
+#pragma unroll
+        for (int k = 0; k < 3; ++k)
+          {
+            const int    o   = (c * 3 + k) * PS + q16;
+            const double bds = sB[o], bsd = sB[o + PW], bss = sB[o + 2 * PW];
+            H[c][0] = fma(Sz[k], bds, H[c][0]);
+            H[c][1] = fma(Sz[k], bsd, H[c][1]);
+            H[c][2] = fma(Dz[k], bss, H[c][2]);
+            V[c]    = fma(Sz[k], bss, V[c]);
+          }
+      }
+  }
+  // the point's kinematics behind it (1D weights at 24, points at 28 of the assembly's Q2 tables)
+  template <bool BOX>
+  __device__ __forceinline__ void postq2_point(const MfParams &prm, const int64_t cell, const double (&H)[3][3], PostPoint &pt)
+  {
+    const int lane = threadIdx.x;
+    post_point<BOX>(prm, cell, prm.tab1d + 24, prm.tab1d + 28, lane & 3, (lane >> 2) & 3, lane >> 4, H, pt);
+  }
+
+  // ---- 3D Q3 (the shape of mf_point_pass_q3 up to the point stage: X in R1, mfq3_gradients, then ...)
+  // ... the point's kinematics at point `it`
+  template <bool BOX>
+  __device__ __forceinline__ void postq3_point(const MfParams &prm, const int64_t cell, const int qz, const int q25, const double (&H)[3][3],
+                                               PostPoint &pt)
+  {
+    const int qy = q25 / 5, qx = q25 - 5 * qy;
+    post_point<BOX>(prm, cell, prm.tab1d + MFQ3_TW, prm.tab1d + MFQ3_TX, qx, qy, qz, H, pt);
+  }
+  // value-only forward pass of NF nodal fields X[f * 64 + a] with the S table alone, the passes E1'-E3' of mf_point_pass_q3:
+  //   E1' item (f, k, j) = tv:          x-line -> A [f,k,j][qx]            NF * 16 items, NF * 80 doubles
+  //   E2' item (f, k, qx) = tv:         contract j -> B [f,k][qy][qx]      NF * 20 items, NF * 100 doubles
+  //   E3' item = point `it`:            contract k -> r[f]
+  // X, A, B are the caller's LDS places (A may not lie over X, B not over A); a thread with tv < 0 has no item in E1', E2'.
+  // A barrier behind E1' and behind E2', none behind E3'.  S_SCALAR: the S table through scalar registers (tab, as
+  // mf_point_pass_q3 has it) or from its staged copy sT in LDS -- the general-geometry instance of stress_error_q3, which holds
+  // the cell's vertices in scalar registers too, spills 8 of them with S beside
+  template <int NF, bool S_SCALAR>
+  __device__ __forceinline__ void postq3_values(const double *__restrict__ tab, const double *sT, const double *X, double *A, double *B,
+                                                const int tv, const int qz, const int q25, double (&r)[NF])
+  {
+    double S[5][4]; // (S_SCALAR: uniform, scalar registers)
+#pragma unroll
+    for (int q = 0; q < 5; ++q)
+#pragma unroll
+      for (int a = 0; a < 4; ++a)
+        S[q][a] = S_SCALAR ? tab[q * 4 + a] : sT[q * 4 + a];
+    if (tv >= 0 && tv < NF * 16)
+      {
+        const double x0 = X[tv * 4], x1 = X[tv * 4 + 1], x2 = X[tv * 4 + 2], x3 = X[tv * 4 + 3];
+#pragma unroll
+        for (int qx = 0; qx < 5; ++qx)
+          A[tv * 5 + qx] = S[qx][0] * x0 + S[qx][1] * x1 + S[qx][2] * x2 + S[qx][3] * x3;
+      }
+    __syncthreads();
+    if (tv >= 0 && tv < NF * 20)
+      {
+        const int fk = tv / 5, qx = tv - 5 * fk;
+        double    as[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          as[j] = A[(fk * 4 + j) * 5 + qx];
+#pragma unroll
+        for (int qy = 0; qy < 5; ++qy)
+          B[fk * 25 + qy * 5 + qx] = S[qy][0] * as[0] + S[qy][1] * as[1] + S[qy][2] * as[2] + S[qy][3] * as[3];
+      }
+    __syncthreads();
+#pragma unroll
+    for (int f = 0; f < NF; ++f)
+      {
+        r[f] = 0.0;
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+          r[f] = fma(sT[qz * 4 + k], B[(f * 4 + k) * 25 + q25], r[f]);
+      }
+  }
+  // the cell's N sums of the points' numbers e[] into o[3] (the rest zero), in a fixed order: each wave's reduction network
+  // (threads 125-127 contribute exact zeros), then the first wave's sum plus the second's through sW
+  template <int N>
+  __device__ __forceinline__ void postq3_cell_sum(double (&e)[N], const int t, double *sW, double *__restrict__ o)
+  {
+#pragma unroll
+    for (int k = 0; k < N; ++k)
+      e[k] = wave_sum_lane63(t < MFQ3_NQ ? e[k] : 0.0);
+    if (t == MFQ3_NT - 1) // lane 63 of the second wave
+      {
+#pragma unroll
+        for (int k = 0; k < N; ++k)
+          sW[k] = e[k];
+      }
+    __syncthreads();
+    if (t == 63)
+      {
+#pragma unroll
+        for (int k = 0; k < N; ++k)
+          o[k] = e[k] + sW[k];
+#pragma unroll
+        for (int k = N; k < 3; ++k)
+          o[k] = 0.0;
+      }
+  }
+
+  // ---- generic form: a rule of NQ1 points per direction on an element of degree P.  LDS of a cell's forward half
+  template <int DIM, int P, int NQ1>
+  struct PostCell
+  {
+    static constexpr int NP1 = P + 1, NPC = Elem<DIM, P>::NPC, NV = 1 << DIM, NQ = DIM == 2 ? NQ1 * NQ1 : NQ1 * NQ1 * NQ1;
+    double *N1, *dN1, *qw, *qx, *u, *verts;
+  };
+#define POST_CELL_LDS(sc_, DIM_, P_, NQ1_)                                                                                      \
+  using C = PostCell<DIM_, P_, NQ1_>;                                                                                           \
+  __shared__ double sc_N1[NQ1_ * C::NP1], sc_dN1[NQ1_ * C::NP1], sc_qw[NQ1_], sc_qx[NQ1_], sc_u[C::NPC * DIM_], sc_verts[C::NV * DIM_]; \
+  const C sc_ = {sc_N1, sc_dN1, sc_qw, sc_qx, sc_u, sc_verts};
+  // the cell's entries of a nodal field x[node][NC] into s_x[a * NC + c]
+  template <int NPC, int NC, int NT>
+  __device__ __forceinline__ void post_cell_field(const int32_t *__restrict__ conn, const int64_t cell, const double *__restrict__ x,
+                                                  double *s_x)
+  {
+    for (int i = threadIdx.x; i < NPC * NC; i += NT)
+      {
+        const int a = i / NC, c = i - a * NC;
+        s_x[i]      = x[int64_t(conn[cell * NPC + a]) * NC + c];
+      }
+  }
+  // tables, vertices and u of the cell (the caller stages its further fields and sets the barrier)
+  template <int DIM, int P, int NQ1, int NT, class Params>
+  __device__ __forceinline__ void post_cell_stage(const Params &p, const int64_t cell, const PostCell<DIM, P, NQ1> &sc)
+  {
+    using C       = PostCell<DIM, P, NQ1>;
+    const int tid = threadIdx.x;
+    for (int i = tid; i < NQ1 * C::NP1; i += NT)
+      {
+        sc.N1[i]  = p.tab[i];
+        sc.dN1[i] = p.tab[NQ1 * C::NP1 + i];
+      }
+    if (tid < NQ1)
+      {
+        sc.qw[tid] = p.tab[2 * NQ1 * C::NP1 + tid];
+        sc.qx[tid] = p.tab[2 * NQ1 * C::NP1 + NQ1 + tid];
+      }
+    if (tid < C::NV * DIM)
+      sc.verts[tid] = p.cverts[cell * (C::NV * DIM) + tid];
+    post_cell_field<C::NPC, DIM, NT>(p.conn, cell, p.u, sc.u);
+  }
+  // point q: G = grad_xi u Jinv embedded in 3 x 3 (the displacement gradient), w = JxW, and the values v0[N0], v1[N1] of two
+  // further staged fields s_f0[a * N0 + k], s_f1[a * N1 + k] (N = 0: none) -- plain loops over the cell's nodes as in phase A
+  // of assemble_cells
+  template <int DIM, int P, int NQ1, int N0, int N1>
+  __device__ __forceinline__ void post_cell_point(const PostCell<DIM, P, NQ1> &sc, const int q, const double *s_f0, const double *s_f1,
+                                                  double *v0, double *v1, double G[9], double &w)
+  {
+    double gxi[9];
+#pragma unroll
+    for (int k = 0; k < 9; ++k)
+      gxi[k] = 0.0;
+#pragma unroll
+    for (int k = 0; k < N0; ++k)
+      v0[k] = 0.0;
+#pragma unroll
+    for (int k = 0; k < N1; ++k)
+      v1[k] = 0.0;
+    for (int a = 0; a < PostCell<DIM, P, NQ1>::NPC; ++a)
+      {
+        double N, dN[3];
+        shape_at_qp<DIM, P, NQ1>(sc.N1, sc.dN1, q, a, N, dN);
+#pragma unroll
+        for (int i = 0; i < DIM; ++i)
+#pragma unroll
+          for (int j = 0; j < DIM; ++j)
+            gxi[i * 3 + j] = fma(sc.u[a * DIM + i], dN[j], gxi[i * 3 + j]);
+#pragma unroll
+        for (int k = 0; k < N0; ++k)
+          v0[k] = fma(s_f0[a * N0 + k], N, v0[k]);
+#pragma unroll
+        for (int k = 0; k < N1; ++k)
+          v1[k] = fma(s_f1[a * N1 + k], N, v1[k]);
+      }
+    double    xi[3] = {0.0, 0.0, 0.0}, wq = 1.0;
+    const int qi[3] = {q % NQ1, (q / NQ1) % NQ1, (DIM == 3) ? q / (NQ1 * NQ1) : 0};
+#pragma unroll
+    for (int d = 0; d < DIM; ++d)
+      {
+        xi[d] = sc.qx[qi[d]];
+        wq *= sc.qw[qi[d]];
+      }
+    double Jg[9], Ji[9];
+    q1_jacobian<DIM>(sc.verts, xi, Jg);
+    const double detJ = det3x3(Jg);
+    inv3x3(Jg, detJ, Ji);
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+      for (int j = 0; j < 3; ++j)
+        G[i * 3 + j] = (i < DIM && j < DIM) ? gxi[i * 3 + 0] * Ji[0 * 3 + j] + gxi[i * 3 + 1] * Ji[1 * 3 + j] +
+                                                (DIM == 3 ? gxi[i * 3 + 2] * Ji[2 * 3 + j] : 0.0) :
+                                              0.0;
+    w = detJ * wq;
+  }
+  // F = I + G in place, J = det F, J^(-2/d), 1/J
+  template <int DIM>
+  __device__ __forceinline__ void post_cell_finite_strain(double F[9], double &J, double &Jm, double &rJ)
+  {
+    F[0] += 1.0, F[4] += 1.0, F[8] += 1.0;
+    J  = det3x3(F);
+    rJ = 1.0 / J;
+    Jm = (DIM == 3) ? 1.0 / (cbrt(J) * cbrt(J)) : rJ;
+  }
+
   // ------------------------------------------------------------------ energy diagnostics (mi_energy)
   // Three numbers per cell, [cell][3] of EnergyParams::cell_e, from the committed state u and the velocity v:
   //   strain   sum_q Psi(F(u)) JxW,  Psi = kappa/4 (J^2 - 1 - 2 ln J) + mu/2 (J^(-2/d) tr(F F^T) - d)
@@ -4570,11 +4946,14 @@ namespace mi
   // has no value there).  The sums are in a fixed order -- the wave's reduction network, then the waves in ascending order
   // through LDS -- so a call repeats bit by bit; energy_sum adds the cells in a fixed order too.  Three forms, chosen by
   // launch_energy as the assembly chooses its kernel: energy_q3 (3D Q3, the shape of mf_point_pass_q3 up to the point stage),
-  // energy_q2 (3D Q2, the forward half of mf_spmv), energy_cells (every other element; plain loops over the cell's nodes).
+  // energy_q2 (3D Q2, the forward half of mf_spmv), energy_cells (every other element; plain loops over the cell's nodes):
+  // each its family's forward half above, with v as the value-only field, and energy_point.
   template <int DIM>
   __device__ __forceinline__ void energy_point(const double *F, const double J, const double Jm, const double *uq, const double *vq,
                                                const double w, const EnergyParams &ep, double e[3])
   {
+    if (!(J > 0.0)) // inverted element (nonlinear_elasticity.cc:935 asserts det F > 0)
+      *ep.inverted = 1.0;
     double ff = 0.0; // tr(F F^T) over the DIM x DIM part
 #pragma unroll
     for (int i = 0; i < DIM; ++i)
@@ -4593,209 +4972,81 @@ namespace mi
     e[1] = 0.5 * ep.rho * w * vv;
     e[2] = -(ep.rho * w * bu);
   }
+  // a cell of a slab's ghost layer is counted by the slab that owns it: here it stores zeros, and the workgroup leaves
+  template <int NPC>
+  __device__ __forceinline__ bool energy_ghost_cell(const int32_t *__restrict__ conn, const int64_t cell, const EnergyParams &ep)
+  {
+    if (conn[cell * NPC] < ep.own_node_end)
+      return false;
+    if (threadIdx.x < 3)
+      ep.cell_e[cell * 3 + threadIdx.x] = 0.0;
+    return true;
+  }
 
   // 3D Q3: 128 threads per cell, thread = point of the 5 x 5 x 5 rule (threads 125-127 contribute exact zeros).  The first wave
-  // gathers u, the second v; v's values come through the value-only passes E1'-E3' of mf_point_pass_q3 (same LDS places), u's
-  // gradients and values from mfq3_gradients; geometry from mf_geometry, F, J, J^(-2/3) from the record's own statements.
+  // gathers u, the second v; v's values come through postq3_values in the LDS places of mf_point_pass_q3's value pass, u's
+  // gradients and values from mfq3_gradients, the kinematics from postq3_point.
   // Launch bounds: the general instance holds the trilinear map's 24 vertices beside H and the record's statements; built for
   // 4 waves per SIMD it spilled 8 registers to scratch, at 3 it needs none (boxes: 110 registers, 4 waves).
   template <bool BOX>
   __global__ __launch_bounds__(MFQ3_NT, BOX ? 4 : 3) void energy_q3(MfParams prm, EnergyParams ep)
   {
     __shared__ double R0[MFQ3_R0], R1[MFQ3_R1], sT[40], sW[3];
-    const int     t    = threadIdx.x, it = t < MFQ3_NQ ? t : MFQ3_NQ - 1;
+    const int     t    = threadIdx.x, it = t < MFQ3_NQ ? t : MFQ3_NQ - 1, qz = it / 25, q25 = it - 25 * qz;
     const int     tv   = t - MFQ3_NPC; // the second wave's item in the value pass
     const int64_t cell = blockIdx.x;
-    if (prm.conn[cell * MFQ3_NPC] >= ep.own_node_end) // ghost layer of a slab: counted by the slab that owns it
-      {
-        if (t < 3)
-          ep.cell_e[cell * 3 + t] = 0.0;
-        return;
-      }
+    if (energy_ghost_cell<MFQ3_NPC>(prm.conn, cell, ep))
+      return;
     if (t < 40)
       sT[t] = prm.tab1d[t];
     {
       const int     a    = t & (MFQ3_NPC - 1);
       const int32_t node = prm.conn[cell * MFQ3_NPC + a];
       if (t < MFQ3_NPC)
-        {
-#pragma unroll
-          for (int c = 0; c < 3; ++c)
-            R1[c * MFQ3_NPC + a] = ep.u[int64_t(node) * 3 + c];
-        }
+        post_gather<3, MFQ3_NPC>(ep.u, node, R1 + a);
       else
-        {
-#pragma unroll
-          for (int c = 0; c < 3; ++c)
-            R0[MFQ3_VX + c * MFQ3_NPC + a] = ep.v[int64_t(node) * 3 + c];
-        }
+        post_gather<3, MFQ3_NPC>(ep.v, node, R0 + MFQ3_VX + a);
     }
     __syncthreads();
     {
-      double S[5][4]; // uniform: scalar registers
-#pragma unroll
-      for (int q = 0; q < 5; ++q)
-#pragma unroll
-        for (int a = 0; a < 4; ++a)
-          S[q][a] = prm.tab1d[q * 4 + a];
-      if (tv >= 0 && tv < 48) // E1': line (c,k,j) = tv
-        {
-          const double x0 = R0[MFQ3_VX + tv * 4], x1 = R0[MFQ3_VX + tv * 4 + 1], x2 = R0[MFQ3_VX + tv * 4 + 2], x3 = R0[MFQ3_VX + tv * 4 + 3];
-#pragma unroll
-          for (int qx = 0; qx < 5; ++qx)
-            R0[MFQ3_VA + tv * 5 + qx] = S[qx][0] * x0 + S[qx][1] * x1 + S[qx][2] * x2 + S[qx][3] * x3;
-        }
-      __syncthreads();
-      if (tv >= 0 && tv < 60) // E2': item (c,k,qx): tv = ck * 5 + qx
-        {
-          const int ck = tv / 5, qx = tv - 5 * ck;
-          double    as[4];
-#pragma unroll
-          for (int j = 0; j < 4; ++j)
-            as[j] = R0[MFQ3_VA + (ck * 4 + j) * 5 + qx];
-#pragma unroll
-          for (int qy = 0; qy < 5; ++qy)
-            R0[MFQ3_VB + ck * 25 + qy * 5 + qx] = S[qy][0] * as[0] + S[qy][1] * as[1] + S[qy][2] * as[2] + S[qy][3] * as[3];
-        }
-      __syncthreads();
-      const int qz = it / 25, q25 = it - 25 * qz; // E3': item = point
+      double vm[3];
+      postq3_values<3, true>(prm.tab1d, sT, R0 + MFQ3_VX, R0 + MFQ3_VA, R0 + MFQ3_VB, tv, qz, q25, vm);
 #pragma unroll
       for (int c = 0; c < 3; ++c)
-        {
-          double vm = 0.0;
-#pragma unroll
-          for (int k = 0; k < 4; ++k)
-            vm = fma(sT[qz * 4 + k], R0[MFQ3_VB + (c * 4 + k) * 25 + q25], vm);
-          R0[MFQ3_VM + c * MFQ3_QS + t] = vm; // (over X' and A', both consumed; read back by this thread alone)
-        }
+        R0[MFQ3_VM + c * MFQ3_QS + t] = vm[c]; // (over X' and A', both consumed; read back by this thread alone)
     }
     double H[3][3], V[3];
     mfq3_gradients(prm.tab1d, sT, R0, R1, t, it, H, V); // (writes R0 below MFQ3_VX only; its barriers stand behind E3')
     double e[3];
     {
-      const int    qz = it / 25, qy = (it - 25 * qz) / 5, qx = it - 25 * qz - 5 * qy;
-      const double wq = prm.tab1d[MFQ3_TW + qx] * prm.tab1d[MFQ3_TW + qy] * prm.tab1d[MFQ3_TW + qz];
-      double       Ji[9], detJ;
-      mf_geometry<BOX>(prm, cell, prm.tab1d + MFQ3_TX, qx, qy, qz, Ji, detJ);
-      MF_RECORD_TAIL(false, false, static_cast<double *>(nullptr), MFQ3_QS)
-      if (!(J > 0.0)) // inverted element (nonlinear_elasticity.cc:935 asserts det F > 0)
-        *ep.inverted = 1.0;
+      PostPoint pt;
+      postq3_point<BOX>(prm, cell, qz, q25, H, pt);
       const double vq[3] = {R0[MFQ3_VM + t], R0[MFQ3_VM + MFQ3_QS + t], R0[MFQ3_VM + 2 * MFQ3_QS + t]};
-      energy_point<3>(F, J, Jm, V, vq, detJ * wq, ep, e);
-      (void)rJ;
+      energy_point<3>(pt.F, pt.J, pt.Jm, V, vq, pt.w, ep, e);
     }
-#pragma unroll
-    for (int k = 0; k < 3; ++k)
-      e[k] = wave_sum_lane63(t < MFQ3_NQ ? e[k] : 0.0);
-    if (t == MFQ3_NT - 1) // lane 63 of the second wave
-      sW[0] = e[0], sW[1] = e[1], sW[2] = e[2];
-    __syncthreads();
-    if (t == 63)
-      {
-        double *__restrict__ o = ep.cell_e + cell * 3;
-        o[0] = e[0] + sW[0], o[1] = e[1] + sW[1], o[2] = e[2] + sW[2];
-      }
+    postq3_cell_sum(e, t, sW, ep.cell_e + cell * 3);
   }
 
-  // 3D Q2: one wave per cell, lane = point of the 4 x 4 x 4 rule -- the gather and the contractions E12, E3 of mf_spmv on u
-  // (unmasked: the energy belongs to the full state), the value-only half of them on v
+  // 3D Q2: postq2_forward on u with v as its value-only field (in mf_spmv's terms: the gather and E12, E3 of the product on
+  // the unmasked state, the value-only half of them on v)
   template <bool BOX>
   __global__ __launch_bounds__(64, 4) void energy_q2(MfParams prm, EnergyParams ep)
   {
-    constexpr int NPC = 27, PS = 20, PW = 9 * PS;
+    constexpr int NPC = PQ2_NPC, PW = PQ2_PW;
     __shared__ double sX[3 * NPC], sXv[3 * NPC], sB[3 * PW], sBv[PW];
     const int     lane = threadIdx.x;
     const int64_t cell = blockIdx.x;
-    if (prm.conn[cell * NPC] >= ep.own_node_end) // ghost layer of a slab
-      {
-        if (lane < 3)
-          ep.cell_e[cell * 3 + lane] = 0.0;
-        return;
-      }
-    if (lane < NPC)
-      {
-        const int32_t node = prm.conn[cell * NPC + lane];
-#pragma unroll
-        for (int c = 0; c < 3; ++c)
-          {
-            sX[c * NPC + lane]  = ep.u[int64_t(node) * 3 + c];
-            sXv[c * NPC + lane] = ep.v[int64_t(node) * 3 + c];
-          }
-      }
-    // 1D tables: S[q][a] = N_a(x_q), D[q][a] = N_a'(x_q) (uniform -> scalar registers)
-    double S[4][3], D[4][3];
-#pragma unroll
-    for (int q = 0; q < 4; ++q)
-#pragma unroll
-      for (int a = 0; a < 3; ++a)
-        {
-          S[q][a] = prm.tab1d[q * 3 + a];
-          D[q][a] = prm.tab1d[12 + q * 3 + a];
-        }
-    const int qz = lane >> 4, q16 = lane & 15;
-    double    Sz[3], Dz[3], Sx[3], Dx[3]; // this lane's rows of the tables: qz for E3, qx = lane & 3 for E12
-#pragma unroll
-    for (int k = 0; k < 3; ++k)
-      {
-        Sz[k] = prm.tab1d[qz * 3 + k];
-        Dz[k] = prm.tab1d[12 + qz * 3 + k];
-        Sx[k] = prm.tab1d[(lane & 3) * 3 + k];
-        Dx[k] = prm.tab1d[12 + (lane & 3) * 3 + k];
-      }
-    const double wq = prm.tab1d[24 + (lane & 3)] * prm.tab1d[24 + ((lane >> 2) & 3)] * prm.tab1d[24 + qz];
-    __syncthreads();
-    // ---- E12: lane = (c*3+k)*4 + qx contracts i, then j: B_DS / B_SD / B_SS [c*3+k][qy][qx] of u, B_SS of v
-    const int pck = lane >> 2, pqx = lane & 3;
-    if (lane < 36)
-      {
-        double as[3], ad[3], av[3];
-#pragma unroll
-        for (int j = 0; j < 3; ++j)
-          {
-            const double x0 = sX[pck * 9 + j * 3], x1 = sX[pck * 9 + j * 3 + 1], x2 = sX[pck * 9 + j * 3 + 2];
-            const double v0 = sXv[pck * 9 + j * 3], v1 = sXv[pck * 9 + j * 3 + 1], v2 = sXv[pck * 9 + j * 3 + 2];
-            as[j] = Sx[0] * x0 + Sx[1] * x1 + Sx[2] * x2;
-            ad[j] = Dx[0] * x0 + Dx[1] * x1 + Dx[2] * x2;
-            av[j] = Sx[0] * v0 + Sx[1] * v1 + Sx[2] * v2;
-          }
-#pragma unroll
-        for (int qy = 0; qy < 4; ++qy)
-          {
-            const int o    = pck * PS + qy * 4 + pqx;
-            sB[o]          = S[qy][0] * ad[0] + S[qy][1] * ad[1] + S[qy][2] * ad[2]; // d/dx
-            sB[o + PW]     = D[qy][0] * as[0] + D[qy][1] * as[1] + D[qy][2] * as[2]; // d/dy
-            sB[o + 2 * PW] = S[qy][0] * as[0] + S[qy][1] * as[1] + S[qy][2] * as[2]; // value / d/dz
-            sBv[o]         = S[qy][0] * av[0] + S[qy][1] * av[1] + S[qy][2] * av[2];
-          }
-      }
-    __syncthreads();
-    // ---- E3: contract k.  lane = quadrature point; H[c][l] = d u_c / d xi_l, V[c] = u_c, Vv[c] = v_c
-    double H[3][3], V[3], Vv[3];
-#pragma unroll
-    for (int c = 0; c < 3; ++c)
-      {
-        H[c][0] = H[c][1] = H[c][2] = V[c] = Vv[c] = 0.0;
-#pragma unroll
-        for (int k = 0; k < 3; ++k)
-          {
-            const int    o   = (c * 3 + k) * PS + q16;
-            const double bds = sB[o], bsd = sB[o + PW], bss = sB[o + 2 * PW];
-            H[c][0] = fma(Sz[k], bds, H[c][0]);
-            H[c][1] = fma(Sz[k], bsd, H[c][1]);
-            H[c][2] = fma(Dz[k], bss, H[c][2]);
-            V[c]    = fma(Sz[k], bss, V[c]);
-            Vv[c]   = fma(Sz[k], sBv[o], Vv[c]);
-          }
-      }
+    if (energy_ghost_cell<NPC>(prm.conn, cell, ep))
+      return;
+    int32_t node;
+    double  H[3][3], V[3], Sz[3], Vv[3];
+    postq2_forward<3>(prm, cell, ep.u, ep.v, sX, sXv, sB, sBv, node, H, V, Sz);
     double e[3];
     {
-      double Ji[9], detJ;
-      mf_geometry<BOX>(prm, cell, prm.tab1d + 28, lane & 3, (lane >> 2) & 3, qz, Ji, detJ);
-      MF_RECORD_TAIL(false, false, static_cast<double *>(nullptr), 64)
-      if (!(J > 0.0)) // inverted element (nonlinear_elasticity.cc:935 asserts det F > 0)
-        *ep.inverted = 1.0;
-      energy_point<3>(F, J, Jm, V, Vv, detJ * wq, ep, e);
-      (void)rJ;
+      PostPoint pt;
+      postq2_point<BOX>(prm, cell, H, pt);
+      postq2_values_e3<3, true>(Sz, sBv, lane & 15, Vv);
+      energy_point<3>(pt.F, pt.J, pt.Jm, V, Vv, pt.w, ep, e);
     }
 #pragma unroll
     for (int k = 0; k < 3; ++k)
@@ -4808,92 +5059,28 @@ namespace mi
   }
 
   // every other element (2D p = 1..4, 3D p = 1, 4 -- the reference's small geometries) and the cross-check of the two forms
-  // above: one workgroup per cell, thread = quadrature point, plain loops over the cell's nodes as in phase A of assemble_cells
+  // above: one workgroup per cell, thread = quadrature point; post_cell_point with u and v as its value fields
   template <int DIM, int P, int NT>
   __global__ __launch_bounds__(NT) void energy_cells(EnergyParams ep)
   {
-    using E = Elem<DIM, P>;
-    constexpr int NPC = E::NPC, NQ = E::NQ, NQ1 = E::NQ1, NP1 = E::NP1, NV = E::NV;
-    static_assert(NQ <= NT && NT % 64 == 0, "one thread per quadrature point, whole waves");
-    __shared__ double s_N1[NQ1 * NP1], s_dN1[NQ1 * NP1], s_qw[NQ1], s_qx[NQ1];
-    __shared__ double s_u[NPC * DIM], s_v[NPC * DIM], s_verts[NV * DIM], s_red[NT / 64];
+    constexpr int NQ1 = Elem<DIM, P>::NQ1; // the assembly's rule
+    POST_CELL_LDS(sc, DIM, P, NQ1)
+    static_assert(C::NQ <= NT && NT % 64 == 0, "one thread per quadrature point, whole waves");
+    __shared__ double s_v[C::NPC * DIM], s_red[NT / 64];
     const int     tid  = threadIdx.x;
     const int64_t cell = blockIdx.x;
-    if (ep.conn[cell * NPC] >= ep.own_node_end) // ghost layer of a slab
-      {
-        if (tid < 3)
-          ep.cell_e[cell * 3 + tid] = 0.0;
-        return;
-      }
-    for (int i = tid; i < NQ1 * NP1; i += NT)
-      {
-        s_N1[i]  = ep.tab1d[i];
-        s_dN1[i] = ep.tab1d[NQ1 * NP1 + i];
-      }
-    if (tid < NQ1)
-      {
-        s_qw[tid] = ep.tab1d[2 * NQ1 * NP1 + tid];
-        s_qx[tid] = ep.tab1d[2 * NQ1 * NP1 + NQ1 + tid];
-      }
-    if (tid < NV * DIM)
-      s_verts[tid] = ep.cverts[cell * (NV * DIM) + tid];
-    for (int i = tid; i < NPC * DIM; i += NT)
-      {
-        const int     a = i / DIM, c = i - a * DIM;
-        const int64_t g = int64_t(ep.conn[cell * NPC + a]) * DIM + c;
-        s_u[i]          = ep.u[g];
-        s_v[i]          = ep.v[g];
-      }
+    if (energy_ghost_cell<C::NPC>(ep.conn, cell, ep))
+      return;
+    post_cell_stage<DIM, P, NQ1, NT>(ep, cell, sc);
+    post_cell_field<C::NPC, DIM, NT>(ep.conn, cell, ep.v, s_v);
     __syncthreads();
     double e[3] = {0.0, 0.0, 0.0};
-    if (tid < NQ)
+    if (tid < C::NQ)
       {
-        const int q = tid;
-        double    gxi[9], uq[3] = {0.0, 0.0, 0.0}, vq[3] = {0.0, 0.0, 0.0};
-#pragma unroll
-        for (int k = 0; k < 9; ++k)
-          gxi[k] = 0.0;
-        for (int a = 0; a < NPC; ++a)
-          {
-            double N, dN[3];
-            shape_at_qp<DIM, P>(s_N1, s_dN1, q, a, N, dN);
-#pragma unroll
-            for (int i = 0; i < DIM; ++i)
-              {
-                const double ui = s_u[a * DIM + i];
-#pragma unroll
-                for (int j = 0; j < DIM; ++j)
-                  gxi[i * 3 + j] = fma(ui, dN[j], gxi[i * 3 + j]);
-                uq[i] = fma(ui, N, uq[i]);
-                vq[i] = fma(s_v[a * DIM + i], N, vq[i]);
-              }
-          }
-        double    xi[3] = {0.0, 0.0, 0.0}, wq = 1.0;
-        const int qi[3] = {q % NQ1, (q / NQ1) % NQ1, (DIM == 3) ? q / (NQ1 * NQ1) : 0};
-#pragma unroll
-        for (int d = 0; d < DIM; ++d)
-          {
-            xi[d] = s_qx[qi[d]];
-            wq *= s_qw[qi[d]];
-          }
-        double Jm[9], Ji[9];
-        q1_jacobian<DIM>(s_verts, xi, Jm);
-        const double detJ = det3x3(Jm);
-        inv3x3(Jm, detJ, Ji);
-        double F[9]; // I + grad_xi u Jinv, embedded in 3 x 3
-#pragma unroll
-        for (int i = 0; i < 3; ++i)
-#pragma unroll
-          for (int j = 0; j < 3; ++j)
-            F[i * 3 + j] = (i < DIM && j < DIM) ? gxi[i * 3 + 0] * Ji[0 * 3 + j] + gxi[i * 3 + 1] * Ji[1 * 3 + j] +
-                                                    (DIM == 3 ? gxi[i * 3 + 2] * Ji[2 * 3 + j] : 0.0) :
-                                                  0.0;
-        F[0] += 1.0, F[4] += 1.0, F[8] += 1.0;
-        const double J = det3x3(F);
-        if (!(J > 0.0)) // inverted element (nonlinear_elasticity.cc:935 asserts det F > 0)
-          *ep.inverted = 1.0;
-        const double Jd = (DIM == 3) ? 1.0 / (cbrt(J) * cbrt(J)) : 1.0 / J; // J^(-2/d)
-        energy_point<DIM>(F, J, Jd, uq, vq, detJ * wq, ep, e);
+        double uq[3] = {0.0, 0.0, 0.0}, vq[3] = {0.0, 0.0, 0.0}, F[9], w, J, Jd, rJ;
+        post_cell_point<DIM, P, NQ1, DIM, DIM>(sc, tid, sc.u, s_v, uq, vq, F, w);
+        post_cell_finite_strain<DIM>(F, J, Jd, rJ);
+        energy_point<DIM>(F, J, Jd, uq, vq, w, ep, e);
       }
 #pragma unroll
     for (int k = 0; k < 3; ++k)
@@ -4940,108 +5127,30 @@ namespace mi
   // acc[nnodes][8] (sym6, W, one spare) with plain loads and stores; the colours run in order on one stream, so the order of
   // the sums depends on the mesh alone and a call repeats bit by bit.  No slot table, no atomics.  stress_finish divides by W.
   // A point with det F <= 0 (model 0) raises *inverted and contributes zeros.
-  // Forms, chosen by launch_stress: stress_q2 (3D Q2, model 0: the forward half of energy_q2 and the transposes of E3, E12 with
-  // the S table alone), stress_q3 (3D Q3, model 0: the shape of energy_q3) and stress_cells (every other element, all of
-  // model 1, and the cross-check of the two).
-  template <int DIM>
-  __device__ __forceinline__ void stress_point(const double *F, const double J, const double Jm, const double rJ, const double w,
-                                               const StressParams &sp, double g[7])
-  {
-    double Finv[9], tau[6], tiso[6], cII, cS;
-    neo_hooke_from_F<DIM>(F, J, Jm, rJ, sp.mu, sp.kappa, Finv, tau, tiso, cII, cS);
-    const bool ok = J > 0.0; // inverted element (nonlinear_elasticity.cc:935 asserts det F > 0)
-    if (!ok)
-      *sp.inverted = 1.0;
-#pragma unroll
-    for (int k = 0; k < 6; ++k)
-      g[k] = ok ? w * tau[k] * rJ : 0.0;
-    g[6] = w;
-    (void)Finv, (void)tiso, (void)cII, (void)cS;
-  }
+  // Forms, chosen by launch_stress: stress_q2 (3D Q2, model 0: postq2_forward and the transposes of E3, E12 with the S table
+  // alone), stress_q3 (3D Q3, model 0: the forward half of energy_q3 on u alone) and stress_cells (every other element, all of
+  // model 1, and the cross-check of the two).  The point's seven numbers: stress_value / linear_stress times w, and w.
 
-  // 3D Q2, model 0: one wave per cell, lane = point of the 4 x 4 x 4 rule.  Forward: the gather and E12, E3 of energy_q2 on u
-  // alone.  Backward, through LDS: B3 contracts qz (item = (k, qy, qx), 48 per field), B12 contracts qy and qx (lane = node
+  // 3D Q2, model 0: one wave per cell, lane = point of the 4 x 4 x 4 rule.  Forward: postq2_forward on u alone.  Backward,
+  // through LDS: B3 contracts qz (item = (k, qy, qx), 48 per field), B12 contracts qy and qx (lane = node
   // (i, j, k), 27 lanes), both with S[q][a] = N_a(x_q).  sG lies over sB (E3 has consumed it, a barrier between).
   template <bool BOX>
   __global__ __launch_bounds__(64, 4) void stress_q2(MfParams prm, StressParams sp)
   {
-    constexpr int NPC = 27, PS = 20, PW = 9 * PS;
+    constexpr int NPC = PQ2_NPC, PW = PQ2_PW;
     __shared__ double sX[3 * NPC], sB[3 * PW], sC[7 * 48];
     double *const sG   = sB; // [7][64]
-    const int     lane = threadIdx.x;
+    const int     lane = threadIdx.x, q16 = lane & 15;
     const int64_t cell = sp.cell_begin + blockIdx.x;
-    int32_t       node = 0;
-    if (lane < NPC)
-      {
-        node = prm.conn[cell * NPC + lane];
-#pragma unroll
-        for (int c = 0; c < 3; ++c)
-          sX[c * NPC + lane] = sp.u[int64_t(node) * 3 + c];
-      }
-    double S[4][3], D[4][3]; // S[q][a] = N_a(x_q), D[q][a] = N_a'(x_q) (uniform -> scalar registers)
-#pragma unroll
-    for (int q = 0; q < 4; ++q)
-#pragma unroll
-      for (int a = 0; a < 3; ++a)
-        {
-          S[q][a] = prm.tab1d[q * 3 + a];
-          D[q][a] = prm.tab1d[12 + q * 3 + a];
-        }
-    const int qz = lane >> 4, q16 = lane & 15;
-    double    Sz[3], Dz[3], Sx[3], Dx[3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k)
-      {
-        Sz[k] = prm.tab1d[qz * 3 + k];
-        Dz[k] = prm.tab1d[12 + qz * 3 + k];
-        Sx[k] = prm.tab1d[(lane & 3) * 3 + k];
-        Dx[k] = prm.tab1d[12 + (lane & 3) * 3 + k];
-      }
-    const double wq = prm.tab1d[24 + (lane & 3)] * prm.tab1d[24 + ((lane >> 2) & 3)] * prm.tab1d[24 + qz];
-    __syncthreads();
-    // ---- E12: lane = (c*3+k)*4 + qx contracts i, then j
-    const int pck = lane >> 2, pqx = lane & 3;
-    if (lane < 36)
-      {
-        double as[3], ad[3];
-#pragma unroll
-        for (int j = 0; j < 3; ++j)
-          {
-            const double x0 = sX[pck * 9 + j * 3], x1 = sX[pck * 9 + j * 3 + 1], x2 = sX[pck * 9 + j * 3 + 2];
-            as[j] = Sx[0] * x0 + Sx[1] * x1 + Sx[2] * x2;
-            ad[j] = Dx[0] * x0 + Dx[1] * x1 + Dx[2] * x2;
-          }
-#pragma unroll
-        for (int qy = 0; qy < 4; ++qy)
-          {
-            const int o    = pck * PS + qy * 4 + pqx;
-            sB[o]          = S[qy][0] * ad[0] + S[qy][1] * ad[1] + S[qy][2] * ad[2]; // d/dx
-            sB[o + PW]     = D[qy][0] * as[0] + D[qy][1] * as[1] + D[qy][2] * as[2]; // d/dy
-            sB[o + 2 * PW] = S[qy][0] * as[0] + S[qy][1] * as[1] + S[qy][2] * as[2]; // d/dz
-          }
-      }
-    __syncthreads();
-    // ---- E3: contract k.  lane = quadrature point; H[c][l] = d u_c / d xi_l
-    double H[3][3];
-#pragma unroll
-    for (int c = 0; c < 3; ++c)
-      {
-        H[c][0] = H[c][1] = H[c][2] = 0.0;
-#pragma unroll
-        for (int k = 0; k < 3; ++k)
-          {
-            const int o = (c * 3 + k) * PS + q16;
-            H[c][0]     = fma(Sz[k], sB[o], H[c][0]);
-            H[c][1]     = fma(Sz[k], sB[o + PW], H[c][1]);
-            H[c][2]     = fma(Dz[k], sB[o + 2 * PW], H[c][2]);
-          }
-      }
-    double g[7];
+    int32_t       node;
+    double        H[3][3], V[3], Sz[3], g[7];
+    postq2_forward<0>(prm, cell, sp.u, nullptr, sX, nullptr, sB, nullptr, node, H, V, Sz);
     {
-      double Ji[9], detJ;
-      mf_geometry<BOX>(prm, cell, prm.tab1d + 28, lane & 3, (lane >> 2) & 3, qz, Ji, detJ);
-      MF_RECORD_TAIL(false, false, static_cast<double *>(nullptr), 64)
-      stress_point<3>(F, J, Jm, rJ, detJ * wq, sp, g);
+      PostPoint pt;
+      postq2_point<BOX>(prm, cell, H, pt);
+      stress_value<3>(pt.F, pt.J, pt.Jm, pt.rJ, sp, pt.w, g);
+      g[6] = pt.w;
+      (void)V, (void)Sz;
     }
     __syncthreads(); // every lane has read sB: sG may overwrite it
 #pragma unroll
@@ -5085,8 +5194,8 @@ namespace mi
       }
   }
 
-  // 3D Q3, model 0: the shape of energy_q3 / mf_point_pass_q3 -- 128 threads per cell, thread = point of the 5 x 5 x 5 rule
-  // (threads 125-127 contribute exact zeros).  Forward: the gather and mfq3_gradients on u.  Backward, value-only, in the LDS
+  // 3D Q3, model 0: 128 threads per cell, thread = point of the 5 x 5 x 5 rule (threads 125-127 contribute exact zeros).
+  // Forward: the gather, mfq3_gradients on u and postq3_point.  Backward, value-only, in the LDS
   // places of the point pass with seven fields where it carries nine:
   //   g  [f][point]           R0, 7 x MFQ3_QS
   //   I3' item (f, qy, qx):   contract qz -> C [f,k][qy][qx]     R1, 175 items (two rounds), 700 doubles
@@ -5098,7 +5207,7 @@ namespace mi
   {
     __shared__ double  R0[MFQ3_R0], R1[MFQ3_R1], sT[40];
     __shared__ int32_t sN[MFQ3_NPC];
-    const int     t    = threadIdx.x, it = t < MFQ3_NQ ? t : MFQ3_NQ - 1;
+    const int     t    = threadIdx.x, it = t < MFQ3_NQ ? t : MFQ3_NQ - 1, qz = it / 25, q25 = it - 25 * qz;
     const int64_t cell = sp.cell_begin + blockIdx.x;
     if (t < 40)
       sT[t] = prm.tab1d[t];
@@ -5106,20 +5215,17 @@ namespace mi
       {
         const int32_t node = prm.conn[cell * MFQ3_NPC + t];
         sN[t]              = node;
-#pragma unroll
-        for (int c = 0; c < 3; ++c)
-          R1[c * MFQ3_NPC + t] = sp.u[int64_t(node) * 3 + c];
+        post_gather<3, MFQ3_NPC>(sp.u, node, R1 + t);
       }
     __syncthreads();
     double H[3][3], V[3];
     mfq3_gradients(prm.tab1d, sT, R0, R1, t, it, H, V); // (ends with a barrier: R0 and R1 are free)
     {
-      const int    qz = it / 25, qy = (it - 25 * qz) / 5, qx = it - 25 * qz - 5 * qy;
-      const double wq = prm.tab1d[MFQ3_TW + qx] * prm.tab1d[MFQ3_TW + qy] * prm.tab1d[MFQ3_TW + qz];
-      double       Ji[9], detJ, g[7];
-      mf_geometry<BOX>(prm, cell, prm.tab1d + MFQ3_TX, qx, qy, qz, Ji, detJ);
-      MF_RECORD_TAIL(false, false, static_cast<double *>(nullptr), MFQ3_QS)
-      stress_point<3>(F, J, Jm, rJ, detJ * wq, sp, g);
+      PostPoint pt;
+      double    g[7];
+      postq3_point<BOX>(prm, cell, qz, q25, H, pt);
+      stress_value<3>(pt.F, pt.J, pt.Jm, pt.rJ, sp, pt.w, g);
+      g[6] = pt.w;
 #pragma unroll
       for (int f = 0; f < 7; ++f)
         R0[f * MFQ3_QS + t] = t < MFQ3_NQ ? g[f] : 0.0;
@@ -5170,96 +5276,34 @@ namespace mi
   }
 
   // every other element (2D p = 1..4, 3D p = 1, 4), all of model 1, and the cross-check of the two forms above: one workgroup per cell,
-  // thread = quadrature point for the point stage (plain loops over the cell's nodes as in energy_cells), thread = node for
+  // thread = quadrature point for the point stage (post_cell_point without value fields), thread = node for
   // the back-contraction (plain loop over the points, in ascending order)
   template <int DIM, int P, int MODEL, int NT>
   __global__ __launch_bounds__(NT) void stress_cells(StressParams sp)
   {
-    constexpr int NP1 = P + 1, NPC = Elem<DIM, P>::NPC, NV = 1 << DIM;
     constexpr int NQ1 = MODEL == 0 ? P + 2 : P + 1; // qf_cell (nonlinear_elasticity.cc:74) / quad_order (linear_elasticity.cc:61)
-    constexpr int NQ  = DIM == 2 ? NQ1 * NQ1 : NQ1 * NQ1 * NQ1;
+    POST_CELL_LDS(sc, DIM, P, NQ1)
+    constexpr int NP1 = C::NP1, NPC = C::NPC, NQ = C::NQ;
     static_assert(NQ <= NT && NPC <= NT && NT % 64 == 0, "one thread per quadrature point and per node, whole waves");
-    __shared__ double s_N1[NQ1 * NP1], s_dN1[NQ1 * NP1], s_qw[NQ1], s_qx[NQ1];
-    __shared__ double s_u[NPC * DIM], s_verts[NV * DIM], s_g[NQ * 8];
+    __shared__ double s_g[NQ * 8];
     const int     tid  = threadIdx.x;
     const int64_t cell = sp.cell_begin + blockIdx.x;
-    for (int i = tid; i < NQ1 * NP1; i += NT)
-      {
-        s_N1[i]  = sp.tab[i];
-        s_dN1[i] = sp.tab[NQ1 * NP1 + i];
-      }
-    if (tid < NQ1)
-      {
-        s_qw[tid] = sp.tab[2 * NQ1 * NP1 + tid];
-        s_qx[tid] = sp.tab[2 * NQ1 * NP1 + NQ1 + tid];
-      }
-    if (tid < NV * DIM)
-      s_verts[tid] = sp.cverts[cell * (NV * DIM) + tid];
-    for (int i = tid; i < NPC * DIM; i += NT)
-      {
-        const int a = i / DIM, c = i - a * DIM;
-        s_u[i]      = sp.u[int64_t(sp.conn[cell * NPC + a]) * DIM + c];
-      }
+    post_cell_stage<DIM, P, NQ1, NT>(sp, cell, sc);
     __syncthreads();
     if (tid < NQ)
       {
-        const int q     = tid;
-        const int qi[3] = {q % NQ1, (q / NQ1) % NQ1, (DIM == 3) ? q / (NQ1 * NQ1) : 0};
-        double    gxi[9];
-#pragma unroll
-        for (int k = 0; k < 9; ++k)
-          gxi[k] = 0.0;
-        for (int a = 0; a < NPC; ++a)
-          {
-            const int    ai[3] = {a % NP1, (a / NP1) % NP1, (DIM == 3) ? a / (NP1 * NP1) : 0};
-            const double n0 = s_N1[qi[0] * NP1 + ai[0]], n1 = s_N1[qi[1] * NP1 + ai[1]], n2 = (DIM == 3) ? s_N1[qi[2] * NP1 + ai[2]] : 1.0;
-            const double dN[3] = {s_dN1[qi[0] * NP1 + ai[0]] * n1 * n2, n0 * s_dN1[qi[1] * NP1 + ai[1]] * n2,
-                                  (DIM == 3) ? n0 * n1 * s_dN1[qi[2] * NP1 + ai[2]] : 0.0};
-#pragma unroll
-            for (int i = 0; i < DIM; ++i)
-#pragma unroll
-              for (int j = 0; j < DIM; ++j)
-                gxi[i * 3 + j] = fma(s_u[a * DIM + i], dN[j], gxi[i * 3 + j]);
-          }
-        double xi[3] = {0.0, 0.0, 0.0}, wq = 1.0;
-#pragma unroll
-        for (int d = 0; d < DIM; ++d)
-          {
-            xi[d] = s_qx[qi[d]];
-            wq *= s_qw[qi[d]];
-          }
-        double Jg[9], Ji[9];
-        q1_jacobian<DIM>(s_verts, xi, Jg);
-        const double detJ = det3x3(Jg);
-        inv3x3(Jg, detJ, Ji);
-        double F[9]; // grad u = grad_xi u Jinv, embedded in 3 x 3 (model 0: + I)
-#pragma unroll
-        for (int i = 0; i < 3; ++i)
-#pragma unroll
-          for (int j = 0; j < 3; ++j)
-            F[i * 3 + j] = (i < DIM && j < DIM) ? gxi[i * 3 + 0] * Ji[0 * 3 + j] + gxi[i * 3 + 1] * Ji[1 * 3 + j] +
-                                                    (DIM == 3 ? gxi[i * 3 + 2] * Ji[2 * 3 + j] : 0.0) :
-                                                  0.0;
-        const double w = detJ * wq;
-        double       g[7];
+        const int q = tid;
+        double    F[9], w, g[7]; // F: grad u (model 0: + I)
+        post_cell_point<DIM, P, NQ1, 0, 0>(sc, q, nullptr, nullptr, nullptr, nullptr, F, w);
         if constexpr (MODEL == 0)
           {
-            F[0] += 1.0, F[4] += 1.0, F[8] += 1.0;
-            const double J  = det3x3(F);
-            const double rJ = 1.0 / J, Jm = (DIM == 3) ? 1.0 / (cbrt(J) * cbrt(J)) : rJ; // J^(-2/d)
-            stress_point<DIM>(F, J, Jm, rJ, w, sp, g);
+            double J, Jm, rJ;
+            post_cell_finite_strain<DIM>(F, J, Jm, rJ);
+            stress_value<DIM>(F, J, Jm, rJ, sp, w, g);
           }
         else
-          {
-            const double ltr = sp.lambda * (F[0] + F[4] + F[8]), m2 = 2.0 * sp.mu;
-            g[0] = w * (ltr + m2 * F[0]);
-            g[1] = w * (ltr + m2 * F[4]);
-            g[2] = (DIM == 3) ? w * (ltr + m2 * F[8]) : 0.0;
-            g[3] = w * sp.mu * (F[1] + F[3]);
-            g[4] = w * sp.mu * (F[2] + F[6]);
-            g[5] = w * sp.mu * (F[5] + F[7]);
-            g[6] = w;
-          }
+          linear_stress<DIM>(F, sp.lambda, sp.mu, w, g);
+        g[6] = w;
 #pragma unroll
         for (int f = 0; f < 7; ++f)
           s_g[q * 8 + f] = g[f];
@@ -5267,9 +5311,10 @@ namespace mi
     __syncthreads();
     if (tid < NPC)
       {
-        const int a     = tid;
-        const int ai[3] = {a % NP1, (a / NP1) % NP1, (DIM == 3) ? a / (NP1 * NP1) : 0};
-        double    r[7]  = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+        const int     a     = tid;
+        const int     ai[3] = {a % NP1, (a / NP1) % NP1, (DIM == 3) ? a / (NP1 * NP1) : 0};
+        const double *s_N1  = sc.N1;
+        double        r[7]  = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
         for (int q = 0; q < NQ; ++q)
           {
             const int    qj[3] = {q % NQ1, (q / NQ1) % NQ1, (DIM == 3) ? q / (NQ1 * NQ1) : 0};
@@ -5327,22 +5372,9 @@ namespace mi
   // three).  Nothing goes to the nodes, so all cells run in one launch; a cell stores eta_K^2, n_K^2 and 0 into cell_e[cell][3]
   // (colour-sorted), launch_energy_sum forms the totals, stress_error_finish the roots in the caller's order and the largest.
   // A point with det F <= 0 (model 0) raises *inverted and contributes zeros.  Forms, chosen by launch_stress_error as
-  // launch_stress chooses: stress_error_q2, stress_error_q3 (3D, model 0), stress_error_cells (every other element, model 1).
-  template <int DIM>
-  __device__ __forceinline__ bool stress_value(const double *F, const double J, const double Jm, const double rJ, const StressErrorParams &ep,
-                                               double s[6])
-  {
-    double Finv[9], tau[6], tiso[6], cII, cS;
-    neo_hooke_from_F<DIM>(F, J, Jm, rJ, ep.mu, ep.kappa, Finv, tau, tiso, cII, cS);
-    const bool ok = J > 0.0; // inverted element (nonlinear_elasticity.cc:935 asserts det F > 0)
-    if (!ok)
-      *ep.inverted = 1.0;
-#pragma unroll
-    for (int k = 0; k < 6; ++k)
-      s[k] = tau[k] * rJ;
-    (void)Finv, (void)tiso, (void)cII, (void)cS;
-    return ok;
-  }
+  // launch_stress chooses: stress_error_q2, stress_error_q3 (3D, model 0), stress_error_cells (every other element, model 1):
+  // each its family's forward half with sigma* as the value-only field, stress_value / linear_stress and stress_error_point.
+
   // the two point numbers from the raw stress s and the recovered one r (both xx yy zz xy xz yz; 2D reads xx, yy, xy alone)
   template <int DIM>
   __device__ __forceinline__ void stress_error_point(const double s[6], const double r[6], const double w, const bool ok,
@@ -5368,108 +5400,27 @@ namespace mi
     e[1] = ok ? wm * (sd + 2.0 * os - ep.c * st * st) : 0.0;
   }
 
-  // 3D Q2, model 0: one wave per cell, lane = point of the 4 x 4 x 4 rule.  The gather of u and E12, E3 of stress_q2 for grad u;
-  // sigma*'s six fields of the 27 nodes go the same way with the S table alone (the transposes of stress_q2's B12 / B3): E12'
-  // item (f, k, qx), 72 items in two rounds, E3' in the point's lane.
+  // 3D Q2, model 0: one wave per cell, lane = point of the 4 x 4 x 4 rule.  postq2_forward on u with sigma*'s six fields of
+  // the 27 nodes as its value-only field (the transposes of stress_q2's B12 / B3): E12' in two rounds, E3' in the point's lane.
   template <bool BOX>
   __global__ __launch_bounds__(64, 4) void stress_error_q2(MfParams prm, StressErrorParams ep)
   {
-    constexpr int NPC = 27, PS = 20, PW = 9 * PS;
-    __shared__ double sX[3 * NPC], sS[6 * NPC], sB[3 * PW], sBs[18 * PS];
+    constexpr int NPC = PQ2_NPC, PW = PQ2_PW;
+    __shared__ double sX[3 * NPC], sS[6 * NPC], sB[3 * PW], sBs[2 * PW];
     const int     lane = threadIdx.x;
     const int64_t cell = blockIdx.x;
-    if (lane < NPC)
-      {
-        const int32_t node = prm.conn[cell * NPC + lane];
-#pragma unroll
-        for (int c = 0; c < 3; ++c)
-          sX[c * NPC + lane] = ep.u[int64_t(node) * 3 + c];
-#pragma unroll
-        for (int f = 0; f < 6; ++f)
-          sS[f * NPC + lane] = ep.sigma[int64_t(node) * 6 + f];
-      }
-    double S[4][3], D[4][3]; // S[q][a] = N_a(x_q), D[q][a] = N_a'(x_q) (uniform -> scalar registers)
-#pragma unroll
-    for (int q = 0; q < 4; ++q)
-#pragma unroll
-      for (int a = 0; a < 3; ++a)
-        {
-          S[q][a] = prm.tab1d[q * 3 + a];
-          D[q][a] = prm.tab1d[12 + q * 3 + a];
-        }
-    const int qz = lane >> 4, q16 = lane & 15;
-    double    Sz[3], Dz[3], Sx[3], Dx[3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k)
-      {
-        Sz[k] = prm.tab1d[qz * 3 + k];
-        Dz[k] = prm.tab1d[12 + qz * 3 + k];
-        Sx[k] = prm.tab1d[(lane & 3) * 3 + k];
-        Dx[k] = prm.tab1d[12 + (lane & 3) * 3 + k];
-      }
-    const double wq = prm.tab1d[24 + (lane & 3)] * prm.tab1d[24 + ((lane >> 2) & 3)] * prm.tab1d[24 + qz];
-    __syncthreads();
-    // ---- E12: lane = (c*3+k)*4 + qx contracts i, then j
-    const int pck = lane >> 2, pqx = lane & 3;
-    if (lane < 36)
-      {
-        double as[3], ad[3];
-#pragma unroll
-        for (int j = 0; j < 3; ++j)
-          {
-            const double x0 = sX[pck * 9 + j * 3], x1 = sX[pck * 9 + j * 3 + 1], x2 = sX[pck * 9 + j * 3 + 2];
-            as[j] = Sx[0] * x0 + Sx[1] * x1 + Sx[2] * x2;
-            ad[j] = Dx[0] * x0 + Dx[1] * x1 + Dx[2] * x2;
-          }
-#pragma unroll
-        for (int qy = 0; qy < 4; ++qy)
-          {
-            const int o    = pck * PS + qy * 4 + pqx;
-            sB[o]          = S[qy][0] * ad[0] + S[qy][1] * ad[1] + S[qy][2] * ad[2]; // d/dx
-            sB[o + PW]     = D[qy][0] * as[0] + D[qy][1] * as[1] + D[qy][2] * as[2]; // d/dy
-            sB[o + 2 * PW] = S[qy][0] * as[0] + S[qy][1] * as[1] + S[qy][2] * as[2]; // d/dz
-          }
-      }
-    // ---- E12': item = (f*3+k)*4 + qx, values only (item & 3 == lane & 3: this lane's row Sx in both rounds)
-#pragma unroll
-    for (int item = lane; item < 72; item += 64)
-      {
-        const int fk = item >> 2;
-        double    as[3];
-#pragma unroll
-        for (int j = 0; j < 3; ++j)
-          as[j] = Sx[0] * sS[fk * 9 + j * 3] + Sx[1] * sS[fk * 9 + j * 3 + 1] + Sx[2] * sS[fk * 9 + j * 3 + 2];
-#pragma unroll
-        for (int qy = 0; qy < 4; ++qy)
-          sBs[fk * PS + qy * 4 + pqx] = S[qy][0] * as[0] + S[qy][1] * as[1] + S[qy][2] * as[2];
-      }
-    __syncthreads();
-    // ---- E3: contract k.  lane = quadrature point; H[c][l] = d u_c / d xi_l
-    double H[3][3];
-#pragma unroll
-    for (int c = 0; c < 3; ++c)
-      {
-        H[c][0] = H[c][1] = H[c][2] = 0.0;
-#pragma unroll
-        for (int k = 0; k < 3; ++k)
-          {
-            const int o = (c * 3 + k) * PS + q16;
-            H[c][0]     = fma(Sz[k], sB[o], H[c][0]);
-            H[c][1]     = fma(Sz[k], sB[o + PW], H[c][1]);
-            H[c][2]     = fma(Dz[k], sB[o + 2 * PW], H[c][2]);
-          }
-      }
+    int32_t       node;
+    double        H[3][3], V[3], Sz[3];
+    postq2_forward<6>(prm, cell, ep.u, ep.sigma, sX, sS, sB, sBs, node, H, V, Sz);
     double e[2];
     {
-      double Ji[9], detJ, s[6], r[6];
-      mf_geometry<BOX>(prm, cell, prm.tab1d + 28, lane & 3, (lane >> 2) & 3, qz, Ji, detJ);
-      MF_RECORD_TAIL(false, false, static_cast<double *>(nullptr), 64)
-      const bool ok = stress_value<3>(F, J, Jm, rJ, ep, s);
-      // ---- E3': sigma*(q)
-#pragma unroll
-      for (int f = 0; f < 6; ++f)
-        r[f] = Sz[0] * sBs[(f * 3) * PS + q16] + Sz[1] * sBs[(f * 3 + 1) * PS + q16] + Sz[2] * sBs[(f * 3 + 2) * PS + q16];
-      stress_error_point<3>(s, r, detJ * wq, ok, ep, e);
+      PostPoint pt;
+      double    s[6], r[6];
+      postq2_point<BOX>(prm, cell, H, pt);
+      const bool ok = stress_value<3>(pt.F, pt.J, pt.Jm, pt.rJ, ep, 1.0, s);
+      postq2_values_e3<6, false>(Sz, sBs, lane & 15, r); // sigma*(q)
+      stress_error_point<3>(s, r, pt.w, ok, ep, e);
+      (void)V;
     }
     e[0] = wave_sum_lane63(e[0]);
     e[1] = wave_sum_lane63(e[1]);
@@ -5480,19 +5431,19 @@ namespace mi
       }
   }
 
-  // 3D Q3, model 0: the shape of stress_q3 / energy_q3 -- 128 threads per cell, thread = point of the 5 x 5 x 5 rule (threads
-  // 125-127 contribute exact zeros).  Both waves gather: u into R1 for mfq3_gradients, sigma*'s six fields (three per wave) into
-  // R0 behind the part the gradients use.  After the point's raw stress, the value-only forward pass of the six fields, laid
-  // over the regions the gradients have consumed:
-  //   X'' [f*64 + a]          R0 at MFQ3_VX, 384 doubles (ends at 864)
-  //   E1'' item (f, k, j):    x-line -> A'' [f,k,j][qx]           R0 at 0, 96 items, 480 doubles
-  //   E2'' item (f, k, qx):   contract j -> B'' [f,k][qy][qx]     R1 at 0, 120 items, 600 doubles
-  //   E3'' item = point:      contract k -> sigma*_f(q)
+  // 3D Q3, model 0: 128 threads per cell, thread = point of the 5 x 5 x 5 rule (threads 125-127 contribute exact zeros).  Both
+  // waves gather: u into R1 for mfq3_gradients, sigma*'s six fields (three per wave) into R0 behind the part the gradients
+  // use.  Behind the gradients postq3_values of the six fields, laid over the regions the gradients have consumed (in front
+  // of the point stage: behind it, as the separate kernel had it, the general instance spills 8 scalar registers through the
+  // shared pieces whichever way S comes; S through scalar registers on boxes, from sT on general cells):
+  //   X [f*64 + a]            R0 at MFQ3_VX, 384 doubles (ends at 864)
+  //   A [f,k,j][qx]           R0 at 0, 96 items, 480 doubles
+  //   B [f,k][qy][qx]         R1 at 0, 120 items, 600 doubles
   template <bool BOX>
   __global__ __launch_bounds__(MFQ3_NT, 4) void stress_error_q3(MfParams prm, StressErrorParams ep)
   {
     __shared__ double R0[MFQ3_R0], R1[MFQ3_R1], sT[40], sW[2];
-    const int     t    = threadIdx.x, it = t < MFQ3_NQ ? t : MFQ3_NQ - 1;
+    const int     t    = threadIdx.x, it = t < MFQ3_NQ ? t : MFQ3_NQ - 1, qz = it / 25, q25 = it - 25 * qz;
     const int64_t cell = blockIdx.x;
     if (t < 40)
       sT[t] = prm.tab1d[t];
@@ -5500,186 +5451,55 @@ namespace mi
       const int     a = t & (MFQ3_NPC - 1), f0 = (t >> 6) * 3;
       const int32_t node = prm.conn[cell * MFQ3_NPC + a];
       if (t < MFQ3_NPC)
-        {
-#pragma unroll
-          for (int c = 0; c < 3; ++c)
-            R1[c * MFQ3_NPC + a] = ep.u[int64_t(node) * 3 + c];
-        }
-#pragma unroll
-      for (int f = 0; f < 3; ++f)
-        R0[MFQ3_VX + (f0 + f) * MFQ3_NPC + a] = ep.sigma[int64_t(node) * 6 + f0 + f];
+        post_gather<3, MFQ3_NPC>(ep.u, node, R1 + a);
+      post_gather<3, MFQ3_NPC, 6>(ep.sigma + f0, node, R0 + MFQ3_VX + f0 * MFQ3_NPC + a);
     }
     __syncthreads();
     double H[3][3], V[3];
     mfq3_gradients(prm.tab1d, sT, R0, R1, t, it, H, V); // (writes R0 below MFQ3_VX only; ends with a barrier: R0 below it and R1 are free)
-    const int qz = it / 25, q25 = it - 25 * qz;
-    double    s[6], w;
-    bool      ok;
-    {
-      const int    qy = q25 / 5, qx = q25 - 5 * qy;
-      const double wq = prm.tab1d[MFQ3_TW + qx] * prm.tab1d[MFQ3_TW + qy] * prm.tab1d[MFQ3_TW + qz];
-      double       Ji[9], detJ;
-      mf_geometry<BOX>(prm, cell, prm.tab1d + MFQ3_TX, qx, qy, qz, Ji, detJ);
-      MF_RECORD_TAIL(false, false, static_cast<double *>(nullptr), MFQ3_QS)
-      ok = stress_value<3>(F, J, Jm, rJ, ep, s);
-      w  = detJ * wq;
-      (void)V;
-    }
-    {
-      double S[5][4]; // uniform: scalar registers
-#pragma unroll
-      for (int q = 0; q < 5; ++q)
-#pragma unroll
-        for (int a = 0; a < 4; ++a)
-          S[q][a] = prm.tab1d[q * 4 + a];
-      if (t < 96) // E1'': line (f,k,j) = t
-        {
-          const double x0 = R0[MFQ3_VX + t * 4], x1 = R0[MFQ3_VX + t * 4 + 1], x2 = R0[MFQ3_VX + t * 4 + 2], x3 = R0[MFQ3_VX + t * 4 + 3];
-#pragma unroll
-          for (int qx = 0; qx < 5; ++qx)
-            R0[t * 5 + qx] = S[qx][0] * x0 + S[qx][1] * x1 + S[qx][2] * x2 + S[qx][3] * x3;
-        }
-      __syncthreads();
-      if (t < 120) // E2'': item (f,k,qx): t = fk * 5 + qx
-        {
-          const int fk = t / 5, qx = t - 5 * fk;
-          double    as[4];
-#pragma unroll
-          for (int j = 0; j < 4; ++j)
-            as[j] = R0[(fk * 4 + j) * 5 + qx];
-#pragma unroll
-          for (int qy = 0; qy < 5; ++qy)
-            R1[fk * 25 + qy * 5 + qx] = S[qy][0] * as[0] + S[qy][1] * as[1] + S[qy][2] * as[2] + S[qy][3] * as[3];
-        }
-      __syncthreads();
-    }
+    double r[6]; // sigma*(q)
+    postq3_values<6, BOX>(prm.tab1d, sT, R0 + MFQ3_VX, R0, R1, t, qz, q25, r);
     double e[2];
     {
-      double r[6]; // E3'': sigma*(q)
-#pragma unroll
-      for (int f = 0; f < 6; ++f)
-        {
-          r[f] = 0.0;
-#pragma unroll
-          for (int k = 0; k < 4; ++k)
-            r[f] = fma(sT[qz * 4 + k], R1[(f * 4 + k) * 25 + q25], r[f]);
-        }
-      stress_error_point<3>(s, r, w, ok, ep, e);
+      PostPoint pt;
+      double    s[6];
+      postq3_point<BOX>(prm, cell, qz, q25, H, pt);
+      const bool ok = stress_value<3>(pt.F, pt.J, pt.Jm, pt.rJ, ep, 1.0, s);
+      stress_error_point<3>(s, r, pt.w, ok, ep, e);
+      (void)V;
     }
-    e[0] = wave_sum_lane63(t < MFQ3_NQ ? e[0] : 0.0);
-    e[1] = wave_sum_lane63(t < MFQ3_NQ ? e[1] : 0.0);
-    if (t == MFQ3_NT - 1) // lane 63 of the second wave
-      sW[0] = e[0], sW[1] = e[1];
-    __syncthreads();
-    if (t == 63)
-      {
-        double *__restrict__ o = ep.cell_e + cell * 3;
-        o[0] = e[0] + sW[0], o[1] = e[1] + sW[1], o[2] = 0.0;
-      }
+    postq3_cell_sum(e, t, sW, ep.cell_e + cell * 3);
   }
 
   // every other element (2D p = 1..4, 3D p = 1, 4), all of model 1, and the cross-check of the two forms above: one workgroup per
-  // cell, thread = quadrature point, plain loops over the cell's nodes as in stress_cells -- grad u and sigma*(q) in one loop
+  // cell, thread = quadrature point; post_cell_point with sigma* as its value field -- grad u and sigma*(q) in one loop
   template <int DIM, int P, int MODEL, int NT>
   __global__ __launch_bounds__(NT) void stress_error_cells(StressErrorParams ep)
   {
-    constexpr int NP1 = P + 1, NPC = Elem<DIM, P>::NPC, NV = 1 << DIM, NC = DIM * (DIM + 1) / 2;
+    constexpr int NC  = DIM * (DIM + 1) / 2;
     constexpr int NQ1 = MODEL == 0 ? P + 2 : P + 1; // qf_cell (nonlinear_elasticity.cc:74) / quad_order (linear_elasticity.cc:61)
-    constexpr int NQ  = DIM == 2 ? NQ1 * NQ1 : NQ1 * NQ1 * NQ1;
-    static_assert(NQ <= NT && NT % 64 == 0, "one thread per quadrature point, whole waves");
-    __shared__ double s_N1[NQ1 * NP1], s_dN1[NQ1 * NP1], s_qw[NQ1], s_qx[NQ1];
-    __shared__ double s_u[NPC * DIM], s_sig[NPC * NC], s_verts[NV * DIM], s_red[NT / 64];
+    POST_CELL_LDS(sc, DIM, P, NQ1)
+    static_assert(C::NQ <= NT && NT % 64 == 0, "one thread per quadrature point, whole waves");
+    __shared__ double s_sig[C::NPC * NC], s_red[NT / 64];
     const int     tid  = threadIdx.x;
     const int64_t cell = blockIdx.x;
-    for (int i = tid; i < NQ1 * NP1; i += NT)
-      {
-        s_N1[i]  = ep.tab[i];
-        s_dN1[i] = ep.tab[NQ1 * NP1 + i];
-      }
-    if (tid < NQ1)
-      {
-        s_qw[tid] = ep.tab[2 * NQ1 * NP1 + tid];
-        s_qx[tid] = ep.tab[2 * NQ1 * NP1 + NQ1 + tid];
-      }
-    if (tid < NV * DIM)
-      s_verts[tid] = ep.cverts[cell * (NV * DIM) + tid];
-    for (int i = tid; i < NPC * DIM; i += NT)
-      {
-        const int a = i / DIM, c = i - a * DIM;
-        s_u[i]      = ep.u[int64_t(ep.conn[cell * NPC + a]) * DIM + c];
-      }
-    for (int i = tid; i < NPC * NC; i += NT)
-      {
-        const int a = i / NC, f = i - a * NC;
-        s_sig[i]    = ep.sigma[int64_t(ep.conn[cell * NPC + a]) * NC + f];
-      }
+    post_cell_stage<DIM, P, NQ1, NT>(ep, cell, sc);
+    post_cell_field<C::NPC, NC, NT>(ep.conn, cell, ep.sigma, s_sig);
     __syncthreads();
     double e[2] = {0.0, 0.0};
-    if (tid < NQ)
+    if (tid < C::NQ)
       {
-        const int q     = tid;
-        const int qi[3] = {q % NQ1, (q / NQ1) % NQ1, (DIM == 3) ? q / (NQ1 * NQ1) : 0};
-        double    gxi[9], rs[NC];
-#pragma unroll
-        for (int k = 0; k < 9; ++k)
-          gxi[k] = 0.0;
-#pragma unroll
-        for (int k = 0; k < NC; ++k)
-          rs[k] = 0.0;
-        for (int a = 0; a < NPC; ++a)
-          {
-            const int    ai[3] = {a % NP1, (a / NP1) % NP1, (DIM == 3) ? a / (NP1 * NP1) : 0};
-            const double n0 = s_N1[qi[0] * NP1 + ai[0]], n1 = s_N1[qi[1] * NP1 + ai[1]], n2 = (DIM == 3) ? s_N1[qi[2] * NP1 + ai[2]] : 1.0;
-            const double dN[3] = {s_dN1[qi[0] * NP1 + ai[0]] * n1 * n2, n0 * s_dN1[qi[1] * NP1 + ai[1]] * n2,
-                                  (DIM == 3) ? n0 * n1 * s_dN1[qi[2] * NP1 + ai[2]] : 0.0};
-            const double N = n0 * n1 * n2;
-#pragma unroll
-            for (int i = 0; i < DIM; ++i)
-#pragma unroll
-              for (int j = 0; j < DIM; ++j)
-                gxi[i * 3 + j] = fma(s_u[a * DIM + i], dN[j], gxi[i * 3 + j]);
-#pragma unroll
-            for (int k = 0; k < NC; ++k)
-              rs[k] = fma(N, s_sig[a * NC + k], rs[k]);
-          }
-        double xi[3] = {0.0, 0.0, 0.0}, wq = 1.0;
-#pragma unroll
-        for (int d = 0; d < DIM; ++d)
-          {
-            xi[d] = s_qx[qi[d]];
-            wq *= s_qw[qi[d]];
-          }
-        double Jg[9], Ji[9];
-        q1_jacobian<DIM>(s_verts, xi, Jg);
-        const double detJ = det3x3(Jg);
-        inv3x3(Jg, detJ, Ji);
-        double F[9]; // grad u = grad_xi u Jinv, embedded in 3 x 3 (model 0: + I)
-#pragma unroll
-        for (int i = 0; i < 3; ++i)
-#pragma unroll
-          for (int j = 0; j < 3; ++j)
-            F[i * 3 + j] = (i < DIM && j < DIM) ? gxi[i * 3 + 0] * Ji[0 * 3 + j] + gxi[i * 3 + 1] * Ji[1 * 3 + j] +
-                                                    (DIM == 3 ? gxi[i * 3 + 2] * Ji[2 * 3 + j] : 0.0) :
-                                                  0.0;
-        double s[6], r[6];
+        double F[9], w, rs[NC], s[6], r[6]; // F: grad u (model 0: + I)
         bool   ok = true;
+        post_cell_point<DIM, P, NQ1, NC, 0>(sc, tid, s_sig, nullptr, rs, nullptr, F, w);
         if constexpr (MODEL == 0)
           {
-            F[0] += 1.0, F[4] += 1.0, F[8] += 1.0;
-            const double J  = det3x3(F);
-            const double rJ = 1.0 / J, Jm = (DIM == 3) ? 1.0 / (cbrt(J) * cbrt(J)) : rJ; // J^(-2/d)
-            ok              = stress_value<DIM>(F, J, Jm, rJ, ep, s);
+            double J, Jm, rJ;
+            post_cell_finite_strain<DIM>(F, J, Jm, rJ);
+            ok = stress_value<DIM>(F, J, Jm, rJ, ep, 1.0, s);
           }
         else
-          {
-            const double ltr = ep.lambda * (F[0] + F[4] + F[8]), m2 = 2.0 * ep.mu;
-            s[0] = ltr + m2 * F[0];
-            s[1] = ltr + m2 * F[4];
-            s[2] = (DIM == 3) ? ltr + m2 * F[8] : 0.0;
-            s[3] = ep.mu * (F[1] + F[3]);
-            s[4] = ep.mu * (F[2] + F[6]);
-            s[5] = ep.mu * (F[5] + F[7]);
-          }
+          linear_stress<DIM>(F, ep.lambda, ep.mu, 1.0, s);
         if constexpr (DIM == 3)
           {
 #pragma unroll
@@ -5688,7 +5508,7 @@ namespace mi
           }
         else
           r[0] = rs[0], r[1] = rs[1], r[2] = 0.0, r[3] = rs[2], r[4] = 0.0, r[5] = 0.0; // the nodal field's xx yy xy
-        stress_error_point<DIM>(s, r, detJ * wq, ok, ep, e);
+        stress_error_point<DIM>(s, r, w, ok, ep, e);
       }
     e[0] = block_sum<NT>(e[0], s_red);
     e[1] = block_sum<NT>(e[1], s_red);
@@ -5698,6 +5518,9 @@ namespace mi
         o[0] = e[0], o[1] = e[1], o[2] = 0.0;
       }
   }
+
+  // (the last generic post-processing kernel)
+#undef POST_CELL_LDS
 
   // the larger of two (value, id) pairs over the workgroup, the smaller id among equal values: maximum and smallest index do
   // not depend on the order in which the pairs meet.  Result in s_v[0], s_i[0]
@@ -8831,6 +8654,28 @@ namespace mi
     auto *kern = p.cellbox ? mf_point_pass_q3<true> : mf_point_pass_q3<false>;
     hipLaunchKernelGGL(kern, dim3(cell_count), dim3(MFQ3_NT), 0, s, p, pp);
   }
+  // the generic post-processing kernels (energy_cells, stress_cells, stress_error_cells): threads per workgroup by element.
+  // fn is called with the CellFamily of (dim, degree); -1 where there is none
+  template <int DIM, int P, int NT_>
+  struct CellFamily
+  {
+    static constexpr int dim = DIM, degree = P, NT = NT_;
+  };
+  template <class Fn>
+  static int post_cells_family(const int dim, const int degree, Fn &&fn)
+  {
+    auto on = [&](auto f) {
+      using F = decltype(f);
+      if (dim != F::dim || degree != F::degree)
+        return false;
+      fn(f);
+      return true;
+    };
+    const bool found = on(CellFamily<3, 1, 64>{}) || on(CellFamily<3, 2, 64>{}) || on(CellFamily<3, 3, 128>{}) ||
+                       on(CellFamily<3, 4, 256>{}) || on(CellFamily<2, 1, 64>{}) || on(CellFamily<2, 2, 64>{}) ||
+                       on(CellFamily<2, 3, 64>{}) || on(CellFamily<2, 4, 64>{});
+    return found ? 0 : -1;
+  }
   int launch_energy(int dim, int degree, const MfParams &p, const EnergyParams &e, int32_t cell_count, bool generic, hipStream_t s)
   {
     if (cell_count <= 0)
@@ -8847,22 +8692,10 @@ namespace mi
         hipLaunchKernelGGL(kern, dim3(cell_count), dim3(64), 0, s, p, e);
         return 0;
       }
-#define MI_EN(D_, P_, NT_)                                                                                          \
-  if (dim == D_ && degree == P_)                                                                                    \
-    {                                                                                                               \
-      hipLaunchKernelGGL((energy_cells<D_, P_, NT_>), dim3(cell_count), dim3(NT_), 0, s, e);                        \
-      return 0;                                                                                                     \
-    }
-    MI_EN(3, 1, 64)
-    MI_EN(3, 2, 64)
-    MI_EN(3, 3, 128)
-    MI_EN(3, 4, 256)
-    MI_EN(2, 1, 64)
-    MI_EN(2, 2, 64)
-    MI_EN(2, 3, 64)
-    MI_EN(2, 4, 64)
-#undef MI_EN
-    return -1;
+    return post_cells_family(dim, degree, [&](auto f) {
+      using F = decltype(f);
+      hipLaunchKernelGGL((energy_cells<F::dim, F::degree, F::NT>), dim3(cell_count), dim3(F::NT), 0, s, e);
+    });
   }
   void launch_energy_sum(const double *cell_e, int64_t ncells, double *scratch, double *out, hipStream_t s)
   {
@@ -8892,25 +8725,11 @@ namespace mi
         hipLaunchKernelGGL(kern, dim3(sp.cell_count), dim3(64), 0, s, p, sp);
         return 0;
       }
-#define MI_ST(D_, P_, NT_)                                                                                          \
-  if (dim == D_ && degree == P_)                                                                                    \
-    {                                                                                                               \
-      if (model == 0)                                                                                               \
-        hipLaunchKernelGGL((stress_cells<D_, P_, 0, NT_>), dim3(sp.cell_count), dim3(NT_), 0, s, sp);               \
-      else                                                                                                          \
-        hipLaunchKernelGGL((stress_cells<D_, P_, 1, NT_>), dim3(sp.cell_count), dim3(NT_), 0, s, sp);               \
-      return 0;                                                                                                     \
-    }
-    MI_ST(3, 1, 64)
-    MI_ST(3, 2, 64)
-    MI_ST(3, 3, 128)
-    MI_ST(3, 4, 256)
-    MI_ST(2, 1, 64)
-    MI_ST(2, 2, 64)
-    MI_ST(2, 3, 64)
-    MI_ST(2, 4, 64)
-#undef MI_ST
-    return -1;
+    return post_cells_family(dim, degree, [&](auto f) {
+      using F = decltype(f);
+      auto *kern = model == 0 ? stress_cells<F::dim, F::degree, 0, F::NT> : stress_cells<F::dim, F::degree, 1, F::NT>;
+      hipLaunchKernelGGL(kern, dim3(sp.cell_count), dim3(F::NT), 0, s, sp);
+    });
   }
   void launch_stress_finish(int dim, const double *acc, int64_t nnodes, double *sigma, double *von_mises, double *weight, hipStream_t s)
   {
@@ -8939,25 +8758,11 @@ namespace mi
         hipLaunchKernelGGL(kern, dim3(cell_count), dim3(64), 0, s, p, ep);
         return 0;
       }
-#define MI_SE(D_, P_, NT_)                                                                                          \
-  if (dim == D_ && degree == P_)                                                                                    \
-    {                                                                                                               \
-      if (model == 0)                                                                                               \
-        hipLaunchKernelGGL((stress_error_cells<D_, P_, 0, NT_>), dim3(cell_count), dim3(NT_), 0, s, ep);            \
-      else                                                                                                          \
-        hipLaunchKernelGGL((stress_error_cells<D_, P_, 1, NT_>), dim3(cell_count), dim3(NT_), 0, s, ep);            \
-      return 0;                                                                                                     \
-    }
-    MI_SE(3, 1, 64)
-    MI_SE(3, 2, 64)
-    MI_SE(3, 3, 128)
-    MI_SE(3, 4, 256)
-    MI_SE(2, 1, 64)
-    MI_SE(2, 2, 64)
-    MI_SE(2, 3, 64)
-    MI_SE(2, 4, 64)
-#undef MI_SE
-    return -1;
+    return post_cells_family(dim, degree, [&](auto f) {
+      using F = decltype(f);
+      auto *kern = model == 0 ? stress_error_cells<F::dim, F::degree, 0, F::NT> : stress_error_cells<F::dim, F::degree, 1, F::NT>;
+      hipLaunchKernelGGL(kern, dim3(cell_count), dim3(F::NT), 0, s, ep);
+    });
   }
   void launch_stress_error_finish(const double *cell_e, const int32_t *cell_orig, int64_t ncells, double *eta_cell, double *norm_cell,
                                   double *scratch, double *max_out, hipStream_t s)
