@@ -164,6 +164,11 @@ def lib():
         L.mi_stress_field.restype = C.c_int
         L.mi_stress_error.argtypes = [vp, C.c_int, C.POINTER(StressErrorInfo), dp, dp]
         L.mi_stress_error.restype = C.c_int
+        L.mi_evaluate_points.argtypes = [vp, C.c_int, C.POINTER(C.c_int), C.c_int64, dp, dp, dp, C.POINTER(C.c_int64),
+                                         C.POINTER(C.c_int64)]
+        L.mi_evaluate_points.restype = C.c_int
+        L.mi_state_transfer.argtypes = [vp, vp]
+        L.mi_state_transfer.restype = C.c_int
         L.mi_linear_modes.argtypes = [vp, C.c_int, C.c_double, C.c_int, dp, dp, dp, C.POINTER(C.c_int)]
         L.mi_block_gram.argtypes = [vp, C.c_int64, dp, C.c_int, dp, C.c_int, dp]
         L.mi_block_combine.argtypes = [vp, C.c_int64, dp, C.c_int, dp, C.c_int, dp]
@@ -507,6 +512,32 @@ class Context:
         self._chk(lib().mi_stress_error(self.h, model, C.byref(info), _dp(eta) if cells else None, _dp(nrm) if cells else None))
         return dict(error=info.error, norm=info.norm, relative=info.relative, max_cell_error=info.max_cell_error,
                     max_cell=int(info.max_cell), eta_cell=eta, norm_cell=nrm)
+
+    def evaluate(self, which, points, gradients=False):
+        """(values, gradients, cell, n_outside) of the state vectors `which` (one V_* / L_* id or a sequence) at the points
+        [npts, dim] of the reference configuration: values [n_which, npts, dim], gradients [n_which, npts, dim, dim] = d u_c / d X_d
+        (None unless asked), cell [npts] the lexicographic id of the cell that answered (-1: outside, zeros), and how many
+        points lie in no cell.  One id instead of a sequence drops the leading axis"""
+        single = np.isscalar(which)
+        ids = np.ascontiguousarray([which] if single else list(which), dtype=np.int32)
+        pts = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, self.dim)
+        npts = pts.shape[0]
+        val = np.zeros((ids.size, npts, self.dim))
+        grad = np.zeros((ids.size, npts, self.dim, self.dim)) if gradients else None
+        cell = np.zeros(npts, dtype=np.int64)
+        nout = C.c_int64(0)
+        self._chk(lib().mi_evaluate_points(self.h, ids.size, ids.ctypes.data_as(C.POINTER(C.c_int)), npts, _dp(pts), _dp(val),
+                                           _dp(grad) if gradients else None, cell.ctypes.data_as(C.POINTER(C.c_int64)),
+                                           C.byref(nout)))
+        if single:
+            val, grad = val[0], (grad[0] if gradients else None)
+        return val, grad, cell, int(nout.value)
+
+    def transfer_state_from(self, src):
+        """this context's six state vectors V_U .. V_A_OLD := src's fields at this context's nodes, constrained dofs exactly 0
+        (mi_state_transfer: evaluate on src at self.coords, device to device).  A node outside src's mesh: MiError, nothing
+        written"""
+        self._chk(lib().mi_state_transfer(self.h, src.h))
 
     def state_save(self):
         self._chk(lib().mi_state_save(self.h))

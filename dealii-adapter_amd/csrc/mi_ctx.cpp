@@ -1398,6 +1398,95 @@ namespace mi_detail
     return MI_OK;
   }
 
+  // ---- fields at points (mi_evaluate_points, mi_state_transfer) -------------------------------------------------------
+  // The scratch of a call lives on `owner` (the context asked, or the destination of a transfer) and grows on demand:
+  // points [npts][dim] (unless the caller has them on the device) | values [n_which][npts][dim] | gradients [n_which][npts][dim][dim]
+  // (where wanted) | cells [npts] (int64) | workgroup partials | the count of points in no cell
+  struct PeBuffers
+  {
+    double  *xyz, *values, *gradients;
+    int64_t *cell;
+    double  *part, *count;
+  };
+  static int pe_carve(mi_ctx *owner, int n_which, int64_t npts, bool own_xyz, bool grads, PeBuffers &b)
+  {
+    const size_t np = size_t(npts), dim = size_t(owner->dim), nv = size_t(n_which) * np * dim;
+    const size_t nx = own_xyz ? np * dim : 0, ng = grads ? nv * dim : 0, npart = size_t(mi::field_at_points_partials(npts));
+    const size_t total = nx + nv + ng + np + npart + 1;
+    if (owner->pe_doubles < total)
+      {
+        if (owner->d_pe)
+          HIPCHK(owner, hipFree(owner->d_pe));
+        owner->d_pe       = nullptr;
+        owner->pe_doubles = 0;
+        HIPCHK(owner, hipMalloc((void **)&owner->d_pe, total * sizeof(double)));
+        owner->pe_doubles = total;
+      }
+    double *q   = owner->d_pe;
+    b.xyz       = own_xyz ? q : nullptr;
+    b.values    = q + nx;
+    b.gradients = grads ? b.values + nv : nullptr;
+    b.cell      = reinterpret_cast<int64_t *>(b.values + nv + ng);
+    b.part      = b.values + nv + ng + np;
+    b.count     = b.part + npart;
+    return MI_OK;
+  }
+  // contexts the point evaluation runs on: one slab that is its own team's (a borrowed multigrid level is not)
+  static bool pe_undecomposed(const mi_ctx *c) { return team_size(c) == 1 && c->team && c->team->members[0] == c; }
+
+  // c's vectors which[0..n_which) at the npts device points xyz into b, enqueued on s (c's tables are uploaded on first use)
+  static int enqueue_point_eval(mi_ctx *c, int n_which, const int *which, int64_t npts, const double *xyz, const PeBuffers &b, hipStream_t s)
+  {
+    const mi::HostMesh &m = c->mesh;
+    if (!c->d_cell_pos)
+      {
+        std::vector<int32_t> pos(size_t(m.ncells));
+        for (int64_t k = 0; k < m.ncells; ++k)
+          pos[size_t(m.cell_orig[size_t(k)])] = int32_t(k);
+        if (int rc = upload(c, &c->d_cell_pos, pos))
+          return rc;
+      }
+    if (c->pe_box < 0)
+      {
+        bool box = true;
+        for (int64_t e = 0; e < m.ncells && box; ++e)
+          {
+            const double *cv = &m.cverts[size_t(e) * m.nv * m.dim];
+            for (int v = 0; v < m.nv && box; ++v)
+              for (int d = 0; d < m.dim; ++d)
+                box = box && cv[v * m.dim + d] == cv[(((v >> d) & 1) ? m.nv - 1 : 0) * m.dim + d];
+          }
+        c->pe_box = box ? 1 : 0;
+      }
+    mi::PointEvalParams p{};
+    p.xyz = xyz, p.npts = npts, p.cverts = c->d_cverts, p.cell_pos = c->d_cell_pos, p.vecs = c->d_vecs, p.n = c->n;
+    p.n_which = n_which;
+    for (int w = 0; w < n_which; ++w)
+      p.which[w] = which[w];
+    const mi_mesh_desc &md = c->team->md; // (one slab: the box as the caller described it, without its perturbation)
+    for (int d = 0; d < 3; ++d)
+      {
+        p.reps[d]  = d < m.dim ? m.reps[d] : 1;
+        p.lo[d]    = d < m.dim ? md.lo[d] : 0.0;
+        p.inv_h[d] = d < m.dim ? double(m.reps[d]) / (md.hi[d] - md.lo[d]) : 1.0;
+      }
+    const std::vector<double> nodes = mi::feq_nodes_unit(c->degree);
+    for (int a = 0; a <= c->degree; ++a)
+      {
+        double denom = 1.0;
+        for (int k = 0; k <= c->degree; ++k)
+          if (k != a)
+            denom *= nodes[size_t(a)] - nodes[size_t(k)];
+        p.nodes[a]  = nodes[size_t(a)];
+        p.rdenom[a] = 1.0 / denom;
+      }
+    p.values = b.values, p.gradients = b.gradients, p.cell = b.cell, p.part = b.part;
+    if (mi::launch_field_at_points(c->dim, c->degree, c->pe_box == 1, p, b.count, s))
+      return fail(c, MI_EINVAL, "no point evaluation kernel for dim=%d degree=%d (or too many points for one launch)", c->dim, c->degree);
+    HIPCHK(c, hipGetLastError());
+    return MI_OK;
+  }
+
   // the Q3 fine level's records (mf_records_q3), slots and cell geometry
   int alloc_records_q3(mi_ctx *c)
   {
@@ -2027,7 +2116,7 @@ namespace mi_detail
                     c->d_pred[0][0], c->d_pred[0][1], c->d_pred[1][0], c->d_pred[1][1], c->d_pred[2][0], c->d_pred[2][1], c->d_pred[3][0], c->d_pred[3][1],
                     c->d_pred_saved[0][0], c->d_pred_saved[0][1], c->d_pred_saved[1][0], c->d_pred_saved[1][1], c->d_pred_saved[2][0],
                     c->d_pred_saved[2][1], c->d_pred_saved[3][0], c->d_pred_saved[3][1], c->d_energy, c->d_energy_box,
-                    c->d_stress, c->d_stress_tab, c->d_stress_err, c->d_cell_orig};
+                    c->d_stress, c->d_stress_tab, c->d_stress_err, c->d_cell_orig, c->d_cell_pos, c->d_pe, c->d_node_xyz};
     for (void *p : ptrs)
       if (p)
         hipFree(p);
@@ -2877,6 +2966,102 @@ int mi_stress_error(mi_ctx *c, int model, mi_stress_error_info *out, double *eta
   out->max_cell_error = h[3];
   out->max_cell       = int64_t(h[4]);
   out->reserved       = 0;
+  return MI_OK;
+}
+
+// The finite-element fields at arbitrary points of the reference configuration: u_h(X) = sum_a N_a(xi(X)) u_a for n_which state
+// vectors in one launch (location and bases shared), optionally d u_c / d X_d, the cell that answered and the count of points
+// in no cell.  Reads the vectors as they are; scratch of its own; no timing slot, no counter.  Undecomposed contexts only
+int mi_evaluate_points(mi_ctx *c, int n_which, const int *which, int64_t npts, const double *xyz, double *values, double *gradients,
+                       int64_t *cell, int64_t *n_outside)
+{
+  static_assert(mi::PE_MAX_VECTORS == MI_V_COUNT, "PointEvalParams::which holds every state vector");
+  if (!c)
+    return MI_EINVAL;
+  if (!which || !xyz || !values)
+    return fail(c, MI_EINVAL, "mi_evaluate_points: null argument");
+  if (n_which < 1 || n_which > MI_V_COUNT)
+    return fail(c, MI_EINVAL, "mi_evaluate_points: n_which %d (1..%d)", n_which, int(MI_V_COUNT));
+  for (int w = 0; w < n_which; ++w)
+    if (which[w] < 0 || which[w] >= MI_V_COUNT)
+      return fail(c, MI_EINVAL, "mi_evaluate_points: bad vector id %d", which[w]);
+  if (npts < 0)
+    return fail(c, MI_EINVAL, "mi_evaluate_points: npts %lld", (long long)npts);
+  if (!pe_undecomposed(c))
+    return fail(c, MI_EINVAL, "mi_evaluate_points: one slab only (an undecomposed mesh)");
+  if (n_outside)
+    *n_outside = 0;
+  if (npts == 0)
+    return MI_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  PeBuffers b{};
+  if (const int rc = pe_carve(c, n_which, npts, true, gradients != nullptr, b))
+    return rc;
+  const size_t np = size_t(npts), dim = size_t(c->dim), nv = size_t(n_which) * np * dim;
+  HIPCHK(c, hipMemcpyAsync(b.xyz, xyz, np * dim * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  if (const int rc = enqueue_point_eval(c, n_which, which, npts, b.xyz, b, c->stream))
+    return rc;
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipMemcpy(values, b.values, nv * sizeof(double), hipMemcpyDeviceToHost));
+  if (gradients)
+    HIPCHK(c, hipMemcpy(gradients, b.gradients, nv * dim * sizeof(double), hipMemcpyDeviceToHost));
+  if (cell)
+    HIPCHK(c, hipMemcpy(cell, b.cell, np * sizeof(int64_t), hipMemcpyDeviceToHost));
+  if (n_outside)
+    {
+      double cnt = 0.0;
+      HIPCHK(c, hipMemcpy(&cnt, b.count, sizeof(double), hipMemcpyDeviceToHost));
+      *n_outside = int64_t(cnt);
+    }
+  return MI_OK;
+}
+
+// dst's six state vectors := src's fields at dst's nodes: mi_evaluate_points of src at mi_get_node_coords(dst) without the
+// host in between -- the same kernel on dst's node coordinates (uploaded once), its values into scratch on dst, and only when
+// every node was found the copy into dst's vectors and zero_constrained on each.  Nodal interpolation, not a projection
+int mi_state_transfer(mi_ctx *dst, mi_ctx *src)
+{
+  if (!dst || !src)
+    return dst ? fail(dst, MI_EINVAL, "mi_state_transfer: null argument") : MI_EINVAL;
+  if (dst->dim != src->dim)
+    return fail(dst, MI_EINVAL, "mi_state_transfer: dst is %dD, src %dD", dst->dim, src->dim);
+  if (dst->device != src->device)
+    return fail(dst, MI_EINVAL, "mi_state_transfer: dst is on device %d, src on %d", dst->device, src->device);
+  if (!pe_undecomposed(dst) || !pe_undecomposed(src))
+    return fail(dst, MI_EINVAL, "mi_state_transfer: one slab only (undecomposed meshes)");
+  HIPCHK(dst, hipSetDevice(dst->device));
+  if (!dst->d_node_xyz)
+    if (const int rc = upload(dst, &dst->d_node_xyz, dst->mesh.node_xyz))
+      return rc;
+  static const int six[6]  = {MI_V_TOTAL_DISPLACEMENT, MI_V_TOTAL_DISPLACEMENT_OLD, MI_V_VELOCITY,
+                              MI_V_VELOCITY_OLD,       MI_V_ACCELERATION,           MI_V_ACCELERATION_OLD};
+  const int64_t    nn      = dst->mesh.nnodes;
+  PeBuffers        b{};
+  if (const int rc = pe_carve(dst, 6, nn, false, false, b))
+    return rc;
+  HIPCHK(dst, hipStreamSynchronize(dst->stream)); // (the scratch and dst's vectors are dst's stream's; the kernel runs on src's)
+  if (const int rc = enqueue_point_eval(src, 6, six, nn, dst->d_node_xyz, b, src->stream))
+    return fail(dst, rc, "%s", src->err.c_str());
+  HIPCHK(dst, hipStreamSynchronize(src->stream));
+  double cnt = 0.0;
+  HIPCHK(dst, hipMemcpy(&cnt, b.count, sizeof(double), hipMemcpyDeviceToHost));
+  if (cnt > 0.0)
+    {
+      std::vector<int64_t> cells(size_t(nn), 0);
+      HIPCHK(dst, hipMemcpy(cells.data(), b.cell, size_t(nn) * sizeof(int64_t), hipMemcpyDeviceToHost));
+      int64_t first = 0;
+      while (first < nn - 1 && cells[size_t(first)] >= 0)
+        ++first;
+      const double *x = &dst->mesh.node_xyz[size_t(first) * dst->dim];
+      return fail(dst, MI_EINVAL, "mi_state_transfer: node %lld of dst at (%.17g, %.17g, %.17g) lies outside src's mesh (%lld nodes do); dst is unchanged",
+                  (long long)first, x[0], x[1], dst->dim == 3 ? x[2] : 0.0, (long long)cnt);
+    }
+  // the six vectors are the first six of d_vecs, in the order of `six`: one copy, then the constraint mask on each
+  HIPCHK(dst, hipMemcpyAsync(dst->d_vecs, b.values, size_t(6) * size_t(dst->n) * sizeof(double), hipMemcpyDeviceToDevice, dst->stream));
+  for (int w = 0; w < 6; ++w)
+    mi::launch_zero_constrained(dst->dim, dst->vec(six[w]), dst->d_cmask, dst->n, dst->stream);
+  HIPCHK(dst, hipGetLastError());
+  HIPCHK(dst, hipStreamSynchronize(dst->stream));
   return MI_OK;
 }
 

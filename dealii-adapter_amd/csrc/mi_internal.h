@@ -257,6 +257,14 @@ struct mi_ctx
   // fixed-order sum, eta_K and n_K [ncells] each in lexicographic order, eight result scalars; HostMesh::cell_orig on the device
   double   *d_stress_err = nullptr;
   int32_t  *d_cell_orig  = nullptr;
+  // fields at points (mi_evaluate_points, mi_state_transfer), allocated on first use: the inverse of HostMesh::cell_orig; whether
+  // every cell is an axis-parallel box (-1: not looked at yet); scratch of the call that grows on demand (points | values |
+  // gradients | cells | workgroup partials | count); this context's node coordinates (the points of a transfer INTO it)
+  int32_t  *d_cell_pos   = nullptr;
+  int       pe_box       = -1;
+  double   *d_pe         = nullptr;
+  size_t    pe_doubles   = 0;
+  double   *d_node_xyz   = nullptr;
   uint16_t *d_off   = nullptr;
   uint8_t  *d_cmask = nullptr;
   double   *h_pinned = nullptr; // pinned host scratch (scalars, flags, interface buffer)

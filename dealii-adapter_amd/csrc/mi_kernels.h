@@ -273,6 +273,27 @@ namespace mi
     double        *inverted;  // as StressParams::inverted
   };
 
+  // fields at arbitrary points (see field_at_points): the points, the mesh they are looked up in, the state vectors wanted and
+  // where the answers go.  All pointers are device memory
+  constexpr int PE_MAX_VECTORS = 10; // MI_V_COUNT
+  struct PointEvalParams
+  {
+    const double  *xyz;      // [npts][dim] reference configuration
+    int64_t        npts;
+    const double  *cverts;   // [ncells][2^dim][dim], colour-sorted cells
+    const int32_t *cell_pos; // [ncells] lexicographic cell id -> colour-sorted position (the inverse of HostMesh::cell_orig)
+    const double  *vecs;     // the state vectors: vector w at vecs + w * n
+    int64_t        n;        // dofs
+    int32_t        n_which, which[PE_MAX_VECTORS];
+    int32_t        reps[3];
+    double         lo[3], inv_h[3];      // the unperturbed lattice: first guess of a point's cell
+    double         nodes[5], rdenom[5];  // 1D support points of the element and 1 / prod_{m != a} (x_a - x_m)
+    double        *values;    // [n_which][npts][dim]
+    double        *gradients; // [n_which][npts][dim][dim] = d u_c / d X_d, or null
+    int64_t       *cell;      // [npts] lexicographic cell id, -1 = in no cell; or null
+    double        *part;      // [field_at_points_partials(npts)] points in no cell, per workgroup
+  };
+
   // matrix-free operator of the linear model on 3D Q3 cells (see mf_linear_q3): y = (c_K K + c_M M) x
   struct MfLinearOp
   {
@@ -457,6 +478,10 @@ namespace mi
                            hipStream_t s);
   void launch_stress_error_finish(const double *cell_e, const int32_t *cell_orig, int64_t ncells, double *eta_cell, double *norm_cell,
                                   double *scratch, double *max_out, hipStream_t s);
+  // fields at points: one thread per point of p.xyz, field_at_points<dim, degree, box> (box: every cell an axis-parallel box, xi
+  // in closed form; else Newton on the Q1 map); then *n_outside = sum of p.part (finish_sum).  -1: no kernel for the element
+  int64_t field_at_points_partials(int64_t npts);
+  int     launch_field_at_points(int dim, int degree, bool box, const PointEvalParams &p, double *n_outside, hipStream_t s);
   // ... the multigrid smoother's operator on the element's full-order rule, 4 x 4 x 4 points (see mf_spmv_q3s): records
   // [ncells][MF_NREC][64] of its own (MfParams::qrec_q3s, written by mf_records_q3s from u + du with the fold rule of
   // mf_records27), the rule's 1D tables MfParams::tab_q3s; one wave per cell, the results into the same cell-major slots

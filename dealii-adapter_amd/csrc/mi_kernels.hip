@@ -5593,6 +5593,324 @@ namespace mi
 #undef MF_DIAG_POINT
 #undef MF_DIAG_ACCUMULATE
 
+  // ------------------------------------------------------------------ fields at arbitrary points (mi_evaluate_points, mi_state_transfer)
+  // u_h(X) = sum_a N_a(xi) u_a at reference-configuration points X, xi the pre-image of X under the d-linear (Q1) map of the
+  // cell's vertices -- the map HostMesh::build places the support points with.  One thread per point:
+  //   1. the cell: the first guess is the cell of the unperturbed lattice; while xi leaves [-tol, 1 + tol]^dim the guess moves one
+  //      cell along every direction xi leaves through (at most PE_WALK moves), and should that walk end without a cell the
+  //      3^dim cells around the first guess are tried in lexicographic order.  Vertex offsets below a quarter of the smallest
+  //      edge keep every point of the mesh within one cell of its first guess, so the last stage finds it.  A point on a shared
+  //      face, edge or corner is answered by the first containing cell of that fixed sequence;
+  //   2. xi: closed form on axis-parallel boxes (BOX), else Newton on the Q1 map from the cell's centre;
+  //   3. the 1D Lagrange bases and their derivatives on the element's support points, once per point;
+  //   4. the n_which vectors, one after the other through the same sums: value and d u_c / d xi_e row by row, plane by plane.
+  // Node ids by lattice arithmetic (undecomposed meshes: the lattice is the reference's node order); the cell's vertices through
+  // cell_pos, the inverse of HostMesh::cell_orig.  A point in no cell (NaN coordinates too: every comparison fails) stores
+  // zeros and cell -1 and counts into the workgroup's partial; plain stores, the partials summed by finish_sum.
+  constexpr double PE_TOL  = 1e-10; // "inside": xi in [-PE_TOL, 1 + PE_TOL]^dim
+  constexpr int    PE_WALK = 3;
+
+  // X (xi) and J[c][d] = d X_c / d xi_d of the Q1 map with vertices V (vertex v: bit d = upper end along d)
+  template <int DIM>
+  __device__ __forceinline__ void pe_q1_map(const double (&V)[1 << DIM][DIM], const double (&xi)[DIM], double (&X)[DIM], double (&J)[DIM][DIM])
+  {
+#pragma unroll
+    for (int c = 0; c < DIM; ++c)
+      {
+        X[c] = 0.0;
+#pragma unroll
+        for (int d = 0; d < DIM; ++d)
+          J[c][d] = 0.0;
+      }
+#pragma unroll
+    for (int v = 0; v < (1 << DIM); ++v)
+      {
+        double w = 1.0, dw[DIM];
+#pragma unroll
+        for (int d = 0; d < DIM; ++d)
+          {
+            w *= ((v >> d) & 1) ? xi[d] : 1.0 - xi[d];
+            dw[d] = ((v >> d) & 1) ? 1.0 : -1.0;
+#pragma unroll
+            for (int e = 0; e < DIM; ++e)
+              if (e != d)
+                dw[d] *= ((v >> e) & 1) ? xi[e] : 1.0 - xi[e];
+          }
+#pragma unroll
+        for (int c = 0; c < DIM; ++c)
+          {
+            X[c] += w * V[v][c];
+#pragma unroll
+            for (int d = 0; d < DIM; ++d)
+              J[c][d] += dw[d] * V[v][c];
+          }
+      }
+  }
+  template <int DIM>
+  __device__ __forceinline__ void pe_invert(const double (&J)[DIM][DIM], double (&I)[DIM][DIM])
+  {
+    if constexpr (DIM == 2)
+      {
+        const double r = 1.0 / (J[0][0] * J[1][1] - J[0][1] * J[1][0]);
+        I[0][0] = J[1][1] * r, I[0][1] = -J[0][1] * r, I[1][0] = -J[1][0] * r, I[1][1] = J[0][0] * r;
+      }
+    else
+      {
+        const double c00 = J[1][1] * J[2][2] - J[1][2] * J[2][1], c01 = J[1][2] * J[2][0] - J[1][0] * J[2][2],
+                     c02 = J[1][0] * J[2][1] - J[1][1] * J[2][0];
+        const double r = 1.0 / (J[0][0] * c00 + J[0][1] * c01 + J[0][2] * c02);
+        I[0][0] = c00 * r, I[1][0] = c01 * r, I[2][0] = c02 * r;
+        I[0][1] = (J[0][2] * J[2][1] - J[0][1] * J[2][2]) * r;
+        I[1][1] = (J[0][0] * J[2][2] - J[0][2] * J[2][0]) * r;
+        I[2][1] = (J[0][1] * J[2][0] - J[0][0] * J[2][1]) * r;
+        I[0][2] = (J[0][1] * J[1][2] - J[0][2] * J[1][1]) * r;
+        I[1][2] = (J[0][2] * J[1][0] - J[0][0] * J[1][2]) * r;
+        I[2][2] = (J[0][0] * J[1][1] - J[0][1] * J[1][0]) * r;
+      }
+  }
+  // is X in cell ci?  xi and Jinv[e][d] = d xi_e / d X_d there (Jinv only where the answer is yes)
+  template <int DIM, bool BOX>
+  __device__ __forceinline__ bool pe_point_in_cell(const PointEvalParams &p, const int (&ci)[DIM], const double (&X)[DIM], double (&xi)[DIM],
+                                                   double (&Jinv)[DIM][DIM])
+  {
+    constexpr int  NV   = 1 << DIM;
+    const int64_t  cell = ci[0] + int64_t(p.reps[0]) * (ci[1] + (DIM == 3 ? int64_t(p.reps[1]) * ci[DIM - 1] : 0));
+    const double  *cv   = p.cverts + int64_t(p.cell_pos[cell]) * (NV * DIM);
+    bool           ok   = true;
+    if constexpr (BOX)
+      {
+#pragma unroll
+        for (int e = 0; e < DIM; ++e)
+#pragma unroll
+          for (int d = 0; d < DIM; ++d)
+            Jinv[e][d] = 0.0;
+#pragma unroll
+        for (int d = 0; d < DIM; ++d)
+          {
+            const double x0 = cv[d], h = cv[(NV - 1) * DIM + d] - x0;
+            xi[d]      = (X[d] - x0) / h;
+            Jinv[d][d] = 1.0 / h;
+          }
+      }
+    else
+      {
+        double V[NV][DIM];
+#pragma unroll
+        for (int v = 0; v < NV; ++v)
+#pragma unroll
+          for (int d = 0; d < DIM; ++d)
+            V[v][d] = cv[v * DIM + d];
+#pragma unroll
+        for (int d = 0; d < DIM; ++d)
+          xi[d] = 0.5;
+        double Xk[DIM], J[DIM][DIM], dmax = 1.0;
+        for (int it = 0; it < 16 && !(dmax < 1e-12); ++it)
+          {
+            pe_q1_map<DIM>(V, xi, Xk, J);
+            pe_invert<DIM>(J, Jinv);
+            dmax = 0.0;
+#pragma unroll
+            for (int e = 0; e < DIM; ++e)
+              {
+                double dx = 0.0;
+#pragma unroll
+                for (int d = 0; d < DIM; ++d)
+                  dx += Jinv[e][d] * (X[d] - Xk[d]);
+                xi[e] += dx;
+                dmax = fmax(dmax, fabs(dx)); // (a NaN step: fmax drops it, the inside test below refuses the NaN xi)
+              }
+          }
+        ok = dmax < 1e-8; // quadratic convergence: xi is then exact to rounding
+        pe_q1_map<DIM>(V, xi, Xk, J);
+        pe_invert<DIM>(J, Jinv);
+      }
+#pragma unroll
+    for (int d = 0; d < DIM; ++d)
+      ok = ok && xi[d] >= -PE_TOL && xi[d] <= 1.0 + PE_TOL;
+    return ok;
+  }
+
+  template <int DIM, int P, bool BOX>
+  __global__ __launch_bounds__(256) void field_at_points(const PointEvalParams p)
+  {
+    constexpr int     NP1 = P + 1, POW3 = DIM == 3 ? 27 : 9;
+    __shared__ double s_red[4];
+    const int64_t     i = int64_t(blockIdx.x) * 256 + threadIdx.x;
+    double            outside = 0.0;
+    if (i < p.npts)
+      {
+        double X[DIM], xi[DIM], Jinv[DIM][DIM];
+        int    g[DIM], cur[DIM];
+#pragma unroll
+        for (int d = 0; d < DIM; ++d)
+          {
+            X[d] = p.xyz[i * DIM + d];
+            // (fmax / fmin return the other operand for a NaN: the conversion is always of a number in range)
+            g[d] = cur[d] = int(fmin(fmax(floor((X[d] - p.lo[d]) * p.inv_h[d]), 0.0), double(p.reps[d] - 1)));
+          }
+        bool found = false;
+        int  walk = PE_WALK, scan = -1; // scan < 0: walking
+        while (true)
+          {
+            if (pe_point_in_cell<DIM, BOX>(p, cur, X, xi, Jinv))
+              {
+                found = true;
+                break;
+              }
+            if (scan < 0)
+              {
+                bool moved = false;
+#pragma unroll
+                for (int d = 0; d < DIM; ++d)
+                  if (xi[d] < -PE_TOL && cur[d] > 0)
+                    --cur[d], moved = true;
+                  else if (xi[d] > 1.0 + PE_TOL && cur[d] < p.reps[d] - 1)
+                    ++cur[d], moved = true;
+                if (moved && walk-- > 0)
+                  continue;
+                scan = 0;
+              }
+            bool have = false;
+            while (scan < POW3 && !have)
+              {
+                int k = scan++;
+                have  = k != POW3 / 2; // (the first guess itself was the walk's first cell)
+#pragma unroll
+                for (int d = 0; d < DIM; ++d)
+                  {
+                    cur[d] = g[d] + k % 3 - 1;
+                    k /= 3;
+                    have = have && cur[d] >= 0 && cur[d] < p.reps[d];
+                  }
+              }
+            if (!have)
+              break;
+          }
+
+        // 1D bases and derivatives at xi (the product form of mi::lagrange_eval)
+        double N[DIM][NP1], dN[DIM][NP1];
+        if (found)
+          {
+#pragma unroll
+            for (int d = 0; d < DIM; ++d)
+#pragma unroll
+              for (int a = 0; a < NP1; ++a)
+                {
+                  double v = 1.0, s = 0.0;
+#pragma unroll
+                  for (int m = 0; m < NP1; ++m)
+                    if (m != a)
+                      v *= xi[d] - p.nodes[m];
+#pragma unroll
+                  for (int k = 0; k < NP1; ++k)
+                    if (k != a)
+                      {
+                        double t = 1.0;
+#pragma unroll
+                        for (int m = 0; m < NP1; ++m)
+                          if (m != a && m != k)
+                            t *= xi[d] - p.nodes[m];
+                        s += t;
+                      }
+                  N[d][a]  = v * p.rdenom[a];
+                  dN[d][a] = s * p.rdenom[a];
+                }
+          }
+        int64_t nn0 = int64_t(P) * p.reps[0] + 1, nn1 = int64_t(P) * p.reps[1] + 1, cell = -1, base = 0;
+        if (found)
+          {
+            cell = cur[0] + int64_t(p.reps[0]) * (cur[1] + (DIM == 3 ? int64_t(p.reps[1]) * cur[DIM - 1] : 0));
+            base = int64_t(P) * cur[0] + nn0 * (int64_t(P) * cur[1] + (DIM == 3 ? nn1 * (int64_t(P) * cur[DIM - 1]) : 0));
+          }
+        else
+          outside = 1.0;
+        if (p.cell)
+          p.cell[i] = cell;
+        for (int w = 0; w < p.n_which; ++w)
+          {
+            double val[DIM], ge[DIM][DIM]; // ge[c][e] = d u_c / d xi_e
+#pragma unroll
+            for (int c = 0; c < DIM; ++c)
+              {
+                val[c] = 0.0;
+#pragma unroll
+                for (int e = 0; e < DIM; ++e)
+                  ge[c][e] = 0.0;
+              }
+            if (found)
+              {
+                const double *__restrict__ u = p.vecs + int64_t(p.which[w]) * p.n;
+#pragma unroll
+                for (int az = 0; az < (DIM == 3 ? NP1 : 1); ++az)
+                  {
+                    double pv[DIM], px[DIM], py[DIM]; // the plane's value, d / d xi_0, d / d xi_1
+#pragma unroll
+                    for (int c = 0; c < DIM; ++c)
+                      pv[c] = px[c] = py[c] = 0.0;
+#pragma unroll
+                    for (int ay = 0; ay < NP1; ++ay)
+                      {
+                        double rv[DIM], rx[DIM];
+#pragma unroll
+                        for (int c = 0; c < DIM; ++c)
+                          rv[c] = rx[c] = 0.0;
+                        const double *__restrict__ row = u + (base + nn0 * (ay + nn1 * az)) * DIM;
+#pragma unroll
+                        for (int ax = 0; ax < NP1; ++ax)
+#pragma unroll
+                          for (int c = 0; c < DIM; ++c)
+                            {
+                              const double uu = row[ax * DIM + c];
+                              rv[c] += N[0][ax] * uu;
+                              rx[c] += dN[0][ax] * uu;
+                            }
+#pragma unroll
+                        for (int c = 0; c < DIM; ++c)
+                          {
+                            pv[c] += N[1][ay] * rv[c];
+                            px[c] += N[1][ay] * rx[c];
+                            py[c] += dN[1][ay] * rv[c];
+                          }
+                      }
+#pragma unroll
+                    for (int c = 0; c < DIM; ++c)
+                      if constexpr (DIM == 3)
+                        {
+                          val[c] += N[DIM - 1][az] * pv[c];
+                          ge[c][0] += N[DIM - 1][az] * px[c];
+                          ge[c][1] += N[DIM - 1][az] * py[c];
+                          ge[c][DIM - 1] += dN[DIM - 1][az] * pv[c];
+                        }
+                      else
+                        val[c] = pv[c], ge[c][0] = px[c], ge[c][1] = py[c];
+                  }
+              }
+            double *__restrict__ vo = p.values + (int64_t(w) * p.npts + i) * DIM;
+#pragma unroll
+            for (int c = 0; c < DIM; ++c)
+              vo[c] = val[c];
+            if (p.gradients)
+              {
+                double *__restrict__ go = p.gradients + (int64_t(w) * p.npts + i) * (DIM * DIM);
+#pragma unroll
+                for (int c = 0; c < DIM; ++c)
+#pragma unroll
+                  for (int d = 0; d < DIM; ++d)
+                    {
+                      double s = 0.0;
+#pragma unroll
+                      for (int e = 0; e < DIM; ++e)
+                        s += ge[c][e] * Jinv[e][d];
+                      go[c * DIM + d] = found ? s : 0.0;
+                    }
+              }
+          }
+      }
+    outside = block_sum<256>(outside, s_red);
+    if (threadIdx.x == 0)
+      p.part[blockIdx.x] = outside;
+  }
+
   // ------------------------------------------------------------------ linear model, 3D Q3: K, M and the stepping matrix without matrices
   // "linear_operator" 1.  The linear model's rule is QGauss(p + 1) (linear_elasticity.cc:61): for Q3 the 4 x 4 x 4 points of
   // mf_spmv_q3s -- one wave per cell, lane = point = node, its region layout, gradients (mfq3s_gradients) and integration
@@ -8773,6 +9091,30 @@ namespace mi
     const int     nblk  = int((ncells + chunk - 1) / chunk);
     hipLaunchKernelGGL(stress_error_finish, dim3(nblk), dim3(256), 0, s, cell_e, cell_orig, ncells, chunk, eta_cell, norm_cell, scratch);
     hipLaunchKernelGGL(stress_error_max, dim3(1), dim3(256), 0, s, scratch, int64_t(nblk), max_out);
+  }
+  template <int DIM, bool BOX>
+  static int field_at_points_degree(int degree, int grid, const PointEvalParams &p, hipStream_t s)
+  {
+    switch (degree)
+      {
+        case 1: hipLaunchKernelGGL((field_at_points<DIM, 1, BOX>), dim3(grid), dim3(256), 0, s, p); return 0;
+        case 2: hipLaunchKernelGGL((field_at_points<DIM, 2, BOX>), dim3(grid), dim3(256), 0, s, p); return 0;
+        case 3: hipLaunchKernelGGL((field_at_points<DIM, 3, BOX>), dim3(grid), dim3(256), 0, s, p); return 0;
+        case 4: hipLaunchKernelGGL((field_at_points<DIM, 4, BOX>), dim3(grid), dim3(256), 0, s, p); return 0;
+      }
+    return -1;
+  }
+  int64_t field_at_points_partials(int64_t npts) { return (npts + 255) / 256; }
+  int launch_field_at_points(int dim, int degree, bool box, const PointEvalParams &p, double *n_outside, hipStream_t s)
+  {
+    const int64_t grid = field_at_points_partials(p.npts);
+    if (grid <= 0 || grid > INT32_MAX || (dim != 2 && dim != 3))
+      return -1;
+    const int rc = dim == 3 ? (box ? field_at_points_degree<3, true>(degree, int(grid), p, s) : field_at_points_degree<3, false>(degree, int(grid), p, s))
+                            : (box ? field_at_points_degree<2, true>(degree, int(grid), p, s) : field_at_points_degree<2, false>(degree, int(grid), p, s));
+    if (rc == 0)
+      hipLaunchKernelGGL(finish_sum, dim3(1), dim3(256), 0, s, p.part, int(grid), n_outside);
+    return rc;
   }
   void launch_mf_diag_q3(const MfParams &p, double *slots6, int32_t cell_count, hipStream_t s)
   {

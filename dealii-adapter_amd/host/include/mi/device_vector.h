@@ -112,6 +112,27 @@ namespace mi
       check(mi_stress_error(ctx_, model, &info, eta_cell ? eta_cell->data() : nullptr, nullptr), "mi_stress_error");
       return true;
     }
+    // the fields at npts points of the reference configuration (mi_evaluate_points): values [n_which][npts][dim] of the state
+    // vectors which[], cells [npts] (the lexicographic id of the cell that answered, -1: outside) where wanted; returns the number
+    // of points in no cell, or -1 on a team (emulated slabs or RCCL), where the library provides none (one slab only); any other
+    // failure throws
+    int64_t evaluate_points(const std::vector<int> &which, int dim, const std::vector<double> &xyz, std::vector<double> &values,
+                            std::vector<int64_t> *cells = nullptr) const
+    {
+      int team = 1, rccl = 0;
+      check(mi_comm_info(ctx_, &team, &rccl), "mi_comm_info");
+      if (team > 1 || rccl > 0)
+        return -1;
+      const size_t npts = xyz.size() / size_t(dim);
+      values.assign(which.size() * npts * size_t(dim), 0.0);
+      if (cells)
+        cells->assign(npts, -1);
+      int64_t n_outside = 0;
+      check(mi_evaluate_points(ctx_, int(which.size()), which.data(), int64_t(npts), xyz.data(), values.data(), nullptr,
+                               cells ? cells->data() : nullptr, &n_outside),
+            "mi_evaluate_points");
+      return n_outside;
+    }
     void    check(int rc, const char *what) const
     {
       if (rc != MI_OK)

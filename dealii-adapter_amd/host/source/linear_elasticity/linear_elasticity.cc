@@ -202,6 +202,7 @@ namespace Linear_Elasticity
   {
     make_grid();
     setup_system();
+    probes.open(*device, dim, MI_L_DISPLACEMENT, MI_L_VELOCITY);
     output_results();
 
     adapter.initialize(DoFSource{device.get()}, displacement);
@@ -249,6 +250,8 @@ namespace Linear_Elasticity
 
         adapter.reload_old_state_if_required(state_variables, time);
 
+        if (adapter.precice.isTimeWindowComplete())
+          probes.write(time.current());
         if (adapter.precice.isTimeWindowComplete() && parameters.output_interval > 0 &&
             time.get_timestep() % parameters.output_interval == 0)
           output_results();

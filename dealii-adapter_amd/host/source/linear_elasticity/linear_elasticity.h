@@ -13,6 +13,7 @@
 #include <adapter/parameters.h>
 #include <adapter/time_handler.h>
 #include <mi/device_vector.h>
+#include <mi/probe_log.h>
 #include <mi/timer_output.h>
 
 namespace Linear_Elasticity
@@ -58,6 +59,7 @@ namespace Linear_Elasticity
     bool                        solver_type_set = false; // "Solver type = Direct" passed on to the library
     mi::Vector                  old_velocity, velocity, old_displacement, displacement, old_stress, stress;
     std::vector<mi::Vector *>   state_variables;
+    mi::ProbeLog                probes; // MI_PROBES=<file>: u and v at the file's points, one row of probes.log per completed window
 
     mutable mi::TimerOutput timer;
     Adapter::Time           time;

@@ -52,6 +52,7 @@ namespace Nonlinear_Elasticity
   {
     make_grid();
     system_setup();
+    probes.open(*device, dim, MI_V_TOTAL_DISPLACEMENT, MI_V_VELOCITY);
     output_results();
 
     adapter.initialize(DoFSource{device.get()}, total_displacement);
@@ -82,6 +83,8 @@ namespace Nonlinear_Elasticity
 
         adapter.reload_old_state_if_required(state_variables, time);
 
+        if (adapter.precice.isTimeWindowComplete())
+          probes.write(time.current());
         if (adapter.precice.isTimeWindowComplete() && parameters.output_interval > 0 &&
             time.get_timestep() % parameters.output_interval == 0)
           output_results();

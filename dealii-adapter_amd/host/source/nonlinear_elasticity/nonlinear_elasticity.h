@@ -13,6 +13,7 @@
 #include <adapter/parameters.h>
 #include <adapter/time_handler.h>
 #include <mi/device_vector.h>
+#include <mi/probe_log.h>
 #include <mi/timer_output.h>
 
 namespace Nonlinear_Elasticity
@@ -63,6 +64,7 @@ namespace Nonlinear_Elasticity
     mi::Vector total_displacement, total_displacement_old, velocity, velocity_old, acceleration, acceleration_old,
       external_stress;
     std::vector<mi::Vector *> state_variables;
+    mi::ProbeLog              probes; // MI_PROBES=<file>: u and v at the file's points, one row of probes.log per completed window
 
     mutable mi::TimerOutput timer;
     Adapter::Time           time;

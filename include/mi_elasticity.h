@@ -268,6 +268,41 @@ typedef struct
 int mi_stress_error(mi_ctx *ctx, int model, mi_stress_error_info *out, double *eta_cell /* [n_cells] or NULL */,
                     double *norm_cell /* [n_cells] or NULL */);
 
+/* Fields at arbitrary points: u_h(X) = sum_a N_a(xi) u_a at npts points X of the REFERENCE configuration, for n_which state
+ * vectors at once (which[]: MI_V_* / MI_L_* ids, 1 <= n_which <= MI_V_COUNT; the vectors as they are, nothing is committed or
+ * combined).  xi is the pre-image of X under the d-linear (Q1) map of the cell's (perturbed) vertices, the map the support
+ * points of mi_get_node_coords are placed with; N_a the element's Lagrange basis, evaluated at that xi without clamping.
+ *   xyz [npts][dim]; values [n_which][npts][dim]; gradients [n_which][npts][dim][dim] = d u_c / d X_d, or NULL; cell [npts] the
+ *   lexicographic id of the cell that answered (x fastest, as mi_stress_error), -1 = outside, or NULL; n_outside or NULL.
+ * INSIDE is a definition, not a measurement: a point is in a cell when xi lies in [-1e-10, 1 + 1e-10]^dim.  On a shared face, edge
+ *   or corner any one of the containing cells may answer: the values are continuous, the gradient and `cell` are those of the
+ *   cell chosen, and the choice is deterministic -- two calls return the same bits.
+ * OUTSIDE: a point in no cell, NaN coordinates included, gets cell -1 and zeros in values / gradients and is counted in
+ *   *n_outside; the call still returns MI_OK.
+ * FOUND are all points of the mesh on meshes whose vertex offsets stay below a quarter of the smallest cell edge (every mesh the
+ *   suite builds; boxes are the closed-form case): the first guess is the cell of the unperturbed lattice, refined by a walk of at
+ *   most three cells along the directions xi leaves through and then by the 3^dim cells around the first guess; xi by Newton
+ *   on the Q1 map.  One thread per point (field_at_points), plain stores, the count by a fixed-order sum; no atomics.
+ * Modifies no state vector, record, matrix, hierarchy, counter or timing: a following mi_newmark_step / mi_linear_step returns
+ *   the bits it would have returned without the call.  Needs no matrix: every (dim, degree) an assembly supports, "fine_level"
+ *   0 and 1, after a "linear_operator" 1 set-up.  Scratch of its own, allocated on first use and grown on demand.
+ * npts = 0: MI_OK, no array is written (*n_outside = 0).  Undecomposed contexts only: an emulated or RCCL team gives MI_EINVAL
+ *   "one slab only", as mi_stress_error.  A NULL ctx, which, xyz or values, a bad vector id, npts < 0 or n_which out of range:
+ *   MI_EINVAL. */
+int mi_evaluate_points(mi_ctx *ctx, int n_which, const int *which, int64_t npts, const double *xyz, double *values,
+                       double *gradients, int64_t *cell, int64_t *n_outside);
+/* State transfer between meshes: dst's six state vectors MI_V_TOTAL_DISPLACEMENT .. MI_V_ACCELERATION_OLD := src's fields at
+ * dst's nodes, device to device.  BY DEFINITION mi_evaluate_points of src at mi_get_node_coords(dst) for the six vectors, written
+ * into dst's vectors with every dof that dst flags constrained (mi_get_constrained) set to exactly 0 -- the same kernel, the same
+ * bits as that host route, without the fields passing through the host.
+ *   Both contexts: the same dim, the same device, undecomposed; else MI_EINVAL.  A node of dst outside src's mesh: MI_EINVAL naming
+ *   the first such node, dst unchanged.
+ *   Nodal interpolation, not a projection: exact when dst's space contains src's (box meshes, dst's cells nested in src's, degree
+ *   not lower); any other pair is allowed (a coarser or lower-order dst samples src).
+ *   Writes nothing else in dst (external stress, delta, update, rhs keep their values) and nothing in src.  Meant for a fresh dst
+ *   before its first step; on a stepped dst it has the consequences mi_vec_set of those vectors has. */
+int mi_state_transfer(mi_ctx *dst, mi_ctx *src);
+
 /* ---- linear model: ElastoDynamics (source/linear_elasticity/linear_elasticity.cc) -------------------------- */
 /* state vectors of the linear model live in the same slots as the nonlinear ones */
 enum
