@@ -82,6 +82,14 @@ class StressErrorInfo(C.Structure):
                 ("max_cell", C.c_int64), ("reserved", C.c_int64)]
 
 
+class ReactionInfo(C.Structure):
+    _VECTORS = ("about", "reaction", "reaction_moment", "unbalanced", "unbalanced_moment", "inertia", "inertia_moment", "body",
+                "body_moment", "load", "load_moment")
+    _fields_ = ([(k, C.c_double * 3) for k in _VECTORS] +
+                [("internal_abs", C.c_double), ("max_unbalanced", C.c_double), ("max_reaction", C.c_double),
+                 ("max_reaction_node", C.c_int64)])
+
+
 class MiError(RuntimeError):
     def __init__(self, code, msg, partial=None):
         super().__init__("mi_elasticity error %d: %s" % (code, msg))
@@ -164,6 +172,8 @@ def lib():
         L.mi_stress_field.restype = C.c_int
         L.mi_stress_error.argtypes = [vp, C.c_int, C.POINTER(StressErrorInfo), dp, dp]
         L.mi_stress_error.restype = C.c_int
+        L.mi_reactions.argtypes = [vp, C.c_int, dp, C.POINTER(ReactionInfo), dp, dp]
+        L.mi_reactions.restype = C.c_int
         L.mi_evaluate_points.argtypes = [vp, C.c_int, C.POINTER(C.c_int), C.c_int64, dp, dp, dp, C.POINTER(C.c_int64),
                                          C.POINTER(C.c_int64)]
         L.mi_evaluate_points.restype = C.c_int
@@ -512,6 +522,22 @@ class Context:
         self._chk(lib().mi_stress_error(self.h, model, C.byref(info), _dp(eta) if cells else None, _dp(nrm) if cells else None))
         return dict(error=info.error, norm=info.norm, relative=info.relative, max_cell_error=info.max_cell_error,
                     max_cell=int(info.max_cell), eta_cell=eta, norm_cell=nrm)
+
+    def reactions(self, model=STRESS_NEOHOOKE, about=None, forces=True, terms=False):
+        """support reactions and load resultants of the committed state (mi_reactions): a dict of the struct's fields -- about,
+        reaction, unbalanced, inertia, body, load and their *_moment as arrays of 3; internal_abs, max_unbalanced, max_reaction,
+        max_reaction_node -- plus forces [n] = internal + inertia - body - load on every dof and terms [4, n] = internal,
+        inertia, body, load (None unless asked).  about: the point the moments are taken about (default: the origin)"""
+        info = ReactionInfo()
+        x0 = None if about is None else np.ascontiguousarray(about, dtype=np.float64).reshape(self.dim)
+        f = np.zeros(self.n) if forces else None
+        t = np.zeros((4, self.n)) if terms else None
+        self._chk(lib().mi_reactions(self.h, model, None if x0 is None else _dp(x0), C.byref(info), _dp(f) if forces else None,
+                                     _dp(t) if terms else None))
+        out = {k: np.array(getattr(info, k)) for k in ReactionInfo._VECTORS}
+        out.update(internal_abs=info.internal_abs, max_unbalanced=info.max_unbalanced, max_reaction=info.max_reaction,
+                   max_reaction_node=int(info.max_reaction_node), forces=f, terms=t)
+        return out
 
     def evaluate(self, which, points, gradients=False):
         """(values, gradients, cell, n_outside) of the state vectors `which` (one V_* / L_* id or a sequence) at the points

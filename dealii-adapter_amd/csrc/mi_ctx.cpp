@@ -1323,6 +1323,15 @@ namespace mi_detail
   }
 
   // ---- nodal stress recovery (mi_stress_field) -----------------------------------------------------------------
+  // the 1D tables of the linear model's rule, on first use (enqueue_stress, enqueue_reactions)
+  static int stress_tab_prepare(mi_ctx *c)
+  {
+    if (c->d_stress_tab)
+      return MI_OK;
+    mi::Tables1D t;
+    t.build(c->degree, c->degree + 1); // quad_order = degree + 1, linear_elasticity.cc:61
+    return upload(c, &c->d_stress_tab, t.packed());
+  }
   // One slab's lumped projection, enqueued: the accumulator zeroed, the local cells colour by colour (ghost layer included:
   // like the residual pass on system_rhs, that completes every OWNED node -- the nodes of the slab's first plane, owned by the
   // slab below, and of the ghost planes stay partial and are never read), then stress_finish.  d_stress: [nnodes][8] accumulator,
@@ -1332,13 +1341,9 @@ namespace mi_detail
     const size_t nn = size_t(c->mesh.nnodes), ncomp = size_t(c->dim * (c->dim + 1) / 2);
     if (!c->d_stress)
       HIPCHK(c, hipMalloc((void **)&c->d_stress, nn * (8 + ncomp + 2) * sizeof(double)));
-    if (model == MI_STRESS_LINEAR && !c->d_stress_tab)
-      {
-        mi::Tables1D t;
-        t.build(c->degree, c->degree + 1); // quad_order = degree + 1, linear_elasticity.cc:61
-        if (int rc = upload(c, &c->d_stress_tab, t.packed()))
-          return rc;
-      }
+    if (model == MI_STRESS_LINEAR)
+      if (int rc = stress_tab_prepare(c))
+        return rc;
     if (int rc = energy_box_prepare(c))
       return rc;
     HIPCHK(c, hipMemsetAsync(c->d_stress, 0, nn * 8 * sizeof(double), c->stream));
@@ -1394,6 +1399,92 @@ namespace mi_detail
     double *scratch = c->d_stress_err + nc * 3, *eta = scratch + (nc / 1024 + 1) * 3, *res = c->d_stress_err + stress_err_results(c);
     mi::launch_energy_sum(c->d_stress_err, int64_t(nc), scratch, res, c->stream);
     mi::launch_stress_error_finish(c->d_stress_err, c->d_cell_orig, int64_t(nc), eta, eta + nc, scratch, res + 3, c->stream);
+    HIPCHK(c, hipGetLastError());
+    return MI_OK;
+  }
+
+  // ---- nodal forces, reactions and resultants (mi_reactions) -------------------------------------------------------------
+  // Enqueued on the context's stream: the accumulator zeroed, the cells colour by colour (launch_nodal_force), the traction term
+  // (model 0: neumann_faces of ALL interface faces into slots of the call's own -- committed displacement, the context's
+  // "correct_face_F" -- and the gather without the mask; model 1: the load vector MI_L_OLD_STRESS as it is), the four terms and
+  // their balance per dof, the resultants.  d_react: accumulator [nnodes][8] | load [n] | terms [4][n] | forces [n] | face slots |
+  // chunk results [(nnodes / 1024 + 1)][REACT_NOUT] | result [REACT_NOUT].  The inverted flag is enqueue_stress's slot
+  struct ReactBuffers
+  {
+    double *acc, *load, *terms, *forces, *slots, *chunks, *result;
+  };
+  static size_t react_carve(const mi_ctx *c, double *base, ReactBuffers &b) // returns the doubles the call needs
+  {
+    const size_t nn = size_t(c->mesh.nnodes), n = size_t(c->n);
+    const size_t ns = std::max<size_t>(1, c->mesh.iface_faces.size() * size_t(c->mesh.npc) * size_t(c->dim));
+    const size_t o_load = nn * 8, o_terms = o_load + n, o_forces = o_terms + 4 * n, o_slots = o_forces + n, o_chunks = o_slots + ns;
+    const size_t o_result = o_chunks + (nn / 1024 + 1) * size_t(mi::REACT_NOUT);
+    if (base)
+      b = ReactBuffers{base, base + o_load, base + o_terms, base + o_forces, base + o_slots, base + o_chunks, base + o_result};
+    return o_result + size_t(mi::REACT_NOUT);
+  }
+  static int enqueue_reactions(mi_ctx *c, int model, const double about[3])
+  {
+    const size_t nn = size_t(c->mesh.nnodes), n = size_t(c->n);
+    ReactBuffers b{};
+    const size_t total = react_carve(c, c->d_react, b);
+    if (!c->d_react)
+      {
+        HIPCHK(c, hipMalloc((void **)&c->d_react, total * sizeof(double)));
+        react_carve(c, c->d_react, b);
+      }
+    if (!c->d_node_xyz)
+      if (int rc = upload(c, &c->d_node_xyz, c->mesh.node_xyz))
+        return rc;
+    if (model == MI_STRESS_LINEAR)
+      if (int rc = stress_tab_prepare(c))
+        return rc;
+    if (int rc = energy_box_prepare(c))
+      return rc;
+    HIPCHK(c, hipMemsetAsync(b.acc, 0, (nn * 8 + n) * sizeof(double), c->stream)); // accumulator and load
+    HIPCHK(c, hipMemsetAsync(c->d_sc + SC_ENERGY + 3, 0, sizeof(double), c->stream));
+    mi::ReactionParams rp{};
+    const mi::MfParams f = post_params(c, model, rp);
+    rp.lambda = lame_lambda(c), rp.rho = c->mat.rho;
+    rp.acc    = b.acc;
+    if (model == MI_STRESS_LINEAR) // a = (v - v_old) / dt
+      rp.a0 = c->vec(MI_L_VELOCITY), rp.a1 = c->vec(MI_L_OLD_VELOCITY), rp.dt = c->nm.delta_t;
+    else
+      rp.a0 = c->vec(MI_V_ACCELERATION), rp.a1 = nullptr, rp.dt = 1.0;
+    static const bool generic = post_generic("MI_REACTIONS_GENERIC");
+    for (int col = 0; col < c->mesh.ncolours; ++col)
+      {
+        rp.cell_begin = c->mesh.colour_begin[col];
+        rp.cell_count = int32_t(c->mesh.colour_begin[col + 1] - c->mesh.colour_begin[col]);
+        if (mi::launch_nodal_force(c->dim, c->degree, model, f, rp, generic, c->stream))
+          return fail(c, MI_EINVAL, "no nodal force kernel for dim=%d degree=%d", c->dim, c->degree);
+      }
+    if (model == MI_STRESS_LINEAR)
+      {
+        const double *f_old = c->vec(MI_L_OLD_STRESS); // the load vector F of the last step
+        HIPCHK(c, hipMemcpyAsync(b.load, f_old, n * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+      }
+    else if (c->n_fn > 0)
+      {
+        mi::AsmParams p = asm_params(c);
+        p.du            = b.load; // zeros until the gather below writes it: the faces see the committed displacement alone
+        p.face_slots    = b.slots;
+        p.inverted      = c->d_sc + SC_ENERGY + 3;
+        if (mi::launch_neumann_faces(c->dim, c->degree, p, c->d_faces, 0, int(c->mesh.iface_faces.size()), c->stream))
+          return fail(c, MI_EINVAL, "no face kernel for dim=%d degree=%d", c->dim, c->degree);
+        mi::launch_nodal_force_gather(c->dim, b.slots, c->d_fn_ids, c->d_fn_start, c->d_fn_src, b.load, c->n_fn, c->stream);
+      }
+    double rho_body[3] = {0.0, 0.0, 0.0};
+    if (model == MI_STRESS_NEOHOOKE)
+      for (int d = 0; d < c->dim; ++d)
+        rho_body[d] = c->mat.rho * c->mat.body_force[d];
+    mi::launch_nodal_force_finish(c->dim, b.acc, b.load, int64_t(nn), rho_body, b.terms, b.forces, c->stream);
+    mi::ReactionSumParams sp{};
+    sp.forces = b.forces, sp.terms = b.terms, sp.xyz = c->d_node_xyz, sp.cmask = c->d_cmask, sp.n = int64_t(n);
+    sp.u = model == MI_STRESS_NEOHOOKE ? c->vec(MI_V_TOTAL_DISPLACEMENT) : nullptr;
+    for (int d = 0; d < 3; ++d)
+      sp.about[d] = about[d];
+    mi::launch_reaction_sums(c->dim, sp, int64_t(nn), b.chunks, b.result, c->stream);
     HIPCHK(c, hipGetLastError());
     return MI_OK;
   }
@@ -2116,7 +2207,7 @@ namespace mi_detail
                     c->d_pred[0][0], c->d_pred[0][1], c->d_pred[1][0], c->d_pred[1][1], c->d_pred[2][0], c->d_pred[2][1], c->d_pred[3][0], c->d_pred[3][1],
                     c->d_pred_saved[0][0], c->d_pred_saved[0][1], c->d_pred_saved[1][0], c->d_pred_saved[1][1], c->d_pred_saved[2][0],
                     c->d_pred_saved[2][1], c->d_pred_saved[3][0], c->d_pred_saved[3][1], c->d_energy, c->d_energy_box,
-                    c->d_stress, c->d_stress_tab, c->d_stress_err, c->d_cell_orig, c->d_cell_pos, c->d_pe, c->d_node_xyz};
+                    c->d_stress, c->d_stress_tab, c->d_stress_err, c->d_cell_orig, c->d_cell_pos, c->d_pe, c->d_node_xyz, c->d_react};
     for (void *p : ptrs)
       if (p)
         hipFree(p);
@@ -2966,6 +3057,54 @@ int mi_stress_error(mi_ctx *c, int model, mi_stress_error_info *out, double *eta
   out->max_cell_error = h[3];
   out->max_cell       = int64_t(h[4]);
   out->reserved       = 0;
+  return MI_OK;
+}
+
+// What the supports carry and whether the structure is in balance with its loads: the unmasked nodal forces of the committed
+// state term by term, their balance per dof, and the resultants and moments of reaction, unbalanced force, inertia, body force
+// and load in a fixed order.  One read-back of the results and the flag, the nodal arrays only where wanted.  Undecomposed
+// contexts only: a slab's first node plane holds partial sums.  No timing slot, no counter
+int mi_reactions(mi_ctx *c, int model, const double *about, mi_reaction_info *out, double *forces, double *terms)
+{
+  if (!c)
+    return MI_EINVAL;
+  if (!out)
+    return fail(c, MI_EINVAL, "mi_reactions: null argument");
+  if (model != MI_STRESS_NEOHOOKE && model != MI_STRESS_LINEAR)
+    return fail(c, MI_EINVAL, "mi_reactions: model %d (0: the Newmark model's committed state, 1: the linear model's)", model);
+  if (team_size(c) != 1)
+    return fail(c, MI_EINVAL, "mi_reactions: one slab only (an undecomposed mesh)");
+  HIPCHK(c, hipSetDevice(c->device));
+  double x0[3] = {0.0, 0.0, 0.0};
+  for (int d = 0; about && d < c->dim; ++d)
+    x0[d] = about[d];
+  if (const int rc = enqueue_reactions(c, model, x0))
+    return rc;
+  ReactBuffers b{};
+  react_carve(c, c->d_react, b);
+  const size_t n = size_t(c->n);
+  double       h[mi::REACT_NOUT + 1];
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipMemcpy(h, b.result, mi::REACT_NOUT * sizeof(double), hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(h + mi::REACT_NOUT, c->d_sc + SC_ENERGY + 3, sizeof(double), hipMemcpyDeviceToHost));
+  if (h[mi::REACT_NOUT] > 0.0) // the same error as an assembly of this state gives
+    return fail(c, MI_EINVAL, "inverted element: det F <= 0 at a quadrature point (the displacement has folded a cell; the "
+                              "reference asserts det F > 0, nonlinear_elasticity.cc:935)");
+  if (forces)
+    HIPCHK(c, hipMemcpy(forces, b.forces, n * sizeof(double), hipMemcpyDeviceToHost));
+  if (terms)
+    HIPCHK(c, hipMemcpy(terms, b.terms, 4 * n * sizeof(double), hipMemcpyDeviceToHost));
+  double *dst[10] = {out->reaction, out->reaction_moment, out->unbalanced, out->unbalanced_moment, out->inertia,
+                     out->inertia_moment, out->body, out->body_moment, out->load, out->load_moment};
+  for (int k = 0; k < 10; ++k)
+    for (int d = 0; d < 3; ++d)
+      dst[k][d] = h[k * 3 + d];
+  for (int d = 0; d < 3; ++d)
+    out->about[d] = x0[d];
+  out->internal_abs      = h[mi::REACT_NSUMS - 1];
+  out->max_unbalanced    = h[mi::REACT_NSUMS];
+  out->max_reaction      = h[mi::REACT_NSUMS + 1];
+  out->max_reaction_node = int64_t(h[mi::REACT_NSUMS + 2]);
   return MI_OK;
 }
 

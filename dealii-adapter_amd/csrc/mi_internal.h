@@ -265,6 +265,9 @@ struct mi_ctx
   double   *d_pe         = nullptr;
   size_t    pe_doubles   = 0;
   double   *d_node_xyz   = nullptr;
+  // nodal forces and reactions (mi_reactions), allocated on first use: accumulator [nnodes][8] | load [n] | terms [4][n] |
+  // forces [n] | face slots of its own (the size of d_face_slots) | chunk results | the result (mi::REACT_NOUT); reads d_node_xyz
+  double   *d_react      = nullptr;
   uint16_t *d_off   = nullptr;
   uint8_t  *d_cmask = nullptr;
   double   *h_pinned = nullptr; // pinned host scratch (scalars, flags, interface buffer)

@@ -273,6 +273,35 @@ namespace mi
     double        *inverted;  // as StressParams::inverted
   };
 
+  // nodal forces (see nodal_force_cells): the state, the acceleration field, the material, the accumulator, the colour's cells.
+  // Mesh tables, 1D tables and geometry as StressParams
+  struct ReactionParams
+  {
+    const int32_t *conn;   // [ncells][npc] colour-sorted
+    const double  *cverts; // [ncells][2^dim][dim]
+    const double  *tab;    // the 1D tables of the model's rule, as StressParams::tab
+    const double  *u;      // total displacement (the committed state)
+    const double  *a0, *a1; // the nodal acceleration: a0 (a1 null: MI_V_ACCELERATION) or (a0 - a1) / dt (the linear model's velocities)
+    double         dt;
+    double         mu, kappa, lambda, rho;
+    double        *acc;      // [nnodes][8]: internal force (3), inertia force (3), sum of N_i w, one spare; zeroed by the caller
+    double        *inverted; // as StressParams::inverted
+    int64_t        cell_begin; // the cells of ONE colour: no two of them share a node
+    int32_t        cell_count;
+  };
+  // resultants of the nodal forces (see reaction_sums).  A workgroup's result: REACT_NSUMS sums -- force and moment (6 each) of
+  // reaction, unbalanced, inertia, body, load, then sum |internal| -- the largest unbalanced entry, the largest nodal reaction and
+  // its node
+  constexpr int REACT_NSUMS = 31, REACT_NOUT = 34;
+  struct ReactionSumParams
+  {
+    const double  *forces, *terms; // [n], [4][n] of nodal_force_finish
+    const double  *xyz, *u;        // node coordinates [nnodes][dim]; the displacement added to them, or null (linear model)
+    const uint8_t *cmask;          // [nnodes] bit c: dof (node, c) is constrained
+    int64_t        n;              // dofs
+    double         about[3];
+  };
+
   // fields at arbitrary points (see field_at_points): the points, the mesh they are looked up in, the state vectors wanted and
   // where the answers go.  All pointers are device memory
   constexpr int PE_MAX_VECTORS = 10; // MI_V_COUNT
@@ -469,6 +498,17 @@ namespace mi
   // sigma[nnodes][dim (dim + 1) / 2] = acc / W, von_mises[nnodes] of that tensor, weight[nnodes] = W
   int  launch_stress(int dim, int degree, int model, const MfParams &p, const StressParams &sp, bool generic, hipStream_t s);
   void launch_stress_finish(int dim, const double *acc, int64_t nnodes, double *sigma, double *von_mises, double *weight, hipStream_t s);
+  // mi_reactions.  launch_nodal_force: one colour of cells into rp.acc by nodal_force_cells (every element, both models); -1: no
+  // kernel for the element.  launch_nodal_force_gather: the face slots of neumann_faces into `load` on every dof of the interface
+  // nodes.  launch_nodal_force_finish: terms [4][n] and forces [n] from the accumulator and the load (rho_body: rho b, or zeros).
+  // launch_reaction_sums: the resultants into out[REACT_NOUT], chunks of 1,024 nodes into scratch [(nnodes / 1024 + 1)][REACT_NOUT]
+  // first
+  int  launch_nodal_force(int dim, int degree, int model, const MfParams &p, const ReactionParams &rp, bool generic, hipStream_t s);
+  void launch_nodal_force_gather(int dim, const double *slots, const int32_t *node_ids, const int32_t *start, const int32_t *src,
+                                 double *load, int nnodes_if, hipStream_t s);
+  void launch_nodal_force_finish(int dim, const double *acc, const double *load, int64_t nnodes, const double rho_body[3], double *terms,
+                                 double *forces, hipStream_t s);
+  void launch_reaction_sums(int dim, const ReactionSumParams &p, int64_t nnodes, double *scratch, double *out, hipStream_t s);
   // stress error indicator: all cells in one launch store their two sums into ep.cell_e, by the kernel of (dim, degree, model)
   // -- stress_error_q3, stress_error_q2 (model 0; p.conn, p.tab1d, p.cverts / p.cellbox) or stress_error_cells; generic:
   // stress_error_cells on 3D Q2 / Q3 too (cross-check).  -1: no kernel for the element.  launch_stress_error_finish:

@@ -4874,9 +4874,10 @@ namespace mi
   // point q: G = grad_xi u Jinv embedded in 3 x 3 (the displacement gradient), w = JxW, and the values v0[N0], v1[N1] of two
   // further staged fields s_f0[a * N0 + k], s_f1[a * N1 + k] (N = 0: none) -- plain loops over the cell's nodes as in phase A
   // of assemble_cells
+  // (Ji: the inverse Jacobian of the cell map there, embedded, for a caller that contracts gradients back -- nodal_force_cells)
   template <int DIM, int P, int NQ1, int N0, int N1>
   __device__ __forceinline__ void post_cell_point(const PostCell<DIM, P, NQ1> &sc, const int q, const double *s_f0, const double *s_f1,
-                                                  double *v0, double *v1, double G[9], double &w)
+                                                  double *v0, double *v1, double G[9], double Ji[9], double &w)
   {
     double gxi[9];
 #pragma unroll
@@ -4912,7 +4913,7 @@ namespace mi
         xi[d] = sc.qx[qi[d]];
         wq *= sc.qw[qi[d]];
       }
-    double Jg[9], Ji[9];
+    double Jg[9];
     q1_jacobian<DIM>(sc.verts, xi, Jg);
     const double detJ = det3x3(Jg);
     inv3x3(Jg, detJ, Ji);
@@ -4924,6 +4925,13 @@ namespace mi
                                                 (DIM == 3 ? gxi[i * 3 + 2] * Ji[2 * 3 + j] : 0.0) :
                                               0.0;
     w = detJ * wq;
+  }
+  template <int DIM, int P, int NQ1, int N0, int N1>
+  __device__ __forceinline__ void post_cell_point(const PostCell<DIM, P, NQ1> &sc, const int q, const double *s_f0, const double *s_f1,
+                                                  double *v0, double *v1, double G[9], double &w)
+  {
+    double Ji[9];
+    post_cell_point<DIM, P, NQ1, N0, N1>(sc, q, s_f0, s_f1, v0, v1, G, Ji, w);
   }
   // F = I + G in place, J = det F, J^(-2/d), 1/J
   template <int DIM>
@@ -5359,6 +5367,566 @@ namespace mi
         von_mises[i] = sqrt(s[0] * s[0] - s[0] * s[1] + s[1] * s[1] + 3.0 * s[3] * s[3]);
       }
     weight[i] = W;
+  }
+
+  // ------------------------------------------------------------------ nodal forces, reactions and resultants (mi_reactions)
+  // The UNMASKED nodal forces of a state, term by term (every node, constrained dofs too):
+  //   internal_i = sum_cells sum_q P(q) grad_X N_i JxW    P = tau(F) F^-T (model 0, qf_cell = QGauss(p + 2), nonlinear_elasticity.cc:74)
+  //                                                       P = lambda tr(eps) I + 2 mu eps (model 1, QGauss(p + 1), linear_elasticity.cc:61)
+  //   inertia_i  = rho sum N_i a_h JxW                    W_i = sum N_i JxW (the lumped weight of the stress recovery)
+  // A cell kernel is the forward half of the stress kernels with the acceleration as a value field, the point stage, and a back
+  // half that contracts GRADIENTS (the dim x dim field P Jinv^T JxW against d N_i / d xi) and VALUES (rho a_h JxW and JxW against
+  // N_i).  It adds to acc[nnodes][8] = internal (3), inertia (3), W, one spare -- colour by colour with plain loads and stores, the
+  // colours in order on one stream, as the stress kernels: the order of the sums depends on the mesh alone, a call repeats bit
+  // by bit; no atomics.  A point with det F <= 0 (model 0) raises *inverted and contributes no internal force.
+  // The traction term is neumann_faces into slots of the call's own and nodal_force_gather, the gather without the constraint
+  // mask.  nodal_force_finish forms the four terms and their balance per dof, reaction_sums the resultants, moments and maxima
+  // in a fixed order.
+
+  // Forms, chosen by launch_nodal_force as launch_stress chooses: nodal_force_q2, nodal_force_q3 (3D, model 0) and
+  // nodal_force_cells (every other element, all of model 1, and the cross-check of the two).
+
+  // the point stage of the two sum-factorised forms, the residual's (mf_point_pass_q3): F from H and the cell's geometry, tau of
+  // neo_hooke_from_F, M = Jinv F^-1, w = JxW;  g[c * 3 + l] = w (tau M^T)[c][l] -- P Jinv^T JxW with P = tau F^-T --,
+  // g[9 + c] = rho w a[c], g[12] = w
+  constexpr int NF_FIELDS = 13;
+  template <bool BOX>
+  __device__ __forceinline__ void nodal_force_point(const MfParams &prm, const ReactionParams &rp, const int64_t cell, const double *tw,
+                                                    const double *tx, const int qx, const int qy, const int qz, const double (&H)[3][3],
+                                                    const double (&aq)[3], double (&g)[NF_FIELDS])
+  {
+    const double wq = tw[qx] * tw[qy] * tw[qz];
+    double       Ji[9], detJ;
+    mf_geometry<BOX>(prm, cell, tx, qx, qy, qz, Ji, detJ);
+    MF_RECORD_TAIL(false, false, static_cast<double *>(nullptr), 1)
+    const bool ok = J > 0.0;
+    if (!ok) // inverted element (nonlinear_elasticity.cc:935 asserts det F > 0)
+      *rp.inverted = 1.0;
+    double Finv[9], tau[6], tiso[6], cII, cS, M[9];
+    neo_hooke_from_F<3>(F, J, Jm, rJ, rp.mu, rp.kappa, Finv, tau, tiso, cII, cS);
+    MF_M(BOX, i_, j_)
+    const double w       = detJ * wq;
+    const double T[3][3] = {{tau[0], tau[3], tau[4]}, {tau[3], tau[1], tau[5]}, {tau[4], tau[5], tau[2]}};
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+      {
+#pragma unroll
+        for (int l = 0; l < 3; ++l)
+          g[i * 3 + l] = ok ? w * fma(T[i][2], M[l * 3 + 2], fma(T[i][1], M[l * 3 + 1], T[i][0] * M[l * 3])) : 0.0;
+        g[9 + i] = rp.rho * w * aq[i];
+      }
+    g[12] = w;
+    (void)tiso, (void)cII, (void)cS;
+  }
+
+  // 3D Q2, model 0: one wave per cell, lane = point of the 4 x 4 x 4 rule.  Forward: postq2_forward on u with the acceleration as
+  // its value-only field.  Backward through LDS, the transposes of E3 and E12 as mf_spmv carries them, thirteen fields: B3
+  // contracts qz (item = (k, qy, qx), 48 per field), B12 contracts qy and qx (lane = node (i, j, k), 27 lanes); gradient field
+  // (c, l) takes D[q][a] = N_a'(x_q) along direction l and S[q][a] = N_a(x_q) along the others, a value field S along all
+  // three.  sG lies over sB and sBv (E3 and E3' have consumed them, a barrier between).
+  // Launch bounds: 12.9 kB of LDS per wave hold twelve workgroups on a CU, three waves per SIMD; 122 registers would allow four.
+  template <bool BOX>
+  __global__ __launch_bounds__(64, 3) void nodal_force_q2(MfParams prm, ReactionParams rp)
+  {
+    constexpr int NPC = PQ2_NPC, PW = PQ2_PW, NF = NF_FIELDS;
+    static_assert(4 * PW <= NF * 64, "sG covers sB and sBv");
+    __shared__ double sX[3 * NPC], sXv[3 * NPC], sL[NF * 64 + NF * 48];
+    double *const sB = sL, *const sBv = sL + 3 * PW, *const sG = sL, *const sC = sL + NF * 64;
+    const int     lane = threadIdx.x, q16 = lane & 15;
+    const int64_t cell = rp.cell_begin + blockIdx.x;
+    int32_t       node;
+    double        H[3][3], V[3], Sz[3], g[NF];
+    postq2_forward<3>(prm, cell, rp.u, rp.a0, sX, sXv, sB, sBv, node, H, V, Sz);
+    {
+      double aq[3];
+      postq2_values_e3<3, true>(Sz, sBv, q16, aq);
+      nodal_force_point<BOX>(prm, rp, cell, prm.tab1d + 24, prm.tab1d + 28, lane & 3, (lane >> 2) & 3, lane >> 4, H, aq, g);
+      (void)V;
+    }
+    __syncthreads(); // every lane has read sB and sBv: sG may overwrite them
+#pragma unroll
+    for (int f = 0; f < NF; ++f)
+      sG[f * 64 + lane] = g[f];
+    __syncthreads();
+    // ---- B3: item (k, q16), lanes 0..47: C_f[k][q16] = sum_qz T[qz][k] g_f(qz, q16), T = D for the fields (c, 2), else S
+    if (lane < 48)
+      {
+        const int k = lane >> 4;
+        double    s[4], d[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+          {
+            s[q] = prm.tab1d[q * 3 + k];
+            d[q] = prm.tab1d[12 + q * 3 + k];
+          }
+#pragma unroll
+        for (int f = 0; f < NF; ++f)
+          {
+            const bool    dz = f < 9 && f % 3 == 2;
+            const double *gf = sG + f * 64 + q16;
+            sC[f * 48 + lane] = dz ? d[0] * gf[0] + d[1] * gf[16] + d[2] * gf[32] + d[3] * gf[48] :
+                                     s[0] * gf[0] + s[1] * gf[16] + s[2] * gf[32] + s[3] * gf[48];
+          }
+      }
+    __syncthreads();
+    // ---- B12: lane = node (i, j, k): sum_qy Ty[qy][j] sum_qx Tx[qx][i] C_f[k][qy][qx], then into the accumulator
+    if (lane < NPC)
+      {
+        const int i = lane % 3, j = (lane / 3) % 3, k = lane / 9;
+        double    si[4], sj[4], di[4], dj[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+          {
+            si[q] = prm.tab1d[q * 3 + i];
+            sj[q] = prm.tab1d[q * 3 + j];
+            di[q] = prm.tab1d[12 + q * 3 + i];
+            dj[q] = prm.tab1d[12 + q * 3 + j];
+          }
+        double r[NF];
+#pragma unroll
+        for (int f = 0; f < NF; ++f)
+          {
+            const bool dx = f < 9 && f % 3 == 0, dy = f < 9 && f % 3 == 1;
+            r[f] = 0.0;
+#pragma unroll
+            for (int qy = 0; qy < 4; ++qy)
+              {
+                const double *c4 = sC + f * 48 + k * 16 + qy * 4;
+                const double  cx = dx ? di[0] * c4[0] + di[1] * c4[1] + di[2] * c4[2] + di[3] * c4[3] :
+                                        si[0] * c4[0] + si[1] * c4[1] + si[2] * c4[2] + si[3] * c4[3];
+                r[f] = fma(dy ? dj[qy] : sj[qy], cx, r[f]);
+              }
+          }
+        double *__restrict__ o = rp.acc + int64_t(node) * 8;
+#pragma unroll
+        for (int c = 0; c < 3; ++c)
+          {
+            o[c] += (r[c * 3] + r[c * 3 + 1]) + r[c * 3 + 2];
+            o[3 + c] += r[9 + c];
+          }
+        o[6] += r[12];
+      }
+  }
+
+  // 3D Q3, model 0: 128 threads per cell, thread = point of the 5 x 5 x 5 rule (threads 125-127 contribute exact zeros).
+  // Forward: the gathers, the acceleration through postq3_values (the second wave, as energy_q3 takes the velocity),
+  // mfq3_gradients on u.  Backward in the LDS places of the point pass, the gradient fields first, then the four value fields:
+  //   g   [f][point]                                                   R0, 13 x MFQ3_QS (rows 0-8 gradients (c, l), 9-12 values)
+  //   I3  item (c, qy, qx):  contract qz -> C_DS / C_SD / C_SS [c,k]   R1, 900 doubles (the transposes mf_point_pass_q3 carries)
+  //   I2  item (c, k, qx):   contract qy -> E_D / E_S [c,k,j][qx]      R0 over rows 0-3, 480 doubles
+  //   I1  item (c, k, j):    contract qx -> internal force of the line's four nodes, into the accumulator
+  //   I3' item (f, qy, qx):  contract qz -> C [f,k][qy][qx]            R1, 400 doubles (beside I1: I2 has consumed R1)
+  //   I2' item (f, k, qx):   contract qy -> E [f,k,j][qx]              R0, 320 doubles (I1 has consumed E_D / E_S)
+  //   I1' item (f, k, j):    contract qx -> inertia force and weight of the line's four nodes, into the accumulator
+  constexpr int NFQ3_R0 = NF_FIELDS * MFQ3_QS;
+  static_assert(MFQ3_VB + 300 <= NFQ3_R0 && 9 * MFQ3_QS >= 480, "the value pass and E lie inside R0, E below the value rows");
+  template <bool BOX>
+  __global__ __launch_bounds__(MFQ3_NT, BOX ? 4 : 3) void nodal_force_q3(MfParams prm, ReactionParams rp)
+  {
+    __shared__ double  R0[NFQ3_R0], R1[MFQ3_R1], sT[40];
+    __shared__ int32_t sN[MFQ3_NPC];
+    const int     t    = threadIdx.x, it = t < MFQ3_NQ ? t : MFQ3_NQ - 1, qz = it / 25, q25 = it - 25 * qz;
+    const int     tv   = t - MFQ3_NPC; // the second wave's item in the value pass
+    const int64_t cell = rp.cell_begin + blockIdx.x;
+    if (t < 40)
+      sT[t] = prm.tab1d[t];
+    {
+      const int     a    = t & (MFQ3_NPC - 1);
+      const int32_t node = prm.conn[cell * MFQ3_NPC + a];
+      if (t < MFQ3_NPC)
+        {
+          sN[t] = node;
+          post_gather<3, MFQ3_NPC>(rp.u, node, R1 + a);
+        }
+      else
+        post_gather<3, MFQ3_NPC>(rp.a0, node, R0 + MFQ3_VX + a);
+    }
+    __syncthreads();
+    {
+      double vm[3];
+      postq3_values<3, true>(prm.tab1d, sT, R0 + MFQ3_VX, R0 + MFQ3_VA, R0 + MFQ3_VB, tv, qz, q25, vm);
+#pragma unroll
+      for (int c = 0; c < 3; ++c)
+        R0[MFQ3_VM + c * MFQ3_QS + t] = vm[c]; // (over X' and A', both consumed; read back by this thread alone)
+    }
+    double H[3][3], V[3];
+    mfq3_gradients(prm.tab1d, sT, R0, R1, t, it, H, V); // (writes R0 below MFQ3_VX only; ends with a barrier: R1 is free)
+    {
+      const int    qy = q25 / 5, qx = q25 - 5 * qy;
+      const double aq[3] = {R0[MFQ3_VM + t], R0[MFQ3_VM + MFQ3_QS + t], R0[MFQ3_VM + 2 * MFQ3_QS + t]};
+      double       g[NF_FIELDS];
+      nodal_force_point<BOX>(prm, rp, cell, prm.tab1d + MFQ3_TW, prm.tab1d + MFQ3_TX, qx, qy, qz, H, aq, g);
+      // (the thread's own column of every row, read above before any row of it is written; B' at MFQ3_VB is consumed)
+#pragma unroll
+      for (int f = 0; f < NF_FIELDS; ++f)
+        R0[f * MFQ3_QS + t] = t < MFQ3_NQ ? g[f] : 0.0;
+      (void)V;
+    }
+    double S[5][4], D[5][4]; // uniform: scalar registers
+#pragma unroll
+    for (int q = 0; q < 5; ++q)
+#pragma unroll
+      for (int a = 0; a < 4; ++a)
+        {
+          S[q][a] = prm.tab1d[q * 4 + a];
+          D[q][a] = prm.tab1d[MFQ3_TD + q * 4 + a];
+        }
+    __syncthreads();
+    if (t < 75) // I3
+      {
+        const int c = t / 25, p25 = t - 25 * c;
+        double    v[3][5];
+#pragma unroll
+        for (int l = 0; l < 3; ++l)
+#pragma unroll
+          for (int z = 0; z < 5; ++z)
+            v[l][z] = R0[(c * 3 + l) * MFQ3_QS + z * 25 + p25];
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+          {
+            double cds = 0.0, csd = 0.0, css = 0.0;
+#pragma unroll
+            for (int z = 0; z < 5; ++z)
+              {
+                cds = fma(S[z][k], v[0][z], cds);
+                csd = fma(S[z][k], v[1][z], csd);
+                css = fma(D[z][k], v[2][z], css);
+              }
+            const int o = (c * 4 + k) * 25 + p25;
+            R1[o] = cds, R1[300 + o] = csd, R1[600 + o] = css;
+          }
+      }
+    __syncthreads();
+    if (t < 60) // I2
+      {
+        const int ck = t / 5, qx = t - 5 * ck;
+        double    cds[5], csd[5], css[5];
+#pragma unroll
+        for (int qy = 0; qy < 5; ++qy)
+          {
+            const int o = ck * 25 + qy * 5 + qx;
+            cds[qy] = R1[o], csd[qy] = R1[300 + o], css[qy] = R1[600 + o];
+          }
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          {
+            double ed = 0.0, es = 0.0;
+#pragma unroll
+            for (int qy = 0; qy < 5; ++qy)
+              {
+                ed = fma(S[qy][j], cds[qy], ed);
+                es = fma(D[qy][j], csd[qy], es);
+                es = fma(S[qy][j], css[qy], es);
+              }
+            R0[(ck * 4 + j) * 5 + qx]       = ed;
+            R0[240 + (ck * 4 + j) * 5 + qx] = es;
+          }
+      }
+    __syncthreads();
+    if (t < 48) // I1: line (c, k, j) = t
+      {
+        const int c = t >> 4, kj = t & 15;
+        double    ed[5], es[5];
+#pragma unroll
+        for (int qx = 0; qx < 5; ++qx)
+          {
+            ed[qx] = R0[t * 5 + qx];
+            es[qx] = R0[240 + t * 5 + qx];
+          }
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+          {
+            double yv = 0.0;
+#pragma unroll
+            for (int qx = 0; qx < 5; ++qx)
+              {
+                yv = fma(D[qx][i], ed[qx], yv);
+                yv = fma(S[qx][i], es[qx], yv);
+              }
+            rp.acc[int64_t(sN[kj * 4 + i]) * 8 + c] += yv;
+          }
+      }
+    for (int item = t; item < 4 * 25; item += MFQ3_NT) // I3'
+      {
+        const int f = item / 25, p25 = item - 25 * f;
+        double    v[5];
+#pragma unroll
+        for (int z = 0; z < 5; ++z)
+          v[z] = R0[(9 + f) * MFQ3_QS + z * 25 + p25];
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+          R1[(f * 4 + k) * 25 + p25] = S[0][k] * v[0] + S[1][k] * v[1] + S[2][k] * v[2] + S[3][k] * v[3] + S[4][k] * v[4];
+      }
+    __syncthreads();
+    for (int item = t; item < 4 * 4 * 5; item += MFQ3_NT) // I2'
+      {
+        const int fk = item / 5, qx = item - 5 * fk;
+        double    c5[5];
+#pragma unroll
+        for (int qy = 0; qy < 5; ++qy)
+          c5[qy] = R1[fk * 25 + qy * 5 + qx];
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          R0[(fk * 4 + j) * 5 + qx] = S[0][j] * c5[0] + S[1][j] * c5[1] + S[2][j] * c5[2] + S[3][j] * c5[3] + S[4][j] * c5[4];
+      }
+    __syncthreads();
+    if (t < 4 * 16) // I1': line (f, k, j) = t; f = 0..2 the inertia force, 3 the weight
+      {
+        const int f = t >> 4, kj = t & 15;
+        double    e5[5];
+#pragma unroll
+        for (int qx = 0; qx < 5; ++qx)
+          e5[qx] = R0[t * 5 + qx];
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+          rp.acc[int64_t(sN[kj * 4 + i]) * 8 + 3 + f] += S[0][i] * e5[0] + S[1][i] * e5[1] + S[2][i] * e5[2] + S[3][i] * e5[3] + S[4][i] * e5[4];
+      }
+  }
+
+  // every other element and all of model 1: one workgroup per cell, thread = quadrature point for the point stage (post_cell_point with
+  // the acceleration as its value field), thread = node for the back-contraction (plain loop over the points, in ascending order)
+  template <int DIM, int P, int MODEL, int NT>
+  __global__ __launch_bounds__(NT) void nodal_force_cells(ReactionParams rp)
+  {
+    constexpr int NQ1 = MODEL == 0 ? P + 2 : P + 1;
+    POST_CELL_LDS(sc, DIM, P, NQ1)
+    constexpr int NPC = C::NPC, NQ = C::NQ, NG = DIM * DIM + DIM + 1; // per point: Q[c][l], rho w a[c], w
+    static_assert(NQ <= NT && NPC <= NT && NT % 64 == 0, "one thread per quadrature point and per node, whole waves");
+    __shared__ double s_a[NPC * DIM], s_g[NQ * NG];
+    const int     tid  = threadIdx.x;
+    const int64_t cell = rp.cell_begin + blockIdx.x;
+    post_cell_stage<DIM, P, NQ1, NT>(rp, cell, sc);
+    for (int i = tid; i < NPC * DIM; i += NT) // the acceleration: a0 as it is, or the difference quotient (a0 - a1) / dt
+      {
+        const int     a = i / DIM, c = i - a * DIM;
+        const int64_t g = int64_t(rp.conn[cell * NPC + a]) * DIM + c;
+        s_a[i]          = rp.a1 ? (rp.a0[g] - rp.a1[g]) / rp.dt : rp.a0[g];
+      }
+    __syncthreads();
+    if (tid < NQ)
+      {
+        const int q = tid;
+        double    aq[3] = {0.0, 0.0, 0.0}, F[9], Ji[9], w, T[6], Pk[9]; // F: grad u (model 0: + I); Pk: P, 3 x 3 embedded
+        bool      ok = true;
+        post_cell_point<DIM, P, NQ1, DIM, 0>(sc, q, s_a, nullptr, aq, nullptr, F, Ji, w);
+        if constexpr (MODEL == 0)
+          {
+            double J, Jm, rJ, Finv[9], tiso[6], cII, cS;
+            post_cell_finite_strain<DIM>(F, J, Jm, rJ);
+            neo_hooke_from_F<DIM>(F, J, Jm, rJ, rp.mu, rp.kappa, Finv, T, tiso, cII, cS);
+            ok = J > 0.0;
+            if (!ok) // inverted element (nonlinear_elasticity.cc:935 asserts det F > 0)
+              *rp.inverted = 1.0;
+            const double S3[9] = {T[0], T[3], T[4], T[3], T[1], T[5], T[4], T[5], T[2]};
+#pragma unroll
+            for (int c = 0; c < 3; ++c)
+#pragma unroll
+              for (int j = 0; j < 3; ++j) // (tau F^-T)[c][j] = sum_k tau[c][k] Finv[j][k]
+                Pk[c * 3 + j] = w * (S3[c * 3] * Finv[j * 3] + S3[c * 3 + 1] * Finv[j * 3 + 1] + S3[c * 3 + 2] * Finv[j * 3 + 2]);
+            (void)tiso, (void)cII, (void)cS;
+          }
+        else
+          {
+            linear_stress<DIM>(F, rp.lambda, rp.mu, w, T);
+            const double S3[9] = {T[0], T[3], T[4], T[3], T[1], T[5], T[4], T[5], T[2]};
+#pragma unroll
+            for (int k = 0; k < 9; ++k)
+              Pk[k] = S3[k];
+          }
+        double *g = s_g + q * NG;
+#pragma unroll
+        for (int c = 0; c < DIM; ++c)
+          {
+#pragma unroll
+            for (int l = 0; l < DIM; ++l) // grad_X N = sum_l d N / d xi_l Jinv[l][.]: Q[c][l] = sum_j P[c][j] Jinv[l][j] JxW
+              {
+                double s = 0.0;
+#pragma unroll
+                for (int j = 0; j < DIM; ++j)
+                  s = fma(Pk[c * 3 + j], Ji[l * 3 + j], s);
+                g[c * DIM + l] = ok ? s : 0.0;
+              }
+            g[DIM * DIM + c] = rp.rho * w * aq[c];
+          }
+        g[DIM * DIM + DIM] = w;
+      }
+    __syncthreads();
+    if (tid < NPC)
+      {
+        const int a    = tid;
+        double    r[7] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+        for (int q = 0; q < NQ; ++q)
+          {
+            double N, dN[3];
+            shape_at_qp<DIM, P, NQ1>(sc.N1, sc.dN1, q, a, N, dN);
+            const double *g = s_g + q * NG;
+#pragma unroll
+            for (int c = 0; c < DIM; ++c)
+              {
+#pragma unroll
+                for (int l = 0; l < DIM; ++l)
+                  r[c] = fma(g[c * DIM + l], dN[l], r[c]);
+                r[3 + c] = fma(N, g[DIM * DIM + c], r[3 + c]);
+              }
+            r[6] = fma(N, g[DIM * DIM + DIM], r[6]);
+          }
+        double *__restrict__ o = rp.acc + int64_t(rp.conn[cell * NPC + a]) * 8;
+#pragma unroll
+        for (int f = 0; f < 7; ++f)
+          o[f] += r[f];
+      }
+  }
+
+  // load = the interface faces' contributions (neumann_faces with face_slots), node by node in entry order as neumann_gather
+  // adds them, but on EVERY dof of an interface node: one thread per (interface node, component); load is zero elsewhere
+  template <int DIM>
+  __global__ __launch_bounds__(256) void nodal_force_gather(const double *__restrict__ slots, const int32_t *__restrict__ node_ids,
+                                                            const int32_t *__restrict__ start, const int32_t *__restrict__ src,
+                                                            double *__restrict__ load, int nnodes_if)
+  {
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    if (t >= nnodes_if * DIM)
+      return;
+    const int k = t / DIM, c = t - k * DIM;
+    double    s = 0.0;
+    for (int32_t j = start[k]; j < start[k + 1]; ++j)
+      s += slots[int64_t(src[j]) * DIM + c];
+    load[int64_t(node_ids[k]) * DIM + c] = s;
+  }
+
+  // one thread per node: terms[4][n] = internal, inertia, body = rho b W (rb = rho b; zeros for the linear model, whose load
+  // vector holds the body force), load; forces = internal + inertia - body - load
+  template <int DIM>
+  __global__ __launch_bounds__(256) void nodal_force_finish(const double *__restrict__ acc, const double *__restrict__ load,
+                                                            const int64_t nnodes, const double rb0, const double rb1, const double rb2,
+                                                            double *__restrict__ terms, double *__restrict__ forces)
+  {
+    const int64_t i = int64_t(blockIdx.x) * 256 + threadIdx.x;
+    if (i >= nnodes)
+      return;
+    const int64_t n     = nnodes * DIM;
+    const double  W     = acc[i * 8 + 6];
+    const double  rb[3] = {rb0, rb1, rb2};
+#pragma unroll
+    for (int c = 0; c < DIM; ++c)
+      {
+        const int64_t d  = i * DIM + c;
+        const double  fi = acc[i * 8 + c], fa = acc[i * 8 + 3 + c], fb = rb[c] * W, fl = load[d];
+        terms[d]         = fi;
+        terms[n + d]     = fa;
+        terms[2 * n + d] = fb;
+        terms[3 * n + d] = fl;
+        forces[d]        = ((fi + fa) - fb) - fl;
+      }
+  }
+
+  // resultants, moments and maxima in a fixed order.  NS sums per node: force (3) and moment (3) about x0 of the reaction (forces
+  // on the constrained dofs), the unbalanced force (on the free dofs), inertia, body and load, and sum_c |internal_c|; behind
+  // them the largest |forces_c| over the free dofs, the largest |reaction of a node|_2 and its node (the smallest id on ties; as a
+  // double).  Workgroup b reduces the items [b chunk, (b + 1) chunk) -- thread-strided, then block_sum; the maxima through LDS
+  // -- into out[b][REACT_NOUT]; FINAL = false: an item is a node, FINAL = true: an item is a workgroup's result in `part`
+  template <int DIM, bool FINAL>
+  __global__ __launch_bounds__(256) void reaction_sums(const ReactionSumParams p, const double *__restrict__ part, const int64_t nitems,
+                                                       const int64_t chunk, double *__restrict__ out)
+  {
+    constexpr int NS = REACT_NSUMS;
+    __shared__ double s_red[4], s_mu[256], s_mr[256], s_id[256], s_part[16 * 256];
+    const int64_t i0 = blockIdx.x * chunk, i1 = imin64(nitems, i0 + chunk);
+    double        s[NS], mu = 0.0, mr = -1.0, id = 0.0;
+#pragma unroll
+    for (int k = 0; k < NS; ++k)
+      s[k] = 0.0;
+#pragma unroll 1
+    for (int64_t i = i0 + threadIdx.x; i < i1; i += 256)
+      {
+        if constexpr (FINAL)
+          {
+            const double *e = part + i * REACT_NOUT;
+#pragma unroll
+            for (int k = 0; k < NS; ++k)
+              s[k] += e[k];
+            mu = fmax(mu, e[NS]);
+            if (e[NS + 1] > mr || (e[NS + 1] == mr && e[NS + 2] < id))
+              mr = e[NS + 1], id = e[NS + 2];
+          }
+        else
+          {
+            const uint8_t cm   = p.cmask[i];
+            double        x[3] = {0.0, 0.0, 0.0}, f[5][3], ia = 0.0, rr = 0.0;
+#pragma unroll
+            for (int c = 0; c < DIM; ++c)
+              {
+                const int64_t d   = i * DIM + c;
+                const bool    con = (cm >> c) & 1;
+                const double  r   = p.forces[d];
+                x[c]    = p.xyz[d] + (p.u ? p.u[d] : 0.0) - p.about[c];
+                f[0][c] = con ? r : 0.0;
+                f[1][c] = con ? 0.0 : r;
+                f[2][c] = p.terms[p.n + d];
+                f[3][c] = p.terms[2 * p.n + d];
+                f[4][c] = p.terms[3 * p.n + d];
+                ia += fabs(p.terms[d]);
+                mu = fmax(mu, fabs(f[1][c]));
+                rr = fma(f[0][c], f[0][c], rr);
+              }
+#pragma unroll
+            for (int c = DIM; c < 3; ++c)
+#pragma unroll
+              for (int k = 0; k < 5; ++k)
+                f[k][c] = 0.0;
+#pragma unroll
+            for (int k = 0; k < 5; ++k)
+              {
+                s[k * 6 + 0] += f[k][0];
+                s[k * 6 + 1] += f[k][1];
+                s[k * 6 + 2] += f[k][2];
+                s[k * 6 + 3] += x[1] * f[k][2] - x[2] * f[k][1];
+                s[k * 6 + 4] += x[2] * f[k][0] - x[0] * f[k][2];
+                s[k * 6 + 5] += x[0] * f[k][1] - x[1] * f[k][0];
+              }
+            s[30] += ia;
+            rr = sqrt(rr);
+            if (rr > mr) // (ascending node ids within a thread: the first of equals stays)
+              mr = rr, id = double(i);
+          }
+      }
+    // the NS sums through block_sum one after the other, in two rounds of 16 through LDS: the loop over a round's sums is not
+    // unrolled, so one reduction network is live at a time (all NS unrolled took 256 registers and one wave per SIMD)
+    double *const o = out + blockIdx.x * REACT_NOUT;
+#pragma unroll
+    for (int r = 0; r < 2; ++r)
+      {
+        __syncthreads();
+#pragma unroll
+        for (int j = 0; j < 16; ++j)
+          if (r * 16 + j < NS)
+            s_part[j * 256 + threadIdx.x] = s[r * 16 + j];
+        const int nj = r * 16 + 16 < NS ? 16 : NS - r * 16;
+#pragma unroll 1
+        for (int j = 0; j < nj; ++j)
+          {
+            const double v = block_sum<256>(s_part[j * 256 + threadIdx.x], s_red);
+            if (threadIdx.x == 0)
+              o[r * 16 + j] = v;
+          }
+      }
+    s_mu[threadIdx.x] = mu, s_mr[threadIdx.x] = mr, s_id[threadIdx.x] = id;
+    __syncthreads();
+    for (int h = 128; h > 0; h >>= 1)
+      {
+        if (threadIdx.x < h)
+          {
+            const int o = threadIdx.x + h;
+            s_mu[threadIdx.x] = fmax(s_mu[threadIdx.x], s_mu[o]);
+            if (s_mr[o] > s_mr[threadIdx.x] || (s_mr[o] == s_mr[threadIdx.x] && s_id[o] < s_id[threadIdx.x]))
+              s_mr[threadIdx.x] = s_mr[o], s_id[threadIdx.x] = s_id[o];
+          }
+        __syncthreads();
+      }
+    if (threadIdx.x == 0)
+      {
+        o[NS] = s_mu[0], o[NS + 1] = s_mr[0], o[NS + 2] = s_id[0];
+      }
   }
 
   // ------------------------------------------------------------------ stress error indicator (mi_stress_error)
@@ -9058,6 +9626,69 @@ namespace mi
       hipLaunchKernelGGL(stress_finish<3>, dim3(grid), dim3(256), 0, s, acc, nnodes, sigma, von_mises, weight);
     else
       hipLaunchKernelGGL(stress_finish<2>, dim3(grid), dim3(256), 0, s, acc, nnodes, sigma, von_mises, weight);
+  }
+  int launch_nodal_force(int dim, int degree, int model, const MfParams &p, const ReactionParams &rp, bool generic, hipStream_t s)
+  {
+    if (rp.cell_count <= 0)
+      return 0;
+    if (dim == 3 && degree == 3 && model == 0 && !generic)
+      {
+        auto *kern = p.cellbox ? nodal_force_q3<true> : nodal_force_q3<false>;
+        hipLaunchKernelGGL(kern, dim3(rp.cell_count), dim3(MFQ3_NT), 0, s, p, rp);
+        return 0;
+      }
+    if (dim == 3 && degree == 2 && model == 0 && !generic)
+      {
+        auto *kern = p.cellbox ? nodal_force_q2<true> : nodal_force_q2<false>;
+        hipLaunchKernelGGL(kern, dim3(rp.cell_count), dim3(64), 0, s, p, rp);
+        return 0;
+      }
+    return post_cells_family(dim, degree, [&](auto f) {
+      using F = decltype(f);
+      auto *kern = model == 0 ? nodal_force_cells<F::dim, F::degree, 0, F::NT> : nodal_force_cells<F::dim, F::degree, 1, F::NT>;
+      hipLaunchKernelGGL(kern, dim3(rp.cell_count), dim3(F::NT), 0, s, rp);
+    });
+  }
+  void launch_nodal_force_gather(int dim, const double *slots, const int32_t *node_ids, const int32_t *start, const int32_t *src,
+                                 double *load, int nnodes_if, hipStream_t s)
+  {
+    if (nnodes_if <= 0)
+      return;
+    const int grid = (nnodes_if * dim + 255) / 256;
+    if (dim == 3)
+      hipLaunchKernelGGL((nodal_force_gather<3>), dim3(grid), dim3(256), 0, s, slots, node_ids, start, src, load, nnodes_if);
+    else
+      hipLaunchKernelGGL((nodal_force_gather<2>), dim3(grid), dim3(256), 0, s, slots, node_ids, start, src, load, nnodes_if);
+  }
+  void launch_nodal_force_finish(int dim, const double *acc, const double *load, int64_t nnodes, const double rho_body[3], double *terms,
+                                 double *forces, hipStream_t s)
+  {
+    if (nnodes <= 0)
+      return;
+    const int grid = int((nnodes + 255) / 256);
+    if (dim == 3)
+      hipLaunchKernelGGL(nodal_force_finish<3>, dim3(grid), dim3(256), 0, s, acc, load, nnodes, rho_body[0], rho_body[1], rho_body[2], terms,
+                         forces);
+    else
+      hipLaunchKernelGGL(nodal_force_finish<2>, dim3(grid), dim3(256), 0, s, acc, load, nnodes, rho_body[0], rho_body[1], rho_body[2], terms,
+                         forces);
+  }
+  void launch_reaction_sums(int dim, const ReactionSumParams &p, int64_t nnodes, double *scratch, double *out, hipStream_t s)
+  {
+    if (nnodes <= 0)
+      return;
+    const int64_t chunk = 1024;
+    const int     nblk  = int((nnodes + chunk - 1) / chunk);
+    if (dim == 3)
+      {
+        hipLaunchKernelGGL((reaction_sums<3, false>), dim3(nblk), dim3(256), 0, s, p, static_cast<const double *>(nullptr), nnodes, chunk, scratch);
+        hipLaunchKernelGGL((reaction_sums<3, true>), dim3(1), dim3(256), 0, s, p, scratch, int64_t(nblk), int64_t(nblk), out);
+      }
+    else
+      {
+        hipLaunchKernelGGL((reaction_sums<2, false>), dim3(nblk), dim3(256), 0, s, p, static_cast<const double *>(nullptr), nnodes, chunk, scratch);
+        hipLaunchKernelGGL((reaction_sums<2, true>), dim3(1), dim3(256), 0, s, p, scratch, int64_t(nblk), int64_t(nblk), out);
+      }
   }
   int launch_stress_error(int dim, int degree, int model, const MfParams &p, const StressErrorParams &ep, int32_t cell_count, bool generic,
                           hipStream_t s)

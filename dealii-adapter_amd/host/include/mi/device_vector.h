@@ -112,6 +112,20 @@ namespace mi
       check(mi_stress_error(ctx_, model, &info, eta_cell ? eta_cell->data() : nullptr, nullptr), "mi_stress_error");
       return true;
     }
+    // support reactions and load resultants of the committed state (mi_reactions), moments about the origin: the resultants
+    // into info, the out-of-balance force on every dof [n_dofs] into forces where wanted.  false on a team (emulated slabs or
+    // RCCL), where the library provides none (one slab only); any other failure throws
+    bool reactions(int model, mi_reaction_info &info, std::vector<double> *forces = nullptr) const
+    {
+      int team = 1, rccl = 0;
+      check(mi_comm_info(ctx_, &team, &rccl), "mi_comm_info");
+      if (team > 1 || rccl > 0)
+        return false;
+      if (forces)
+        forces->assign(size_t(mi_n_dofs(ctx_)), 0.0);
+      check(mi_reactions(ctx_, model, nullptr, &info, forces ? forces->data() : nullptr, nullptr), "mi_reactions");
+      return true;
+    }
     // the fields at npts points of the reference configuration (mi_evaluate_points): values [n_which][npts][dim] of the state
     // vectors which[], cells [npts] (the lexicographic id of the cell that answered, -1: outside) where wanted; returns the number
     // of points in no cell, or -1 on a team (emulated slabs or RCCL), where the library provides none (one slab only); any other

@@ -15,6 +15,9 @@
 // stress_error_model >= 0 (the executables' MI_VTK_STRESS_ERROR=1): CELL_DATA `stress_error` behind the point data, eta_K of
 // mi_stress_error (the distance between that nodal stress and the elements' raw stress) -- one value per Lagrange cell; with
 // linear sub-cells every sub-cell carries its element's value.  Without it the file is byte for byte what it was.
+// reaction_model >= 0 (the executables' MI_VTK_REACTIONS=1): the point-data vector `reaction_force` behind whatever the stress
+// switches add (before the cell data) -- the out-of-balance force of mi_reactions on the constrained dofs of the patch point's
+// node, zero elsewhere: the force the support exerts there.  Without it the file is byte for byte what it was.
 #pragma once
 #include <cmath>
 #include <fstream>
@@ -116,7 +119,7 @@ namespace mi
   // team collectives (ncclAllReduce under RCCL), which hang or pair up with the wrong collective when only one rank
   // enters them.  write = false (ranks > 0): take part in the gathers, write nothing.
   inline void write_vtk(const Device &dev, int dim, int p, const int reps[3], const std::string &path, bool write = true,
-                        bool higher_order = true, int stress_model = -1, int stress_error_model = -1)
+                        bool higher_order = true, int stress_model = -1, int stress_error_model = -1, int reaction_model = -1)
   {
     const int64_t       nn = mi_n_nodes(dev.ctx()), n = mi_n_dofs(dev.ctx());
     std::vector<double> xyz(size_t(nn) * dim), u(size_t(n), 0.0);
@@ -139,6 +142,23 @@ namespace mi
         if (!have_error && write)
           std::cout << "\t MI_VTK_STRESS_ERROR: mi_stress_error runs on one slab only, no stress error is written on a team" << std::endl;
       }
+    std::vector<double> react;
+    bool                have_react = false;
+    if (reaction_model >= 0)
+      {
+        mi_reaction_info info{};
+        have_react = dev.reactions(reaction_model, info, &react);
+        if (!have_react && write)
+          std::cout << "\t MI_VTK_REACTIONS: mi_reactions runs on one slab only, no reaction force is written on a team" << std::endl;
+        if (have_react)
+          {
+            std::vector<uint8_t> con(size_t(n), 0);
+            dev.check(mi_get_constrained(dev.ctx(), con.data()), "mi_get_constrained");
+            for (size_t i = 0; i < size_t(n); ++i)
+              if (!con[i])
+                react[i] = 0.0;
+          }
+      }
     if (!write)
       return;
     std::ofstream out(path);
@@ -159,7 +179,7 @@ namespace mi
 
     std::vector<double> pts(size_t(ncells) * npc * 3, 0.0), disp(size_t(ncells) * npc * 3, 0.0),
       strain(size_t(ncells) * npc * dim * dim, 0.0);
-    std::vector<int64_t> node((size_t)npc, 0), pnode(have_stress ? size_t(ncells) * npc : 0, 0); // pnode: the node of every patch point
+    std::vector<int64_t> node((size_t)npc, 0), pnode(have_stress || have_react ? size_t(ncells) * npc : 0, 0); // pnode: the node of every patch point
     for (int64_t c = 0; c < ncells; ++c)
       {
         const int ci[3] = {int(c % rr[0]), int((c / rr[0]) % rr[1]), int(c / (int64_t(rr[0]) * rr[1]))};
@@ -231,7 +251,7 @@ namespace mi
                     gx[i][j] += gu[i][k] * Fi[k][j]; // grad_x u: gradient in the (displaced) output mapping
                 }
             const size_t q = size_t(c) * npc + a;
-            if (have_stress)
+            if (have_stress || have_react)
               pnode[q] = node[size_t(a)];
             for (int d = 0; d < dim; ++d)
               {
@@ -313,6 +333,15 @@ namespace mi
         out << "SCALARS von_mises double 1\nLOOKUP_TABLE default\n";
         for (int64_t i = 0; i < npts; ++i)
           out << vm[size_t(pnode[size_t(i)])] << '\n';
+      }
+    if (have_react)
+      {
+        out << "VECTORS reaction_force double\n";
+        for (int64_t i = 0; i < npts; ++i)
+          {
+            const double *r = &react[size_t(pnode[size_t(i)]) * dim];
+            out << r[0] << ' ' << r[1] << ' ' << (dim == 3 ? r[2] : 0.0) << '\n';
+          }
       }
     if (have_error)
       {

@@ -192,7 +192,8 @@ namespace Linear_Elasticity
     mi::write_vtk(*device, dim, int(parameters.poly_degree), mesh_desc.reps, parameters.output_folder + "/" + name.str(), mi::host_rank() == 0,
                   !std::getenv("MI_VTK_LINEAR_CELLS"), // higher-order cells as the reference (:1222-1225); the switch: linear sub-cells
                   std::getenv("MI_VTK_STRESS") && std::atoi(std::getenv("MI_VTK_STRESS")) != 0 ? MI_STRESS_LINEAR : -1, // + nodal stress
-                  std::getenv("MI_VTK_STRESS_ERROR") && std::atoi(std::getenv("MI_VTK_STRESS_ERROR")) != 0 ? MI_STRESS_LINEAR : -1); // + eta_K
+                  std::getenv("MI_VTK_STRESS_ERROR") && std::atoi(std::getenv("MI_VTK_STRESS_ERROR")) != 0 ? MI_STRESS_LINEAR : -1, // + eta_K
+                  std::getenv("MI_VTK_REACTIONS") && std::atoi(std::getenv("MI_VTK_REACTIONS")) != 0 ? MI_STRESS_LINEAR : -1); // + reaction force
     timer.leave_subsection("Output results");
   }
 
@@ -203,6 +204,7 @@ namespace Linear_Elasticity
     make_grid();
     setup_system();
     probes.open(*device, dim, MI_L_DISPLACEMENT, MI_L_VELOCITY);
+    reactions.open(*device, MI_STRESS_LINEAR);
     output_results();
 
     adapter.initialize(DoFSource{device.get()}, displacement);
@@ -251,7 +253,10 @@ namespace Linear_Elasticity
         adapter.reload_old_state_if_required(state_variables, time);
 
         if (adapter.precice.isTimeWindowComplete())
-          probes.write(time.current());
+          {
+            probes.write(time.current());
+            reactions.write(time.current());
+          }
         if (adapter.precice.isTimeWindowComplete() && parameters.output_interval > 0 &&
             time.get_timestep() % parameters.output_interval == 0)
           output_results();

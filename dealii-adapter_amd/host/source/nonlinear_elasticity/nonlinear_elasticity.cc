@@ -53,6 +53,7 @@ namespace Nonlinear_Elasticity
     make_grid();
     system_setup();
     probes.open(*device, dim, MI_V_TOTAL_DISPLACEMENT, MI_V_VELOCITY);
+    reactions.open(*device, MI_STRESS_NEOHOOKE);
     output_results();
 
     adapter.initialize(DoFSource{device.get()}, total_displacement);
@@ -84,7 +85,10 @@ namespace Nonlinear_Elasticity
         adapter.reload_old_state_if_required(state_variables, time);
 
         if (adapter.precice.isTimeWindowComplete())
-          probes.write(time.current());
+          {
+            probes.write(time.current());
+            reactions.write(time.current());
+          }
         if (adapter.precice.isTimeWindowComplete() && parameters.output_interval > 0 &&
             time.get_timestep() % parameters.output_interval == 0)
           output_results();
@@ -414,7 +418,8 @@ namespace Nonlinear_Elasticity
     mi::write_vtk(*device, dim, int(degree), mesh_desc.reps, parameters.output_folder + "/" + name.str(), mi::host_rank() == 0,
                   !std::getenv("MI_VTK_LINEAR_CELLS"), // higher-order cells as the reference (:1222-1225); the switch: linear sub-cells
                   std::getenv("MI_VTK_STRESS") && std::atoi(std::getenv("MI_VTK_STRESS")) != 0 ? MI_STRESS_NEOHOOKE : -1, // + nodal stress
-                  std::getenv("MI_VTK_STRESS_ERROR") && std::atoi(std::getenv("MI_VTK_STRESS_ERROR")) != 0 ? MI_STRESS_NEOHOOKE : -1); // + eta_K
+                  std::getenv("MI_VTK_STRESS_ERROR") && std::atoi(std::getenv("MI_VTK_STRESS_ERROR")) != 0 ? MI_STRESS_NEOHOOKE : -1, // + eta_K
+                  std::getenv("MI_VTK_REACTIONS") && std::atoi(std::getenv("MI_VTK_REACTIONS")) != 0 ? MI_STRESS_NEOHOOKE : -1); // + reaction force
     std::cout << "\t Output written to " << name.str() << " \n" << std::endl;
     timer.leave_subsection("Output results");
   }

@@ -14,6 +14,7 @@
 #include <adapter/time_handler.h>
 #include <mi/device_vector.h>
 #include <mi/probe_log.h>
+#include <mi/reaction_log.h>
 #include <mi/timer_output.h>
 
 namespace Nonlinear_Elasticity
@@ -65,6 +66,7 @@ namespace Nonlinear_Elasticity
       external_stress;
     std::vector<mi::Vector *> state_variables;
     mi::ProbeLog              probes; // MI_PROBES=<file>: u and v at the file's points, one row of probes.log per completed window
+    mi::ReactionLog           reactions; // MI_REACTIONS=1: reaction, load, inertia and body resultants, one row of reactions.log per completed window
 
     mutable mi::TimerOutput timer;
     Adapter::Time           time;

@@ -268,6 +268,54 @@ typedef struct
 int mi_stress_error(mi_ctx *ctx, int model, mi_stress_error_info *out, double *eta_cell /* [n_cells] or NULL */,
                     double *norm_cell /* [n_cells] or NULL */);
 
+/* Support reactions and load resultants: what the supports carry, and whether the structure is in balance with its loads.
+ * Every residual path of the library masks the constrained dofs; this forms the UNMASKED nodal forces, term by term, on every
+ * dof (node and dof order of the reference, as every array of this interface), with N_i the scalar shape function of node i:
+ * MI_STRESS_NEOHOOKE (0): the Newmark model's COMMITTED state as mi_energy reads it -- u = MI_V_TOTAL_DISPLACEMENT alone (not
+ *   + MI_V_SOLUTION_DELTA), a = MI_V_ACCELERATION and MI_V_EXTERNAL_STRESS as they are -- on qf_cell = QGauss(p+2):
+ *     internal_i = sum_cells sum_q tau(F) F^-T grad_X N_i JxW      the force the body exerts on the node
+ *     inertia_i  = rho sum N_i a_h JxW
+ *     body_i     = rho b W_i,  W_i = sum N_i JxW                   the lumped weight of mi_stress_field
+ *     load_i     = the interface faces' contribution exactly as the assembly forms it (nonlinear_elasticity.cc:791-859): the
+ *                  pull-back at the cell point whose index is the face-point counter, or at the face point with
+ *                  "correct_face_F" 1, at the committed displacement
+ * MI_STRESS_LINEAR (1), no mi_linear_setup needed for the internal term, on QGauss(p+1):
+ *     internal   = K d, formed element by element as the integral of (lambda tr eps I + 2 mu eps) grad N, d = MI_L_DISPLACEMENT
+ *     inertia_i  = rho sum N_i a_h JxW,  a = (MI_L_VELOCITY - MI_L_OLD_VELOCITY) / delta_t
+ *     load       = MI_L_OLD_STRESS, the load vector F of the last step as assemble_rhs left it (body force and either coupling
+ *                  form are in it);  body = 0
+ *   THESE ARE THE TERMS OF THE THETA SCHEME, NOT AN EQUILIBRIUM AT ONE TIME.  On the free dofs the scheme's identity is
+ *     inertia_{n+1} + theta (internal - load)_{n+1} + (1 - theta) (internal - load)_n = (A v - rhs) / delta_t,
+ *   so a single call balances (to the solver's residual) only for theta = 1; for another theta combine the terms of two calls.
+ * forces = internal + inertia - body - load, the out-of-balance force r.  Reaction: r on the dofs mi_get_constrained flags, zero
+ * elsewhere; unbalanced: r on the free dofs.  Resultant of a nodal vector f over a dof set: sum f_i; moment about x0:
+ * sum (x_i - x0) x f_i with x_i = X_i + u_i, the CURRENT positions, for model 0 and x_i = X_i for model 1.  2D: the moment is
+ * the z entry alone; entries [0], [1] and the force's [2] are 0.  For any state sum_all internal = 0 and
+ * sum_all (x_i - x0) x internal_i = 0 at round-off of internal_abs (translation and rotation invariance), so
+ * reaction + unbalanced = inertia - body - load for force and moment.
+ * about [dim] or NULL (the origin); forces [n_dofs] or NULL; terms [4][n_dofs] = internal, inertia, body, load, or NULL.
+ * The contract of mi_stress_error: every (dim, degree) an assembly supports, "fine_level" 0 and 1, after a "linear_operator" 1
+ * set-up has released the tangent array.  Modifies no state vector, record, matrix, hierarchy, tuning key, counter or timing
+ * (scratch of its own is allocated on first use).  Bitwise repeatable: the cells add to the nodes colour by colour, the colours
+ * in order; the resultants in chunks of 1,024 nodes, then the chunks; no floating-point atomics.  Model 0 with a point of
+ * det F <= 0: MI_EINVAL "inverted element"; the context works afterwards.  Undecomposed contexts only: on an emulated or RCCL
+ * team MI_EINVAL "one slab only".  A bad model, a NULL out or a NULL ctx: MI_EINVAL. */
+typedef struct
+{
+  double  about[3];                            /* x0 as used */
+  double  reaction[3], reaction_moment[3];     /* r over constrained dofs */
+  double  unbalanced[3], unbalanced_moment[3]; /* r over free dofs */
+  double  inertia[3], inertia_moment[3];       /* all dofs */
+  double  body[3], body_moment[3];
+  double  load[3], load_moment[3];
+  double  internal_abs;                        /* sum |internal_i|: the scale of the round-off identities */
+  double  max_unbalanced;                      /* max |r_i| over free dofs */
+  double  max_reaction;                        /* largest |R_node|_2 ... */
+  int64_t max_reaction_node;                   /* ... and its node, the smallest id on ties */
+} mi_reaction_info;
+int mi_reactions(mi_ctx *ctx, int model, const double *about /* [dim] or NULL = origin */, mi_reaction_info *out,
+                 double *forces /* [n_dofs] r, or NULL */, double *terms /* [4][n_dofs] internal, inertia, body, load, or NULL */);
+
 /* Fields at arbitrary points: u_h(X) = sum_a N_a(xi) u_a at npts points X of the REFERENCE configuration, for n_which state
  * vectors at once (which[]: MI_V_* / MI_L_* ids, 1 <= n_which <= MI_V_COUNT; the vectors as they are, nothing is committed or
  * combined).  xi is the pre-image of X under the d-linear (Q1) map of the cell's (perturbed) vertices, the map the support
@@ -654,7 +702,7 @@ int mi_set_profiling(mi_ctx *ctx, int enable);
  * and timing-only ablations of the two element kernels), MI_ENERGY_GENERIC (mi_energy through the generic kernel on 3D Q2 / Q3
  * too: the cross-check of tools/energy_generic_check.py), MI_STRESS_GENERIC (mi_stress_field likewise:
  * tools/stress_generic_check.py), MI_STRESS_ERROR_GENERIC (the second pass of mi_stress_error likewise:
- * tools/stress_error_generic_check.py). */
+ * tools/stress_error_generic_check.py), MI_REACTIONS_GENERIC (mi_reactions likewise: tools/reactions_time.py). */
 int mi_set_tuning(mi_ctx *ctx, const char *key, int value);
 /* Read back.  Counters since the last mi_reset_timings (what a solve costs in latency-bound events; counted on one slab
  * as well, where the collectives themselves are no-ops): "count_scalar_allreduce", "count_scalar_allreduce_cg" (those inside
