@@ -90,6 +90,11 @@ class ReactionInfo(C.Structure):
                  ("max_reaction_node", C.c_int64)])
 
 
+class ProjectInfo(C.Structure):
+    _fields_ = [("its", C.c_int32), ("sub", C.c_int32), ("n_points", C.c_int64), ("res", C.c_double),
+                ("src_sq", C.c_double * 6), ("dst_sq", C.c_double * 6)]
+
+
 class MiError(RuntimeError):
     def __init__(self, code, msg, partial=None):
         super().__init__("mi_elasticity error %d: %s" % (code, msg))
@@ -179,6 +184,12 @@ def lib():
         L.mi_evaluate_points.restype = C.c_int
         L.mi_state_transfer.argtypes = [vp, vp]
         L.mi_state_transfer.restype = C.c_int
+        L.mi_mass_apply.argtypes = [vp, C.c_int, C.c_int, dp, dp]
+        L.mi_mass_solve.argtypes = [vp, C.c_int, C.c_int, dp, dp, C.c_double, C.c_int, C.POINTER(C.c_int), dp]
+        L.mi_project_load.argtypes = [vp, vp, C.c_int, C.POINTER(C.c_int), C.c_int, dp]
+        L.mi_state_project.argtypes = [vp, vp, C.c_int, C.c_double, C.c_int, C.POINTER(ProjectInfo)]
+        for f in ("mi_mass_apply", "mi_mass_solve", "mi_project_load", "mi_state_project"):
+            getattr(L, f).restype = C.c_int
         L.mi_linear_modes.argtypes = [vp, C.c_int, C.c_double, C.c_int, dp, dp, dp, C.POINTER(C.c_int)]
         L.mi_block_gram.argtypes = [vp, C.c_int64, dp, C.c_int, dp, C.c_int, dp]
         L.mi_block_combine.argtypes = [vp, C.c_int64, dp, C.c_int, dp, C.c_int, dp]
@@ -564,6 +575,49 @@ class Context:
         (mi_state_transfer: evaluate on src at self.coords, device to device).  A node outside src's mesh: MiError, nothing
         written"""
         self._chk(lib().mi_state_transfer(self.h, src.h))
+
+    def mass_apply(self, x, masked=False):
+        """y = M x for the columns x [nrhs, n] (or one vector [n]): the unit-density consistent mass on the assembly's rule
+        (mi_mass_apply).  masked: x read as 0 and y written 0 on constrained dofs"""
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        y = np.zeros_like(x)
+        nrhs = 1 if x.ndim == 1 else x.shape[0]
+        self._chk(lib().mi_mass_apply(self.h, nrhs, int(masked), _dp(x), _dp(y)))
+        return y
+
+    def mass_solve(self, b, masked=False, tol=1e-12, max_it=500, check=True):
+        """(x, its, res[nrhs], rc) with M x = b for the columns b [nrhs, n] (or one vector [n]) by the device's Jacobi-PCG
+        (mi_mass_solve).  Not converged: MiError with code MI_ENOCONV_LIN whose .partial is that tuple; check=False returns it"""
+        b = np.ascontiguousarray(b, dtype=np.float64)
+        x = np.zeros_like(b)
+        nrhs = 1 if b.ndim == 1 else b.shape[0]
+        its, res = C.c_int(0), np.zeros(max(nrhs, 1))
+        rc = lib().mi_mass_solve(self.h, nrhs, int(masked), _dp(b), _dp(x), float(tol), int(max_it), C.byref(its), _dp(res))
+        out = (x, its.value, res[:nrhs], rc)
+        if rc == MI_ENOCONV_LIN:
+            if check:
+                raise MiError(rc, lib().mi_last_error(self.h).decode(), partial=out)
+            return out
+        self._chk(rc)
+        return out
+
+    def project_load(self, src, which, sub=1):
+        """b [n_which, n] (one id: [n]): the load of src's state vectors `which` against this context's test functions on the
+        composite rule sub^dim x QGauss(p + 2) per cell (mi_project_load); every dof, nothing masked"""
+        single = np.isscalar(which)
+        ids = np.ascontiguousarray([which] if single else list(which), dtype=np.int32)
+        b = np.zeros((ids.size, self.n))
+        self._chk(lib().mi_project_load(self.h, src.h, ids.size, ids.ctypes.data_as(C.POINTER(C.c_int)), int(sub), _dp(b)))
+        return b[0] if single else b
+
+    def project_state_from(self, src, sub=1, tol=1e-12, max_it=500):
+        """this context's six state vectors V_U .. V_A_OLD := the L2 projection of src's fields onto this context's space,
+        constrained dofs exactly 0 (mi_state_project).  Returns dict(its, sub, n_points, res, src_sq[6], dst_sq[6]); on an
+        error -- a point outside src's mesh, no convergence -- MiError and nothing is written"""
+        info = ProjectInfo()
+        self._chk(lib().mi_state_project(self.h, src.h, int(sub), float(tol), int(max_it), C.byref(info)))
+        return dict(its=info.its, sub=info.sub, n_points=int(info.n_points), res=info.res, src_sq=np.array(info.src_sq),
+                    dst_sq=np.array(info.dst_sq))
 
     def state_save(self):
         self._chk(lib().mi_state_save(self.h))

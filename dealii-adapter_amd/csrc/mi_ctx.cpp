@@ -3850,6 +3850,11 @@ int mi_set_tuning(mi_ctx *c, const char *key, int value)
           m->face_slots = value;
           continue;
         }
+      if (k == "project_chunk_cells" && value >= 0) // load pass of the L2 projection: cells of dst per chunk (0: automatic)
+        {
+          m->project_chunk_cells = value;
+          continue;
+        }
       if (k == "mf_point_slots" && (value == 0 || value == 1)) // matrix-free fine level: point pass in one launch (1) | eight colour launches
         {
           m->mf_point_slots = value;
@@ -4072,6 +4077,8 @@ int mi_get_tuning(mi_ctx *c, const char *key, int *value)
     *value = m->linear_precond;
   else if (k == "linear_precond_active") // 1: the solve of the current linear set-up is multigrid-preconditioned (0 without one)
     *value = mi_linear_mg_n_levels(m) > 1 ? 1 : 0;
+  else if (k == "project_chunk_cells")
+    *value = m->project_chunk_cells;
   else if (k == "mf_diag_lag")
     *value = m->mf_diag_lag;
   else if (k == "smoother_quadrature")
@@ -4325,3 +4332,7 @@ int mi_bench_assemble(mi_ctx *c, int reps, double *ms_per_assembly)
 }
 
 } // extern "C"
+
+// consistent mass and L2 projection (mi_mass_apply, mi_mass_solve, mi_project_load, mi_state_project): part of this translation
+// unit, as csrc/mi_modes.cpp is of mi_linear.cpp -- it uses enqueue_point_eval and the helpers above
+#include "mi_project.cpp"

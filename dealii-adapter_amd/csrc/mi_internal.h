@@ -265,6 +265,9 @@ struct mi_ctx
   double   *d_pe         = nullptr;
   size_t    pe_doubles   = 0;
   double   *d_node_xyz   = nullptr;
+  // L2 projection (mi_project_load, mi_state_project): tuning "project_chunk_cells" -- cells of dst per chunk of the load pass,
+  // 0: as many as keep the point scratch at or below 256 MiB.  A test's key: the result does not depend on it
+  int       project_chunk_cells = 0;
   // nodal forces and reactions (mi_reactions), allocated on first use: accumulator [nnodes][8] | load [n] | terms [4][n] |
   // forces [n] | face slots of its own (the size of d_face_slots) | chunk results | the result (mi::REACT_NOUT); reads d_node_xyz
   double   *d_react      = nullptr;

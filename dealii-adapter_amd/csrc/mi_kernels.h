@@ -323,6 +323,48 @@ namespace mi
     double        *part;      // [field_at_points_partials(npts)] points in no cell, per workgroup
   };
 
+  // consistent mass (see mass_apply_cells): y += M x for nrhs columns over the cells of one colour, or the diagonal of M
+  constexpr int MASS_MAX_RHS = 6;    // MI_MASS_MAX_RHS
+  constexpr int MASS_CHUNK   = 1024; // entries of a column per workgroup of the column algebra
+  struct MassParams
+  {
+    const int32_t *conn;   // [ncells][npc] colour-sorted
+    const double  *cverts; // [ncells][2^dim][dim]
+    const double  *tab;    // the assembly's tables (AsmParams::tab1d)
+    const uint8_t *cmask;  // [nnodes] bit c: dof (node, c) is constrained
+    const double  *x;      // [nrhs][n]
+    double        *y;      // [nrhs][n] (diag: [n]); zeroed by the caller
+    int64_t        n;      // dofs
+    int32_t        nrhs, masked, diag;
+    int64_t        cell_begin; // the cells of ONE colour: no two of them share a node
+    int32_t        cell_count;
+  };
+  // the columns' scalars and flags of the mass solve, on the device (see mass_cg_scalars)
+  struct MassCgState
+  {
+    double  bb[MASS_MAX_RHS], rz[MASS_MAX_RHS], pq[MASS_MAX_RHS], rr[MASS_MAX_RHS], beta[MASS_MAX_RHS], fresh[MASS_MAX_RHS];
+    int32_t done[MASS_MAX_RHS], its[MASS_MAX_RHS];
+    int32_t nactive, reserved; // columns still running: the word the host reads once per iteration
+  };
+  // load pass of the L2 projection (see project_load_cells): a chunk of dst's cells inside one colour and src's fields at its points
+  constexpr int PROJ_FIELDS = 6, PROJ_MAX_SUB = 4, PROJ_TILE = 64;
+  struct ProjectParams
+  {
+    const int32_t *conn;   // dst: [ncells][npc] colour-sorted
+    const double  *cverts; // dst: [ncells][2^dim][dim]
+    const double  *tab;    // dst: the assembly's tables (weights and points of QGauss(p + 2))
+    const double  *ntab;   // [sub (p + 2)][p + 1]: dst's 1D basis at the composite rule's points
+    const double  *values; // [n_which][npts][dim]: src's fields at the chunk's points (field_at_points)
+    int64_t        npts;   // points of the chunk
+    double        *b;      // [n_which][n]; zeroed by the caller
+    double        *cell_sq; // [PROJ_FIELDS][ncells]: sum_q |w_src|^2 JxW of every cell
+    int64_t        n, ncells;
+    int32_t        n_which, sub;
+    int64_t        chunk_begin; // the chunk's first cell (its points start there)
+    int64_t        cell_begin;  // the cells of this launch
+    int32_t        cell_count;
+  };
+
   // matrix-free operator of the linear model on 3D Q3 cells (see mf_linear_q3): y = (c_K K + c_M M) x
   struct MfLinearOp
   {
@@ -522,6 +564,28 @@ namespace mi
   // in closed form; else Newton on the Q1 map); then *n_outside = sum of p.part (finish_sum).  -1: no kernel for the element
   int64_t field_at_points_partials(int64_t npts);
   int     launch_field_at_points(int dim, int degree, bool box, const PointEvalParams &p, double *n_outside, hipStream_t s);
+  // consistent mass and L2 projection.  launch_mass_apply: the cells of one colour by the kernel of (dim, degree) -- mass_apply_q3,
+  // mass_apply_q2 (p.conn, p.tab1d, p.cverts / p.cellbox) or mass_apply_cells; generic: mass_apply_cells on 3D Q2 / Q3 too
+  // (cross-check); the diagonal is always mass_apply_cells' (-1: no kernel for the element).  Column algebra: mass_chunks(n) workgroups per column; part arrays hold [nrhs][mass_chunks(n)] doubles.
+  // launch_mass_col_dots: out[j] = a_j . b_j.  The solve's two fused updates and its scalars: see the kernels
+  int  launch_mass_apply(int dim, int degree, const MfParams &p, const MassParams &mp, bool generic, hipStream_t s);
+  int  mass_chunks(int64_t n);
+  void launch_mass_col_dots(const double *a, const double *b, int64_t n, int nrhs, double *part, double *out, hipStream_t s);
+  void launch_mass_cg_update_xr(bool first, double *x, double *r, const double *p, const double *q, const double *dinv, int64_t n,
+                                int nrhs, const MassCgState *st, double *part_rr, double *part_rz, hipStream_t s);
+  void launch_mass_cg_scalars(const double *part_rr, const double *part_rz, int64_t n, int nrhs, int it, double tol, MassCgState *st,
+                              hipStream_t s);
+  void launch_mass_cg_update_p(bool first, double *p, const double *r, const double *dinv, int64_t n, int nrhs, const MassCgState *st,
+                               hipStream_t s);
+  void launch_mass_diag_invert(int dim, double *d, const uint8_t *cmask, int masked, int64_t n, hipStream_t s);
+  void launch_mass_fresh_residual(int dim, const double *b, const double *q, const uint8_t *cmask, int masked, int64_t n, int nrhs,
+                                  double *r, hipStream_t s);
+  // load pass: the points of a chunk of cells (qx: the nq1 Gauss points on [0, 1]), the chunk's cells of one colour into b and
+  // cell_sq (-1: no kernel, or sub / n_which out of range), the fields' sums over the cells
+  void launch_project_points(int dim, const double *cverts, const double *qx, int64_t cell_begin, int64_t npts, int nq1, int sub,
+                             double *xyz, hipStream_t s);
+  int  launch_project_load(int dim, int degree, const ProjectParams &pp, hipStream_t s);
+  void launch_project_sq_sum(const double *cell_sq, int ncells, double *out, hipStream_t s);
   // ... the multigrid smoother's operator on the element's full-order rule, 4 x 4 x 4 points (see mf_spmv_q3s): records
   // [ncells][MF_NREC][64] of its own (MfParams::qrec_q3s, written by mf_records_q3s from u + du with the fold rule of
   // mf_records27), the rule's 1D tables MfParams::tab_q3s; one wave per cell, the results into the same cell-major slots

@@ -6479,6 +6479,595 @@ namespace mi
       p.part[blockIdx.x] = outside;
   }
 
+  // ------------------------------------------------------------------ consistent mass and L2 projection (mi_mass_apply, mi_mass_solve, mi_state_project)
+  // M is the unit-density vector mass on the assembly's rule QGauss(p + 2): M_(i,c)(j,d) = delta_cd sum_cells sum_q N_i N_j JxW.
+  // mass_apply_cells: one workgroup per cell of ONE colour.  The cell's tables, vertices and JxW are formed once; then every
+  // column goes through the value-only forward contraction (thread = point: v(q) = sum_a N_a(q) x_a, times JxW) and the
+  // value-only back contraction (thread = node: sum_q N_a(q) (v JxW)(q), points in ascending order), and is added into y with
+  // plain loads and stores -- within a colour no two cells share a node, the colours run in order on one stream, so the order
+  // of the sums depends on the mesh alone and a call repeats bit by bit (the scheme of stress_cells).  No atomics.
+  // masked: x is read as zero on constrained dofs (on the gather) and y is not written there (on the store; the caller zeroed y).
+  // diag: instead of the columns, sum_q N_a(q)^2 JxW into y -- the diagonal of M by the kernel's own sums.
+  // the product of the three 1D entries of the table s_N1[q1][a1] for point (q0, q1, q2) and node (a0, a1, a2), z first
+  template <int DIM, int NP1>
+  __device__ __forceinline__ double mass_shape(const double *s_N1, const int *qi, const int *ai)
+  {
+    const double nyx = s_N1[qi[1] * NP1 + ai[1]] * s_N1[qi[0] * NP1 + ai[0]];
+    return DIM == 3 ? s_N1[qi[2] * NP1 + ai[2]] * nyx : nyx;
+  }
+  template <int DIM, int P, int NT>
+  __global__ __launch_bounds__(NT) void mass_apply_cells(MassParams mp)
+  {
+    using E           = Elem<DIM, P>;
+    constexpr int NP1 = E::NP1, NPC = E::NPC, NQ1 = E::NQ1, NQ = E::NQ, NV = E::NV;
+    static_assert(NQ <= NT && NPC <= NT && NT % 64 == 0, "one thread per quadrature point and per node, whole waves");
+    __shared__ double s_N1[NQ1 * NP1], s_qw[NQ1], s_qx[NQ1], s_verts[NV * DIM], s_w[NQ], s_x[NPC * DIM], s_g[NQ * DIM];
+    const int     tid  = threadIdx.x;
+    const int64_t cell = mp.cell_begin + blockIdx.x;
+    for (int i = tid; i < NQ1 * NP1; i += NT)
+      s_N1[i] = mp.tab[i];
+    if (tid < NQ1)
+      {
+        s_qw[tid] = mp.tab[2 * NQ1 * NP1 + tid];
+        s_qx[tid] = mp.tab[2 * NQ1 * NP1 + NQ1 + tid];
+      }
+    if (tid < NV * DIM)
+      s_verts[tid] = mp.cverts[cell * (NV * DIM) + tid];
+    // this thread as a point and as a node
+    const int qi[3] = {tid % NQ1, (tid / NQ1) % NQ1, (DIM == 3) ? tid / (NQ1 * NQ1) : 0};
+    const int ai[3] = {tid % NP1, (tid / NP1) % NP1, (DIM == 3) ? tid / (NP1 * NP1) : 0};
+    int64_t   dof0  = 0;
+    int       cm    = 0;
+    if (tid < NPC)
+      {
+        const int32_t node = mp.conn[cell * NPC + tid];
+        dof0               = int64_t(node) * DIM;
+        cm                 = mp.masked ? int(mp.cmask[node]) : 0;
+      }
+    __syncthreads();
+    if (tid < NQ)
+      {
+        double xi[3] = {0.0, 0.0, 0.0}, wq = 1.0, Jg[9];
+#pragma unroll
+        for (int d = 0; d < DIM; ++d)
+          {
+            xi[d] = s_qx[qi[d]];
+            wq *= s_qw[qi[d]];
+          }
+        q1_jacobian<DIM>(s_verts, xi, Jg);
+        s_w[tid] = det3x3(Jg) * wq;
+      }
+    __syncthreads();
+    if (mp.diag)
+      {
+        if (tid < NPC)
+          {
+            double r = 0.0;
+            for (int q = 0; q < NQ; ++q)
+              {
+                const int    qj[3] = {q % NQ1, (q / NQ1) % NQ1, (DIM == 3) ? q / (NQ1 * NQ1) : 0};
+                const double N     = mass_shape<DIM, NP1>(s_N1, qj, ai);
+                r                  = fma(N * N, s_w[q], r);
+              }
+#pragma unroll
+            for (int c = 0; c < DIM; ++c)
+              mp.y[dof0 + c] += r;
+          }
+        return;
+      }
+    for (int col = 0; col < mp.nrhs; ++col)
+      {
+        const double *__restrict__ x = mp.x + int64_t(col) * mp.n;
+        double *__restrict__ y       = mp.y + int64_t(col) * mp.n;
+        if (tid < NPC)
+          {
+#pragma unroll
+            for (int c = 0; c < DIM; ++c)
+              s_x[tid * DIM + c] = ((cm >> c) & 1) ? 0.0 : x[dof0 + c];
+          }
+        __syncthreads();
+        if (tid < NQ)
+          {
+            double v[DIM];
+#pragma unroll
+            for (int c = 0; c < DIM; ++c)
+              v[c] = 0.0;
+            for (int a = 0; a < NPC; ++a)
+              {
+                const int    aj[3] = {a % NP1, (a / NP1) % NP1, (DIM == 3) ? a / (NP1 * NP1) : 0};
+                const double N     = mass_shape<DIM, NP1>(s_N1, qi, aj);
+#pragma unroll
+                for (int c = 0; c < DIM; ++c)
+                  v[c] = fma(N, s_x[a * DIM + c], v[c]);
+              }
+#pragma unroll
+            for (int c = 0; c < DIM; ++c)
+              s_g[tid * DIM + c] = v[c] * s_w[tid];
+          }
+        __syncthreads();
+        if (tid < NPC)
+          {
+            double r[DIM];
+#pragma unroll
+            for (int c = 0; c < DIM; ++c)
+              r[c] = 0.0;
+            for (int q = 0; q < NQ; ++q)
+              {
+                const int    qj[3] = {q % NQ1, (q / NQ1) % NQ1, (DIM == 3) ? q / (NQ1 * NQ1) : 0};
+                const double N     = mass_shape<DIM, NP1>(s_N1, qj, ai);
+#pragma unroll
+                for (int c = 0; c < DIM; ++c)
+                  r[c] = fma(N, s_g[q * DIM + c], r[c]);
+              }
+#pragma unroll
+            for (int c = 0; c < DIM; ++c)
+              if (!((cm >> c) & 1))
+                y[dof0 + c] += r[c];
+          }
+        // (the next column's gather writes s_x, which the points have read before the barrier above; its forward half writes
+        // s_g behind the next barrier, which every node reaches after it has read s_g)
+      }
+  }
+
+  // ---- the sum-factorised forms, chosen by launch_mass_apply as launch_stress chooses.  Both form the point's JxW once
+  // (mf_geometry; boxes: the cell's 1/h) and loop over the columns inside the kernel, the LDS regions reused column after
+  // column with the barriers of the passes between them; three fields per column where the stress kernels carry seven.
+  // 3D Q2: one wave per cell, lane = point of the 4 x 4 x 4 rule.  Forward: the value path of postq2_forward alone -- the
+  // masked gather, postq2_values_e12 and postq2_values_e3 with the S table.  Backward: the value-only half of stress_q2 (B3
+  // contracts qz, B12 contracts qy and qx), into y with the mask on the store
+  template <bool BOX>
+  __global__ __launch_bounds__(64, 4) void mass_apply_q2(MfParams prm, MassParams mp)
+  {
+    constexpr int NPC = PQ2_NPC, PW = PQ2_PW;
+    __shared__ double sX[3 * NPC], sB[PW], sG[3 * 64], sC[3 * 48];
+    const int     lane = threadIdx.x, q16 = lane & 15, qz = lane >> 4;
+    const int64_t cell = mp.cell_begin + blockIdx.x;
+    int32_t       node = 0;
+    int           cm   = 0;
+    if (lane < NPC)
+      {
+        node = prm.conn[cell * NPC + lane];
+        cm   = mp.masked ? int(mp.cmask[node]) : 0;
+      }
+    double S[4][3], Sx[3], Sz[3]; // S: uniform -> scalar registers; this lane's rows qx = lane & 3 and qz
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+#pragma unroll
+      for (int a = 0; a < 3; ++a)
+        S[q][a] = prm.tab1d[q * 3 + a];
+#pragma unroll
+    for (int k = 0; k < 3; ++k)
+      {
+        Sx[k] = prm.tab1d[(lane & 3) * 3 + k];
+        Sz[k] = prm.tab1d[qz * 3 + k];
+      }
+    double w;
+    {
+      const double *tw = prm.tab1d + 24, *tx = prm.tab1d + 28; // (1D weights and points of the assembly's Q2 tables)
+      double        Ji[9], detJ;
+      mf_geometry<BOX>(prm, cell, tx, lane & 3, (lane >> 2) & 3, qz, Ji, detJ);
+      w = detJ * (tw[lane & 3] * tw[(lane >> 2) & 3] * tw[qz]);
+    }
+    for (int col = 0; col < mp.nrhs; ++col)
+      {
+        const double *__restrict__ x = mp.x + int64_t(col) * mp.n;
+        double *__restrict__ y       = mp.y + int64_t(col) * mp.n;
+        if (lane < NPC)
+          {
+#pragma unroll
+            for (int c = 0; c < 3; ++c)
+              sX[c * NPC + lane] = ((cm >> c) & 1) ? 0.0 : x[int64_t(node) * 3 + c];
+          }
+        __syncthreads();
+        postq2_values_e12<3>(S, Sx, sX, sB, lane);
+        __syncthreads();
+        double v[3];
+        postq2_values_e3<3, true>(Sz, sB, q16, v);
+#pragma unroll
+        for (int f = 0; f < 3; ++f)
+          sG[f * 64 + lane] = v[f] * w;
+        __syncthreads();
+        if (lane < 48) // B3: item (k, q16): C_f[k][q16] = sum_qz S[qz][k] g_f(qz, q16)
+          {
+            const int    k  = lane >> 4;
+            const double s0 = prm.tab1d[k], s1 = prm.tab1d[3 + k], s2 = prm.tab1d[6 + k], s3 = prm.tab1d[9 + k];
+#pragma unroll
+            for (int f = 0; f < 3; ++f)
+              sC[f * 48 + lane] = s0 * sG[f * 64 + q16] + s1 * sG[f * 64 + 16 + q16] + s2 * sG[f * 64 + 32 + q16] + s3 * sG[f * 64 + 48 + q16];
+          }
+        __syncthreads();
+        if (lane < NPC) // B12: lane = node (i, j, k)
+          {
+            const int i = lane % 3, j = (lane / 3) % 3, k = lane / 9;
+#pragma unroll
+            for (int f = 0; f < 3; ++f)
+              {
+                double r = 0.0;
+#pragma unroll
+                for (int qy = 0; qy < 4; ++qy)
+                  {
+                    const double *c4 = sC + f * 48 + k * 16 + qy * 4;
+                    r = fma(S[qy][j], S[0][i] * c4[0] + S[1][i] * c4[1] + S[2][i] * c4[2] + S[3][i] * c4[3], r);
+                  }
+                if (!((cm >> f) & 1))
+                  y[int64_t(node) * 3 + f] += r;
+              }
+          }
+        // (no barrier here: the next column writes sX behind E12' of this one, sB behind E3', sG behind B3, sC behind B12 --
+        // each behind at least one of the barriers above)
+      }
+  }
+  // 3D Q3: 128 threads per cell, thread = point of the 5 x 5 x 5 rule (threads 125-127 contribute exact zeros).  Forward: the
+  // masked gather and postq3_values (E1'-E3' with the S table alone; no gradient rows).  Backward: I3', I2', I1' of stress_q3
+  // with three fields, into y with the mask on the store.  LDS regions of its own: X, A, B forward; G, C, E backward
+  template <bool BOX>
+  __global__ __launch_bounds__(MFQ3_NT) void mass_apply_q3(MfParams prm, MassParams mp)
+  {
+    __shared__ double  sT[40], X[3 * MFQ3_NPC], A[3 * 80], B[3 * 100], G[3 * MFQ3_QS], Cq[3 * 100], Eq[3 * 80];
+    __shared__ int32_t sN[MFQ3_NPC], sM[MFQ3_NPC];
+    const int     t    = threadIdx.x, it = t < MFQ3_NQ ? t : MFQ3_NQ - 1, qz = it / 25, q25 = it - 25 * qz;
+    const int64_t cell = mp.cell_begin + blockIdx.x;
+    if (t < 40)
+      sT[t] = prm.tab1d[t];
+    if (t < MFQ3_NPC)
+      {
+        const int32_t node = prm.conn[cell * MFQ3_NPC + t];
+        sN[t]              = node;
+        sM[t]              = mp.masked ? int32_t(mp.cmask[node]) : 0;
+      }
+    double S[5][4]; // uniform: scalar registers
+#pragma unroll
+    for (int q = 0; q < 5; ++q)
+#pragma unroll
+      for (int a = 0; a < 4; ++a)
+        S[q][a] = prm.tab1d[q * 4 + a];
+    double w;
+    {
+      const double *tw = prm.tab1d + MFQ3_TW, *tx = prm.tab1d + MFQ3_TX;
+      const int     qy = q25 / 5, qx = q25 - 5 * qy;
+      double        Ji[9], detJ;
+      mf_geometry<BOX>(prm, cell, tx, qx, qy, qz, Ji, detJ);
+      w = t < MFQ3_NQ ? detJ * (tw[qx] * tw[qy] * tw[qz]) : 0.0;
+    }
+    __syncthreads();
+    for (int col = 0; col < mp.nrhs; ++col)
+      {
+        const double *__restrict__ x = mp.x + int64_t(col) * mp.n;
+        double *__restrict__ y       = mp.y + int64_t(col) * mp.n;
+        if (t < MFQ3_NPC)
+          {
+            const int32_t node = sN[t], cm = sM[t];
+#pragma unroll
+            for (int c = 0; c < 3; ++c)
+              X[c * MFQ3_NPC + t] = ((cm >> c) & 1) ? 0.0 : x[int64_t(node) * 3 + c];
+          }
+        __syncthreads();
+        double v[3];
+        postq3_values<3, true>(prm.tab1d, sT, X, A, B, t, qz, q25, v); // (a barrier behind E1' and behind E2')
+#pragma unroll
+        for (int f = 0; f < 3; ++f)
+          G[f * MFQ3_QS + t] = v[f] * w;
+        __syncthreads();
+        if (t < 3 * 25) // I3': item (f, qy, qx) contracts qz
+          {
+            const int f = t / 25, p25 = t - 25 * f;
+            double    g5[5];
+#pragma unroll
+            for (int z = 0; z < 5; ++z)
+              g5[z] = G[f * MFQ3_QS + z * 25 + p25];
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+              Cq[(f * 4 + k) * 25 + p25] = S[0][k] * g5[0] + S[1][k] * g5[1] + S[2][k] * g5[2] + S[3][k] * g5[3] + S[4][k] * g5[4];
+          }
+        __syncthreads();
+        if (t < 3 * 4 * 5) // I2': item (f, k, qx) contracts qy
+          {
+            const int fk = t / 5, qx = t - 5 * fk;
+            double    c5[5];
+#pragma unroll
+            for (int qy = 0; qy < 5; ++qy)
+              c5[qy] = Cq[fk * 25 + qy * 5 + qx];
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+              Eq[(fk * 4 + j) * 5 + qx] = S[0][j] * c5[0] + S[1][j] * c5[1] + S[2][j] * c5[2] + S[3][j] * c5[3] + S[4][j] * c5[4];
+          }
+        __syncthreads();
+        if (t < 3 * 16) // I1': line (f, k, j) contracts qx onto the line's four nodes
+          {
+            const int f = t >> 4, kj = t & 15;
+            double    e5[5];
+#pragma unroll
+            for (int qx = 0; qx < 5; ++qx)
+              e5[qx] = Eq[t * 5 + qx];
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+              if (!((sM[kj * 4 + i] >> f) & 1))
+                y[int64_t(sN[kj * 4 + i]) * 3 + f] += S[0][i] * e5[0] + S[1][i] * e5[1] + S[2][i] * e5[2] + S[3][i] * e5[3] + S[4][i] * e5[4];
+          }
+        // (the next column writes X behind E1' of this one, A behind E2', B behind E3', G behind I3', Cq behind I2', Eq behind
+        // I1': each behind at least one barrier)
+      }
+  }
+
+  // ---- column algebra of the mass solve: blocks [nrhs][n], every column on its own.  A workgroup takes MASS_CHUNK entries of
+  // one column (grid: chunks x columns), its partial goes to part[column][chunk], and the partials of a column are summed in a
+  // fixed order by one workgroup (reduce_partials) -- so a column's numbers do not depend on how many columns run with it.
+  // part[j][b] = sum over chunk b of a_j[i] b_j[i]
+  __global__ __launch_bounds__(256) void mass_col_dots(const double *__restrict__ a, const double *__restrict__ b, const int64_t n,
+                                                       double *__restrict__ part)
+  {
+    __shared__ double s_red[4];
+    const int64_t i0 = int64_t(blockIdx.x) * MASS_CHUNK, i1 = imin64(n, i0 + MASS_CHUNK), o = int64_t(blockIdx.y) * n;
+    double        s  = 0.0;
+    for (int64_t i = i0 + threadIdx.x; i < i1; i += 256)
+      s = fma(a[o + i], b[o + i], s);
+    s = block_sum<256>(s, s_red);
+    if (threadIdx.x == 0)
+      part[int64_t(blockIdx.y) * gridDim.x + blockIdx.x] = s;
+  }
+  // out[j] = the sum of column j's partials (workgroup j)
+  __global__ __launch_bounds__(256) void mass_col_dots_finish(const double *__restrict__ part, const int nblk, double *__restrict__ out)
+  {
+    __shared__ double s_red[4];
+    const double s = reduce_partials<256>(part + int64_t(blockIdx.x) * nblk, nblk, s_red);
+    if (threadIdx.x == 0)
+      out[blockIdx.x] = s;
+  }
+  // first fused update of an iteration: x_j += alpha_j p_j, r_j -= alpha_j q_j with alpha_j = rz_j / pq_j, columns that are done
+  // untouched; then the chunk's partials of r.r and r.(D^-1 r).  FIRST: the start of the solve -- nothing is updated (x = 0,
+  // r = b), only the partials
+  template <bool FIRST>
+  __global__ __launch_bounds__(256) void mass_cg_update_xr(double *__restrict__ x, double *__restrict__ r, const double *__restrict__ p,
+                                                           const double *__restrict__ q, const double *__restrict__ dinv, const int64_t n,
+                                                           const MassCgState *__restrict__ st, double *__restrict__ part_rr,
+                                                           double *__restrict__ part_rz)
+  {
+    __shared__ double s_red[4];
+    const int         j  = blockIdx.y;
+    const int64_t     i0 = int64_t(blockIdx.x) * MASS_CHUNK, i1 = imin64(n, i0 + MASS_CHUNK), o = int64_t(j) * n;
+    const bool        upd   = !FIRST && !st->done[j];
+    const double      alpha = upd ? st->rz[j] / st->pq[j] : 0.0;
+    double            srr = 0.0, srz = 0.0;
+    for (int64_t i = i0 + threadIdx.x; i < i1; i += 256)
+      {
+        double ri = r[o + i];
+        if (upd)
+          {
+            x[o + i] = fma(alpha, p[o + i], x[o + i]);
+            ri       = fma(-alpha, q[o + i], ri);
+            r[o + i] = ri;
+          }
+        srr = fma(ri, ri, srr);
+        srz = fma(ri * dinv[i], ri, srz);
+      }
+    srr = block_sum<256>(srr, s_red);
+    srz = block_sum<256>(srz, s_red);
+    if (threadIdx.x == 0)
+      {
+        part_rr[int64_t(j) * gridDim.x + blockIdx.x] = srr;
+        part_rz[int64_t(j) * gridDim.x + blockIdx.x] = srz;
+      }
+  }
+  // one workgroup: the columns' r.r and r.z from the partials, beta_j = (r.z)_new / (r.z)_old, the done-flags
+  // (|r_j| <= tol |b_j|; a zero column is done at the start) and the count of columns still running -- the one word the host
+  // reads per iteration.  it: the iteration these numbers close (0: the start, where b.b = r.r is kept)
+  __global__ __launch_bounds__(256) void mass_cg_scalars(const double *__restrict__ part_rr, const double *__restrict__ part_rz,
+                                                         const int nblk, const int nrhs, const int it, const double tol,
+                                                         MassCgState *__restrict__ st)
+  {
+    __shared__ double s_red[4];
+    int               active = 0;
+    for (int j = 0; j < nrhs; ++j)
+      {
+        const double rr = reduce_partials<256>(part_rr + int64_t(j) * nblk, nblk, s_red);
+        const double rz = reduce_partials<256>(part_rz + int64_t(j) * nblk, nblk, s_red);
+        if (it == 0)
+          {
+            const bool done = !(sqrt(rr) > tol * sqrt(rr)) || rr == 0.0;
+            if (threadIdx.x == 0)
+              st->bb[j] = rr, st->rr[j] = rr, st->rz[j] = rz, st->beta[j] = 0.0, st->done[j] = done, st->its[j] = 0;
+            active += done ? 0 : 1;
+          }
+        else if (!st->done[j])
+          {
+            const bool done = !(sqrt(rr) > tol * sqrt(st->bb[j]));
+            __syncthreads(); // (every thread has read done[j] and bb[j])
+            if (threadIdx.x == 0)
+              st->beta[j] = rz / st->rz[j], st->rz[j] = rz, st->rr[j] = rr, st->done[j] = done, st->its[j] = it;
+            active += done ? 0 : 1;
+          }
+      }
+    if (threadIdx.x == 0)
+      st->nactive = active;
+  }
+  // second fused update: p_j = D^-1 r_j + beta_j p_j (FIRST: p_j = D^-1 r_j), columns that are done untouched
+  template <bool FIRST>
+  __global__ __launch_bounds__(256) void mass_cg_update_p(double *__restrict__ p, const double *__restrict__ r,
+                                                          const double *__restrict__ dinv, const int64_t n,
+                                                          const MassCgState *__restrict__ st)
+  {
+    const int j = blockIdx.y;
+    if (st->done[j])
+      return;
+    const double  beta = st->beta[j];
+    const int64_t i0 = int64_t(blockIdx.x) * MASS_CHUNK, i1 = imin64(n, i0 + MASS_CHUNK), o = int64_t(j) * n;
+    for (int64_t i = i0 + threadIdx.x; i < i1; i += 256)
+      p[o + i] = FIRST ? r[i + o] * dinv[i] : fma(beta, p[o + i], r[o + i] * dinv[i]);
+  }
+  // dinv = 1 / diag on the dofs that take part (masked: the free ones), 0 elsewhere
+  template <int D>
+  __global__ __launch_bounds__(256) void mass_diag_invert(double *__restrict__ d, const uint8_t *__restrict__ cmask, const int masked,
+                                                          const int64_t n)
+  {
+    const int64_t i = int64_t(blockIdx.x) * 256 + threadIdx.x;
+    if (i >= n)
+      return;
+    const int64_t nd = i / D;
+    d[i]             = (masked && ((cmask[nd] >> int(i - nd * D)) & 1)) ? 0.0 : 1.0 / d[i];
+  }
+  // r_j = b_j - q_j (masked: 0 on constrained dofs, where b is ignored): the freshly formed residual behind the solve
+  template <int D>
+  __global__ __launch_bounds__(256) void mass_fresh_residual(const double *__restrict__ b, const double *__restrict__ q,
+                                                             const uint8_t *__restrict__ cmask, const int masked, const int64_t n,
+                                                             double *__restrict__ r)
+  {
+    const int64_t i = int64_t(blockIdx.x) * 256 + threadIdx.x;
+    if (i >= n)
+      return;
+    const int64_t nd = i / D, o = int64_t(blockIdx.y) * n;
+    r[o + i]         = (masked && ((cmask[nd] >> int(i - nd * D)) & 1)) ? 0.0 : b[o + i] - q[o + i];
+  }
+
+  // ---- load pass of the projection: b_(i,c) = sum_{dst cells} sum_q N_i(xi_q) w_c^src(X_q) JxW(q) on the composite rule -- every
+  // dst cell cut into sub^dim equal boxes in xi, QGauss(p + 2) on each: NS1 = sub (p + 2) points per direction,
+  // xi = (s + x_g) / sub for box s and Gauss point g, weight w_g / sub.
+  // one thread per point of a chunk of cells: X_q, the point's image under the cell's Q1 map, into xyz[point][dim]
+  template <int DIM>
+  __global__ __launch_bounds__(256) void project_points(const double *__restrict__ cverts, const double *__restrict__ qx,
+                                                        const int64_t cell_begin, const int64_t npts, const int nq1, const int sub,
+                                                        double *__restrict__ xyz)
+  {
+    const int64_t i = int64_t(blockIdx.x) * 256 + threadIdx.x;
+    if (i >= npts)
+      return;
+    const int     ns1 = nq1 * sub, pc = DIM == 3 ? ns1 * ns1 * ns1 : ns1 * ns1;
+    const int64_t e   = i / pc;
+    const int     q   = int(i - e * pc);
+    const int     qi[3] = {q % ns1, (q / ns1) % ns1, DIM == 3 ? q / (ns1 * ns1) : 0};
+    double        xi[DIM];
+#pragma unroll
+    for (int d = 0; d < DIM; ++d)
+      xi[d] = (double(qi[d] / nq1) + qx[qi[d] % nq1]) / double(sub);
+    const double *__restrict__ verts = cverts + (cell_begin + e) * ((1 << DIM) * DIM);
+    double X[DIM];
+#pragma unroll
+    for (int d = 0; d < DIM; ++d)
+      X[d] = 0.0;
+#pragma unroll
+    for (int v = 0; v < (1 << DIM); ++v)
+      {
+        double phi = 1.0;
+#pragma unroll
+        for (int d = 0; d < DIM; ++d)
+          phi *= ((v >> d) & 1) ? xi[d] : 1.0 - xi[d];
+#pragma unroll
+        for (int d = 0; d < DIM; ++d)
+          X[d] = fma(phi, verts[v * DIM + d], X[d]);
+      }
+#pragma unroll
+    for (int d = 0; d < DIM; ++d)
+      xyz[i * DIM + d] = X[d];
+  }
+  // one workgroup per cell of one colour (a chunk of it): the points in tiles of PROJ_TILE -- the first wave forms JxW of a
+  // tile's points and puts w^src JxW of the six fields into LDS, then thread = node adds N_a(xi_q) times them, points in
+  // ascending order -- and the node's sums go into b with plain loads and stores, colour by colour as mass_apply_cells.
+  // The cell's sum_q |w^src|^2 JxW of every field goes to cell_sq[field][cell] (the wave's reduction network: a fixed order).
+  // Neither depends on how the colour was cut into chunks.  Fields beyond n_which run as zeros
+  template <int DIM, int P, int NT>
+  __global__ __launch_bounds__(NT) void project_load_cells(ProjectParams pp)
+  {
+    using E           = Elem<DIM, P>;
+    constexpr int NP1 = E::NP1, NPC = E::NPC, NQ1 = E::NQ1, NV = E::NV, NF = PROJ_FIELDS * DIM, T = PROJ_TILE;
+    static_assert(NPC <= NT && T == 64 && NT % 64 == 0, "one thread per node; the first wave takes a tile's points");
+    __shared__ double  s_T[PROJ_MAX_SUB * NQ1 * NP1], s_qw[NQ1], s_qx[NQ1], s_verts[NV * DIM], s_g[T * NF], s_red[NT / 64];
+    __shared__ int32_t s_qi[T];
+    const int     tid = threadIdx.x, sub = pp.sub, ns1 = sub * NQ1, pc = DIM == 3 ? ns1 * ns1 * ns1 : ns1 * ns1;
+    const int64_t cell = pp.cell_begin + blockIdx.x;
+    const int64_t pt0  = (cell - pp.chunk_begin) * pc; // the cell's first point among the chunk's
+    for (int i = tid; i < ns1 * NP1; i += NT)
+      s_T[i] = pp.ntab[i];
+    if (tid < NQ1)
+      {
+        s_qw[tid] = pp.tab[2 * NQ1 * NP1 + tid];
+        s_qx[tid] = pp.tab[2 * NQ1 * NP1 + NQ1 + tid];
+      }
+    if (tid < NV * DIM)
+      s_verts[tid] = pp.cverts[cell * (NV * DIM) + tid];
+    const int ai[3] = {tid % NP1, (tid / NP1) % NP1, (DIM == 3) ? tid / (NP1 * NP1) : 0};
+    double    acc[NF], sq[PROJ_FIELDS];
+#pragma unroll
+    for (int f = 0; f < NF; ++f)
+      acc[f] = 0.0;
+#pragma unroll
+    for (int w = 0; w < PROJ_FIELDS; ++w)
+      sq[w] = 0.0;
+    __syncthreads();
+    for (int q0 = 0; q0 < pc; q0 += T)
+      {
+        const int nt = min(T, pc - q0);
+        if (tid < T)
+          {
+            const int q = q0 + tid;
+            if (tid < nt)
+              {
+                const int qi[3] = {q % ns1, (q / ns1) % ns1, DIM == 3 ? q / (ns1 * ns1) : 0};
+                double    xi[3] = {0.0, 0.0, 0.0}, wq = 1.0, Jg[9];
+#pragma unroll
+                for (int d = 0; d < DIM; ++d)
+                  {
+                    xi[d] = (double(qi[d] / NQ1) + s_qx[qi[d] % NQ1]) / double(sub);
+                    wq *= s_qw[qi[d] % NQ1] / double(sub);
+                  }
+                q1_jacobian<DIM>(s_verts, xi, Jg);
+                const double JxW = det3x3(Jg) * wq;
+                s_qi[tid]        = qi[0] | (qi[1] << 8) | (qi[2] << 16);
+#pragma unroll
+                for (int w = 0; w < PROJ_FIELDS; ++w)
+                  {
+                    double v2 = 0.0;
+#pragma unroll
+                    for (int c = 0; c < DIM; ++c)
+                      {
+                        const double v = w < pp.n_which ? pp.values[(int64_t(w) * pp.npts + pt0 + q) * DIM + c] : 0.0;
+                        s_g[tid * NF + w * DIM + c] = v * JxW;
+                        v2 = fma(v, v, v2);
+                      }
+                    sq[w] = fma(v2, JxW, sq[w]);
+                  }
+              }
+          }
+        __syncthreads();
+        if (tid < NPC)
+          for (int k = 0; k < nt; ++k)
+            {
+              const int    pq    = s_qi[k];
+              const int    qj[3] = {pq & 255, (pq >> 8) & 255, pq >> 16};
+              const double N     = mass_shape<DIM, NP1>(s_T, qj, ai);
+#pragma unroll
+              for (int f = 0; f < NF; ++f)
+                acc[f] = fma(N, s_g[k * NF + f], acc[f]);
+            }
+        __syncthreads();
+      }
+    if (tid < NPC)
+      {
+        const int64_t dof0 = int64_t(pp.conn[cell * NPC + tid]) * DIM;
+#pragma unroll
+        for (int w = 0; w < PROJ_FIELDS; ++w)
+          if (w < pp.n_which)
+            {
+#pragma unroll
+              for (int c = 0; c < DIM; ++c)
+                pp.b[int64_t(w) * pp.n + dof0 + c] += acc[w * DIM + c];
+            }
+      }
+#pragma unroll
+    for (int w = 0; w < PROJ_FIELDS; ++w)
+      {
+        const double s = block_sum<NT>(tid < T ? sq[w] : 0.0, s_red);
+        if (tid == 0)
+          pp.cell_sq[int64_t(w) * pp.ncells + cell] = s;
+      }
+  }
+  // out[w] = the sum of field w's cell numbers cell_sq[w][ncells], in a fixed order (workgroup w)
+  __global__ __launch_bounds__(256) void project_sq_sum(const double *__restrict__ cell_sq, const int ncells, double *__restrict__ out)
+  {
+    __shared__ double s_red[4];
+    const double s = reduce_partials<256>(cell_sq + int64_t(blockIdx.x) * ncells, ncells, s_red);
+    if (threadIdx.x == 0)
+      out[blockIdx.x] = s;
+  }
+
   // ------------------------------------------------------------------ linear model, 3D Q3: K, M and the stepping matrix without matrices
   // "linear_operator" 1.  The linear model's rule is QGauss(p + 1) (linear_elasticity.cc:61): for Q3 the 4 x 4 x 4 points of
   // mf_spmv_q3s -- one wave per cell, lane = point = node, its region layout, gradients (mfq3s_gradients) and integration
@@ -9746,6 +10335,93 @@ namespace mi
     if (rc == 0)
       hipLaunchKernelGGL(finish_sum, dim3(1), dim3(256), 0, s, p.part, int(grid), n_outside);
     return rc;
+  }
+  // consistent mass and L2 projection
+  int launch_mass_apply(int dim, int degree, const MfParams &p, const MassParams &mp, bool generic, hipStream_t s)
+  {
+    if (mp.cell_count <= 0)
+      return 0;
+    if (dim == 3 && degree == 3 && !generic && !mp.diag)
+      {
+        auto *kern = p.cellbox ? mass_apply_q3<true> : mass_apply_q3<false>;
+        hipLaunchKernelGGL(kern, dim3(mp.cell_count), dim3(MFQ3_NT), 0, s, p, mp);
+        return 0;
+      }
+    if (dim == 3 && degree == 2 && !generic && !mp.diag)
+      {
+        auto *kern = p.cellbox ? mass_apply_q2<true> : mass_apply_q2<false>;
+        hipLaunchKernelGGL(kern, dim3(mp.cell_count), dim3(64), 0, s, p, mp);
+        return 0;
+      }
+    return post_cells_family(dim, degree, [&](auto f) {
+      using F = decltype(f);
+      hipLaunchKernelGGL((mass_apply_cells<F::dim, F::degree, F::NT>), dim3(mp.cell_count), dim3(F::NT), 0, s, mp);
+    });
+  }
+  int  mass_chunks(int64_t n) { return int((n + MASS_CHUNK - 1) / MASS_CHUNK); }
+  void launch_mass_col_dots(const double *a, const double *b, int64_t n, int nrhs, double *part, double *out, hipStream_t s)
+  {
+    const int nblk = mass_chunks(n);
+    hipLaunchKernelGGL(mass_col_dots, dim3(nblk, nrhs), dim3(256), 0, s, a, b, n, part);
+    hipLaunchKernelGGL(mass_col_dots_finish, dim3(nrhs), dim3(256), 0, s, part, nblk, out);
+  }
+  void launch_mass_cg_update_xr(bool first, double *x, double *r, const double *p, const double *q, const double *dinv, int64_t n,
+                                int nrhs, const MassCgState *st, double *part_rr, double *part_rz, hipStream_t s)
+  {
+    auto *kern = first ? mass_cg_update_xr<true> : mass_cg_update_xr<false>;
+    hipLaunchKernelGGL(kern, dim3(mass_chunks(n), nrhs), dim3(256), 0, s, x, r, p, q, dinv, n, st, part_rr, part_rz);
+  }
+  void launch_mass_cg_scalars(const double *part_rr, const double *part_rz, int64_t n, int nrhs, int it, double tol, MassCgState *st,
+                              hipStream_t s)
+  {
+    hipLaunchKernelGGL(mass_cg_scalars, dim3(1), dim3(256), 0, s, part_rr, part_rz, mass_chunks(n), nrhs, it, tol, st);
+  }
+  void launch_mass_cg_update_p(bool first, double *p, const double *r, const double *dinv, int64_t n, int nrhs, const MassCgState *st,
+                               hipStream_t s)
+  {
+    auto *kern = first ? mass_cg_update_p<true> : mass_cg_update_p<false>;
+    hipLaunchKernelGGL(kern, dim3(mass_chunks(n), nrhs), dim3(256), 0, s, p, r, dinv, n, st);
+  }
+  void launch_mass_diag_invert(int dim, double *d, const uint8_t *cmask, int masked, int64_t n, hipStream_t s)
+  {
+    const int grid = int((n + 255) / 256);
+    if (dim == 3)
+      hipLaunchKernelGGL((mass_diag_invert<3>), dim3(grid), dim3(256), 0, s, d, cmask, masked, n);
+    else
+      hipLaunchKernelGGL((mass_diag_invert<2>), dim3(grid), dim3(256), 0, s, d, cmask, masked, n);
+  }
+  void launch_mass_fresh_residual(int dim, const double *b, const double *q, const uint8_t *cmask, int masked, int64_t n, int nrhs,
+                                  double *r, hipStream_t s)
+  {
+    const dim3 grid(int((n + 255) / 256), nrhs);
+    if (dim == 3)
+      hipLaunchKernelGGL((mass_fresh_residual<3>), grid, dim3(256), 0, s, b, q, cmask, masked, n, r);
+    else
+      hipLaunchKernelGGL((mass_fresh_residual<2>), grid, dim3(256), 0, s, b, q, cmask, masked, n, r);
+  }
+  void launch_project_points(int dim, const double *cverts, const double *qx, int64_t cell_begin, int64_t npts, int nq1, int sub,
+                             double *xyz, hipStream_t s)
+  {
+    const int grid = int((npts + 255) / 256);
+    if (dim == 3)
+      hipLaunchKernelGGL((project_points<3>), dim3(grid), dim3(256), 0, s, cverts, qx, cell_begin, npts, nq1, sub, xyz);
+    else
+      hipLaunchKernelGGL((project_points<2>), dim3(grid), dim3(256), 0, s, cverts, qx, cell_begin, npts, nq1, sub, xyz);
+  }
+  int launch_project_load(int dim, int degree, const ProjectParams &pp, hipStream_t s)
+  {
+    if (pp.cell_count <= 0)
+      return 0;
+    if (pp.sub < 1 || pp.sub > PROJ_MAX_SUB || pp.n_which < 1 || pp.n_which > PROJ_FIELDS)
+      return -1;
+    return post_cells_family(dim, degree, [&](auto f) {
+      using F = decltype(f);
+      hipLaunchKernelGGL((project_load_cells<F::dim, F::degree, F::NT>), dim3(pp.cell_count), dim3(F::NT), 0, s, pp);
+    });
+  }
+  void launch_project_sq_sum(const double *cell_sq, int ncells, double *out, hipStream_t s)
+  {
+    hipLaunchKernelGGL(project_sq_sum, dim3(PROJ_FIELDS), dim3(256), 0, s, cell_sq, ncells, out);
   }
   void launch_mf_diag_q3(const MfParams &p, double *slots6, int32_t cell_count, hipStream_t s)
   {

@@ -147,6 +147,23 @@ namespace mi
             "mi_evaluate_points");
       return n_outside;
     }
+    // this device's six state vectors := the L2 projection of src's fields onto its space (mi_state_project: the load on the
+    // composite rule sub^dim x QGauss(p + 2) per cell, the consistent-mass solve on the free dofs, device to device); the
+    // iteration count, residual and the two integrals of |w|^2 into info where wanted.  false on a team (emulated slabs or
+    // RCCL) on either side, where the library provides none (one slab only); any other failure throws and leaves this device
+    // unchanged
+    bool project_state(const Device &src, int sub = 1, double tol = 1e-12, int max_it = 500, mi_project_info *info = nullptr)
+    {
+      for (const mi_ctx *c : {ctx_, src.ctx_})
+        {
+          int team = 1, rccl = 0;
+          check(mi_comm_info(c, &team, &rccl), "mi_comm_info");
+          if (team > 1 || rccl > 0)
+            return false;
+        }
+      check(mi_state_project(ctx_, src.ctx_, sub, tol, max_it, info), "mi_state_project");
+      return true;
+    }
     void    check(int rc, const char *what) const
     {
       if (rc != MI_OK)

@@ -1,5 +1,7 @@
 // CPU-only unit tests of the host-side boundary code (no device calls): parameter file reader, Adapter::Time,
 // replay participant, Adapter call sequence with a mock vector type.  Run by tests/test_host_cpu.py.
+// Built with -DMI_HOST_DEVICE_CASES and linked to the device library (make test_host_device), `test_host_device project` runs
+// the one case that needs a GPU instead: mi::Device::project_state.  Run by tests/test_host_gpu_project.py.
 #include <cassert>
 #include <condition_variable>
 #include <mutex>
@@ -20,6 +22,9 @@
 #include <adapter/parameters.h>
 #include <adapter/time_handler.h>
 #include <mi/vtk_lagrange.h>
+#ifdef MI_HOST_DEVICE_CASES
+#include <mi/device_vector.h>
+#endif
 
 static int g_fail = 0;
 #define CHECK(cond)                                                          \
@@ -155,8 +160,71 @@ static void test_vtk_lagrange_order()
   CHECK(L2(1, 1) == 12 && L2(2, 1) == 13 && L2(1, 2) == 14 && L2(2, 2) == 15);
 }
 
-int main()
+#ifdef MI_HOST_DEVICE_CASES
+// mi::Device::project_state: a 4 x 2 x 4 Q2 box with all faces free carries six quadratic fields, polynomials of degree <= 2 per
+// direction that the coarse space holds too; projected onto the same box in 2 x 1 x 2 cells with sub = 2 (the exact pair) they
+// come back as themselves at the coarse nodes, and the integral of |w|^2 is kept
+static int test_device_project_state()
 {
+  auto field = [](int k, int c, const double *X) {
+    const double x = X[0] / 0.2, y = X[1] / 0.13, z = X[2] / 0.14;
+    return (1.0 + k) * (0.3 + x * x - 0.5 * y + (c + 1) * z * z * y * y) + 0.25 * c * x * y * z;
+  };
+  auto make = [](int rx, int ry, int rz) {
+    mi_mesh_desc md;
+    std::memset(&md, 0, sizeof(md));
+    md.dim = 3, md.degree = 2;
+    md.reps[0] = rx, md.reps[1] = ry, md.reps[2] = rz;
+    md.hi[0] = 0.2, md.hi[1] = 0.13, md.hi[2] = 0.14;
+    mi_material_desc mat;
+    std::memset(&mat, 0, sizeof(mat));
+    mat.mu = 0.5e6, mat.nu = 0.4, mat.rho = 1000.0;
+    mi_newmark_desc nm = {0.25, 0.5, 0.005};
+    return std::make_unique<mi::Device>(md, mat, nm, 0);
+  };
+  auto src = make(4, 2, 4), dst = make(2, 1, 2);
+  auto nodal = [&](mi::Device &d, int k) {
+    const size_t        nn = size_t(mi_n_nodes(d.ctx()));
+    std::vector<double> xyz(nn * 3), v(nn * 3);
+    d.check(mi_get_node_coords(d.ctx(), xyz.data()), "mi_get_node_coords");
+    for (size_t i = 0; i < nn; ++i)
+      for (int c = 0; c < 3; ++c)
+        v[i * 3 + c] = field(k, c, &xyz[i * 3]);
+    return v;
+  };
+  for (int k = 0; k < 6; ++k)
+    {
+      const std::vector<double> v = nodal(*src, k);
+      src->check(mi_vec_set(src->ctx(), k, v.data(), int64_t(v.size())), "mi_vec_set");
+    }
+  mi_project_info info;
+  CHECK(dst->project_state(*src, 2, 1e-12, 500, &info));
+  CHECK(info.sub == 2 && info.its > 0 && info.res <= 1e-12 && info.n_points == 4 * 8 * 8 * 8);
+  for (int k = 0; k < 6; ++k)
+    {
+      const std::vector<double> want = nodal(*dst, k);
+      std::vector<double>       got(want.size());
+      dst->check(mi_vec_get(dst->ctx(), k, got.data(), int64_t(got.size())), "mi_vec_get");
+      double err = 0.0, big = 0.0;
+      for (size_t i = 0; i < want.size(); ++i)
+        err = std::max(err, std::abs(got[i] - want[i])), big = std::max(big, std::abs(want[i]));
+      std::printf("vector %d: max error %.3e of %.3e, dst_sq / src_sq - 1 = %.3e\n", k, err, big, info.dst_sq[k] / info.src_sq[k] - 1.0);
+      CHECK(err <= 1e-9 * big); // kappa_2 (res + 64 eps) with kappa_2 ~ 2e2 of one Q2 cell row
+      CHECK(std::abs(info.dst_sq[k] / info.src_sq[k] - 1.0) <= 1e-9);
+    }
+  CHECK(throws([&] { dst->project_state(*src, 5); }, "sub"));
+  std::printf(g_fail ? "HOST DEVICE TESTS FAILED (%d)\n" : "HOST DEVICE TESTS OK\n", g_fail);
+  return g_fail ? 1 : 0;
+}
+#endif
+
+int main(int argc, char **argv)
+{
+#ifdef MI_HOST_DEVICE_CASES
+  if (argc > 1 && std::string(argv[1]) == "project")
+    return test_device_project_state();
+#endif
+  (void)argc, (void)argv;
   test_vtk_lagrange_order();
   // every file the tests write goes into a scratch directory of their own (under $TMPDIR), removed at the end
   std::string scratch = std::string(std::getenv("TMPDIR") ? std::getenv("TMPDIR") : "/tmp") + "/mi_test_host_XXXXXX";

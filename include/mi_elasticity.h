@@ -351,6 +351,59 @@ int mi_evaluate_points(mi_ctx *ctx, int n_which, const int *which, int64_t npts,
  *   before its first step; on a stepped dst it has the consequences mi_vec_set of those vectors has. */
 int mi_state_transfer(mi_ctx *dst, mi_ctx *src);
 
+/* ---- consistent mass and L2 projection of a state onto another mesh --------------------------------------- */
+/* M is the unit-density vector mass of the context's space on the assembly's rule QGauss(p + 2):
+ *   M_(i,c)(j,d) = delta_cd sum_cells sum_q N_i N_j JxW,
+ * so rho M is the mass the Newmark model integrates its inertia with (1/2 rho v^T M v = mi_energy's kinetic).  On box meshes it
+ * equals the linear model's M / rho to rounding; on perturbed cells the linear model's rule QGauss(p + 1) differs (2e-5
+ * relative at a 5 % vertex perturbation).  No matrix is formed: the product runs cell by cell, colour by colour, with plain
+ * loads and stores in an order the mesh alone fixes -- no atomics, two calls return the same bits.
+ * Blocks are [nrhs][n_dofs], 0 <= nrhs <= MI_MASS_MAX_RHS (nrhs = 0: MI_OK, nothing is read or written).
+ * masked = 1: x is read as 0 on the dofs mi_get_constrained flags, y and the solution are written exactly 0 there, b is ignored
+ *   there; masked = 0: all dofs take part.
+ * The calls of this section modify no state vector (but the six target vectors of mi_state_project), record, matrix, hierarchy,
+ *   counter or timing, need no matrix ("fine_level" 0 and 1, after a "linear_operator" 1 set-up), and allocate their scratch per
+ *   call and free it before they return (mi_mass_solve: 3 nrhs + 1 work vectors).  Undecomposed contexts only, else MI_EINVAL
+ *   "one slab only"; a NULL argument or nrhs / masked out of range: MI_EINVAL. */
+#define MI_MASS_MAX_RHS 6
+int mi_mass_apply(mi_ctx *ctx, int nrhs, int masked, const double *x, double *y); /* y = M x, [nrhs][n_dofs] */
+/* x = M^-1 b by a Jacobi-preconditioned CG on all columns at once, start vector 0; the diagonal of M comes from the product
+ * kernel's own sums, once per solve.  Column j is converged when |r_j|_2 <= tol |b_j|_2 (the recurrence's residual); a zero
+ * column gives x = 0 at once.  A converged column is not updated any more, and every column's dot products are its own: solving
+ * columns together returns, column by column, the bits of solving each alone.  The scalars and done-flags stay on the device;
+ * the host reads one word per iteration.
+ *   res[j] (or NULL) = |b_j - M x_j| / |b_j| on a freshly formed M x_j (0 for a zero column); *its (or NULL) the iteration
+ *   count of the slowest column.  Not converged in max_it iterations: MI_ENOCONV_LIN with x, res and its still written. */
+int mi_mass_solve(mi_ctx *ctx, int nrhs, int masked, const double *b, double *x, double tol, int max_it, int *its, double *res);
+/* Load of src's fields against dst's test functions, b [n_which][n_dofs(dst)] (every dof, nothing masked):
+ *   b_(i,c) = sum_{dst cells} sum_q N_i^dst(xi_q) w_c^src(X_q) JxW(q)
+ * on a COMPOSITE rule: every dst cell is cut into sub^dim equal boxes in xi (1 <= sub <= 4) with QGauss(p_dst + 2) on each;
+ * X_q is the point's image under dst's Q1 map and w^src(X_q) exactly what mi_evaluate_points(src, ...) returns there.
+ * When src.reps = sub * dst.reps on the same box the integrand is a polynomial of degree p_dst + p_src <= 2 p_dst + 3 per
+ * direction on each sub-box and b is exact; the same holds for sub = 1 on equal cells with any pair of degrees.  Otherwise b is
+ * the discrete load of this rule: a definition, not a measurement.  which[]: MI_V_* ids, 0 <= n_which <= 6 (0: MI_OK).
+ *   Conditions as mi_state_transfer (same dim, same device, both undecomposed).  A quadrature point outside src's mesh:
+ *   MI_EINVAL naming the first dst cell (lexicographic id) and its point.  The points go through the evaluation in chunks of
+ *   whole cells of one colour (point scratch <= 256 MiB; tuning key "project_chunk_cells", 0 = automatic, forces a size for
+ *   tests): the result does not depend on the chunk size bit for bit. */
+int mi_project_load(mi_ctx *dst, mi_ctx *src, int n_which, const int *which, int sub, double *b);
+typedef struct
+{
+  int32_t its, sub;
+  int64_t n_points;  /* points of the composite rule over dst */
+  double  res;       /* worst column's |b - M w| / |b| */
+  double  src_sq[6]; /* sum_q |w_src(X_q)|^2 JxW on the composite rule */
+  double  dst_sq[6]; /* w_dst^T M w_dst */
+} mi_project_info;
+/* L2 projection of src's state onto dst's space: for each of the six vectors MI_V_TOTAL_DISPLACEMENT .. MI_V_ACCELERATION_OLD,
+ * w_dst = 0 on dst's constrained dofs and M_ff w_f = b_f on the free ones.  BY DEFINITION mi_project_load for the six vectors,
+ * then mi_mass_solve with masked = 1, then the result into dst's six vectors, device to device -- the same bits as that host
+ * route.  The best approximation of src's fields in dst's (constrained) space on the exact pairs above: orthogonal to dst's test
+ * functions, never increasing the integral of |w|^2 -- where mi_state_transfer samples.
+ *   Writes nothing else in dst and nothing in src.  On any error -- a point outside src's mesh (MI_EINVAL), no convergence
+ *   (MI_ENOCONV_LIN; *out is still written), a refusal -- dst is unchanged.  out or NULL. */
+int mi_state_project(mi_ctx *dst, mi_ctx *src, int sub, double tol, int max_it, mi_project_info *out);
+
 /* ---- linear model: ElastoDynamics (source/linear_elasticity/linear_elasticity.cc) -------------------------- */
 /* state vectors of the linear model live in the same slots as the nonlinear ones */
 enum
