@@ -154,6 +154,10 @@ def lib():
         L.mi_vec_set.argtypes = [vp, C.c_int, dp, C.c_int64]
         L.mi_matrix_get_csr.argtypes = [vp, C.POINTER(C.c_int64), i32p, dp]
         L.mi_spmv.argtypes = [vp, dp, dp]
+        L.mi_spmm.argtypes = [vp, C.c_int, dp, dp]
+        L.mi_spmm.restype = C.c_int
+        L.mi_bench_spmm.argtypes = [vp, C.c_int, C.c_int, C.c_int, dp, dp]
+        L.mi_bench_spmm.restype = C.c_int
         L.mi_get_diagonal_blocks.argtypes = [vp, dp]
         L.mi_get_diagonal_blocks.restype = C.c_int
         L.mi_linear_setup.argtypes = [vp, C.c_double]
@@ -194,7 +198,8 @@ def lib():
         L.mi_block_gram.argtypes = [vp, C.c_int64, dp, C.c_int, dp, C.c_int, dp]
         L.mi_block_combine.argtypes = [vp, C.c_int64, dp, C.c_int, dp, C.c_int, dp]
         L.mi_dense_sym_eig.argtypes = [C.c_int, dp, dp, dp, dp]
-        for f in ("mi_linear_modes", "mi_block_gram", "mi_block_combine", "mi_dense_sym_eig"):
+        L.mi_tangent_modes.argtypes = [vp, C.c_int, C.c_double, C.c_int, dp, dp, dp, C.POINTER(C.c_int)]
+        for f in ("mi_linear_modes", "mi_tangent_modes", "mi_block_gram", "mi_block_combine", "mi_dense_sym_eig"):
             getattr(L, f).restype = C.c_int
         L.mi_set_profiling.argtypes = [vp, C.c_int]
         L.mi_get_timings.argtypes = [vp, C.POINTER(Timings)]
@@ -646,6 +651,14 @@ class Context:
         self._chk(lib().mi_get_diagonal_blocks(self.h, _dp(b)))
         return b
 
+    def spmm(self, X, out=None):
+        """Y [n, nv] with Y[:, j] = K X[:, j] through the block product where the context is eligible (mi_spmm), else column by
+        column; out [n, nv]: its values stand where nobody computes a row"""
+        xt = np.ascontiguousarray(np.asarray(X, dtype=np.float64).T)
+        yt = np.zeros_like(xt) if out is None else np.ascontiguousarray(np.asarray(out, dtype=np.float64).T)
+        self._chk(lib().mi_spmm(self.h, xt.shape[0], _dp(xt), _dp(yt)))
+        return yt.T.copy()
+
     # ---- the multigrid hierarchy as the last linear solve left it, read-only (tests)
     def mg_n_levels(self):
         return lib().mi_mg_n_levels(self.h)
@@ -710,6 +723,21 @@ class Context:
         self._chk(rc)
         return out
 
+    def tangent_modes(self, n_modes, tol=1e-8, max_it=1000, want_modes=True):
+        """the n_modes algebraically smallest eigenpairs of K_T(u) phi = lam rho M phi on the free dofs, K_T the nonlinear model's
+        tangent stiffness at the committed state V_U (mi_tangent_modes): dict(lam[n_modes], modes[n_modes, n] or None,
+        residual[n_modes], its).  A negative lam is a buckled state.  Not converged within max_it: MiError with code
+        MI_ENOCONV_LIN whose .partial is that dict"""
+        lam, res, its = np.zeros(n_modes), np.zeros(n_modes), C.c_int(0)
+        modes = np.zeros((n_modes, self.n)) if want_modes else None
+        rc = lib().mi_tangent_modes(self.h, int(n_modes), float(tol), int(max_it), _dp(lam), _dp(modes) if want_modes else None,
+                                    _dp(res), C.byref(its))
+        out = dict(lam=lam, modes=modes, residual=res, its=its.value)
+        if rc == MI_ENOCONV_LIN:
+            raise MiError(rc, lib().mi_last_error(self.h).decode(), partial=out)
+        self._chk(rc)
+        return out
+
     def linear_apply(self, which, x):
         """y = K x (0), M x (1), A x (2) through the device kernels of the current set-up; 3: one V-cycle of its multigrid"""
         x = np.ascontiguousarray(x, dtype=np.float64)
@@ -762,6 +790,12 @@ class Context:
         ms = C.c_double(0)
         self._chk(lib().mi_bench_spmv(self.h, reps, C.byref(ms)))
         return ms.value
+
+    def bench_spmm(self, nv, reps=10, rounds=5):
+        """(ms_block[rounds], ms_single[rounds]): the block product on nv columns against nv single products, alternated"""
+        a, b = np.zeros(rounds), np.zeros(rounds)
+        self._chk(lib().mi_bench_spmm(self.h, int(nv), int(reps), int(rounds), _dp(a), _dp(b)))
+        return a, b
 
     def bench_assemble(self, reps=3):
         ms = C.c_double(0)

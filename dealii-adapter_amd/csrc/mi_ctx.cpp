@@ -712,6 +712,45 @@ namespace mi_detail
                       c->maxrow);
   }
 
+  static bool spmm_eligible(const mi_ctx *c)
+  {
+    if (c->dim != 3 || c->mf_fine || c->active_linear_mf || c->active_sell_vals || c->spmv_variant != 3 || c->unassembled_now ||
+        team_size(c) != 1)
+      return false;
+    const int64_t nin = c->mesh.sell_nslices_interior, nbd = c->mesh.sell_nslices - nin;
+    return !(nin > 0 && c->split_int) && !(nbd > 0 && c->split_bnd);
+  }
+
+  void enqueue_spmm(mi_ctx *c, int nv, const double *x, int64_t ldx, double *y, int64_t ldy, bool block)
+  {
+    if (!block || !spmm_eligible(c))
+      {
+        for (int j = 0; j < nv; ++j)
+          enqueue_spmv(c, x + int64_t(j) * ldx, y + int64_t(j) * ldy, nullptr, nullptr, nullptr);
+        return;
+      }
+    const int32_t nin = int32_t(c->mesh.sell_nslices_interior), nbd = int32_t(c->mesh.sell_nslices) - nin;
+    for (int j0 = 0; j0 < nv; j0 += mi::SELL_SPMM_NV)
+      {
+        const int      g = std::min(mi::SELL_SPMM_NV, nv - j0);
+        mi::SellParams p = sell_params(c, x + int64_t(j0) * ldx, y + int64_t(j0) * ldy, nullptr, nullptr, nullptr);
+        p.vals32         = nullptr;
+        p.split          = 0;
+        if (nin > 0)
+          {
+            p.slice0 = 0, p.nslices = nin, p.part0 = 0;
+            mi::launch_sell_spmm(p, g, ldx, ldy, c->grid_spmv_int, c->stream, c->sell_unroll);
+            ++c->n_spmm_launches;
+          }
+        if (nbd > 0)
+          {
+            p.slice0 = nin, p.nslices = nbd, p.part0 = 0;
+            mi::launch_sell_spmm(p, g, ldx, ldy, c->grid_spmv_bnd, c->stream, c->sell_unroll);
+            ++c->n_spmm_launches;
+          }
+      }
+  }
+
   // y = K x on every slab of the team with the ghost planes of x exchanged on the way: the halo travels (RCCL: on
   // the team's communication stream) while the interior rows are computed; the boundary rows follow it.
   int team_spmv(Team &T, const std::function<mi_ctx *(mi_ctx *)> &ctx_of, const std::function<double *(mi_ctx *)> &x_of,
@@ -2942,6 +2981,39 @@ int mi_assemble_residual(mi_ctx *c, double *res_norm)
   return assemble_impl(c, true, res_norm);
 }
 
+// What mi_tangent_modes does before it iterates (one slab, checked by the caller): the tangent selected, du = 0 as
+// mi_newton_begin_step leaves it, the assembly of mi_assemble (diagonal blocks formed afresh under "mf_diag_lag" too), and where
+// the V-cycle preconditions the refresh of the hierarchy as cg_run makes it -- here always, whatever "mg_refresh_every" says
+extern "C++" int mi_detail::tangent_prepare(mi_ctx *c)
+{
+  HIPCHK(c, hipSetDevice(c->device));
+  if (c->linear)
+    linear_select(c, -1);
+  c->active_sell_vals = nullptr;
+  c->active_dinv      = nullptr;
+  HIPCHK(c, hipMemsetAsync(c->vec(MI_V_SOLUTION_DELTA), 0, size_t(c->n) * sizeof(double), c->stream));
+  HIPCHK(c, hipMemsetAsync(c->vec(MI_V_NEWTON_UPDATE), 0, size_t(c->n) * sizeof(double), c->stream));
+  c->newton_update_is_zero = true;
+  c->mf_diag_fresh         = false;
+  if (int rc = assemble_impl(c, false, nullptr))
+    return rc;
+  if (mg_active(c))
+    {
+      if (int rc = check_mf_tangent(c)) // (cg_run's guard; an assembly has just run)
+        return rc;
+      refresh_vals32(c);
+      mg_reset_estimates(*c->team); // (the estimates of a refresh continue from the last one's: from scratch, two calls agree bit for bit)
+      c->mg_force = true;
+      if (int rc = mg_update(*c->team)) // (the hierarchy stays marked stale and forced: the next solve rebuilds it)
+        return rc;
+      c->mg_force               = false;
+      c->mg_steps_since_refresh = 0;
+      c->mg_its_ref             = 0;
+      ++c->n_mg_refresh;
+    }
+  return MI_OK;
+}
+
 // Strain energy, kinetic energy and body-force potential of the committed state (MI_V_TOTAL_DISPLACEMENT, MI_V_VELOCITY).
 // Needs no matrix, record or hierarchy and changes none: every mode of a context, every slab of a team (each sums the cells
 // it owns; one all-reduce of the three sums and the inverted flag); no timing slot, no counter
@@ -3779,6 +3851,41 @@ int mi_spmv(mi_ctx *c, const double *x_host, double *y_host)
   return gbuf_to_host(c, y_host);
 }
 
+// test hook: y_j = K x_j for nv columns (host arrays [nv][n_dofs]) through enqueue_spmm on the plain tangent: the block product
+// where the context is eligible, else column by column.  One slab only
+int mi_spmm(mi_ctx *c, int nv, const double *x_host, double *y_host)
+{
+  if (!c || !x_host || !y_host || nv < 1 || nv > 64)
+    return c ? fail(c, MI_EINVAL, "mi_spmm: null argument or nv outside 1 .. 64") : MI_EINVAL;
+  if (int e = check_tangent_array(c, "mi_spmm"))
+    return e;
+  if (team_size(c) != 1)
+    return fail(c, MI_EINVAL, "mi_spmm: one slab only (an undecomposed mesh)");
+  HIPCHK(c, hipSetDevice(c->device));
+  if (int e = check_mf_tangent(c))
+    return e;
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  c->active_sell_vals = nullptr;
+  const size_t blk = size_t(nv) * size_t(c->n);
+  double      *d   = nullptr;
+  HIPCHK(c, hipMalloc((void **)&d, 2 * blk * sizeof(double)));
+  hipError_t e = hipMemcpy(d, x_host, blk * sizeof(double), hipMemcpyHostToDevice);
+  if (e == hipSuccess)
+    e = hipMemcpy(d + blk, y_host, blk * sizeof(double), hipMemcpyHostToDevice); // (what nobody computes keeps the caller's value)
+  if (e == hipSuccess)
+    {
+      enqueue_spmm(c, nv, d, c->n, d + blk, c->n);
+      e = hipGetLastError();
+    }
+  if (e == hipSuccess)
+    e = hipStreamSynchronize(c->stream);
+  if (e == hipSuccess)
+    e = hipMemcpy(y_host, d + blk, blk * sizeof(double), hipMemcpyDeviceToHost);
+  hipFree(d);
+  HIPCHK(c, e);
+  return MI_OK;
+}
+
 int mi_set_tuning(mi_ctx *c, const char *key, int value)
 {
   const std::string k(key ? key : "");
@@ -3848,6 +3955,11 @@ int mi_set_tuning(mi_ctx *c, const char *key, int value)
       if (k == "face_slots" && (value == 0 || value == 1)) // Neumann faces: one launch + gather (1) | colour by colour (0)
         {
           m->face_slots = value;
+          continue;
+        }
+      if (k == "modes_block_product" && (value == 0 || value == 1)) // mi_tangent_modes: block product where eligible (1) | column by column
+        {
+          m->modes_block_product = value;
           continue;
         }
       if (k == "project_chunk_cells" && value >= 0) // load pass of the L2 projection: cells of dst per chunk (0: automatic)
@@ -4079,6 +4191,10 @@ int mi_get_tuning(mi_ctx *c, const char *key, int *value)
     *value = mi_linear_mg_n_levels(m) > 1 ? 1 : 0;
   else if (k == "project_chunk_cells")
     *value = m->project_chunk_cells;
+  else if (k == "modes_block_product")
+    *value = m->modes_block_product;
+  else if (k == "spmm_launches") // launches of the block product sell_spmm so far (no setter)
+    *value = int(m->n_spmm_launches);
   else if (k == "mf_diag_lag")
     *value = m->mf_diag_lag;
   else if (k == "smoother_quadrature")
@@ -4259,6 +4375,50 @@ int mi_bench_spmv(mi_ctx *c, int reps, double *ms_per_launch)
       for (int i = 0; i < 5; ++i)
         fprintf(stderr, "  %-42s %8.0f ticks  %5.1f %%\n", name[i], sum[i] / double(ncell), 100.0 * sum[i] / tot);
     }
+  return MI_OK;
+}
+
+// sell_spmm on nv columns against nv launches of the single-vector product on the same matrix: `rounds` alternated measurements
+// of each (device events around `reps` products of the whole block), ms per block product into ms_block / ms_single [rounds]
+int mi_bench_spmm(mi_ctx *c, int nv, int reps, int rounds, double *ms_block, double *ms_single)
+{
+  if (!c || !ms_block || !ms_single || nv < 1 || nv > mi::BLOCK_MAX_OUT || reps < 1 || rounds < 1)
+    return c ? fail(c, MI_EINVAL, "mi_bench_spmm: null argument, nv outside 1 .. %d, reps < 1 or rounds < 1", mi::BLOCK_MAX_OUT) : MI_EINVAL;
+  if (int e = check_tangent_array(c, "mi_bench_spmm"))
+    return e;
+  if (team_size(c) != 1)
+    return fail(c, MI_EINVAL, "mi_bench_spmm: one slab only (an undecomposed mesh)");
+  HIPCHK(c, hipSetDevice(c->device));
+  if (int e = check_mf_tangent(c))
+    return e;
+  c->active_sell_vals = nullptr;
+  const size_t blk = size_t(nv) * size_t(c->n);
+  double      *d   = nullptr;
+  HIPCHK(c, hipMalloc((void **)&d, 2 * blk * sizeof(double)));
+  mi::launch_block_hash_init(c->dim, d, c->n, nv, c->d_cmask, c->n, c->stream);
+  hipEvent_t a, b;
+  HIPCHK(c, hipEventCreate(&a));
+  HIPCHK(c, hipEventCreate(&b));
+  hipError_t err = hipSuccess;
+  for (int r = -1; r < rounds && err == hipSuccess; ++r) // (round -1: warm-up)
+    for (int form = 0; form < 2 && err == hipSuccess; ++form)
+      {
+        hipEventRecord(a, c->stream);
+        for (int i = 0; i < reps; ++i)
+          enqueue_spmm(c, nv, d, c->n, d + blk, c->n, form == 0);
+        hipEventRecord(b, c->stream);
+        err      = hipEventSynchronize(b);
+        float ms = 0;
+        if (err == hipSuccess)
+          err = hipEventElapsedTime(&ms, a, b);
+        if (r >= 0)
+          (form == 0 ? ms_block : ms_single)[r] = double(ms) / reps;
+      }
+  hipEventDestroy(a);
+  hipEventDestroy(b);
+  hipFree(d);
+  HIPCHK(c, err);
+  HIPCHK(c, hipGetLastError());
   return MI_OK;
 }
 

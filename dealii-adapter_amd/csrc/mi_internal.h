@@ -268,6 +268,11 @@ struct mi_ctx
   // L2 projection (mi_project_load, mi_state_project): tuning "project_chunk_cells" -- cells of dst per chunk of the load pass,
   // 0: as many as keep the point scratch at or below 256 MiB.  A test's key: the result does not depend on it
   int       project_chunk_cells = 0;
+  // tuning "modes_block_product" (read by mi_tangent_modes alone): 1 (default) the stiffness images of a block go through the
+  // block product sell_spmm where the context is eligible (enqueue_spmm), 0 column by column.  n_spmm_launches: launches of
+  // sell_spmm so far ("spmm_launches", read-only)
+  int       modes_block_product = 1;
+  int64_t   n_spmm_launches     = 0;
   // nodal forces and reactions (mi_reactions), allocated on first use: accumulator [nnodes][8] | load [n] | terms [4][n] |
   // forces [n] | face slots of its own (the size of d_face_slots) | chunk results | the result (mi::REACT_NOUT); reads d_node_xyz
   double   *d_react      = nullptr;
@@ -359,6 +364,11 @@ namespace mi_detail
   // smoother: the product belongs to the multigrid preconditioner and may use the fp32-rounded copy of the values
   void enqueue_spmv(mi_ctx *c, const double *x, double *y, const double *dotv, double *partials, const int32_t *done,
                     int part = 0, bool smoother = false, const ChebFusion *cheb = nullptr);
+  // y_j = K x_j for nv columns (column j at x + j ldx, y + j ldy) on the current tangent.  Where every sliced-ELL launch of the
+  // context is an LDS-staged one (3D, assembled fp64 tangent, more than mi::SELL_SPLIT_MAX_SLICES slices per launch) the columns go
+  // mi::SELL_SPMM_NV at a time through sell_spmm -- the matrix read once per group, every column bit for bit what enqueue_spmv
+  // gives --, else (and with block == false) one by one through enqueue_spmv
+  void enqueue_spmm(mi_ctx *c, int nv, const double *x, int64_t ldx, double *y, int64_t ldy, bool block = true);
   int  set_precond_storage(mi_ctx *c, int bits); // 64 | 32, for the context and its multigrid levels
   // Jacobi-PCG on the active matrix (all slabs of the team): x = vector x_id (warm start), b = vector b_id;
   // tol >= 0 relative to ||b||, tol < 0 absolute (-tol)
@@ -382,6 +392,12 @@ namespace mi_detail
                      mi_ctx **out);
   void destroy_team(Team *T);
   int  enqueue_assembly(mi_ctx *c, bool residual_only = false);
+  // y = M x for the device blocks x, y [nrhs][n] (nrhs <= mi::MASS_MAX_RHS; diag: y [n] = the diagonal of M), the unit-density
+  // consistent mass of mi_mass_apply, enqueued on c's stream (mi_project.cpp)
+  int  enqueue_mass_apply(mi_ctx *c, int nrhs, int masked, bool diag, const double *x, double *y);
+  // mi_tangent_modes (mi_modes.cpp): du = 0, the assembly of mi_assemble at the committed state, and with the V-cycle on the
+  // hierarchy brought to that tangent by cg_run's route (mi_ctx.cpp)
+  int  tangent_prepare(mi_ctx *c);
   int  ensure_element_tangents(mi_ctx *c);
   // multigrid (mi_mg.cpp)
   int  mg_setup(mi_ctx *c);

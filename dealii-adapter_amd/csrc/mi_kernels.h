@@ -498,6 +498,10 @@ namespace mi
                              const uint8_t *cmask, double *rhs, int nnodes_if, hipStream_t s);
   void launch_spmv(int dim, const SpmvParams &p, int grid, hipStream_t s, int variant, int maxrow);
   void launch_sell_spmv(int dim, const SellParams &p, int grid, hipStream_t s, int unroll);
+  // columns per launch of the block product sell_spmm: 3 columns take 249 VGPRs at the occupancy of sell_spmv (2 waves per SIMD,
+  // set by the 69 KB of staging buffers); 4 spill into 44 AGPRs and halve it (profiles/tangent_modes/resources.tsv)
+  constexpr int SELL_SPMM_NV = 3;
+  int  launch_sell_spmm(const SellParams &p, int nv, int64_t ldx, int64_t ldy, int grid, hipStream_t s, int unroll);
   void set_next_sell_launch_events(hipEvent_t start, hipEvent_t stop); // profiling: bracket exactly the next launch
   // ev_start / ev_stop (optional): bracket exactly this launch (dispatch-level events, profiling)
   void launch_ebe_spmv(const EbeParams &p, int64_t cell_begin, int32_t cell_count, hipStream_t s,
@@ -647,6 +651,8 @@ namespace mi
   void launch_vec_residual(double *res, const double *b, const double *q, int64_t n, hipStream_t s);
   void launch_vec_lincomb2(double *x, double a, const double *h1, double b, const double *h2, int64_t n, hipStream_t s);
   void launch_scale_start(double *x, double *q, const double *sc, int64_t n, hipStream_t s);
+  void launch_tangent_images(int dim, double *ks, const double *mx, double *ms, const uint8_t *cmask, double shift, double rho, int64_t n,
+                             int cols, hipStream_t s);
   void launch_copy_owned(double *y, const double *x, int64_t n, int64_t own0, int64_t own_n, hipStream_t s);
   void launch_lattice_interp(int dim, bool add, const LatticeParams &p, double *tgt, const double *src,
                              const uint8_t *cmask_tgt, hipStream_t s);

@@ -2291,6 +2291,143 @@ namespace mi
       }
   }
 
+  // ------------------------------------------------------------------ block product: the matrix read once for NV columns
+  // sell_slice for D = 3, fp64 values and the plain epilogue, on NV columns at once (column j of x at x + j ldx, of y at y + j ldy):
+  // the same staging of a slice's x-line chunk into LDS, the same chunk halves and x-widths; each staged block is multiplied
+  // into NV accumulator triples.  Per row and column the operations and their order are sell_slice's, written as the same
+  // expressions, so column j of the result equals the single-vector product of column j bit for bit
+  template <int NV, int WXT, bool NTL, bool ICOL>
+  __device__ __forceinline__ void sell_spmm_slice(const SellParams &prm, const int64_t ldx, const int64_t ldy, const int sl, const int wx_rt,
+                                                  const int lane, char *stage)
+  {
+    constexpr int D = 3, DD = 9, VB = 8;
+    typedef const volatile __attribute__((address_space(3))) double *lds_cvp;
+    typedef __attribute__((address_space(3))) void                  *lds_vp;
+    typedef const __attribute__((address_space(1))) void            *glb_vp;
+    const int     wx    = WXT ? WXT : wx_rt;
+    const int     len   = prm.len[sl], ng = len / wx;
+    const int64_t off   = prm.off[sl];
+    const int     node  = prm.perm[int64_t(sl) * 64 + lane];
+    const int     chunk = 64 * wx * DD * VB;                    // bytes of one x-line of the slice
+    const int     ns    = chunk > SELL_STAGE_BYTES ? 2 : 1;     // staged whole, or in two halves of 32 rows
+    const int     rows  = 64 / ns, seg = chunk / ns, nfull = seg / 1024, rem = (seg % 1024) / 16;
+    const char *__restrict__ vbytes = reinterpret_cast<const char *>(prm.vals) + off * (64 * DD * VB) + lane * 16;
+    const int32_t *__restrict__ cp  = prm.col + off * 64 + lane;
+    const lds_cvp rd = (lds_cvp)(reinterpret_cast<double *>(stage) + (lane % rows) * (wx * DD));
+    double        acc[NV][D];
+#pragma unroll
+    for (int c = 0; c < NV; ++c)
+#pragma unroll
+      for (int i = 0; i < D; ++i)
+        acc[c][i] = 0.0;
+    int32_t c0 = 0, gy = 0, wy = 1;
+    if constexpr (ICOL)
+      {
+        c0 = prm.rowbox[(int64_t(sl) * 64 + lane) * 2];
+        wy = (prm.rowbox[(int64_t(sl) * 64 + lane) * 2 + 1] >> 8) & 255;
+      }
+    constexpr int WXM = WXT ? WXT : 9;
+    for (int g = 0; g < ng; ++g)
+      {
+        double xx[NV][WXM * D];
+        if constexpr (ICOL)
+          {
+#pragma unroll
+            for (int c = 0; c < NV; ++c)
+#pragma unroll
+              for (int j = 0; j < WXM * D; ++j)
+                if (WXT || j < wx * D)
+                  xx[c][j] = prm.x[int64_t(c) * ldx + int64_t(c0) * D + j];
+            c0 += prm.nn0;
+            if (++gy == wy)
+              {
+                gy = 0;
+                c0 += prm.nn0 * (prm.nn1 - wy);
+              }
+          }
+        else
+          {
+#pragma unroll
+            for (int kx = 0; kx < WXM; ++kx)
+              if (WXT || kx < wx)
+                {
+                  const int32_t cn = cp[int64_t(g * wx + kx) * 64];
+#pragma unroll
+                  for (int c = 0; c < NV; ++c)
+#pragma unroll
+                    for (int j = 0; j < D; ++j)
+                      xx[c][kx * D + j] = prm.x[int64_t(c) * ldx + int64_t(cn) * D + j];
+                }
+          }
+        for (int s = 0; s < ns; ++s)
+          {
+            const char *src = vbytes + int64_t(g) * chunk + s * seg;
+            if constexpr (WXT != 0)
+              {
+#pragma unroll
+                for (int j = 0; j < (64 * WXT * DD * VB) / 1024; ++j)
+                  __builtin_amdgcn_global_load_lds((glb_vp)(src + j * 1024), (lds_vp)(stage + j * 1024), 16, 0, NTL ? 2 : 0);
+              }
+            else
+              for (int j = 0; j < nfull; ++j)
+                __builtin_amdgcn_global_load_lds((glb_vp)(src + j * 1024), (lds_vp)(stage + j * 1024), 16, 0, NTL ? 2 : 0);
+            if (lane < rem)
+              __builtin_amdgcn_global_load_lds((glb_vp)(src + nfull * 1024), (lds_vp)(stage + nfull * 1024), 16, 0, NTL ? 2 : 0);
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // the chunk has landed (and x has arrived)
+            MI_WAVE_SYNC();
+            if (ns == 1 || lane / rows == s)
+              {
+#pragma unroll
+                for (int kx = 0; kx < WXM; ++kx)
+                  if (WXT || kx < wx)
+                    {
+                      double v[DD];
+#pragma unroll
+                      for (int e = 0; e < DD; ++e)
+                        v[e] = double(rd[kx * DD + e]);
+#pragma unroll
+                      for (int c = 0; c < NV; ++c)
+#pragma unroll
+                        for (int i = 0; i < D; ++i)
+#pragma unroll
+                          for (int j = 0; j < D; ++j)
+                            acc[c][i] += v[i * D + j] * xx[c][kx * D + j];
+                    }
+              }
+            MI_WAVE_SYNC(); // the buffer is free again
+          }
+      }
+    if (node < 0)
+      return;
+#pragma unroll
+    for (int c = 0; c < NV; ++c)
+#pragma unroll
+      for (int i = 0; i < D; ++i)
+        prm.y[int64_t(c) * ldy + int64_t(node) * D + i] = acc[c][i];
+  }
+
+  template <int NV, bool NTL, bool ICOL>
+  __global__ __launch_bounds__(SELL_WPB * 64) void sell_spmm(SellParams prm, int64_t ldx, int64_t ldy)
+  {
+    __shared__ __attribute__((aligned(16))) char s_stage[SELL_WPB][SELL_STAGE_BYTES];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int nwg = gridDim.x, b = blockIdx.x;
+    const int lb  = (prm.xcd_remap && nwg % 8 == 0) ? (b % 8) * (nwg / 8) + b / 8 : b;
+    const int per = (prm.nslices + nwg - 1) / nwg;
+    const int s0 = prm.slice0 + lb * per, s1 = min(prm.slice0 + prm.nslices, s0 + per);
+    for (int sl0 = s0 + wave; sl0 < s1; sl0 += SELL_WPB)
+      {
+        const int sl = __builtin_amdgcn_readfirstlane(sl0);
+        const int wx = prm.wx[sl];
+        if (wx == 3) // the two x-widths of 3D Q2 rows, unrolled
+          sell_spmm_slice<NV, 3, NTL, ICOL>(prm, ldx, ldy, sl, wx, lane, s_stage[wave]);
+        else if (wx == 5)
+          sell_spmm_slice<NV, 5, NTL, ICOL>(prm, ldx, ldy, sl, wx, lane, s_stage[wave]);
+        else
+          sell_spmm_slice<NV, 0, NTL, ICOL>(prm, ldx, ldy, sl, wx, lane, s_stage[wave]);
+      }
+  }
+
   // ------------------------------------------------------------------ product with unassembled element tangents
   // y += sum over the cells of one colour of P_e^T K_e P_e x, with K_e stored as its 378 lower-triangle node-pair
   // blocks (3D Q2), layout [cell][e][block]: a wave reads 512 contiguous bytes per load, every stored number is read
@@ -7564,6 +7701,20 @@ namespace mi
     if (i < n)
       x[i] = b != 0.0 ? a * h1[i] + b * h2[i] : a * h1[i];
   }
+  // mi_tangent_modes: the images of a block of columns from A x (in ks) and the unit-density M x (mx, zero on constrained dofs):
+  // ks = A x - shift M x, zero on constrained dofs, in place; ms = rho M x.  total = columns * n, column-major
+  __global__ __launch_bounds__(256) void tangent_images(int dim, double *ks, const double *__restrict__ mx, double *__restrict__ ms,
+                                                        const uint8_t *__restrict__ cmask, double shift, double rho, int64_t n, int64_t total)
+  {
+    const int64_t i = int64_t(blockIdx.x) * 256 + threadIdx.x;
+    if (i >= total)
+      return;
+    const int64_t r   = i % n;
+    const bool    con = (cmask[r / dim] >> int(r % dim)) & 1;
+    const double  m   = mx[i];
+    ks[i]             = con ? 0.0 : ks[i] - shift * m;
+    ms[i]             = rho * m;
+  }
   // start vector h of a solve scaled to its best multiple: x = alpha h, q = alpha (A h) with alpha = h.b / h.Ah (the
   // multiple with the smallest energy-norm error; sc = {h.b, h.Ah}; alpha = 0 if h.Ah is not positive)
   __global__ __launch_bounds__(256) void scale_start(double *x, double *q, const double *__restrict__ sc, int64_t n)
@@ -9870,6 +10021,26 @@ namespace mi
       MI_SELL_GO(2);
 #undef MI_SELL_GO
   }
+  template <int NV>
+  static void sell_spmm_go(const SellParams &p, int64_t ldx, int64_t ldy, int grid, hipStream_t s, bool nt, bool icol)
+  {
+    auto *kern = nt ? (icol ? sell_spmm<NV, true, true> : sell_spmm<NV, true, false>) : (icol ? sell_spmm<NV, false, true> : sell_spmm<NV, false, false>);
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(SELL_WPB * 64), 0, s, p, ldx, ldy);
+  }
+  // y_j = K x_j for nv <= SELL_SPMM_NV columns (3D, fp64 values, plain epilogue, not a split launch: the caller checks); unroll as
+  // launch_sell_spmv.  1: nv out of range
+  int launch_sell_spmm(const SellParams &p, int nv, int64_t ldx, int64_t ldy, int grid, hipStream_t s, int unroll)
+  {
+    static_assert(SELL_SPMM_NV == 3, "one instance per column count");
+    const bool nt = unroll == 5, icol = p.rowbox != nullptr;
+    switch (nv)
+      {
+      case 1: sell_spmm_go<1>(p, ldx, ldy, grid, s, nt, icol); return 0;
+      case 2: sell_spmm_go<2>(p, ldx, ldy, grid, s, nt, icol); return 0;
+      case 3: sell_spmm_go<3>(p, ldx, ldy, grid, s, nt, icol); return 0;
+      }
+    return 1;
+  }
   void launch_mf_spmv(const MfParams &p, int64_t cell_begin, int32_t cell_count, hipStream_t s, hipEvent_t ev_start,
                       hipEvent_t ev_stop)
   {
@@ -10577,6 +10748,12 @@ namespace mi
   void launch_vec_lincomb2(double *x, double a, const double *h1, double b, const double *h2, int64_t n, hipStream_t s)
   {
     hipLaunchKernelGGL(vec_lincomb2, dim3(int((n + 255) / 256)), dim3(256), 0, s, x, a, h1, b, h2, n);
+  }
+  void launch_tangent_images(int dim, double *ks, const double *mx, double *ms, const uint8_t *cmask, double shift, double rho, int64_t n,
+                             int cols, hipStream_t s)
+  {
+    const int64_t total = n * cols;
+    hipLaunchKernelGGL(tangent_images, dim3(unsigned((total + 255) / 256)), dim3(256), 0, s, dim, ks, mx, ms, cmask, shift, rho, n, total);
   }
   void launch_scale_start(double *x, double *q, const double *sc, int64_t n, hipStream_t s)
   {

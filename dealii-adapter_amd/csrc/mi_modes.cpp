@@ -1,8 +1,17 @@
-// mi_modes.cpp -- the lowest vibration modes of the linear model:  K phi = lambda M phi  on the free dofs (mi_linear_modes).
+// mi_modes.cpp -- the lowest vibration modes of the linear model:  K phi = lambda M phi  on the free dofs (mi_linear_modes), and of
+// the nonlinear model's tangent at the committed state:  K_T(u) phi = lambda rho M phi  (mi_tangent_modes).  One eigensolver over
+// an operator pair: the two entry points differ in products() and in where the preconditioner comes from.
 // Compiled as part of mi_linear.cpp's translation unit (included at its end), not as an object of its own.
 //
+// The tangent's pair.  The context holds A = K_T + alpha_1 rho M (what mi_assemble forms and the Newmark step's CG solves with), in
+// whichever form it runs: assembled (sell_spmv / sell_spmv_split) or matrix-free (mf_spmv, mf_spmv_q3 + their gathers).  K_T x is
+// formed as A x - alpha_1 rho (M x), M x from enqueue_mass_apply (masked, six columns per launch group); that difference carries
+// a rounding floor of order eps alpha_1 / |lambda| relative to |lambda| |rho M x| (1e-11 at worst in the tested cases), which
+// the stopping tolerance must stay above.  The preconditioner is the context's own for A -- the tangent's V-cycle or the
+// Jacobi diagonal of the assembly -- and needs A positive definite, lambda_min > -alpha_1: the condition of the step's CG.
+//
 // LOBPCG (Knyazev 2001) on a block of m = n_modes + guard vectors.  The device holds S = [X W P] and its images KS, MS
-// (9 m n doubles, allocated per call); the host sees only Gram matrices.  One iteration:
+// (9 m n doubles, allocated per call; the tangent's pair one block more for M x); the host sees only Gram matrices.  One iteration:
 //
 //   R = KX - MX diag(lambda), masked, with |R_j| and |MX_j| of the same pass        block_residual            (1 launch + finish)
 //   W_j = T R_j, masked; T = the preconditioner the current set-up has for the stepping matrix A = M + theta^2 dt^2 K
@@ -20,6 +29,14 @@
 //
 // If the Cholesky factor meets a pivot below CHOL_MIN (the scaled Gram matrix is numerically singular: P has run into the span
 // of X and W) the iteration is repeated without P; if it fails again X is re-orthonormalised and P restarted.
+//
+// The tangent's pair runs every Rayleigh-Ritz step of the iteration in another form (rayleigh_ritz with drop): the columns that
+// depend on those before them are left out, and the problem is solved in two passes.  mi_linear_modes never takes that form.  Its preconditioner approximates (K_T + sigma
+// rho M)^-1 with sigma = alpha_1 far above the wanted lambda, so T R_j lies almost inside span X and what is left after the
+// projection is small and noisy: W and P run close to X and to each other long before convergence.  Dropping all of P at a
+// pivot of 1e-8 then happens in most iterations and leaves block steepest descent at a rate of 1 - gap / sigma (2400 iterations
+// on the 3 x 1 x 1 Q2 beam at u = 0 with the V-cycle, or none at all), and a one-pass solve at smaller pivots returns spurious
+// Ritz values.  With the second pass that case takes 45 iterations, as its neighbours do.
 #include <algorithm>
 #include <cmath>
 
@@ -135,13 +152,45 @@ namespace
     return 0;
   }
 
-  // what a call of mi_linear_modes holds on the device
+  // The columns of the symmetric n x n matrix B that a Cholesky factorisation accepts, taken in order: a column whose pivot against
+  // the accepted ones before it is not above min_pivot is left out
+  std::vector<int> independent_columns(int n, const double *B, double min_pivot)
+  {
+    const size_t                     N = size_t(n);
+    std::vector<int>                 keep;
+    std::vector<std::vector<double>> L; // row k: the factor's row of keep[k]
+    for (int i = 0; i < n; ++i)
+      {
+        std::vector<double> row(keep.size() + 1);
+        double              s = B[i * N + i];
+        for (size_t k = 0; k < keep.size(); ++k)
+          {
+            double t = 0.5 * (B[i * N + size_t(keep[k])] + B[size_t(keep[k]) * N + i]);
+            for (size_t q = 0; q < k; ++q)
+              t -= row[q] * L[k][q];
+            row[k] = t / L[k][k];
+            s -= row[k] * row[k];
+          }
+        if (!(s > min_pivot))
+          continue;
+        row[keep.size()] = std::sqrt(s);
+        L.push_back(row);
+        keep.push_back(i);
+      }
+    return keep;
+  }
+
+  // what a call of mi_linear_modes / mi_tangent_modes holds on the device
   struct Blocks
   {
-    mi_ctx *c = nullptr;
-    int64_t n = 0;
-    int     m = 0;
+    mi_ctx     *c = nullptr;
+    int64_t     n = 0;
+    int         m = 0;
+    const char *name    = "mi_linear_modes";
+    bool        tangent = false; // the pair (K_T, rho M) of the nonlinear model, else (K, M) of the linear model
+    double      rho = 1.0, shift = 0.0; // tangent: density; alpha_1 rho, the mass term inside the context's tangent
     double *S = nullptr, *KS = nullptr, *MS = nullptr; // [X W P], each block m columns of n
+    double *MX = nullptr;                              // tangent: M x of the m columns of one products() call (unit density)
     double *part = nullptr, *gram = nullptr, *coef = nullptr, *sums = nullptr;
     ~Blocks()
     {
@@ -159,11 +208,28 @@ namespace
     enqueue_spmv(c, x, y, nullptr, nullptr, nullptr);
     mi::launch_zero_constrained(c->dim, y, c->d_cmask, c->n, c->stream);
   }
-  void products(const Blocks &b, size_t col0)
+  // the images of the m columns from col0 on.  Tangent: M x six columns at a time; A x_j through enqueue_spmm; K_T x_j = A x_j -
+  // alpha_1 rho M x_j, zeroed on the constrained dofs, and rho M x_j (tangent_images)
+  int products(const Blocks &b, size_t col0)
   {
-    for (int j = 0; j < b.m; ++j)
-      for (int w = 0; w < 2; ++w)
-        product(b.c, w, b.S + (col0 + size_t(j)) * size_t(b.n), (w ? b.MS : b.KS) + (col0 + size_t(j)) * size_t(b.n));
+    mi_ctx      *c = b.c;
+    const size_t n = size_t(b.n);
+    if (!b.tangent)
+      {
+        for (int j = 0; j < b.m; ++j)
+          for (int w = 0; w < 2; ++w)
+            product(c, w, b.S + (col0 + size_t(j)) * n, (w ? b.MS : b.KS) + (col0 + size_t(j)) * n);
+        return MI_OK;
+      }
+    for (int j0 = 0; j0 < b.m; j0 += mi::MASS_MAX_RHS)
+      if (int rc = enqueue_mass_apply(c, std::min(mi::MASS_MAX_RHS, b.m - j0), 1, false, b.S + (col0 + size_t(j0)) * n, b.MX + size_t(j0) * n))
+        return rc;
+    // A x of the block: sell_spmm where the context is eligible and "modes_block_product" allows it, else column by column (the
+    // same bits either way); then both images of all columns in one pass
+    enqueue_spmm(c, b.m, b.S + col0 * n, b.n, b.KS + col0 * n, b.n, c->modes_block_product != 0);
+    mi::launch_tangent_images(c->dim, b.KS + col0 * n, b.MX, b.MS + col0 * n, c->d_cmask, b.shift, b.rho, c->n, b.m, c->stream);
+    HIPCHK(c, hipGetLastError());
+    return MI_OK;
   }
 
   // host <- a^T b of the first ka / kb columns
@@ -191,8 +257,13 @@ namespace
   }
 
   // Rayleigh-Ritz on the leading ks columns: the m lowest pairs of (S^T K S, S^T M S) after scaling the columns to unit
-  // M-norm.  C [ks][m] row-major.  1: the scaled Gram matrix is numerically singular
-  int rayleigh_ritz(const Blocks &b, int ks, double min_pivot, std::vector<double> &lam, std::vector<double> &C, int *status)
+  // M-norm.  C [ks][m] row-major.  1: the scaled Gram matrix is numerically singular.
+  // drop: columns that depend on those before them (independent_columns) are left out of the problem, their rows of C zero (1
+  // where fewer than m remain), and the problem is solved in two passes: a Gram matrix formed once on an ill-conditioned basis
+  // carries an error of eps |K|_S / pivot into the Ritz values, so the kept columns are first M-orthonormalised on the device by
+  // the factor of their Gram matrix, and the Gram matrices formed again on that basis (the CholeskyQR2 idea)
+  int rayleigh_ritz(const Blocks &b, int ks, double min_pivot, std::vector<double> &lam, std::vector<double> &C, int *status,
+                    bool drop = false)
   {
     std::vector<double> gk, gm;
     if (int rc = gram(b, b.S, ks, b.KS, ks, gk))
@@ -214,27 +285,102 @@ namespace
           gk[i * K + j] *= d[i] * d[j];
           gm[i * K + j] *= d[i] * d[j];
         }
-    if (dense_sym_eig(ks, gk.data(), gm.data(), w.data(), V.data(), min_pivot))
+    std::vector<int> keep(K);
+    for (size_t i = 0; i < K; ++i)
+      keep[i] = int(i);
+    if (drop)
+      {
+        keep = independent_columns(ks, gm.data(), min_pivot);
+        if (int(keep.size()) < b.m)
+          return MI_OK;
+        const size_t        R = keep.size();
+        std::vector<double> rk(R * R), rm(R * R);
+        for (size_t i = 0; i < R; ++i)
+          for (size_t j = 0; j < R; ++j)
+            {
+              rk[i * R + j] = gk[size_t(keep[i]) * K + size_t(keep[j])];
+              rm[i * R + j] = gm[size_t(keep[i]) * K + size_t(keep[j])];
+            }
+        gk.swap(rk), gm.swap(rm);
+      }
+    const size_t R = keep.size();
+    if (drop)
+      {
+        // second pass: the kept columns M-orthonormalised on the device by the factor of their scaled Gram matrix (q_i = sum_{j <= i}
+        // s_j d_j (L^-T)_ji, all three images), the Gram matrices formed again on that basis
+        std::vector<double> L(R * R, 0.0), Li(R * R, 0.0);
+        for (size_t i = 0; i < R; ++i)
+          for (size_t j = 0; j <= i; ++j)
+            {
+              double t = gm[i * R + j];
+              for (size_t q = 0; q < j; ++q)
+                t -= L[i * R + q] * L[j * R + q];
+              L[i * R + j] = i == j ? std::sqrt(t) : t / L[j * R + j];
+            }
+        for (size_t c0 = 0; c0 < R; ++c0) // Li = L^-1, column by column
+          for (size_t i = c0; i < R; ++i)
+            {
+              double t = i == c0 ? 1.0 : 0.0;
+              for (size_t q = c0; q < i; ++q)
+                t -= L[i * R + q] * Li[q * R + c0];
+              Li[i * R + c0] = t / L[i * R + i];
+            }
+        std::vector<double> T(K * K, 0.0);
+        for (size_t i = 0; i < K; ++i)
+          T[i * K + i] = 1.0; // (a column that was left out stays what it is)
+        for (size_t i = 0; i < R; ++i)
+          {
+            T[size_t(keep[i]) * K + size_t(keep[i])] = 0.0;
+            for (size_t j = 0; j <= i; ++j)
+              T[size_t(keep[j]) * K + size_t(keep[i])] = d[size_t(keep[j])] * Li[i * R + j];
+          }
+        const size_t m = size_t(b.m);
+        for (int blk = ks / b.m - 1; blk >= 0; --blk) // last block first: column i reads the columns <= i
+          {
+            std::vector<double> coef(K * m);
+            for (size_t r = 0; r < K; ++r)
+              for (size_t cc = 0; cc < m; ++cc)
+                coef[r * m + cc] = T[r * K + size_t(blk) * m + cc];
+            if (int rc = combine3(b, 0, ks, coef, b.m, size_t(blk) * m))
+              return rc;
+          }
+        std::vector<double> fk, fm;
+        if (int rc = gram(b, b.S, ks, b.KS, ks, fk))
+          return rc;
+        if (int rc = gram(b, b.S, ks, b.MS, ks, fm))
+          return rc;
+        for (size_t i = 0; i < R; ++i)
+          for (size_t j = 0; j < R; ++j)
+            {
+              gk[i * R + j] = fk[size_t(keep[i]) * K + size_t(keep[j])];
+              gm[i * R + j] = fm[size_t(keep[i]) * K + size_t(keep[j])];
+            }
+        for (size_t i = 0; i < K; ++i)
+          d[i] = 1.0;
+        min_pivot = 0.25;
+      }
+    if (dense_sym_eig(int(R), gk.data(), gm.data(), w.data(), V.data(), min_pivot))
       return MI_OK;
     *status = 0;
     lam.assign(w.begin(), w.begin() + b.m);
     C.assign(K * size_t(b.m), 0.0);
-    for (size_t i = 0; i < K; ++i)
+    for (size_t i = 0; i < R; ++i)
       for (int j = 0; j < b.m; ++j)
-        C[i * size_t(b.m) + size_t(j)] = d[i] * V[size_t(j) * K + i];
+        C[size_t(keep[i]) * size_t(b.m) + size_t(j)] = d[size_t(keep[i])] * V[size_t(j) * R + i];
     return MI_OK;
   }
 
   // KX, MX afresh, X Rayleigh-Ritz'ed on its own (a well-conditioned m x m problem): M-orthonormal X, Ritz values
   int polish(const Blocks &b, std::vector<double> &lam)
   {
-    products(b, 0);
+    if (int rc = products(b, 0))
+      return rc;
     std::vector<double> C;
     int                 st = 0;
     if (int rc = rayleigh_ritz(b, b.m, 0.0, lam, C, &st))
       return rc;
     if (st)
-      return fail(b.c, MI_ENOCONV_LIN, "mi_linear_modes: the iterates have become linearly dependent");
+      return fail(b.c, MI_ENOCONV_LIN, "%s: the iterates have become linearly dependent", b.name);
     return combine3(b, 0, b.m, C, b.m, 0);
   }
 
@@ -267,14 +413,18 @@ namespace
     return true;
   }
 
-  int modes_run(mi_ctx *c, int n_modes, int m, double tol, int max_it, double *lambda, double *modes, double *residual_out, int *its)
+  int modes_run(mi_ctx *c, bool tangent, int n_modes, int m, double tol, int max_it, double *lambda, double *modes, double *residual_out,
+                int *its)
   {
     Blocks b;
     b.c = c, b.n = c->n, b.m = m;
+    b.tangent = tangent;
+    if (tangent)
+      b.name = "mi_tangent_modes", b.rho = c->mat.rho, b.shift = c->alpha[1] * c->mat.rho;
     const size_t n = size_t(c->n), blk = size_t(m) * n;
     const size_t npart = size_t(mi::block_chunks(c->n)) * size_t(9 * m * m);
-    HIPCHK(c, hipMalloc((void **)&b.S, 9 * blk * sizeof(double)));
-    b.KS = b.S + 3 * blk, b.MS = b.S + 6 * blk;
+    HIPCHK(c, hipMalloc((void **)&b.S, (tangent ? 10 : 9) * blk * sizeof(double)));
+    b.KS = b.S + 3 * blk, b.MS = b.S + 6 * blk, b.MX = tangent ? b.S + 9 * blk : nullptr;
     HIPCHK(c, hipMalloc((void **)&b.part, npart * sizeof(double)));
     HIPCHK(c, hipMalloc((void **)&b.gram, size_t(9 * m * m) * sizeof(double)));
     HIPCHK(c, hipMalloc((void **)&b.coef, size_t(3 * m * m) * sizeof(double)));
@@ -306,8 +456,10 @@ namespace
           }
         ++it;
         // W = T R (R lies in the W block), one vector at a time through the solver's residual vector
-        linear_select(c, 2);
-        const bool cycle = mg_active(c);
+        if (!tangent)
+          linear_select(c, 2);
+        const bool    cycle = mg_active(c);
+        const double *dinv  = tangent ? c->work(W_DINV) : c->active_dinv;
         for (int j = 0; j < m && !rc; ++j)
           {
             double *wj = b.W(b.S) + size_t(j) * n;
@@ -319,7 +471,7 @@ namespace
                 HIPCHK(c, hipMemcpyAsync(wj, c->work(W_Z), n * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
               }
             else
-              mi::launch_vec_scale_mul(wj, c->active_dinv, c->work(W_R), 1.0, c->n, c->stream);
+              mi::launch_vec_scale_mul(wj, dinv, c->work(W_R), 1.0, c->n, c->stream);
             mi::launch_zero_constrained(c->dim, wj, c->d_cmask, c->n, c->stream);
           }
         if (rc)
@@ -337,19 +489,24 @@ namespace
         mi::launch_block_combine(b.S, 2 * m, b.n, b.coef, m, b.W(b.S), b.n, b.n, c->stream);
         HIPCHK(c, hipGetLastError());
         HIPCHK(c, hipStreamSynchronize(c->stream));
-        products(b, size_t(m));
+        if ((rc = products(b, size_t(m))))
+          break;
         // Rayleigh-Ritz on [X W P]; without P, then with X re-orthonormalised, where the Gram matrix is singular
         int st = 1, ks = 0;
         for (int attempt = 0; attempt < 3 && st && !rc; ++attempt)
           {
             ks = (have_p ? 3 : 2) * m;
-            if ((rc = rayleigh_ritz(b, ks, CHOL_MIN, lam, C, &st)) || !st)
+            if ((rc = rayleigh_ritz(b, ks, CHOL_MIN, lam, C, &st, tangent)) || !st)
               break;
             if (have_p)
               have_p = false;
             else
               rc = polish(b, lam);
           }
+        // still singular with X orthonormal and no P: columns of W depend on X and on each other (with a preconditioner as good
+        // as a V-cycle the residuals of a late iteration can all point at the same slow mode).  Those columns are left out
+        if (st && !rc && tangent)
+          rc = rayleigh_ritz(b, ks, CHOL_MIN, lam, C, &st, true);
         if (rc)
           break;
         if (st) // (not seen: the pairs of the last residual evaluation are returned as not converged)
@@ -363,7 +520,8 @@ namespace
           break;
         have_p = true;
       }
-    linear_select(c, -1);
+    if (!tangent)
+      linear_select(c, -1);
     if (rc)
       return rc;
     for (int j = 0; j < n_modes; ++j)
@@ -377,7 +535,22 @@ namespace
     if (modes)
       HIPCHK(c, hipMemcpy(modes, b.S, size_t(n_modes) * n * sizeof(double), hipMemcpyDeviceToHost));
     if (status)
-      return fail(c, status, "mi_linear_modes: not converged within %d iterations", max_it);
+      return fail(c, status, "%s: not converged within %d iterations", b.name, max_it);
+    return MI_OK;
+  }
+
+  // the arguments the two entry points share; *m = block size, the wanted modes and their guard vectors
+  int modes_arguments(mi_ctx *c, const char *name, int n_modes, double tol, int max_it, int *m)
+  {
+    if (n_modes < 1 || n_modes > 16 || !(tol > 0) || max_it < 1)
+      return fail(c, MI_EINVAL, "%s: 1 <= n_modes <= 16, tol > 0 and max_it >= 1 are required", name);
+    *m             = n_modes + std::max(2, n_modes / 4);
+    int64_t n_free = 0;
+    for (int64_t nd = 0; nd < c->mesh.nnodes; ++nd)
+      for (int k = 0; k < c->dim; ++k)
+        n_free += !((c->mesh.cmask[size_t(nd)] >> k) & 1);
+    if (*m > n_free)
+      return fail(c, MI_EINVAL, "%s: %d modes and %d guard vectors on %lld free dofs", name, n_modes, *m - n_modes, (long long)n_free);
     return MI_OK;
   }
 } // namespace
@@ -392,19 +565,33 @@ int mi_linear_modes(mi_ctx *c, int n_modes, double tol, int max_it, double *lamb
     return fail(c, MI_EINVAL, "mi_linear_setup has not been called");
   if (team_size(c) != 1)
     return fail(c, MI_EINVAL, "mi_linear_modes: one slab only (an undecomposed mesh)");
-  if (n_modes < 1 || n_modes > 16 || !(tol > 0) || max_it < 1)
-    return fail(c, MI_EINVAL, "mi_linear_modes: 1 <= n_modes <= 16, tol > 0 and max_it >= 1 are required");
-  const int m = n_modes + std::max(2, n_modes / 4);
-  int64_t   n_free = 0;
-  for (int64_t nd = 0; nd < c->mesh.nnodes; ++nd)
-    for (int k = 0; k < c->dim; ++k)
-      n_free += !((c->mesh.cmask[size_t(nd)] >> k) & 1);
-  if (m > n_free)
-    return fail(c, MI_EINVAL, "mi_linear_modes: %d modes and %d guard vectors on %lld free dofs", n_modes, m - n_modes, (long long)n_free);
+  int m = 0;
+  if (int rc = modes_arguments(c, "mi_linear_modes", n_modes, tol, max_it, &m))
+    return rc;
   HIPCHK(c, hipSetDevice(c->device));
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  const int rc = modes_run(c, n_modes, m, tol, max_it, lambda, modes, residual, its);
+  const int rc = modes_run(c, false, n_modes, m, tol, max_it, lambda, modes, residual, its);
   linear_select(c, -1);
+  hipStreamSynchronize(c->stream);
+  return rc;
+}
+
+int mi_tangent_modes(mi_ctx *c, int n_modes, double tol, int max_it, double *lambda, double *modes, double *residual, int *its)
+{
+  if (!c || !lambda)
+    return c ? fail(c, MI_EINVAL, "mi_tangent_modes: null argument") : MI_EINVAL;
+  if (team_size(c) != 1 || !c->team || c->team->members[0] != c)
+    return fail(c, MI_EINVAL, "mi_tangent_modes: one slab only (an undecomposed mesh)");
+  if (c->linear_mf)
+    return fail(c, MI_EINVAL, "mi_tangent_modes: the matrix-free linear model keeps no assembled tangent (\"linear_operator\" 0 and mi_linear_setup)");
+  int m = 0;
+  if (int rc = modes_arguments(c, "mi_tangent_modes", n_modes, tol, max_it, &m))
+    return rc;
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  int rc = tangent_prepare(c);
+  if (!rc)
+    rc = modes_run(c, true, n_modes, m, tol, max_it, lambda, modes, residual, its);
   hipStreamSynchronize(c->stream);
   return rc;
 }

@@ -23,7 +23,7 @@ namespace mi_detail
                                      MI_V_VELOCITY_OLD,       MI_V_ACCELERATION,           MI_V_ACCELERATION_OLD};
 
   // y = M x for the device blocks x, y [nrhs][n] (diag: y [n] = the diagonal of M), enqueued on c's stream
-  static int enqueue_mass_apply(mi_ctx *c, int nrhs, int masked, bool diag, const double *x, double *y)
+  int enqueue_mass_apply(mi_ctx *c, int nrhs, int masked, bool diag, const double *x, double *y)
   {
     if (int rc = energy_box_prepare(c)) // (the cells' boxes for the sum-factorised forms, where the context keeps none)
       return rc;

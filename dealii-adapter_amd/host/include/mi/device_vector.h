@@ -164,6 +164,23 @@ namespace mi
       check(mi_state_project(ctx_, src.ctx_, sub, tol, max_it, info), "mi_state_project");
       return true;
     }
+    // the n_modes algebraically smallest eigenvalues of K_T(u) phi = lambda rho M phi at the committed state (mi_tangent_modes, no
+    // mode shapes): lambda and residual [n_modes], the iteration count.  Returns MI_OK or MI_ENOCONV_LIN (the best pairs are
+    // written); -1 on a team (emulated slabs or RCCL), where the library provides none (one slab only); any other failure throws
+    int tangent_modes(int n_modes, std::vector<double> &lambda, std::vector<double> &residual, int &its, double tol = 1e-8,
+                      int max_it = 1000)
+    {
+      int team = 1, rccl = 0;
+      check(mi_comm_info(ctx_, &team, &rccl), "mi_comm_info");
+      if (team > 1 || rccl > 0)
+        return -1;
+      lambda.assign(size_t(n_modes > 0 ? n_modes : 0), 0.0);
+      residual.assign(lambda.size(), 0.0);
+      const int rc = mi_tangent_modes(ctx_, n_modes, tol, max_it, lambda.data(), nullptr, residual.data(), &its);
+      if (rc != MI_ENOCONV_LIN)
+        check(rc, "mi_tangent_modes");
+      return rc;
+    }
     void    check(int rc, const char *what) const
     {
       if (rc != MI_OK)

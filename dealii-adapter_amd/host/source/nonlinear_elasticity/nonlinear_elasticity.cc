@@ -93,7 +93,74 @@ namespace Nonlinear_Elasticity
             time.get_timestep() % parameters.output_interval == 0)
           output_results();
       }
+    // MI_TANGENT_MODES=k: the k lowest vibration modes of the structure as it stands after the last time step (a switch of this
+    // PROGRAM): printed, and written to tangent_modes.json beside the displacement log.  Nothing of it exists without the variable
+    if (const char *f = std::getenv("MI_TANGENT_MODES"))
+      report_tangent_modes(std::atoi(f));
     adapter.precice.finalize();
+  }
+
+  // lambda, omega = sqrt(lambda) and f = omega / 2 pi of the k lowest modes of K_T(u) phi = lambda rho M phi at the committed state
+  // (mi_tangent_modes, tol 1e-8, at most 1000 iterations); a negative lambda is a buckled state and prints as "unstable"
+  template <int dim>
+  void Solid<dim>::report_tangent_modes(const int k)
+  {
+    std::vector<double> lambda, residual;
+    int                 its = 0, rc = 0, precond = 0;
+    // the analysis runs with the V-cycle whatever the time steps ran with (alpha_1 lies far above lambda: with the diagonal the
+    // shipped 2D flap needs 2670 iterations, with the V-cycle 70); the key is put back afterwards
+    mi_get_tuning(device->ctx(), "precond", &precond);
+    try
+      {
+        if (precond != 1)
+          device->check(mi_set_tuning(device->ctx(), "precond", 1), "mi_set_tuning");
+        rc = device->tangent_modes(k, lambda, residual, its);
+        if (precond != 1)
+          device->check(mi_set_tuning(device->ctx(), "precond", precond), "mi_set_tuning");
+      }
+    catch (const std::exception &e)
+      {
+        if (mi_set_tuning(device->ctx(), "precond", precond) != MI_OK)
+          std::cout << "MI_TANGENT_MODES: \"precond\" could not be put back: " << mi_last_error(device->ctx()) << std::endl;
+        std::cout << "MI_TANGENT_MODES ignored: " << e.what() << std::endl;
+        return;
+      }
+    if (rc == -1)
+      {
+        std::cout << "MI_TANGENT_MODES ignored: one slab only (an undecomposed mesh)" << std::endl;
+        return;
+      }
+    if (rc == MI_ENOCONV_LIN)
+      std::cout << "Tangent modes: " << mi_last_error(device->ctx()) << "; the best pairs follow" << std::endl;
+    const double two_pi = 2.0 * std::acos(-1.0);
+    std::cout << "Tangent modes at t = " << time.current() << " (" << its << " LOBPCG iterations):" << std::endl;
+    for (int j = 0; j < k; ++j)
+      {
+        const double l = lambda[size_t(j)];
+        std::cout << "\t mode " << j + 1 << ": lambda = " << l;
+        if (l >= 0.0)
+          std::cout << ", omega = " << std::sqrt(l) << " rad/s, frequency = " << std::sqrt(l) / two_pi << " Hz" << std::endl;
+        else
+          std::cout << ", unstable" << std::endl;
+      }
+    std::ofstream out("tangent_modes.json");
+    if (!out)
+      return;
+    auto list = [&](const char *key, auto value) {
+      out << "\"" << key << "\": [";
+      for (int j = 0; j < k; ++j)
+        out << (j ? ", " : "") << value(j);
+      out << "]";
+    };
+    out << std::setprecision(17) << "{\"time\": " << time.current() << ", ";
+    list("lambda", [&](int j) { return lambda[size_t(j)]; });
+    out << ", ";
+    list("frequency_hz", [&](int j) { return lambda[size_t(j)] >= 0.0 ? std::sqrt(lambda[size_t(j)]) / two_pi : 0.0; });
+    out << ", ";
+    list("stable", [&](int j) { return lambda[size_t(j)] >= 0.0 ? "true" : "false"; });
+    out << ", ";
+    list("residual", [&](int j) { return residual[size_t(j)]; });
+    out << ", \"iterations\": " << its << ", \"converged\": " << (rc == MI_OK ? "true" : "false") << "}\n";
   }
 
   // geometry and boundary roles of nonlinear_elasticity.cc:171-301 (+ the additive "Block" scenario)

@@ -49,6 +49,7 @@ namespace Nonlinear_Elasticity
     void system_setup();
     void solve_nonlinear_timestep();
     void output_results() const;
+    void report_tangent_modes(int k); // MI_TANGENT_MODES=k
     static void print_conv_header();
     void        print_conv_footer();
 

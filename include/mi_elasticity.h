@@ -473,6 +473,48 @@ int mi_linear_get_diagonal_blocks(mi_ctx *ctx, double *blocks);
  *   "count_cg_*" counter, and a following mi_linear_step returns the bits it would have returned without the call. */
 int mi_linear_modes(mi_ctx *ctx, int n_modes, double tol, int max_it, double *lambda /* n_modes */,
                     double *modes /* [n_modes][n_dofs] or NULL */, double *residual /* n_modes or NULL */, int *its /* or NULL */);
+/* Vibration modes of the loaded structure: the n_modes algebraically smallest eigenpairs of  K_T(u) phi = lambda rho M phi  on the
+ * free dofs of the NONLINEAR model (phi = 0 on the dofs mi_get_constrained flags), lambda ascending.  K_T is the tangent
+ * stiffness of the committed state u = MI_V_TOTAL_DISPLACEMENT -- the tangent as mi_assemble forms it, without its mass term
+ * alpha_1 rho M, alpha_1 = 1 / (beta dt^2) -- and rho M the mass of mi_mass_apply times the density.  lambda = omega^2 while the
+ * state is stable; lambda_min -> 0 announces buckling, and a negative lambda is returned as such (a buckled state).
+ *   The call (1) zeroes MI_V_SOLUTION_DELTA and MI_V_NEWTON_UPDATE as mi_newton_begin_step does (after a finished step the delta is
+ *   folded into u already), (2) runs the assembly of mi_assemble -- with "fine_level" 1 the point pass and the diagonal blocks,
+ *   formed afresh under "mf_diag_lag" too --, (3) with "precond" 1 refreshes the multigrid hierarchy for this tangent by the route
+ *   a linear solve takes, whatever "mg_refresh_every" says, and (4) iterates: the LOBPCG of mi_linear_modes with the same block
+ *   size, guard vectors, hashed start block, Rayleigh-Ritz with its fall-backs, final polish and residual ratios on fresh
+ *   products.  One difference: every Rayleigh-Ritz step leaves out the columns of [X W P] that depend on those before them and
+ *   is solved in two passes (basis M-orthonormalised on the device by the factor of its Gram matrix, Gram matrices formed again),
+ *   because with sigma = alpha_1 far above lambda the search directions run close to X; three more block_combine triples and
+ *   two more block_gram launches per iteration.  The eigenvalue estimates of the hierarchy are taken from scratch in (3), so two
+ *   calls return the same bits.
+ *   Products: the context holds A = K_T + alpha_1 rho M in whichever form it runs (the sliced-ELL product, or mf_spmv /
+ *   mf_spmv_q3 and their gathers with "fine_level" 1), output zeroed on constrained dofs -- three columns per launch through the
+ *   block kernel sell_spmm where the context is eligible (see mi_spmm; "modes_block_product" 0: one column at a time, same bits); K_T x = A x -
+ *   alpha_1 rho (M x) with M x from the matrix-free mass, six columns per launch group.  The preconditioner is the context's own
+ *   for A: the tangent's V-cycle with "precond" 1, else the Jacobi diagonal of the assembly.
+ *   Stopping: converged when every wanted j has |K_T x_j - lambda_j rho M x_j|_2 <= tol max_{k < n_modes} |lambda_k| |rho M x_j|_2;
+ *   residual[j] is that ratio on freshly formed products.  FLOOR: forming K_T x as a difference leaves a rounding error of order
+ *   eps alpha_1 / max_k |lambda_k| in that ratio (about 1e-11 where dt = 0.005 meets lambda of order 1..10); tol must stay above
+ *   it, and a context made for this analysis takes a large time step, which also helps the preconditioner (mi_linear_modes).
+ *   The method needs A positive definite, lambda_min > -alpha_1: the condition under which a Newmark step's CG works at all.
+ *   Not converged within max_it iterations: MI_ENOCONV_LIN, with the best pairs, residual and its still written.
+ *   modes ([n_modes][n_dofs], or NULL): rho M-orthonormal, exactly zero on constrained dofs, global dof order.
+ *   Undecomposed contexts only (a team: MI_EINVAL "one slab only"); 2D and 3D, degrees 1-4, "fine_level" 0 and 1.  MI_EINVAL with
+ *   nothing changed: a context whose tangent array a "linear_operator" 1 set-up has released, and the argument errors of
+ *   mi_linear_modes.  A folded cell is NOT among them: it is found by the assembly itself, which reports MI_EINVAL "inverted
+ *   element" as mi_assemble does.  By then MI_V_SOLUTION_DELTA and MI_V_NEWTON_UPDATE are zero and tangent, diagonal, records and
+ *   MI_V_SYSTEM_RHS are what that assembly wrote (the hierarchy is untouched and marked stale); the six state vectors and
+ *   MI_V_EXTERNAL_STRESS are unchanged, and the context is usable once the state is.
+ *   Effects: none on the six state vectors or MI_V_EXTERNAL_STRESS, on the stored start vectors of "cg_warm_start" or on the
+ *   "count_cg_*" counters.  Tangent, diagonal, point records and hierarchy are left as an assembly plus a preconditioner refresh
+ *   at the committed state leave them; the solver's work vectors and MI_V_SYSTEM_RHS are overwritten.  With "precond" 0 a
+ *   following mi_newmark_step returns the bits of an undisturbed run; with the V-cycle it is a run whose hierarchy was refreshed
+ *   one step early (same answers to the solver's tolerance, iteration counts may differ; "count_mg_refresh" grows by one).
+ *   Block storage of 10 m n_dofs doubles (+ the Gram partials), m = n_modes + max(2, n_modes / 4), is allocated per call and
+ *   freed before return. */
+int mi_tangent_modes(mi_ctx *ctx, int n_modes, double tol, int max_it, double *lambda /* n_modes */,
+                     double *modes /* [n_modes][n_dofs] or NULL */, double *residual /* n_modes or NULL */, int *its /* or NULL */);
 
 /* per-vector device snapshots: what `old_state_data[i] = *state_variables[i]` (adapter.h:457-460) and its
  * inverse (:481-482) become when VectorType is a handle to a device-resident vector */
@@ -502,6 +544,16 @@ int mi_vec_set(mi_ctx *ctx, int which, const double *host, int64_t n);
 /* tangent as scalar CSR (host arrays: rowptr n_dofs+1 (int64), col nnz (int32), val nnz) */
 int mi_matrix_get_csr(mi_ctx *ctx, int64_t *rowptr, int32_t *col, double *val);
 int mi_spmv(mi_ctx *ctx, const double *x_host, double *y_host); /* y = K x through the device kernel */
+/* y_j = K x_j for nv columns (host arrays [nv][n_dofs], 1 <= nv <= 64) on the current tangent, undecomposed contexts.  Where every
+ * sliced-ELL launch of the context is an LDS-staged one (3D, assembled fp64 tangent, more than 160 slices) the columns go three at
+ * a time through the block kernel sell_spmm -- the matrix read once per group; column j bit for bit what mi_spmv returns for it --,
+ * else one by one through the product mi_spmv runs.  y_host is copied in first: a row nobody computes keeps the caller's value.
+ * Tuning read-back "spmm_launches": launches of sell_spmm so far.  "modes_block_product" 0 makes mi_tangent_modes go column by
+ * column (same bits); the key has no effect here. */
+int mi_spmm(mi_ctx *ctx, int nv, const double *x_host, double *y_host);
+/* the block product against nv single products on the same matrix (1 <= nv <= 20): `rounds` alternated measurements of each, device
+ * events around `reps` products of the block; ms per block into ms_block / ms_single [rounds].  Undecomposed contexts */
+int mi_bench_spmm(mi_ctx *ctx, int nv, int reps, int rounds, double *ms_block, double *ms_single);
 /* the dim x dim diagonal block of every node of the current tangent (host array [n_nodes][dim * dim], row-major, node order of
  * the reference) under the constraint rule of the assembly (nonlinear_elasticity.cc:760-774): out of the assembled tangent or,
  * with "fine_level" 1, as formed from the point records.  One process only (single or emulated slabs). */
