@@ -533,10 +533,19 @@ namespace mi_detail
           return;
         const LinearMf &lm = *c->active_linear_mf;
         mi::MfParams    f  = mf_params(c);
-        f.tab_q3s = lm.tab, f.vals = lm.diag, f.diagpos = lm.diagpos, f.cmask = lm.cmask, f.x = x, f.y = y;
+        f.vals = lm.diag, f.diagpos = lm.diagpos, f.cmask = lm.cmask, f.x = x, f.y = y;
         f.yc = c->d_mf_yc, f.dst = c->d_mf_dst, f.slot_base = c->d_mf_slot_base, f.slot_src = c->d_mf_src;
         f.slot_inline = c->slots_layout == 1;
-        mi::launch_mf_linear_q3(f, lm.op, int32_t(c->mesh.ncells), c->stream);
+        if (lm.degree == 2) // the kernel of the element family, each with the tables of its own rule
+          {
+            f.tab27 = lm.tab;
+            mi::launch_mf_linear_q2(f, lm.op, int32_t(c->mesh.ncells), c->stream);
+          }
+        else
+          {
+            f.tab_q3s = lm.tab;
+            mi::launch_mf_linear_q3(f, lm.op, int32_t(c->mesh.ncells), c->stream);
+          }
         enqueue_slot_gather(c, f, cheb, dotv, partials, false);
         return;
       }
@@ -1733,8 +1742,10 @@ namespace mi_detail
     return MI_OK;
   }
 
-  // matrix-free linear model ("linear_operator" 1): what its products need beside the operators' own data -- the Q3 slot
-  // tables, the slots and the cell boxes, built where absent -- and the nonlinear tangent array released, as set_fine_level does
+  // matrix-free linear model ("linear_operator" 1 / 2): what its products need beside the operators' own data -- the slot
+  // tables of the element (Q3: cell-major; Q2: in the layout the context has or, where it has none yet, the one its keys ask for
+  // -- mf_linear_q2 stores through MfParams::dst / slot_inline and the gathers read through slot_src, so any of them serves),
+  // the slots and the cell boxes, built where absent -- and the nonlinear tangent array released, as set_fine_level does
   int linear_mf_prepare(mi_ctx *c)
   {
     if (!c->d_mf_dst || !c->d_mf_yc)
@@ -3983,13 +3994,18 @@ int mi_set_tuning(mi_ctx *c, const char *key, int value)
           m->mf_diag_fresh = false;
           continue;
         }
-      if (k == "linear_operator" && (value == 0 || value == 1))
+      if (k == "linear_operator" && value >= 0 && value <= 2)
         {
           // (checked on every member before any changes: a refused team keeps its assembled operators)
+          // 1: mf_linear_q3 and nothing else; 2: the kernel of the mesh's element family (mf_linear_q2 | mf_linear_q3)
           if (value == 1)
             for (const mi_ctx *q : c->team->members)
               if (c->team->size != 1 || q->dim != 3 || q->degree != 3)
                 return fail(c, MI_EINVAL, "the matrix-free linear model exists for 3D Q3 meshes on an undecomposed mesh only");
+          if (value == 2)
+            for (const mi_ctx *q : c->team->members)
+              if (c->team->size != 1 || q->dim != 3 || (q->degree != 2 && q->degree != 3))
+                return fail(c, MI_EINVAL, "\"linear_operator\" 2: the matrix-free linear model exists for 3D Q2 and Q3 meshes on an undecomposed mesh only");
           m->linear_operator = value;
           continue;
         }
@@ -4183,8 +4199,8 @@ int mi_get_tuning(mi_ctx *c, const char *key, int *value)
     *value = m->mf_fine;
   else if (k == "linear_operator")
     *value = m->linear_operator;
-  else if (k == "linear_operator_active") // what the current linear set-up runs (0 without one)
-    *value = (m->linear && m->linear_mf) ? 1 : 0;
+  else if (k == "linear_operator_active") // what the current linear set-up runs (0 without one): 1 mf_linear_q3 | 2 mf_linear_q2
+    *value = (m->linear && m->linear_mf) ? (m->degree == 2 ? 2 : 1) : 0;
   else if (k == "linear_precond")
     *value = m->linear_precond;
   else if (k == "linear_precond_active") // 1: the solve of the current linear set-up is multigrid-preconditioned (0 without one)

@@ -51,12 +51,13 @@ namespace mi_detail
     double       *xnext = nullptr;
   };
   struct LinearModel; // mi_linear.cpp
-  // one operator of the matrix-free linear model ("linear_operator" 1, 3D Q3): what enqueue_spmv hands to mf_linear_q3 and the
-  // slot gathers.  K, M and the stepping matrix differ in `op` alone
+  // one operator of the matrix-free linear model ("linear_operator" 1 / 2, 3D Q3 or Q2): what enqueue_spmv hands to mf_linear_q3
+  // or mf_linear_q2 and the slot gathers.  K, M and the stepping matrix differ in `op` alone
   struct LinearMf
   {
     mi::MfLinearOp op;
-    const double  *tab;     // 1D tables of the model's 4-point rule (MfParams::tab_q3s)
+    int            degree;  // the element family: 3 mf_linear_q3 | 2 mf_linear_q2
+    const double  *tab;     // 1D tables of the model's rule: 4 points (MfParams::tab_q3s) | 3 points (MfParams::tab27)
     const double  *diag;    // [nnodes][9] diagonal of the stepping matrix, read as MfParams::vals ...
     const int32_t *diagpos; // ... at [nnodes] the node's own id
     const uint8_t *cmask;   // [nnodes] dofs whose row is diag x: the context's mask (stepping matrix) | none (K, M)
@@ -304,7 +305,8 @@ struct mi_ctx
   const double *active_sell_vals = nullptr;
   const double *active_dinv      = nullptr;
   // tuning "linear_operator": 0 the linear model's K, M and stepping matrix assembled (sliced-ELL, active_sell_vals) | 1 matrix-free
-  // (3D Q3 on one slab: mf_linear_q3, active_linear_mf names the operator of the next product).  Read by the next mi_linear_setup;
+  // (3D Q3 on one slab: mf_linear_q3, active_linear_mf names the operator of the next product) | 2 matrix-free on the kernel of the
+  // mesh's element family (3D Q2: mf_linear_q2, 3D Q3: as 1).  Read by the next mi_linear_setup;
   // linear_mf: what the current set-up runs.  While it holds the context keeps NO assembled array: d_vals is released too
   int           linear_operator = 0;
   bool          linear_mf       = false;

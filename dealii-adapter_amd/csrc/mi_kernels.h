@@ -365,7 +365,7 @@ namespace mi
     int32_t        cell_count;
   };
 
-  // matrix-free operator of the linear model on 3D Q3 cells (see mf_linear_q3): y = (c_K K + c_M M) x
+  // matrix-free operator of the linear model on 3D Q3 and Q2 cells (see mf_linear_q3, mf_linear_q2): y = (c_K K + c_M M) x
   struct MfLinearOp
   {
     double  lambda, mu, rho; // Lame parameters, density
@@ -605,6 +605,14 @@ namespace mi
   // "linear_precond" 1: the nodes' whole 3 x 3 blocks of that operator, every cell's symmetric halves into slots6 [ncells * 64][6]
   // (slot = the product's); launch_mf_diag_gather sums them, applies the constraint rule and inverts
   void launch_mf_linear_diag_blk_q3(const MfParams &p, const MfLinearOp &op, int32_t cell_count, double *slots6, hipStream_t s);
+  // linear model, "linear_operator" 2 on 3D Q2 (see mf_linear_q2): the same three on the 3 x 3 x 3 rule, two cells per wave as
+  // mf_spmv27 (the rule's 1D tables MfParams::tab27; x masked by MfParams::cmask whatever op.masked says; any slot layout;
+  // slots6 [ncells * 27][6])
+  void launch_mf_linear_q2(const MfParams &p, const MfLinearOp &op, int32_t cell_count, hipStream_t s, hipEvent_t ev_start = nullptr,
+                           hipEvent_t ev_stop = nullptr);
+  void launch_mf_linear_diag_q2(const MfParams &p, const MfLinearOp &op, int32_t cell_count, double *blk, double *dinv, int64_t ndofs,
+                                hipStream_t s);
+  void launch_mf_linear_diag_blk_q2(const MfParams &p, const MfLinearOp &op, int32_t cell_count, double *slots6, hipStream_t s);
   // the matrix-free fine level's point pass over ALL cells in one launch (assemble_q2sf<true> with the residual into slots:
   // AsmParams::res_slots / slot_dst; cell_begin = 0, cell_count = all) and the sum of the slots into system_rhs
   void launch_point_pass_slots(const AsmParams &p, hipStream_t s);

@@ -7354,6 +7354,251 @@ namespace mi
     dinv[g] = 1.0 / s;
   }
 
+  // ------------------------------------------------------------------ linear model, 3D Q2: K, M and the stepping matrix without matrices
+  // "linear_operator" 2 on a Q2 mesh.  QGauss(p + 1) is the 3 x 3 x 3 rule of mf_spmv27, so its shape is taken whole: one wave
+  // carries two cells (lanes 0-26 and 32-58; idle lanes mirror item 26, the second half of an odd last pair mirrors the last
+  // cell), one batch of loads at the head of the wave, E12 + E3 by mf27_gradients, the stages I3 / I2 / I1 and the slot stores
+  // of mf_spmv27 word for word, the launch in XCD chunks of pairs.  What differs from mf_spmv27:
+  //   - no point record: the batch is x, the constraint bits, the table rows, BOX: the cell's box (and the slots where they are
+  //     not arithmetic) -- 11 values per lane fewer, in registers as in traffic;
+  //   - the point stage is mf_linear_q3's (G = H Jinv, sigma = lambda tr G I + mu (G + G^T), Q = JxW c_K sigma Jinv^T, value
+  //     row JxW c_M rho V), and on this rule it is the model's own: the product is the assembled operator up to rounding;
+  //   - no launch over layers of a slab (MfParams::sel_*): the form runs on one slab.
+  // From mf_linear_q3 it differs in the masking: x is masked by a select on the mask the launch hands in (MfParams::cmask: the
+  // constraint mask for A, the model's all-zero mask for K and M, which stay unconstrained), so the mask's load is part of the
+  // batch whatever the operator; MfLinearOp::masked is not read.  1D tables: MfParams::tab27.
+#ifndef MFL2_OCC
+#define MFL2_OCC 8 // waves per SIMD on box meshes, from the compiled register count (profiles/linear_matrix_free_q2/resources.tsv)
+#endif
+#ifndef MFL2_OCC_GEN
+#define MFL2_OCC_GEN 4 // ... general geometry (24 vertex coordinates per lane in the point stage; 5 spills two registers)
+#endif
+  template <bool BOX, bool LAT>
+  __global__ __launch_bounds__(64, BOX ? MFL2_OCC : MFL2_OCC_GEN) void mf_linear_q2(MfParams prm, MfLinearOp op)
+  {
+    __shared__ double s_lds[2 * H27];
+    const int     lane = threadIdx.x, cw = lane >> 5, il = lane & 31, it = il < Q27 ? il : Q27 - 1;
+    const int64_t pair = int64_t(blockIdx.x & 7) * prm.xcd_chunk + (blockIdx.x >> 3);
+    if (pair * 2 >= prm.count)
+      return;
+    const int64_t cell0 = pair * 2, cell1 = pair * 2 + 1 < prm.count ? pair * 2 + 1 : int64_t(prm.count) - 1; // uniform
+    const int64_t cell = cw ? cell1 : cell0;
+    constexpr bool act = true;
+    double *const R = s_lds + cw * H27, *const X = R + 243;
+    MF27_TABLES(prm.tab27)
+    // the batch of loads: x and the mask of this lane's node, BOX: the cell's box, the table rows, the slots of its results
+    // where they are not arithmetic
+    const int32_t node = mf27_node<LAT>(prm, cell0, cell1, cw, it);
+    double        xv[3], sx[3], dx[3], sz[3], dz[3], bx = 0.0;
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+      xv[c] = prm.x[int64_t(node) * 3 + c];
+    const int cm = prm.cmask[node];
+    if constexpr (BOX)
+      bx = mf27_load_box(prm, cell, il);
+    mf27_table_rows(prm.tab27, it, sx, dx, sz, dz);
+    const int qz = it / 9, qy = (it - 9 * qz) / 3, qx = it - 9 * qz - 3 * qy; // this lane's point
+    // I1's item of this lane: line (c,k,j) = it, its three nodes i (cell-major slots: no table to read)
+    int32_t   ydst[3];
+    const int lkj = it - 9 * (it / 9);
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+      ydst[i] = prm.slot_inline ? int32_t(cell) * Q27 + lkj * 3 + i : prm.dst[cell * Q27 + lkj * 3 + i];
+    // the gather: masked entries by a select (never a product: they may hold anything)
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+      X[c * Q27 + it] = ((cm >> c) & 1) ? 0.0 : xv[c];
+    if constexpr (BOX)
+      mf27_stage_box(R, il, bx);
+    __syncthreads();
+    double H[3][3], V[3];
+    mf27_gradients(S27, D27, sx, dx, sz, dz, R, X, it, act, H, V);
+    // ---- point stage: Q = JxW c_K sigma Jinv^T, JxW c_M rho V -- 12 numbers per point on top of B
+    {
+      // (the point's weight and, general geometry, its coordinates by selection among the uniform values: see mf_spmv27)
+#define MFL2_PICK(t_, q_) ((q_) == 0 ? (t_)[0] : (q_) == 1 ? (t_)[1] : (t_)[2])
+      const double *__restrict__ qw = prm.tab27 + 18;
+      const double wq = MFL2_PICK(qw, qx) * MFL2_PICK(qw, qy) * MFL2_PICK(qw, qz);
+      double       Ji[9], detJ = 1.0, G[3][3];
+      if constexpr (BOX)
+        mf_box_geometry(R + MF27_BOX, Ji, detJ);
+      else
+        {
+          const double *__restrict__ tq = prm.tab27 + 21;
+          const double xiq[3] = {MFL2_PICK(tq, qx), MFL2_PICK(tq, qy), MFL2_PICK(tq, qz)};
+          mf_geometry<false>(prm, cell, xiq, Ji, detJ);
+        }
+#undef MFL2_PICK
+#pragma unroll
+      for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j)
+          G[i][j] = BOX ? H[i][j] * Ji[j * 4] : H[i][0] * Ji[j] + H[i][1] * Ji[3 + j] + H[i][2] * Ji[6 + j];
+      const double w = detJ * wq, wk = w * op.c_K, wm = w * op.c_M * op.rho;
+      const double ltr = op.lambda * (G[0][0] + G[1][1] + G[2][2]);
+      if (act)
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+          {
+            double sg[3];
+#pragma unroll
+            for (int j = 0; j < 3; ++j)
+              sg[j] = wk * (op.mu * (G[i][j] + G[j][i]) + (i == j ? ltr : 0.0));
+#pragma unroll
+            for (int l = 0; l < 3; ++l)
+              R[(i * 4 + l) * Q27 + it] = BOX ? sg[l] * Ji[l * 4] : sg[0] * Ji[l * 3] + sg[1] * Ji[l * 3 + 1] + sg[2] * Ji[l * 3 + 2];
+            R[(i * 4 + 3) * Q27 + it] = wm * V[i];
+          }
+    }
+    __syncthreads();
+    // ---- I3: contract qz.  item (c, q9 = qy*3+qx)
+    {
+      const int c = it / 9, q9 = it - 9 * c;
+      double    v[4][3];
+      if (act)
+#pragma unroll
+        for (int d = 0; d < 4; ++d)
+#pragma unroll
+          for (int z = 0; z < 3; ++z)
+            v[d][z] = R[(c * 4 + d) * Q27 + z * 9 + q9];
+      __syncthreads(); // Q is consumed: C goes on top of it
+      if (act)
+#pragma unroll
+        for (int k = 0; k < 3; ++k)
+          {
+            double cds = 0.0, csd = 0.0, css = 0.0;
+#pragma unroll
+            for (int z = 0; z < 3; ++z)
+              {
+                cds = fma(S27[z][k], v[0][z], cds);
+                csd = fma(S27[z][k], v[1][z], csd);
+                css = fma(D27[z][k], v[2][z], css);
+                css = fma(S27[z][k], v[3][z], css);
+              }
+            R[(0 * 3 + k) * Q27 + it] = cds; // C[kind][k][c][qy][qx]: consecutive lanes
+            R[(1 * 3 + k) * Q27 + it] = csd;
+            R[(2 * 3 + k) * Q27 + it] = css;
+          }
+    }
+    __syncthreads();
+    // ---- I2: contract qy.  item (c, k, qx)
+    {
+      const int ck = it / 3, qx = it - 3 * ck, c = ck / 3, k = ck - 3 * c;
+      double    cds[3], csd[3], css[3];
+      if (act)
+#pragma unroll
+        for (int qy = 0; qy < 3; ++qy)
+          {
+            const int o = k * Q27 + c * 9 + qy * 3 + qx;
+            cds[qy]     = R[0 * 81 + o];
+            csd[qy]     = R[1 * 81 + o];
+            css[qy]     = R[2 * 81 + o];
+          }
+      __syncthreads(); // C is consumed: E goes on top of it
+      if (act)
+#pragma unroll
+        for (int j = 0; j < 3; ++j)
+          {
+            double ed = 0.0, es = 0.0;
+#pragma unroll
+            for (int qy = 0; qy < 3; ++qy)
+              {
+                ed = fma(S27[qy][j], cds[qy], ed);
+                es = fma(D27[qy][j], csd[qy], es);
+                es = fma(S27[qy][j], css[qy], es);
+              }
+            R[j * Q27 + it]      = ed; // E[kind][j][(c,k)][qx]: consecutive lanes
+            R[81 + j * Q27 + it] = es;
+          }
+    }
+    __syncthreads();
+    // ---- I1: contract qx, results into the cell's slots.  item = line (c,k,j) = it
+    if (act)
+      {
+        const int lc = it / 9, ckl = it / 3, jl = it - 3 * ckl; // the line (c,k,j)
+        double    ed[3], es[3];
+#pragma unroll
+        for (int qx = 0; qx < 3; ++qx)
+          {
+            ed[qx] = R[jl * Q27 + ckl * 3 + qx];
+            es[qx] = R[81 + jl * Q27 + ckl * 3 + qx];
+          }
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+          {
+            double yv = 0.0;
+#pragma unroll
+            for (int qx = 0; qx < 3; ++qx)
+              {
+                yv = fma(D27[qx][i], ed[qx], yv);
+                yv = fma(S27[qx][i], es[qx], yv);
+              }
+            prm.yc[int64_t(ydst[i]) * 3 + lc] = yv;
+          }
+      }
+  }
+
+  // diagonal of A = M + theta^2 dt^2 K per cell and node, the Q2 counterpart of mf_linear_diag_q3 with its expressions: one wave
+  // per cell, lane = node a = (k*3+j)*3+i (lanes 27-63 leave), a loop over the 27 points; once per set-up, written for clarity.
+  // Out: the three entries into the product's slots (prm.yc; mf_linear_diag_gather sums them) or, BLK, the symmetric half of the
+  // node's block xx yy zz xy xz yz into slots6 [nslots][6] (mf_diag_gather sums them under the constraint rule and inverts).
+  template <bool BOX, bool BLK>
+  __global__ __launch_bounds__(64) void mf_linear_diag_q2(MfParams prm, MfLinearOp op, double *__restrict__ slots6)
+  {
+    const int     t    = threadIdx.x;
+    const int64_t cell = blockIdx.x;
+    if (cell >= prm.count || t >= Q27)
+      return;
+    const int     ia[3] = {t % 3, (t / 3) % 3, t / 9};
+    const double *tab   = prm.tab27; // N1[3][3], dN1[3][3], qw[3], qx[3]
+    double        d[3]  = {0.0, 0.0, 0.0};
+    double        o[3]  = {0.0, 0.0, 0.0}; // BLK: xy xz yz
+    for (int q = 0; q < Q27; ++q)
+      {
+        const int qi[3] = {q % 3, (q / 3) % 3, q / 9};
+        double    v[3], dv[3], Ji[9], detJ, g[3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k)
+          {
+            v[k]  = tab[qi[k] * 3 + ia[k]];
+            dv[k] = tab[9 + qi[k] * 3 + ia[k]];
+          }
+        const double n = v[0] * v[1] * v[2], dn[3] = {dv[0] * v[1] * v[2], v[0] * dv[1] * v[2], v[0] * v[1] * dv[2]};
+        mf_geometry<BOX>(prm, cell, tab + 21, qi[0], qi[1], qi[2], Ji, detJ);
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+          g[i] = dn[0] * Ji[i] + dn[1] * Ji[3 + i] + dn[2] * Ji[6 + i];
+        const double w  = detJ * tab[18 + qi[0]] * tab[18 + qi[1]] * tab[18 + qi[2]];
+        const double gg = g[0] * g[0] + g[1] * g[1] + g[2] * g[2];
+#pragma unroll
+        for (int c = 0; c < 3; ++c)
+          d[c] += w * (op.c_K * ((op.lambda + op.mu) * g[c] * g[c] + op.mu * gg) + op.c_M * op.rho * n * n);
+        if constexpr (BLK)
+          {
+            const double wl = w * op.c_K * (op.lambda + op.mu);
+            o[0] += wl * g[0] * g[1];
+            o[1] += wl * g[0] * g[2];
+            o[2] += wl * g[1] * g[2];
+          }
+      }
+    const int64_t slot = prm.slot_inline ? cell * Q27 + t : int64_t(prm.dst[cell * Q27 + t]);
+    if constexpr (BLK)
+      {
+#pragma unroll
+        for (int c = 0; c < 3; ++c)
+          {
+            slots6[slot * 6 + c]     = d[c];
+            slots6[slot * 6 + 3 + c] = o[c];
+          }
+      }
+    else
+      {
+#pragma unroll
+        for (int c = 0; c < 3; ++c)
+          prm.yc[slot * 3 + c] = d[c];
+      }
+  }
+
   // system_rhs from the cells' residual slots (point pass in one launch): rhs = 0 - r_1 - r_2 - ... in slot order, the
   // subtractions of the colour-by-colour update in their order; constrained rows get no rhs (:769-773).  One thread per dof.
   __global__ __launch_bounds__(256) void residual_gather(const double *__restrict__ slots3, const int32_t *__restrict__ slot_base,
@@ -10655,6 +10900,40 @@ namespace mi
     q.count    = cell_count;
     auto *kern = q.cellbox ? mf_linear_diag_q3<true, true> : mf_linear_diag_q3<false, true>;
     hipLaunchKernelGGL(kern, dim3((cell_count + MFQ3S_WPB - 1) / MFQ3S_WPB), dim3(64 * MFQ3S_WPB), 0, s, q, op, slots6);
+  }
+  void launch_mf_linear_q2(const MfParams &p, const MfLinearOp &op, int32_t cell_count, hipStream_t s, hipEvent_t ev_start, hipEvent_t ev_stop)
+  {
+    if (cell_count <= 0)
+      return;
+    MfParams q  = p;
+    q.count     = cell_count;
+    q.xcd_chunk = ((cell_count + 1) / 2 + 7) / 8; // PAIRS of cells per XCD, as mf_spmv27
+    auto *kern  = q.lat.ncol > 0 ? (q.cellbox ? mf_linear_q2<true, true> : mf_linear_q2<false, true>) :
+                                   (q.cellbox ? mf_linear_q2<true, false> : mf_linear_q2<false, false>);
+    if (ev_start || ev_stop)
+      hipExtLaunchKernelGGL(kern, dim3(q.xcd_chunk * 8), dim3(64), 0, s, ev_start, ev_stop, 0, q, op);
+    else
+      hipLaunchKernelGGL(kern, dim3(q.xcd_chunk * 8), dim3(64), 0, s, q, op);
+  }
+  void launch_mf_linear_diag_q2(const MfParams &p, const MfLinearOp &op, int32_t cell_count, double *blk, double *dinv, int64_t ndofs,
+                                hipStream_t s)
+  {
+    if (cell_count <= 0)
+      return;
+    MfParams q = p;
+    q.count    = cell_count;
+    auto *kern = q.cellbox ? mf_linear_diag_q2<true, false> : mf_linear_diag_q2<false, false>;
+    hipLaunchKernelGGL(kern, dim3(cell_count), dim3(64), 0, s, q, op, (double *)nullptr);
+    hipLaunchKernelGGL(mf_linear_diag_gather, dim3(int((ndofs + 255) / 256)), dim3(256), 0, s, q, blk, dinv, ndofs);
+  }
+  void launch_mf_linear_diag_blk_q2(const MfParams &p, const MfLinearOp &op, int32_t cell_count, double *slots6, hipStream_t s)
+  {
+    if (cell_count <= 0)
+      return;
+    MfParams q = p;
+    q.count    = cell_count;
+    auto *kern = q.cellbox ? mf_linear_diag_q2<true, true> : mf_linear_diag_q2<false, true>;
+    hipLaunchKernelGGL(kern, dim3(cell_count), dim3(64), 0, s, q, op, slots6);
   }
   void launch_mf_diag_gather(const double *slots6, const int32_t *slot_base, const int32_t *slot_src, const uint8_t *cmask,
                              const int32_t *diagpos, double *blk, double *dinv, double *dinv_blk, double *sym6, int64_t nnodes, hipStream_t s)

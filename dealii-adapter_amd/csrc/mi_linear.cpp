@@ -11,11 +11,13 @@
 // (mf_linear_q3: (c_K K + c_M M) x on the model's own 4 x 4 x 4 rule, one wave per cell) + the slot gathers; the set-up forms
 // the diagonal of the stepping matrix (mf_linear_diag_q3) and the body-force vector as M (b, b, ...), and releases the
 // nonlinear tangent array.  The per-step path is the same; the solve is the PCG whatever "solver_type" says.
+// "linear_operator" 2: the same on the kernel of the mesh's element family -- 3D Q2: mf_linear_q2 on the 3 x 3 x 3 rule, two
+// cells per wave, and mf_linear_diag_q2; 3D Q3: exactly what 1 does.
 //
 // Tuning "linear_precond" 1 (one slab): the PCG is preconditioned by a geometric multigrid V-cycle on a hierarchy of the
 // stepping matrix that the model owns (mg_setup_linear): built once per set-up, never refreshed, independent of "precond" and
 // of the tangent's hierarchy.  Level 0 is the context with the stepping matrix selected, in either operator form; its
-// block-Jacobi D is the model's (the node blocks of d_A, or mf_linear_diag_q3<., true> + mf_diag_gather without a matrix).
+// block-Jacobi D is the model's (the node blocks of d_A, or mf_linear_diag_q3 / _q2 <., true> + mf_diag_gather without a matrix).
 #include <cmath>
 #include <cstring>
 #include <map>
@@ -30,12 +32,12 @@ namespace mi_detail
     double *d_K = nullptr, *d_M = nullptr, *d_A = nullptr, *d_dinvA = nullptr, *d_body = nullptr;
     bool    body_force_enabled = false;
     bool    factored = false; // the banded Cholesky factor of the (constant) system matrix is in the context's band
-    // "linear_operator" 1: no d_K / d_M / d_A; the three operators as mf_linear_q3 runs them, the diagonal of the stepping
+    // "linear_operator" 1 / 2: no d_K / d_M / d_A; the three operators as mf_linear_q3 / mf_linear_q2 runs them, the diagonal of the stepping
     // matrix in the layout the slot gathers read (mi_ctx::d_diag_blk's), the rule's tables -- all the model's own, so that
     // no key of the nonlinear path can take them away
     bool     mf = false;
     LinearMf op[3]; // K, M, stepping matrix
-    double  *d_diag = nullptr, *d_tab4 = nullptr;
+    double  *d_diag = nullptr, *d_tab_mf = nullptr; // (the tables of QGauss(p + 1): Tables1D(3, 4) | Tables1D(2, 3), tab27's layout)
     int32_t *d_diagpos_mf = nullptr;
     uint8_t *d_nomask = nullptr; // [nnodes] zeros: the constraint mask of K and M (no row replaced)
     // "linear_precond" 1: the hierarchy of the stepping matrix, the inverse node blocks of level 0 (full, and in 3D their
@@ -55,7 +57,7 @@ namespace mi_detail
     mg_free(c->linear->mg);
     c->mg_linear = nullptr;
     for (double *p : {c->linear->d_K, c->linear->d_M, c->linear->d_A, c->linear->d_dinvA, c->linear->d_body, c->linear->d_diag,
-                      c->linear->d_tab4, c->linear->d_dinv_blk, c->linear->d_dinv_sym6})
+                      c->linear->d_tab_mf, c->linear->d_dinv_blk, c->linear->d_dinv_sym6})
       if (p)
         hipFree(p);
     if (c->linear->d_diagpos_mf)
@@ -93,8 +95,8 @@ using namespace mi_detail;
 
 extern "C" {
 
-// "linear_operator" 1: nothing is assembled.  Slot tables, slots and cell boxes where absent; the rule's tables; the three
-// operators; the diagonal of the stepping matrix and its inverse; body = M (b, b, ...)
+// "linear_operator" 1 / 2: nothing is assembled.  Slot tables, slots and cell boxes where absent; the rule's tables; the three
+// operators; the diagonal of the stepping matrix and its inverse; body = M (b, b, ...).  Tables and kernels by the degree
 static int linear_setup_matrix_free(mi_ctx *c, LinearModel &L, const mi::Tables1D &t, double lambda, double theta)
 {
   const mi::HostMesh &m  = c->mesh;
@@ -102,7 +104,8 @@ static int linear_setup_matrix_free(mi_ctx *c, LinearModel &L, const mi::Tables1
   const double        mu = c->mat.mu, rho = c->mat.rho, dt = c->nm.delta_t;
   if (int rc = linear_mf_prepare(c))
     return rc;
-  if (int rc = upload(c, &L.d_tab4, t.packed()))
+  const bool q2 = c->degree == 2;
+  if (int rc = upload(c, &L.d_tab_mf, t.packed()))
     return rc;
   std::vector<int32_t> dp(nn);
   for (size_t n = 0; n < nn; ++n)
@@ -116,10 +119,11 @@ static int linear_setup_matrix_free(mi_ctx *c, LinearModel &L, const mi::Tables1
   // K and M are unconstrained (assemble_linear_cells drops entries in A only): x unmasked, no row replaced
   const double cK[3] = {1.0, 0.0, dt * dt * theta * theta}, cM[3] = {0.0, 1.0, 1.0};
   for (int w = 0; w < 3; ++w)
-    L.op[w] = LinearMf{mi::MfLinearOp{lambda, mu, rho, cK[w], cM[w], w == 2 ? 1 : 0}, L.d_tab4, L.d_diag, L.d_diagpos_mf,
+    L.op[w] = LinearMf{mi::MfLinearOp{lambda, mu, rho, cK[w], cM[w], w == 2 ? 1 : 0}, c->degree, L.d_tab_mf, L.d_diag, L.d_diagpos_mf,
                        w == 2 ? c->d_cmask : L.d_nomask};
   mi::MfParams f = mf_params(c);
-  f.tab_q3s = L.d_tab4, f.yc = c->d_mf_yc, f.dst = c->d_mf_dst, f.slot_base = c->d_mf_slot_base, f.slot_src = c->d_mf_src;
+  (q2 ? f.tab27 : f.tab_q3s) = L.d_tab_mf;
+  f.yc = c->d_mf_yc, f.dst = c->d_mf_dst, f.slot_base = c->d_mf_slot_base, f.slot_src = c->d_mf_src;
   f.slot_inline = c->slots_layout == 1;
   if (c->linear_precond == 1)
     {
@@ -127,10 +131,10 @@ static int linear_setup_matrix_free(mi_ctx *c, LinearModel &L, const mi::Tables1
       // constraint rule (row and column of a constrained dof dropped, |diagonal contribution| kept) is the model's: the
       // diagonal contributions are sums of squares, so nothing changes sign.  Out: the blocks, 1 / diagonal, D^-1 in both forms
       double *d_slots6 = nullptr;
-      HIPCHK(c, hipMalloc((void **)&d_slots6, size_t(m.ncells) * 64 * 6 * sizeof(double)));
+      HIPCHK(c, hipMalloc((void **)&d_slots6, size_t(m.ncells) * m.npc * 6 * sizeof(double)));
       HIPCHK(c, hipMalloc((void **)&L.d_dinv_blk, nn * 9 * sizeof(double)));
       HIPCHK(c, hipMalloc((void **)&L.d_dinv_sym6, nn * 6 * sizeof(double)));
-      mi::launch_mf_linear_diag_blk_q3(f, L.op[2].op, int32_t(m.ncells), d_slots6, c->stream);
+      (q2 ? mi::launch_mf_linear_diag_blk_q2 : mi::launch_mf_linear_diag_blk_q3)(f, L.op[2].op, int32_t(m.ncells), d_slots6, c->stream);
       mi::launch_mf_diag_gather(d_slots6, c->d_mf_slot_base, c->d_mf_src, c->d_cmask, L.d_diagpos_mf, L.d_diag, L.d_dinvA, L.d_dinv_blk,
                                 L.d_dinv_sym6, m.nnodes, c->stream);
       const hipError_t e1 = hipGetLastError(), e2 = hipStreamSynchronize(c->stream);
@@ -139,7 +143,7 @@ static int linear_setup_matrix_free(mi_ctx *c, LinearModel &L, const mi::Tables1
       HIPCHK(c, e2);
     }
   else
-    mi::launch_mf_linear_diag_q3(f, L.op[2].op, int32_t(m.ncells), L.d_diag, L.d_dinvA, c->n, c->stream);
+    (q2 ? mi::launch_mf_linear_diag_q2 : mi::launch_mf_linear_diag_q3)(f, L.op[2].op, int32_t(m.ncells), L.d_diag, L.d_dinvA, c->n, c->stream);
   HIPCHK(c, hipGetLastError());
   if (L.body_force_enabled)
     {
@@ -242,7 +246,7 @@ static int linear_setup_member(mi_ctx *c, double theta)
     bn += c->mat.body_force[d] * c->mat.body_force[d];
   L.body_force_enabled = std::sqrt(bn) > 1e-15; // :62
 
-  L.mf = c->linear_operator == 1;
+  L.mf = c->linear_operator != 0; // (1 and 2: set_tuning has checked the mesh)
   if (int rc = L.mf ? linear_setup_matrix_free(c, L, t, lambda, theta) : linear_assemble_operators(c, L, t, lambda, theta))
     return rc;
 
@@ -561,7 +565,7 @@ int mi_linear_matrix_get_csr(mi_ctx *c, int which, int64_t *rowptr, int32_t *col
 }
 
 // y = K x (0), M x (1) or A x (2) through the device kernels of the current mode: the sliced-ELL product on the assembled
-// arrays or mf_linear_q3 + mf_gather.  The product is timed as MI_T_SPMV (device stamps) when profiling is on.
+// arrays or mf_linear_q3 / mf_linear_q2 + mf_gather.  The product is timed as MI_T_SPMV (device stamps) when profiling is on.
 int mi_linear_apply(mi_ctx *c, int which, const double *x_host, double *y_host)
 {
   if (!c->linear || which < 0 || which > 3 || !x_host || !y_host)
@@ -598,7 +602,7 @@ int mi_linear_apply(mi_ctx *c, int which, const double *x_host, double *y_host)
 }
 
 // the Jacobi diagonal of the stepping matrix in use: the diagonal entries whose reciprocals the PCG multiplies with -- out of
-// the assembled array, or as mf_linear_diag_q3 formed them
+// the assembled array, or as mf_linear_diag_q3 / mf_linear_diag_q2 formed them
 int mi_linear_get_diagonal(mi_ctx *c, double *diag_host)
 {
   if (!c->linear || !diag_host)
@@ -631,7 +635,7 @@ int mi_linear_get_diagonal(mi_ctx *c, double *diag_host)
 }
 
 // the node blocks of the stepping matrix in use, [nnodes][dim][dim]: what the block-Jacobi smoother of "linear_precond" 1 inverts
-// -- out of the assembled array, or as mf_linear_diag_q3 + the gather formed them (diagonal entries alone with the key at 0)
+// -- out of the assembled array, or as mf_linear_diag_q3 / _q2 + the gather formed them (diagonal entries alone with the key at 0)
 int mi_linear_get_diagonal_blocks(mi_ctx *c, double *blocks)
 {
   if (!c->linear || !blocks)

@@ -98,9 +98,10 @@ namespace Linear_Elasticity
       dev_id = std::atoi(e);
     device = std::make_unique<mi::Device>(mesh_desc, mat, nm, dev_id);
     // MI_LINEAR_OPERATOR=1: K, M and the stepping matrix matrix-free (3D Q3 on one rank; a switch of this PROGRAM, handed on
-    // as a tuning key: the library itself reads no environment variable).  Refused elsewhere: said once, the run is assembled
+    // as a tuning key: the library itself reads no environment variable).  Refused elsewhere: said once, the run is assembled.
+    // MI_LINEAR_OPERATOR=2: value 2 of the key -- matrix-free on the kernel of the mesh's element family (3D Q2 and Q3)
     if (const char *f = std::getenv("MI_LINEAR_OPERATOR"))
-      if (std::atoi(f) != 0 && mi_set_tuning(device->ctx(), "linear_operator", 1) != MI_OK)
+      if (std::atoi(f) != 0 && mi_set_tuning(device->ctx(), "linear_operator", std::atoi(f) == 2 ? 2 : 1) != MI_OK)
         std::cout << "MI_LINEAR_OPERATOR ignored: " << mi_last_error(device->ctx()) << std::endl;
     // MI_LINEAR_PRECOND=1: the solve preconditioned by the linear model's multigrid V-cycle (one rank), handed on as the tuning key
     // "linear_precond" in the same way.  Refused on a team: said once, the run is Jacobi-PCG
@@ -111,7 +112,9 @@ namespace Linear_Elasticity
     {
       int mf = 0, mg = 0;
       device->check(mi_get_tuning(device->ctx(), "linear_operator_active", &mf), "mi_get_tuning");
-      if (mf)
+      if (mf == 2)
+        std::cout << "Linear operators: matrix-free (K, M and the stepping matrix on mf_linear_q2, nothing assembled)" << std::endl;
+      else if (mf)
         std::cout << "Linear operators: matrix-free (K, M and the stepping matrix on mf_linear_q3, nothing assembled)" << std::endl;
       device->check(mi_get_tuning(device->ctx(), "linear_precond_active", &mg), "mi_get_tuning");
       if (mg)

@@ -425,12 +425,12 @@ int mi_linear_setup(mi_ctx *ctx, double theta);
 int mi_linear_step(mi_ctx *ctx, int data_consistent, double abs_tol, int64_t max_it, int *its, double *res);
 /* energies of the linear model after mi_linear_setup (MI_EINVAL without one): 1/2 u . (K u), 1/2 v . (M v) and -u . f_body with
  * u = MI_L_DISPLACEMENT, v = MI_L_VELOCITY, through the products the current set-up runs -- the sliced-ELL product on the
- * assembled K and M, or mf_linear_q3 + the slot gather ("linear_operator" 1), each with the dot product fused.  Runs
+ * assembled K and M, or mf_linear_q3 / mf_linear_q2 + the slot gather ("linear_operator" 1 / 2), each with the dot product fused.  Runs
  * wherever mi_linear_step runs, teams included (collective).  Overwrites the solver's work vectors, no state vector. */
 int mi_linear_energy(mi_ctx *ctx, mi_energy_info *out);
 /* K (0), M (1) or the constrained stepping matrix (2) as scalar CSR, for parity tests */
 int mi_linear_matrix_get_csr(mi_ctx *ctx, int which, int64_t *rowptr, int32_t *col, double *val);
-/* y = K x (0), M x (1) or A x (2) through the device kernels the current set-up runs, in either mode of "linear_operator"
+/* y = K x (0), M x (1) or A x (2) through the device kernels the current set-up runs, in every mode of "linear_operator"
  * (host arrays of n_dofs; undecomposed mesh).  A: constrained columns dropped, row of a constrained dof = diag(A) x.  K, M:
  * unconstrained, as assembled.  With profiling on, the product alone is timed under MI_T_SPMV.
  * 3: y = B x, one multigrid V-cycle of the current set-up ("linear_precond" 1) as the solve applies it to its residual;
@@ -451,7 +451,7 @@ int mi_linear_get_diagonal_blocks(mi_ctx *ctx, double *blocks);
  *   "linear_operator" and with both values of "linear_precond", 2D and 3D, degrees 1-4.
  *   Method: LOBPCG on a block of m = n_modes + max(2, n_modes / 4) vectors (the surplus are guard vectors), so 3 m <= 60.  The
  *   products K x and M x go one vector at a time through the products of the current set-up (the sliced-ELL product or
- *   mf_linear_q3 + the slot gather), their output zeroed on the constrained dofs.  The preconditioner is what the set-up has for
+ *   mf_linear_q3 / mf_linear_q2 + the slot gather), their output zeroed on the constrained dofs.  The preconditioner is what the set-up has for
  *   the stepping matrix A = M + theta^2 dt^2 K = (theta dt)^2 (K + sigma M), sigma = 1 / (theta dt)^2: the reciprocal diagonal,
  *   or one multigrid V-cycle with "linear_precond" 1.  The images K S and M S of the search space S = [X W P] are kept, so an
  *   iteration costs 2 m products and m preconditioner applications; all 9 m^2 scalar products of an iteration are two
@@ -672,27 +672,33 @@ int mi_set_profiling(mi_ctx *ctx, int enable);
  *                                                  memory is released.  Same results (nonlinear_elasticity.cc:1044-1087,
  *                                                  1153-1191); excludes "solver_type" 1, "precond_storage" 32 and matrix
  *                                                  export
- *  linear_operator      0 | 1                      linear model (mi_linear_setup / mi_linear_step): K, M and the stepping  -
+ *  linear_operator      0 | 1 | 2                  linear model (mi_linear_setup / mi_linear_step): K, M and the stepping  -
  *                                                  matrix assembled in the tangent's sliced-ELL layout | matrix-free on 3D
  *                                                  Q3 meshes of one slab (elsewhere: MI_EINVAL, the key stays 0): one
  *                                                  kernel, mf_linear_q3, applies (c_K K + c_M M) x on the model's own
  *                                                  4 x 4 x 4 rule (linear_elasticity.cc:61), one wave per cell, no point
  *                                                  record; the diagonal of the stepping matrix comes from mf_linear_diag_q3,
- *                                                  the body force as M (b, b, ...).  Read by the next mi_linear_setup, which
+ *                                                  the body force as M (b, b, ...) | matrix-free on the kernel of the mesh's
+ *                                                  element family: 3D Q2 of one slab: mf_linear_q2 on the model's own
+ *                                                  3 x 3 x 3 rule, two cells per wave, no point record, the diagonal from
+ *                                                  mf_linear_diag_q2, in whichever slot layout the context has; 3D Q3 of one
+ *                                                  slab: exactly what 1 does; elsewhere (2D, degrees 1 and 4, teams):
+ *                                                  MI_EINVAL, the key keeps its value.  Read by the next mi_linear_setup, which
  *                                                  then keeps no assembled array: the nonlinear tangent array is released
  *                                                  too, and mi_assemble, mi_newmark_step, mi_cg_solve, mi_spmv and the matrix
  *                                                  exports return MI_EINVAL until a set-up with 0.  "solver_type" 1 takes
  *                                                  the PCG route there; "fine_level" cannot change meanwhile.  Same
- *                                                  operators up to rounding.  Read-back "linear_operator_active": what the
- *                                                  current linear set-up runs (0 without one)
+ *                                                  operators up to rounding.  Read-back "linear_operator": the value set;
+ *                                                  "linear_operator_active": what the current linear set-up runs -- 0
+ *                                                  assembled (or no set-up), 1 mf_linear_q3, 2 mf_linear_q2
  *  linear_precond       0 | 1                      linear model: the solve of mi_linear_step is the Jacobi-PCG | the PCG   -
  *                                                  preconditioned by a geometric multigrid V-cycle on a hierarchy of the
  *                                                  (constant) stepping matrix that the model owns: the shape rules of the
  *                                                  tangent's ("mg_coarsest", "mg_dense"; nu 3 / 2 over ratio 20), every level
  *                                                  >= 1 the assembled linear model of its own unperturbed mesh, level 0 the
  *                                                  context in either mode of "linear_operator" (matrix-free: the smoother
- *                                                  steps and the residual in the slot gathers, D from mf_linear_diag_q3's
- *                                                  block form).  Built once by the next mi_linear_setup, never refreshed;
+ *                                                  steps and the residual in the slot gathers, D from the block form of
+ *                                                  mf_linear_diag_q3 / mf_linear_diag_q2).  Built once by the next mi_linear_setup, never refreshed;
  *                                                  independent of "precond" and of the tangent's hierarchy.  Undecomposed
  *                                                  contexts only (a team: MI_EINVAL, the key stays 0).  "solver_type" 1
  *                                                  keeps precedence where the band solver applies.  Read-back
