@@ -18,6 +18,7 @@ HEADER = os.path.join(ROOT, "include", "mi_elasticity.h")
 MI_OK, MI_EINVAL, MI_EHIP, MI_ENOCONV_LIN, MI_ENOCONV_NR, MI_ECOMM = 0, -1, -2, -3, -4, -5
 FACE_FREE, FACE_CLAMPED, FACE_INTERFACE, FACE_ZCLAMP = 0, 1, 7, 8
 STRESS_NEOHOOKE, STRESS_LINEAR = 0, 1  # mi_stress_field's models
+STRESS_AT_RAW, STRESS_AT_RECOVERED = 0, 1  # mi_evaluate_stress's kinds
 (V_U, V_U_OLD, V_V, V_V_OLD, V_A, V_A_OLD, V_STRESS, V_DELTA, V_NEWTON, V_RHS) = range(10)
 (T_ASSEMBLE_CELLS, T_ASSEMBLE_TOTAL, T_SPMV, T_CG_VECTOR, T_CG_TOTAL, T_NEWMARK, T_STEP, T_ASSEMBLE_DIAG, T_ASSEMBLE_RESIDUAL,
  T_SPMV_PRECOND, T_EBE_LAUNCH, T_COUNT) = range(12)
@@ -186,6 +187,11 @@ def lib():
         L.mi_evaluate_points.argtypes = [vp, C.c_int, C.POINTER(C.c_int), C.c_int64, dp, dp, dp, C.POINTER(C.c_int64),
                                          C.POINTER(C.c_int64)]
         L.mi_evaluate_points.restype = C.c_int
+        L.mi_evaluate_stress.argtypes = [vp, C.c_int, C.c_int, C.c_int64, dp, dp, dp, dp, dp, C.POINTER(C.c_int64),
+                                         C.POINTER(C.c_int64)]
+        L.mi_evaluate_stress.restype = C.c_int
+        L.mi_principal_stress.argtypes = [vp, C.c_int64, dp, dp, dp]
+        L.mi_principal_stress.restype = C.c_int
         L.mi_state_transfer.argtypes = [vp, vp]
         L.mi_state_transfer.restype = C.c_int
         L.mi_mass_apply.argtypes = [vp, C.c_int, C.c_int, dp, dp]
@@ -574,6 +580,34 @@ class Context:
         if single:
             val, grad = val[0], (grad[0] if gradients else None)
         return val, grad, cell, int(nout.value)
+
+    def evaluate_stress(self, xyz, model=STRESS_NEOHOOKE, kind=STRESS_AT_RAW, principal=False, directions=False):
+        """the stress of the committed state at the points xyz [npts, dim] of the reference configuration (mi_evaluate_stress):
+        dict(sigma [npts, ncomp], von_mises [npts], principal [npts, dim] descending, directions [npts, dim, dim] with row k the
+        unit eigenvector of principal[k] (each None unless asked), cell [npts] (-1: outside, zeros), n_outside).  kind
+        STRESS_AT_RAW: the answering element's own stress at the point; STRESS_AT_RECOVERED: stress_field(model) interpolated"""
+        pts = np.ascontiguousarray(xyz, dtype=np.float64).reshape(-1, self.dim)
+        npts, ncomp = pts.shape[0], self.dim * (self.dim + 1) // 2
+        sigma, vm = np.zeros((npts, ncomp)), np.zeros(npts)
+        pr = np.zeros((npts, self.dim)) if principal else None
+        dr = np.zeros((npts, self.dim, self.dim)) if directions else None
+        cell = np.zeros(npts, dtype=np.int64)
+        nout = C.c_int64(0)
+        self._chk(lib().mi_evaluate_stress(self.h, int(model), int(kind), npts, _dp(pts), _dp(sigma), _dp(vm),
+                                           _dp(pr) if principal else None, _dp(dr) if directions else None,
+                                           cell.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(nout)))
+        return dict(sigma=sigma, von_mises=vm, principal=pr, directions=dr, cell=cell, n_outside=int(nout.value))
+
+    def principal_stress(self, sigma, directions=False):
+        """(principal [n, dim] descending, directions [n, dim, dim] or None) of the symmetric tensors sigma [n, ncomp] in
+        stress_field's component order (mi_principal_stress); row k of a tensor's directions is the unit eigenvector of its
+        principal[k], its component of largest magnitude positive"""
+        ncomp = self.dim * (self.dim + 1) // 2
+        s = np.ascontiguousarray(sigma, dtype=np.float64).reshape(-1, ncomp)
+        pr = np.zeros((s.shape[0], self.dim))
+        dr = np.zeros((s.shape[0], self.dim, self.dim)) if directions else None
+        self._chk(lib().mi_principal_stress(self.h, s.shape[0], _dp(s), _dp(pr), _dp(dr) if directions else None))
+        return pr, dr
 
     def transfer_state_from(self, src):
         """this context's six state vectors V_U .. V_A_OLD := src's fields at this context's nodes, constrained dofs exactly 0

@@ -1380,10 +1380,14 @@ namespace mi_detail
     t.build(c->degree, c->degree + 1); // quad_order = degree + 1, linear_elasticity.cc:61
     return upload(c, &c->d_stress_tab, t.packed());
   }
+  // the end of the pass under tuning "stress_projection" 1 (mi_project.cpp, next to the mass solve it runs)
+  static int stress_consistent_solve(mi_ctx *c);
   // One slab's lumped projection, enqueued: the accumulator zeroed, the local cells colour by colour (ghost layer included:
   // like the residual pass on system_rhs, that completes every OWNED node -- the nodes of the slab's first plane, owned by the
   // slab below, and of the ghost planes stay partial and are never read), then stress_finish.  d_stress: [nnodes][8] accumulator,
-  // behind it sigma [nnodes][ncomp], von Mises [nnodes], weight [nnodes]; allocated on first use, as the linear model's tables
+  // behind it sigma [nnodes][ncomp], von Mises [nnodes], weight [nnodes]; allocated on first use, as the linear model's tables.
+  // Tuning "stress_projection" 1 (one slab only): stress_consistent_solve in place of stress_finish; that one waits for the
+  // stream between its iterations, so the pass is then not merely enqueued
   static int enqueue_stress(mi_ctx *c, int model)
   {
     const size_t nn = size_t(c->mesh.nnodes), ncomp = size_t(c->dim * (c->dim + 1) / 2);
@@ -1409,6 +1413,8 @@ namespace mi_detail
           return fail(c, MI_EINVAL, "no stress kernel for dim=%d degree=%d", c->dim, c->degree);
       }
     double *out = c->d_stress + nn * 8;
+    if (c->stress_projection == 1) // the accumulator is the load b and W: solve instead of dividing
+      return stress_consistent_solve(c);
     mi::launch_stress_finish(c->dim, c->d_stress, int64_t(nn), out, out + nn * ncomp, out + nn * (ncomp + 1), c->stream);
     HIPCHK(c, hipGetLastError());
     return MI_OK;
@@ -1547,11 +1553,8 @@ namespace mi_detail
     int64_t *cell;
     double  *part, *count;
   };
-  static int pe_carve(mi_ctx *owner, int n_which, int64_t npts, bool own_xyz, bool grads, PeBuffers &b)
+  static int pe_reserve(mi_ctx *owner, size_t total)
   {
-    const size_t np = size_t(npts), dim = size_t(owner->dim), nv = size_t(n_which) * np * dim;
-    const size_t nx = own_xyz ? np * dim : 0, ng = grads ? nv * dim : 0, npart = size_t(mi::field_at_points_partials(npts));
-    const size_t total = nx + nv + ng + np + npart + 1;
     if (owner->pe_doubles < total)
       {
         if (owner->d_pe)
@@ -1561,6 +1564,14 @@ namespace mi_detail
         HIPCHK(owner, hipMalloc((void **)&owner->d_pe, total * sizeof(double)));
         owner->pe_doubles = total;
       }
+    return MI_OK;
+  }
+  static int pe_carve(mi_ctx *owner, int n_which, int64_t npts, bool own_xyz, bool grads, PeBuffers &b)
+  {
+    const size_t np = size_t(npts), dim = size_t(owner->dim), nv = size_t(n_which) * np * dim;
+    const size_t nx = own_xyz ? np * dim : 0, ng = grads ? nv * dim : 0, npart = size_t(mi::field_at_points_partials(npts));
+    if (int rc = pe_reserve(owner, nx + nv + ng + np + npart + 1))
+      return rc;
     double *q   = owner->d_pe;
     b.xyz       = own_xyz ? q : nullptr;
     b.values    = q + nx;
@@ -1573,8 +1584,9 @@ namespace mi_detail
   // contexts the point evaluation runs on: one slab that is its own team's (a borrowed multigrid level is not)
   static bool pe_undecomposed(const mi_ctx *c) { return team_size(c) == 1 && c->team && c->team->members[0] == c; }
 
-  // c's vectors which[0..n_which) at the npts device points xyz into b, enqueued on s (c's tables are uploaded on first use)
-  static int enqueue_point_eval(mi_ctx *c, int n_which, const int *which, int64_t npts, const double *xyz, const PeBuffers &b, hipStream_t s)
+  // what the point kernels need to locate the npts device points xyz in c's mesh and to form the element's bases, into p (c's
+  // tables are uploaded on first use)
+  static int pe_mesh_params(mi_ctx *c, int64_t npts, const double *xyz, mi::PointEvalParams &p)
   {
     const mi::HostMesh &m = c->mesh;
     if (!c->d_cell_pos)
@@ -1597,11 +1609,7 @@ namespace mi_detail
           }
         c->pe_box = box ? 1 : 0;
       }
-    mi::PointEvalParams p{};
     p.xyz = xyz, p.npts = npts, p.cverts = c->d_cverts, p.cell_pos = c->d_cell_pos, p.vecs = c->d_vecs, p.n = c->n;
-    p.n_which = n_which;
-    for (int w = 0; w < n_which; ++w)
-      p.which[w] = which[w];
     const mi_mesh_desc &md = c->team->md; // (one slab: the box as the caller described it, without its perturbation)
     for (int d = 0; d < 3; ++d)
       {
@@ -1619,6 +1627,17 @@ namespace mi_detail
         p.nodes[a]  = nodes[size_t(a)];
         p.rdenom[a] = 1.0 / denom;
       }
+    return MI_OK;
+  }
+  // c's vectors which[0..n_which) at the npts device points xyz into b, enqueued on s
+  static int enqueue_point_eval(mi_ctx *c, int n_which, const int *which, int64_t npts, const double *xyz, const PeBuffers &b, hipStream_t s)
+  {
+    mi::PointEvalParams p{};
+    if (int rc = pe_mesh_params(c, npts, xyz, p))
+      return rc;
+    p.n_which = n_which;
+    for (int w = 0; w < n_which; ++w)
+      p.which[w] = which[w];
     p.values = b.values, p.gradients = b.gradients, p.cell = b.cell, p.part = b.part;
     if (mi::launch_field_at_points(c->dim, c->degree, c->pe_box == 1, p, b.count, s))
       return fail(c, MI_EINVAL, "no point evaluation kernel for dim=%d degree=%d (or too many points for one launch)", c->dim, c->degree);
@@ -3238,6 +3257,112 @@ int mi_evaluate_points(mi_ctx *c, int n_which, const int *which, int64_t npts, c
   return MI_OK;
 }
 
+// The stress at arbitrary points of the reference configuration, located as mi_evaluate_points locates them: the answering
+// element's own stress from grad u_h at the point (MI_STRESS_AT_RAW; no mesh pass) or the recovered nodal field of
+// mi_stress_field interpolated with the element's basis (MI_STRESS_AT_RECOVERED; enqueue_stress first), its von Mises stress, and
+// -- by a second kernel over the points' tensors -- principal values and directions.  Scratch is the point evaluation's; reads
+// the state as it is; no timing slot, no counter.  Undecomposed contexts only
+int mi_evaluate_stress(mi_ctx *c, int model, int kind, int64_t npts, const double *xyz, double *sigma, double *von_mises, double *principal,
+                       double *directions, int64_t *cell, int64_t *n_outside)
+{
+  if (!c)
+    return MI_EINVAL;
+  if (!xyz || !sigma)
+    return fail(c, MI_EINVAL, "mi_evaluate_stress: null argument");
+  if (model != MI_STRESS_NEOHOOKE && model != MI_STRESS_LINEAR)
+    return fail(c, MI_EINVAL, "mi_evaluate_stress: model %d (0: neo-Hookean Cauchy stress, 1: linear stress)", model);
+  if (kind != MI_STRESS_AT_RAW && kind != MI_STRESS_AT_RECOVERED)
+    return fail(c, MI_EINVAL, "mi_evaluate_stress: kind %d (0: the element's stress at the point, 1: the recovered nodal field)", kind);
+  if (npts < 0)
+    return fail(c, MI_EINVAL, "mi_evaluate_stress: npts %lld", (long long)npts);
+  if (!pe_undecomposed(c))
+    return fail(c, MI_EINVAL, "mi_evaluate_stress: one slab only (an undecomposed mesh)");
+  if (n_outside)
+    *n_outside = 0;
+  if (npts == 0)
+    return MI_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  if (kind == MI_STRESS_AT_RECOVERED)
+    if (const int rc = enqueue_stress(c, model))
+      return rc;
+  // points | sigma | von Mises | principal | directions | cells (int64) | workgroup partials | count | inverted flag
+  const size_t np = size_t(npts), dim = size_t(c->dim), ncomp = dim * (dim + 1) / 2, npart = size_t(mi::field_at_points_partials(npts));
+  if (const int rc = pe_reserve(c, np * (dim + ncomp + 1 + dim + dim * dim + 1) + npart + 2))
+    return rc;
+  double  *d_xyz = c->d_pe, *d_sigma = d_xyz + np * dim, *d_vm = d_sigma + np * ncomp, *d_pr = d_vm + np, *d_dir = d_pr + np * dim;
+  int64_t *d_cell = reinterpret_cast<int64_t *>(d_dir + np * dim * dim);
+  double  *d_part = d_dir + np * dim * dim + np, *d_count = d_part + npart, *d_flag = d_count + 1;
+  HIPCHK(c, hipMemcpyAsync(d_xyz, xyz, np * dim * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  mi::StressPointParams sp{};
+  if (const int rc = pe_mesh_params(c, npts, d_xyz, sp.pe))
+    return rc;
+  sp.pe.cell = d_cell, sp.pe.part = d_part;
+  sp.u     = c->vec(MI_V_TOTAL_DISPLACEMENT); // (MI_L_DISPLACEMENT is the same slot)
+  sp.nodal = kind == MI_STRESS_AT_RECOVERED ? c->d_stress + size_t(c->mesh.nnodes) * 8 : nullptr;
+  sp.kind = kind, sp.model = model;
+  sp.mu = c->mat.mu, sp.kappa = c->kappa, sp.lambda = lame_lambda(c);
+  sp.sigma = d_sigma, sp.von_mises = d_vm;
+  // the raw kind's flag is the call's own; the recovered kind reads the mesh pass's
+  sp.inverted = kind == MI_STRESS_AT_RAW ? d_flag : c->d_sc + SC_ENERGY + 3;
+  if (kind == MI_STRESS_AT_RAW)
+    HIPCHK(c, hipMemsetAsync(d_flag, 0, sizeof(double), c->stream));
+  if (mi::launch_stress_at_points(c->dim, c->degree, c->pe_box == 1, sp, d_count, c->stream))
+    return fail(c, MI_EINVAL, "no stress point kernel for dim=%d degree=%d (or too many points for one launch)", c->dim, c->degree);
+  if (principal || directions)
+    mi::launch_sym_eig_batch(c->dim, npts, d_sigma, d_pr, directions ? d_dir : nullptr, c->stream);
+  HIPCHK(c, hipGetLastError());
+  double h[2] = {0.0, 0.0};
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipMemcpy(h, d_count, sizeof(double), hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(h + 1, sp.inverted, sizeof(double), hipMemcpyDeviceToHost));
+  if (h[1] > 0.0) // the Cauchy stress has no meaning there; the same error as mi_stress_field gives
+    return fail(c, MI_EINVAL, "%s",
+                kind == MI_STRESS_AT_RAW ? "inverted element: det F <= 0 at a requested point (the displacement has folded its cell)" :
+                                           "inverted element: det F <= 0 at a quadrature point (the displacement has folded a cell; the "
+                                           "reference asserts det F > 0, nonlinear_elasticity.cc:935)");
+  HIPCHK(c, hipMemcpy(sigma, d_sigma, np * ncomp * sizeof(double), hipMemcpyDeviceToHost));
+  if (von_mises)
+    HIPCHK(c, hipMemcpy(von_mises, d_vm, np * sizeof(double), hipMemcpyDeviceToHost));
+  if (principal)
+    HIPCHK(c, hipMemcpy(principal, d_pr, np * dim * sizeof(double), hipMemcpyDeviceToHost));
+  if (directions)
+    HIPCHK(c, hipMemcpy(directions, d_dir, np * dim * dim * sizeof(double), hipMemcpyDeviceToHost));
+  if (cell)
+    HIPCHK(c, hipMemcpy(cell, d_cell, np * sizeof(int64_t), hipMemcpyDeviceToHost));
+  if (n_outside)
+    *n_outside = int64_t(h[0]);
+  return MI_OK;
+}
+
+// Principal values [n][dim] (descending) and, where wanted, unit eigenvectors [n][dim][dim] (row k belongs to principal[k]) of n
+// symmetric tensors [n][ncomp] in mi_stress_field's component order, host arrays in and out: the kernel mi_evaluate_stress
+// runs on its points' tensors (sym_eig_batch).  Reads no state and changes none; any context of the tensors' dimension will do
+int mi_principal_stress(mi_ctx *c, int64_t n, const double *sigma, double *principal, double *directions)
+{
+  if (!c)
+    return MI_EINVAL;
+  if (n < 0)
+    return fail(c, MI_EINVAL, "mi_principal_stress: n %lld", (long long)n);
+  if (n == 0)
+    return MI_OK;
+  if (!sigma || !principal)
+    return fail(c, MI_EINVAL, "mi_principal_stress: null argument");
+  HIPCHK(c, hipSetDevice(c->device));
+  const size_t nt = size_t(n), dim = size_t(c->dim), ncomp = dim * (dim + 1) / 2;
+  if (const int rc = pe_reserve(c, nt * (ncomp + dim + dim * dim)))
+    return rc;
+  double *d_sigma = c->d_pe, *d_pr = d_sigma + nt * ncomp, *d_dir = d_pr + nt * dim;
+  HIPCHK(c, hipMemcpyAsync(d_sigma, sigma, nt * ncomp * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  if (mi::launch_sym_eig_batch(c->dim, n, d_sigma, d_pr, directions ? d_dir : nullptr, c->stream))
+    return fail(c, MI_EINVAL, "mi_principal_stress: too many tensors for one launch");
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipMemcpy(principal, d_pr, nt * dim * sizeof(double), hipMemcpyDeviceToHost));
+  if (directions)
+    HIPCHK(c, hipMemcpy(directions, d_dir, nt * dim * dim * sizeof(double), hipMemcpyDeviceToHost));
+  return MI_OK;
+}
+
 // dst's six state vectors := src's fields at dst's nodes: mi_evaluate_points of src at mi_get_node_coords(dst) without the
 // host in between -- the same kernel on dst's node coordinates (uploaded once), its values into scratch on dst, and only when
 // every node was found the copy into dst's vectors and zero_constrained on each.  Nodal interpolation, not a projection
@@ -4009,6 +4134,15 @@ int mi_set_tuning(mi_ctx *c, const char *key, int value)
           m->linear_operator = value;
           continue;
         }
+      if (k == "stress_projection" && (value == 0 || value == 1)) // nodal stress: 0 lumped | 1 consistent (M sigma* = b)
+        {
+          if (value == 1 && c->team->size != 1) // (before any member changes)
+            return fail(c, MI_EINVAL, "\"stress_projection\" 1: the consistent stress recovery exists on an undecomposed mesh only");
+          m->stress_projection = value;
+          if (value == 0)
+            m->stress_projection_its = 0;
+          continue;
+        }
       if (k == "linear_precond" && (value == 0 || value == 1))
         {
           if (value == 1 && c->team->size != 1) // (before any member changes)
@@ -4207,6 +4341,10 @@ int mi_get_tuning(mi_ctx *c, const char *key, int *value)
     *value = mi_linear_mg_n_levels(m) > 1 ? 1 : 0;
   else if (k == "project_chunk_cells")
     *value = m->project_chunk_cells;
+  else if (k == "stress_projection")
+    *value = m->stress_projection;
+  else if (k == "stress_projection_its") // iterations of the last consistent stress solve (0 under "stress_projection" 0; no setter)
+    *value = m->stress_projection_its;
   else if (k == "modes_block_product")
     *value = m->modes_block_product;
   else if (k == "spmm_launches") // launches of the block product sell_spmm so far (no setter)

@@ -254,6 +254,9 @@ struct mi_ctx
   // nodal stress recovery (mi_stress_field), allocated on first use: the accumulator [nnodes][8] with the results behind it
   // (sigma, von Mises, weight); the 1D tables of the linear model's rule QGauss(p + 1) (model MI_STRESS_LINEAR)
   double   *d_stress = nullptr, *d_stress_tab = nullptr;
+  // tuning "stress_projection": 0 the lumped projection sigma_i = b_i / W_i | 1 the consistent one, M sigma* = b with the
+  // unit-density mass of mi_mass_apply, unmasked (one slab only); the iterations of its last solve ("stress_projection_its")
+  int       stress_projection = 0, stress_projection_its = 0;
   // stress error indicator (mi_stress_error), allocated on first use: the cells' [ncells][3] sums, the scratch of their
   // fixed-order sum, eta_K and n_K [ncells] each in lexicographic order, eight result scalars; HostMesh::cell_orig on the device
   double   *d_stress_err = nullptr;

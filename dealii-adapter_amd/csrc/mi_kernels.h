@@ -323,6 +323,20 @@ namespace mi
     double        *part;      // [field_at_points_partials(npts)] points in no cell, per workgroup
   };
 
+  // stress at arbitrary points (see stress_at_points): pe's points, mesh and lattice (its vecs, which, values and gradients are
+  // not read), what to evaluate and where the answers go
+  struct StressPointParams
+  {
+    PointEvalParams pe;
+    const double   *u;     // kind 0: the displacement [nnodes][dim]
+    const double   *nodal; // kind 1: the recovered nodal stress [nnodes][ncomp] (enqueue_stress)
+    int32_t         kind, model; // MI_STRESS_AT_*, MI_STRESS_*
+    double          mu, kappa, lambda;
+    double         *sigma;     // [npts][ncomp]
+    double         *von_mises; // [npts]
+    double         *inverted;  // raised by a point with det F <= 0 (kind 0, model 0)
+  };
+
   // consistent mass (see mass_apply_cells): y += M x for nrhs columns over the cells of one colour, or the diagonal of M
   constexpr int MASS_MAX_RHS = 6;    // MI_MASS_MAX_RHS
   constexpr int MASS_CHUNK   = 1024; // entries of a column per workgroup of the column algebra
@@ -544,6 +558,11 @@ namespace mi
   // sigma[nnodes][dim (dim + 1) / 2] = acc / W, von_mises[nnodes] of that tensor, weight[nnodes] = W
   int  launch_stress(int dim, int degree, int model, const MfParams &p, const StressParams &sp, bool generic, hipStream_t s);
   void launch_stress_finish(int dim, const double *acc, int64_t nnodes, double *sigma, double *von_mises, double *weight, hipStream_t s);
+  // the consistent projection's columns: b [2][nnodes][dim] := the accumulator's sums as components of two vector columns
+  // (stress_pack); sigma, von_mises and weight from the solved columns x and the accumulator's W (stress_unpack)
+  void launch_stress_pack(int dim, const double *acc, int64_t nnodes, double *b, hipStream_t s);
+  void launch_stress_unpack(int dim, const double *x, const double *acc, int64_t nnodes, double *sigma, double *von_mises, double *weight,
+                            hipStream_t s);
   // mi_reactions.  launch_nodal_force: one colour of cells into rp.acc by nodal_force_cells (every element, both models); -1: no
   // kernel for the element.  launch_nodal_force_gather: the face slots of neumann_faces into `load` on every dof of the interface
   // nodes.  launch_nodal_force_finish: terms [4][n] and forces [n] from the accumulator and the load (rho_body: rho b, or zeros).
@@ -568,6 +587,11 @@ namespace mi
   // in closed form; else Newton on the Q1 map); then *n_outside = sum of p.part (finish_sum).  -1: no kernel for the element
   int64_t field_at_points_partials(int64_t npts);
   int     launch_field_at_points(int dim, int degree, bool box, const PointEvalParams &p, double *n_outside, hipStream_t s);
+  // stress at points: stress_at_points<dim, degree, box> over p.pe's points with field_at_points' location, then *n_outside as
+  // above (p.pe.part holds field_at_points_partials(npts) doubles).  launch_sym_eig_batch: principal values [n][dim], descending,
+  // and unit eigenvectors [n][dim][dim] (or null) of n tensors [n][ncomp], sym_eig_batch<dim>.  -1: no kernel / too many for one launch
+  int launch_stress_at_points(int dim, int degree, bool box, const StressPointParams &p, double *n_outside, hipStream_t s);
+  int launch_sym_eig_batch(int dim, int64_t n, const double *sigma, double *principal, double *directions, hipStream_t s);
   // consistent mass and L2 projection.  launch_mass_apply: the cells of one colour by the kernel of (dim, degree) -- mass_apply_q3,
   // mass_apply_q2 (p.conn, p.tab1d, p.cverts / p.cellbox) or mass_apply_cells; generic: mass_apply_cells on 3D Q2 / Q3 too
   // (cross-check); the diagonal is always mass_apply_cells' (-1: no kernel for the element).  Column algebra: mass_chunks(n) workgroups per column; part arrays hold [nrhs][mass_chunks(n)] doubles.

@@ -5506,6 +5506,55 @@ namespace mi
     weight[i] = W;
   }
 
+  // The consistent projection ("stress_projection" 1) solves M sigma*_k = b_k, b the accumulator's sym6 sums, with the VECTOR
+  // mass of mass_apply_*: the scalar fields travel as components of two vector columns [2][nnodes][dim] --
+  // 3D (xx, yy, zz) | (xy, xz, yz), 2D (xx, yy) | (xy, 0).  stress_pack fills the columns from the accumulator, stress_unpack is
+  // stress_finish on the solved columns: sigma, the von Mises stress of the solved tensor, and W from the accumulator.
+  template <int DIM>
+  __global__ __launch_bounds__(256) void stress_pack(const double *__restrict__ acc, const int64_t nnodes, double *__restrict__ b)
+  {
+    const int64_t i = int64_t(blockIdx.x) * 256 + threadIdx.x;
+    if (i >= nnodes)
+      return;
+    double *__restrict__ b0 = b + i * DIM, *__restrict__ b1 = b + (nnodes + i) * DIM;
+    if constexpr (DIM == 3)
+      {
+#pragma unroll
+        for (int k = 0; k < 3; ++k)
+          b0[k] = acc[i * 8 + k], b1[k] = acc[i * 8 + 3 + k];
+      }
+    else
+      b0[0] = acc[i * 8], b0[1] = acc[i * 8 + 1], b1[0] = acc[i * 8 + 3], b1[1] = 0.0;
+  }
+  template <int DIM>
+  __global__ __launch_bounds__(256) void stress_unpack(const double *__restrict__ x, const double *__restrict__ acc, const int64_t nnodes,
+                                                       double *__restrict__ sigma, double *__restrict__ von_mises, double *__restrict__ weight)
+  {
+    const int64_t i = int64_t(blockIdx.x) * 256 + threadIdx.x;
+    if (i >= nnodes)
+      return;
+    const double *__restrict__ x0 = x + i * DIM, *__restrict__ x1 = x + (nnodes + i) * DIM;
+    double s[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    if constexpr (DIM == 3)
+      {
+#pragma unroll
+        for (int k = 0; k < 3; ++k)
+          s[k] = x0[k], s[3 + k] = x1[k];
+#pragma unroll
+        for (int k = 0; k < 6; ++k)
+          sigma[i * 6 + k] = s[k];
+        const double m = (s[0] + s[1] + s[2]) / 3.0, d0 = s[0] - m, d1 = s[1] - m, d2 = s[2] - m;
+        von_mises[i]   = sqrt(1.5 * (d0 * d0 + d1 * d1 + d2 * d2 + 2.0 * (s[3] * s[3] + s[4] * s[4] + s[5] * s[5])));
+      }
+    else
+      {
+        s[0] = x0[0], s[1] = x0[1], s[3] = x1[0];
+        sigma[i * 3] = s[0], sigma[i * 3 + 1] = s[1], sigma[i * 3 + 2] = s[3];
+        von_mises[i] = sqrt(s[0] * s[0] - s[0] * s[1] + s[1] * s[1] + 3.0 * s[3] * s[3]);
+      }
+    weight[i] = acc[i * 8 + 6];
+  }
+
   // ------------------------------------------------------------------ nodal forces, reactions and resultants (mi_reactions)
   // The UNMASKED nodal forces of a state, term by term (every node, constrained dofs too):
   //   internal_i = sum_cells sum_q P(q) grad_X N_i JxW    P = tau(F) F^-T (model 0, qf_cell = QGauss(p + 2), nonlinear_elasticity.cc:74)
@@ -6435,98 +6484,169 @@ namespace mi
     return ok;
   }
 
+  // stage 1 and 2 for the point X: the cell that answers into cur (lattice coordinates), xi and Jinv there; false: X lies in no cell
+  template <int DIM, bool BOX>
+  __device__ __forceinline__ bool pe_locate(const PointEvalParams &p, const double (&X)[DIM], int (&cur)[DIM], double (&xi)[DIM],
+                                            double (&Jinv)[DIM][DIM])
+  {
+    constexpr int POW3 = DIM == 3 ? 27 : 9;
+    int           g[DIM];
+#pragma unroll
+    for (int d = 0; d < DIM; ++d)
+      // (fmax / fmin return the other operand for a NaN: the conversion is always of a number in range)
+      g[d] = cur[d] = int(fmin(fmax(floor((X[d] - p.lo[d]) * p.inv_h[d]), 0.0), double(p.reps[d] - 1)));
+    bool found = false;
+    int  walk = PE_WALK, scan = -1; // scan < 0: walking
+    while (true)
+      {
+        if (pe_point_in_cell<DIM, BOX>(p, cur, X, xi, Jinv))
+          {
+            found = true;
+            break;
+          }
+        if (scan < 0)
+          {
+            bool moved = false;
+#pragma unroll
+            for (int d = 0; d < DIM; ++d)
+              if (xi[d] < -PE_TOL && cur[d] > 0)
+                --cur[d], moved = true;
+              else if (xi[d] > 1.0 + PE_TOL && cur[d] < p.reps[d] - 1)
+                ++cur[d], moved = true;
+            if (moved && walk-- > 0)
+              continue;
+            scan = 0;
+          }
+        bool have = false;
+        while (scan < POW3 && !have)
+          {
+            int k = scan++;
+            have  = k != POW3 / 2; // (the first guess itself was the walk's first cell)
+#pragma unroll
+            for (int d = 0; d < DIM; ++d)
+              {
+                cur[d] = g[d] + k % 3 - 1;
+                k /= 3;
+                have = have && cur[d] >= 0 && cur[d] < p.reps[d];
+              }
+          }
+        if (!have)
+          break;
+      }
+    return found;
+  }
+  // stage 3: the 1D bases and derivatives at xi (the product form of mi::lagrange_eval)
+  template <int DIM, int P>
+  __device__ __forceinline__ void pe_basis(const PointEvalParams &p, const double (&xi)[DIM], double (&N)[DIM][P + 1], double (&dN)[DIM][P + 1])
+  {
+    constexpr int NP1 = P + 1;
+#pragma unroll
+    for (int d = 0; d < DIM; ++d)
+#pragma unroll
+      for (int a = 0; a < NP1; ++a)
+        {
+          double v = 1.0, s = 0.0;
+#pragma unroll
+          for (int m = 0; m < NP1; ++m)
+            if (m != a)
+              v *= xi[d] - p.nodes[m];
+#pragma unroll
+          for (int k = 0; k < NP1; ++k)
+            if (k != a)
+              {
+                double t = 1.0;
+#pragma unroll
+                for (int m = 0; m < NP1; ++m)
+                  if (m != a && m != k)
+                    t *= xi[d] - p.nodes[m];
+                s += t;
+              }
+          N[d][a]  = v * p.rdenom[a];
+          dN[d][a] = s * p.rdenom[a];
+        }
+  }
+  // the answering cell's lexicographic id and the lattice id of its first node (nn0, nn1: nodes per lattice row, rows per plane)
+  template <int DIM, int P>
+  __device__ __forceinline__ void pe_cell_base(const PointEvalParams &p, const int (&cur)[DIM], const int64_t nn0, const int64_t nn1,
+                                               int64_t &cell, int64_t &base)
+  {
+    cell = cur[0] + int64_t(p.reps[0]) * (cur[1] + (DIM == 3 ? int64_t(p.reps[1]) * cur[DIM - 1] : 0));
+    base = int64_t(P) * cur[0] + nn0 * (int64_t(P) * cur[1] + (DIM == 3 ? nn1 * (int64_t(P) * cur[DIM - 1]) : 0));
+  }
+  // stage 4 for one nodal field u[node][NC] of the cell at base: val[c] = sum_a N_a u_a and ge[c][e] = d u_c / d xi_e, row by row,
+  // plane by plane
+  template <int DIM, int P, int NC>
+  __device__ __forceinline__ void pe_sums(const double *__restrict__ u, const int64_t base, const int64_t nn0, const int64_t nn1,
+                                          const double (&N)[DIM][P + 1], const double (&dN)[DIM][P + 1], double (&val)[NC], double (&ge)[NC][DIM])
+  {
+    constexpr int NP1 = P + 1;
+#pragma unroll
+    for (int az = 0; az < (DIM == 3 ? NP1 : 1); ++az)
+      {
+        double pv[NC], px[NC], py[NC]; // the plane's value, d / d xi_0, d / d xi_1
+#pragma unroll
+        for (int c = 0; c < NC; ++c)
+          pv[c] = px[c] = py[c] = 0.0;
+#pragma unroll
+        for (int ay = 0; ay < NP1; ++ay)
+          {
+            double rv[NC], rx[NC];
+#pragma unroll
+            for (int c = 0; c < NC; ++c)
+              rv[c] = rx[c] = 0.0;
+            const double *__restrict__ row = u + (base + nn0 * (ay + nn1 * az)) * NC;
+#pragma unroll
+            for (int ax = 0; ax < NP1; ++ax)
+#pragma unroll
+              for (int c = 0; c < NC; ++c)
+                {
+                  const double uu = row[ax * NC + c];
+                  rv[c] += N[0][ax] * uu;
+                  rx[c] += dN[0][ax] * uu;
+                }
+#pragma unroll
+            for (int c = 0; c < NC; ++c)
+              {
+                pv[c] += N[1][ay] * rv[c];
+                px[c] += N[1][ay] * rx[c];
+                py[c] += dN[1][ay] * rv[c];
+              }
+          }
+#pragma unroll
+        for (int c = 0; c < NC; ++c)
+          if constexpr (DIM == 3)
+            {
+              val[c] += N[DIM - 1][az] * pv[c];
+              ge[c][0] += N[DIM - 1][az] * px[c];
+              ge[c][1] += N[DIM - 1][az] * py[c];
+              ge[c][DIM - 1] += dN[DIM - 1][az] * pv[c];
+            }
+          else
+            val[c] = pv[c], ge[c][0] = px[c], ge[c][1] = py[c];
+      }
+  }
+
   template <int DIM, int P, bool BOX>
   __global__ __launch_bounds__(256) void field_at_points(const PointEvalParams p)
   {
-    constexpr int     NP1 = P + 1, POW3 = DIM == 3 ? 27 : 9;
+    constexpr int     NP1 = P + 1;
     __shared__ double s_red[4];
     const int64_t     i = int64_t(blockIdx.x) * 256 + threadIdx.x;
     double            outside = 0.0;
     if (i < p.npts)
       {
         double X[DIM], xi[DIM], Jinv[DIM][DIM];
-        int    g[DIM], cur[DIM];
+        int    cur[DIM];
 #pragma unroll
         for (int d = 0; d < DIM; ++d)
-          {
-            X[d] = p.xyz[i * DIM + d];
-            // (fmax / fmin return the other operand for a NaN: the conversion is always of a number in range)
-            g[d] = cur[d] = int(fmin(fmax(floor((X[d] - p.lo[d]) * p.inv_h[d]), 0.0), double(p.reps[d] - 1)));
-          }
-        bool found = false;
-        int  walk = PE_WALK, scan = -1; // scan < 0: walking
-        while (true)
-          {
-            if (pe_point_in_cell<DIM, BOX>(p, cur, X, xi, Jinv))
-              {
-                found = true;
-                break;
-              }
-            if (scan < 0)
-              {
-                bool moved = false;
-#pragma unroll
-                for (int d = 0; d < DIM; ++d)
-                  if (xi[d] < -PE_TOL && cur[d] > 0)
-                    --cur[d], moved = true;
-                  else if (xi[d] > 1.0 + PE_TOL && cur[d] < p.reps[d] - 1)
-                    ++cur[d], moved = true;
-                if (moved && walk-- > 0)
-                  continue;
-                scan = 0;
-              }
-            bool have = false;
-            while (scan < POW3 && !have)
-              {
-                int k = scan++;
-                have  = k != POW3 / 2; // (the first guess itself was the walk's first cell)
-#pragma unroll
-                for (int d = 0; d < DIM; ++d)
-                  {
-                    cur[d] = g[d] + k % 3 - 1;
-                    k /= 3;
-                    have = have && cur[d] >= 0 && cur[d] < p.reps[d];
-                  }
-              }
-            if (!have)
-              break;
-          }
-
-        // 1D bases and derivatives at xi (the product form of mi::lagrange_eval)
-        double N[DIM][NP1], dN[DIM][NP1];
+          X[d] = p.xyz[i * DIM + d];
+        const bool found = pe_locate<DIM, BOX>(p, X, cur, xi, Jinv);
+        double     N[DIM][NP1], dN[DIM][NP1];
         if (found)
-          {
-#pragma unroll
-            for (int d = 0; d < DIM; ++d)
-#pragma unroll
-              for (int a = 0; a < NP1; ++a)
-                {
-                  double v = 1.0, s = 0.0;
-#pragma unroll
-                  for (int m = 0; m < NP1; ++m)
-                    if (m != a)
-                      v *= xi[d] - p.nodes[m];
-#pragma unroll
-                  for (int k = 0; k < NP1; ++k)
-                    if (k != a)
-                      {
-                        double t = 1.0;
-#pragma unroll
-                        for (int m = 0; m < NP1; ++m)
-                          if (m != a && m != k)
-                            t *= xi[d] - p.nodes[m];
-                        s += t;
-                      }
-                  N[d][a]  = v * p.rdenom[a];
-                  dN[d][a] = s * p.rdenom[a];
-                }
-          }
+          pe_basis<DIM, P>(p, xi, N, dN);
         int64_t nn0 = int64_t(P) * p.reps[0] + 1, nn1 = int64_t(P) * p.reps[1] + 1, cell = -1, base = 0;
         if (found)
-          {
-            cell = cur[0] + int64_t(p.reps[0]) * (cur[1] + (DIM == 3 ? int64_t(p.reps[1]) * cur[DIM - 1] : 0));
-            base = int64_t(P) * cur[0] + nn0 * (int64_t(P) * cur[1] + (DIM == 3 ? nn1 * (int64_t(P) * cur[DIM - 1]) : 0));
-          }
+          pe_cell_base<DIM, P>(p, cur, nn0, nn1, cell, base);
         else
           outside = 1.0;
         if (p.cell)
@@ -6543,53 +6663,7 @@ namespace mi
                   ge[c][e] = 0.0;
               }
             if (found)
-              {
-                const double *__restrict__ u = p.vecs + int64_t(p.which[w]) * p.n;
-#pragma unroll
-                for (int az = 0; az < (DIM == 3 ? NP1 : 1); ++az)
-                  {
-                    double pv[DIM], px[DIM], py[DIM]; // the plane's value, d / d xi_0, d / d xi_1
-#pragma unroll
-                    for (int c = 0; c < DIM; ++c)
-                      pv[c] = px[c] = py[c] = 0.0;
-#pragma unroll
-                    for (int ay = 0; ay < NP1; ++ay)
-                      {
-                        double rv[DIM], rx[DIM];
-#pragma unroll
-                        for (int c = 0; c < DIM; ++c)
-                          rv[c] = rx[c] = 0.0;
-                        const double *__restrict__ row = u + (base + nn0 * (ay + nn1 * az)) * DIM;
-#pragma unroll
-                        for (int ax = 0; ax < NP1; ++ax)
-#pragma unroll
-                          for (int c = 0; c < DIM; ++c)
-                            {
-                              const double uu = row[ax * DIM + c];
-                              rv[c] += N[0][ax] * uu;
-                              rx[c] += dN[0][ax] * uu;
-                            }
-#pragma unroll
-                        for (int c = 0; c < DIM; ++c)
-                          {
-                            pv[c] += N[1][ay] * rv[c];
-                            px[c] += N[1][ay] * rx[c];
-                            py[c] += dN[1][ay] * rv[c];
-                          }
-                      }
-#pragma unroll
-                    for (int c = 0; c < DIM; ++c)
-                      if constexpr (DIM == 3)
-                        {
-                          val[c] += N[DIM - 1][az] * pv[c];
-                          ge[c][0] += N[DIM - 1][az] * px[c];
-                          ge[c][1] += N[DIM - 1][az] * py[c];
-                          ge[c][DIM - 1] += dN[DIM - 1][az] * pv[c];
-                        }
-                      else
-                        val[c] = pv[c], ge[c][0] = px[c], ge[c][1] = py[c];
-                  }
-              }
+              pe_sums<DIM, P, DIM>(p.vecs + int64_t(p.which[w]) * p.n, base, nn0, nn1, N, dN, val, ge);
             double *__restrict__ vo = p.values + (int64_t(w) * p.npts + i) * DIM;
 #pragma unroll
             for (int c = 0; c < DIM; ++c)
@@ -6614,6 +6688,238 @@ namespace mi
     outside = block_sum<256>(outside, s_red);
     if (threadIdx.x == 0)
       p.part[blockIdx.x] = outside;
+  }
+
+  // ------------------------------------------------------------------ stress at arbitrary points (mi_evaluate_stress, mi_principal_stress)
+  // One thread per point, located exactly as field_at_points locates it (pe_locate, pe_basis: the same cell on shared faces, the
+  // same NaN rule).  kind 0 (raw): grad u_h at X itself from pe_sums on the displacement, then the element's own stress there --
+  // model 0 tau(F)/J by stress_value (a point with det F <= 0 raises *inverted and gets zeros), model 1 linear_stress; it is
+  // discontinuous across cells, the answering cell's value.  kind 1 (recovered): sum_a N_a(xi) sigma*_a of the nodal field
+  // [nnodes][ncomp] that enqueue_stress left, value sums alone.  The von Mises stress is formed from the point's tensor by
+  // stress_finish's formulas.  A point in no cell stores zeros and cell -1 and counts into the workgroup's partial.
+  // The principal values are a kernel of their own (sym_eig_batch), so this one keeps the registers of field_at_points.
+  template <int DIM>
+  __device__ __forceinline__ double von_mises_of(const double (&s)[6])
+  {
+    if constexpr (DIM == 3)
+      {
+        const double m = (s[0] + s[1] + s[2]) / 3.0, d0 = s[0] - m, d1 = s[1] - m, d2 = s[2] - m;
+        return sqrt(1.5 * (d0 * d0 + d1 * d1 + d2 * d2 + 2.0 * (s[3] * s[3] + s[4] * s[4] + s[5] * s[5])));
+      }
+    else
+      return sqrt(s[0] * s[0] - s[0] * s[1] + s[1] * s[1] + 3.0 * s[3] * s[3]);
+  }
+  template <int DIM, int P, bool BOX>
+  __global__ __launch_bounds__(256) void stress_at_points(const StressPointParams sp)
+  {
+    constexpr int          NP1 = P + 1, NCOMP = DIM * (DIM + 1) / 2;
+    const PointEvalParams &p = sp.pe;
+    __shared__ double      s_red[4];
+    const int64_t          i = int64_t(blockIdx.x) * 256 + threadIdx.x;
+    double                 outside = 0.0;
+    if (i < p.npts)
+      {
+        double X[DIM], xi[DIM], Jinv[DIM][DIM];
+        int    cur[DIM];
+#pragma unroll
+        for (int d = 0; d < DIM; ++d)
+          X[d] = p.xyz[i * DIM + d];
+        const bool found = pe_locate<DIM, BOX>(p, X, cur, xi, Jinv);
+        double     N[DIM][NP1], dN[DIM][NP1];
+        if (found)
+          pe_basis<DIM, P>(p, xi, N, dN);
+        int64_t nn0 = int64_t(P) * p.reps[0] + 1, nn1 = int64_t(P) * p.reps[1] + 1, cell = -1, base = 0;
+        if (found)
+          pe_cell_base<DIM, P>(p, cur, nn0, nn1, cell, base);
+        else
+          outside = 1.0;
+        if (p.cell)
+          p.cell[i] = cell;
+        double s[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0}; // xx yy zz xy xz yz
+        if (found && sp.kind == 0)
+          {
+            double val[DIM], ge[DIM][DIM], G[9]; // G: the 3 x 3 embedded d u_c / d X_d
+#pragma unroll
+            for (int c = 0; c < DIM; ++c)
+              {
+                val[c] = 0.0;
+#pragma unroll
+                for (int e = 0; e < DIM; ++e)
+                  ge[c][e] = 0.0;
+              }
+            pe_sums<DIM, P, DIM>(sp.u, base, nn0, nn1, N, dN, val, ge);
+#pragma unroll
+            for (int k = 0; k < 9; ++k)
+              G[k] = 0.0;
+#pragma unroll
+            for (int c = 0; c < DIM; ++c)
+#pragma unroll
+              for (int d = 0; d < DIM; ++d)
+                {
+                  double g = 0.0;
+#pragma unroll
+                  for (int e = 0; e < DIM; ++e)
+                    g += ge[c][e] * Jinv[e][d];
+                  G[c * 3 + d] = g;
+                }
+            if (sp.model == 0)
+              {
+                double J, Jm, rJ;
+                post_cell_finite_strain<DIM>(G, J, Jm, rJ);
+                stress_value<DIM>(G, J, Jm, rJ, sp, 1.0, s);
+              }
+            else
+              linear_stress<DIM>(G, sp.lambda, sp.mu, 1.0, s);
+          }
+        else if (found)
+          {
+            double val[NCOMP], ge[NCOMP][DIM];
+#pragma unroll
+            for (int c = 0; c < NCOMP; ++c)
+              {
+                val[c] = 0.0;
+#pragma unroll
+                for (int e = 0; e < DIM; ++e)
+                  ge[c][e] = 0.0;
+              }
+            pe_sums<DIM, P, NCOMP>(sp.nodal, base, nn0, nn1, N, dN, val, ge);
+            if constexpr (DIM == 3)
+              {
+#pragma unroll
+                for (int k = 0; k < 6; ++k)
+                  s[k] = val[k];
+              }
+            else
+              s[0] = val[0], s[1] = val[1], s[3] = val[2];
+          }
+        double *__restrict__ so = sp.sigma + i * NCOMP;
+        if constexpr (DIM == 3)
+          {
+#pragma unroll
+            for (int k = 0; k < 6; ++k)
+              so[k] = s[k];
+          }
+        else
+          so[0] = s[0], so[1] = s[1], so[2] = s[3];
+        sp.von_mises[i] = von_mises_of<DIM>(s);
+      }
+    outside = block_sum<256>(outside, s_red);
+    if (threadIdx.x == 0)
+      p.part[blockIdx.x] = outside;
+  }
+
+  // Eigenvalues and unit eigenvectors of n symmetric tensors [n][ncomp] (xx yy zz xy xz yz; 2D xx yy xy), one thread per tensor:
+  // principal [n][dim] in descending order, directions [n][dim][dim] with row k the eigenvector of principal[k] (or null).
+  //   3D: cyclic Jacobi, SYM_EIG_SWEEPS sweeps over the pairs (0,1), (0,2), (1,2); a pair whose entry is exactly zero is skipped
+  //       (the thread's own converged test), nothing else depends on the data: every lane runs every sweep.
+  //   2D: lambda = m +- r with m = (xx + yy) / 2, d = (xx - yy) / 2, r = hypot(d, xy); the first vector (d + r, xy) for d >= 0,
+  //       (xy, r - d) otherwise, over its hypot, the second its quarter turn; r = 0 gives the coordinate axes.
+  // Ties keep the order of the diagonal (strict comparisons in the sort).  Sign: the component of largest magnitude of every
+  // vector is positive, the first such on ties.  Plain arithmetic in a fixed order: a call repeats bit by bit, and a degenerate
+  // tensor gets the basis these statements give it, always the same one.
+  constexpr int SYM_EIG_SWEEPS = 8;
+  template <int PI, int QI, int RI>
+  __device__ __forceinline__ void jacobi_rotate(double (&A)[3][3], double (&V)[3][3])
+  {
+    const double apq = A[PI][QI];
+    if (apq != 0.0)
+      {
+        const double theta = (A[QI][QI] - A[PI][PI]) / (2.0 * apq);
+        // (theta^2 overflows to inf, or theta is inf: t = 0, the entry is below the diagonal's rounding and is dropped)
+        const double t = copysign(1.0, theta) / (fabs(theta) + sqrt(theta * theta + 1.0));
+        const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
+        A[PI][PI] -= t * apq;
+        A[QI][QI] += t * apq;
+        A[PI][QI] = A[QI][PI] = 0.0;
+        const double arp = A[RI][PI], arq = A[RI][QI];
+        A[RI][PI] = A[PI][RI] = c * arp - s * arq;
+        A[RI][QI] = A[QI][RI] = s * arp + c * arq;
+#pragma unroll
+        for (int k = 0; k < 3; ++k)
+          {
+            const double vkp = V[k][PI], vkq = V[k][QI];
+            V[k][PI] = c * vkp - s * vkq;
+            V[k][QI] = s * vkp + c * vkq;
+          }
+      }
+  }
+  template <int DIM>
+  __global__ __launch_bounds__(256) void sym_eig_batch(const int64_t n, const double *__restrict__ sigma, double *__restrict__ principal,
+                                                       double *__restrict__ directions)
+  {
+    constexpr int NCOMP = DIM * (DIM + 1) / 2;
+    const int64_t i = int64_t(blockIdx.x) * 256 + threadIdx.x;
+    if (i >= n)
+      return;
+    double lam[DIM], E[DIM][DIM]; // E[k]: the eigenvector of lam[k]
+    if constexpr (DIM == 3)
+      {
+        const double *__restrict__ a = sigma + i * NCOMP;
+        double A[3][3] = {{a[0], a[3], a[4]}, {a[3], a[1], a[5]}, {a[4], a[5], a[2]}};
+        double V[3][3] = {{1.0, 0.0, 0.0}, {0.0, 1.0, 0.0}, {0.0, 0.0, 1.0}};
+        for (int sweep = 0; sweep < SYM_EIG_SWEEPS; ++sweep)
+          {
+            jacobi_rotate<0, 1, 2>(A, V);
+            jacobi_rotate<0, 2, 1>(A, V);
+            jacobi_rotate<1, 2, 0>(A, V);
+          }
+#pragma unroll
+        for (int k = 0; k < 3; ++k)
+          {
+            lam[k] = A[k][k];
+#pragma unroll
+            for (int c = 0; c < 3; ++c)
+              E[k][c] = V[c][k];
+          }
+      }
+    else
+      {
+        const double xx = sigma[i * NCOMP], yy = sigma[i * NCOMP + 1], xy = sigma[i * NCOMP + 2];
+        const double m = 0.5 * (xx + yy), d = 0.5 * (xx - yy), r = hypot(d, xy);
+        lam[0] = m + r, lam[1] = m - r;
+        double x = 1.0, y = 0.0;
+        if (r > 0.0)
+          {
+            const double ex = d >= 0.0 ? d + r : xy, ey = d >= 0.0 ? xy : r - d, h = hypot(ex, ey);
+            x = ex / h, y = ey / h;
+          }
+        E[0][0] = x, E[0][1] = y, E[1][0] = -y, E[1][1] = x;
+      }
+    // descending, ties in the order they stand (the 2D pair is ordered: r >= 0)
+    if constexpr (DIM == 3)
+      {
+#pragma unroll
+        for (int pass = 0; pass < 3; ++pass)
+          {
+            const int lo = pass == 1 ? 1 : 0;
+            if (lam[lo] < lam[lo + 1])
+              {
+                const double t = lam[lo];
+                lam[lo] = lam[lo + 1], lam[lo + 1] = t;
+#pragma unroll
+                for (int c = 0; c < 3; ++c)
+                  {
+                    const double e = E[lo][c];
+                    E[lo][c] = E[lo + 1][c], E[lo + 1][c] = e;
+                  }
+              }
+          }
+      }
+#pragma unroll
+    for (int k = 0; k < DIM; ++k)
+      {
+        principal[i * DIM + k] = lam[k];
+        double big = E[k][0];
+#pragma unroll
+        for (int c = 1; c < DIM; ++c)
+          if (fabs(E[k][c]) > fabs(big))
+            big = E[k][c];
+        const double sg = big < 0.0 ? -1.0 : 1.0;
+        if (directions)
+#pragma unroll
+          for (int c = 0; c < DIM; ++c)
+            directions[(i * DIM + k) * DIM + c] = sg * E[k][c];
+      }
   }
 
   // ------------------------------------------------------------------ consistent mass and L2 projection (mi_mass_apply, mi_mass_solve, mi_state_project)
@@ -10632,6 +10938,27 @@ namespace mi
     else
       hipLaunchKernelGGL(stress_finish<2>, dim3(grid), dim3(256), 0, s, acc, nnodes, sigma, von_mises, weight);
   }
+  void launch_stress_pack(int dim, const double *acc, int64_t nnodes, double *b, hipStream_t s)
+  {
+    if (nnodes <= 0)
+      return;
+    const int grid = int((nnodes + 255) / 256);
+    if (dim == 3)
+      hipLaunchKernelGGL(stress_pack<3>, dim3(grid), dim3(256), 0, s, acc, nnodes, b);
+    else
+      hipLaunchKernelGGL(stress_pack<2>, dim3(grid), dim3(256), 0, s, acc, nnodes, b);
+  }
+  void launch_stress_unpack(int dim, const double *x, const double *acc, int64_t nnodes, double *sigma, double *von_mises, double *weight,
+                            hipStream_t s)
+  {
+    if (nnodes <= 0)
+      return;
+    const int grid = int((nnodes + 255) / 256);
+    if (dim == 3)
+      hipLaunchKernelGGL(stress_unpack<3>, dim3(grid), dim3(256), 0, s, x, acc, nnodes, sigma, von_mises, weight);
+    else
+      hipLaunchKernelGGL(stress_unpack<2>, dim3(grid), dim3(256), 0, s, x, acc, nnodes, sigma, von_mises, weight);
+  }
   int launch_nodal_force(int dim, int degree, int model, const MfParams &p, const ReactionParams &rp, bool generic, hipStream_t s)
   {
     if (rp.cell_count <= 0)
@@ -10751,6 +11078,40 @@ namespace mi
     if (rc == 0)
       hipLaunchKernelGGL(finish_sum, dim3(1), dim3(256), 0, s, p.part, int(grid), n_outside);
     return rc;
+  }
+  template <int DIM, bool BOX>
+  static int stress_at_points_degree(int degree, int grid, const StressPointParams &p, hipStream_t s)
+  {
+    switch (degree)
+      {
+        case 1: hipLaunchKernelGGL((stress_at_points<DIM, 1, BOX>), dim3(grid), dim3(256), 0, s, p); return 0;
+        case 2: hipLaunchKernelGGL((stress_at_points<DIM, 2, BOX>), dim3(grid), dim3(256), 0, s, p); return 0;
+        case 3: hipLaunchKernelGGL((stress_at_points<DIM, 3, BOX>), dim3(grid), dim3(256), 0, s, p); return 0;
+        case 4: hipLaunchKernelGGL((stress_at_points<DIM, 4, BOX>), dim3(grid), dim3(256), 0, s, p); return 0;
+      }
+    return -1;
+  }
+  int launch_stress_at_points(int dim, int degree, bool box, const StressPointParams &p, double *n_outside, hipStream_t s)
+  {
+    const int64_t grid = field_at_points_partials(p.pe.npts);
+    if (grid <= 0 || grid > INT32_MAX || (dim != 2 && dim != 3))
+      return -1;
+    const int rc = dim == 3 ? (box ? stress_at_points_degree<3, true>(degree, int(grid), p, s) : stress_at_points_degree<3, false>(degree, int(grid), p, s))
+                            : (box ? stress_at_points_degree<2, true>(degree, int(grid), p, s) : stress_at_points_degree<2, false>(degree, int(grid), p, s));
+    if (rc == 0)
+      hipLaunchKernelGGL(finish_sum, dim3(1), dim3(256), 0, s, p.pe.part, int(grid), n_outside);
+    return rc;
+  }
+  int launch_sym_eig_batch(int dim, int64_t n, const double *sigma, double *principal, double *directions, hipStream_t s)
+  {
+    const int64_t grid = (n + 255) / 256;
+    if (grid <= 0 || grid > INT32_MAX || (dim != 2 && dim != 3))
+      return -1;
+    if (dim == 3)
+      hipLaunchKernelGGL(sym_eig_batch<3>, dim3(int(grid)), dim3(256), 0, s, n, sigma, principal, directions);
+    else
+      hipLaunchKernelGGL(sym_eig_batch<2>, dim3(int(grid)), dim3(256), 0, s, n, sigma, principal, directions);
+    return 0;
   }
   // consistent mass and L2 projection
   int launch_mass_apply(int dim, int degree, const MfParams &p, const MassParams &mp, bool generic, hipStream_t s)

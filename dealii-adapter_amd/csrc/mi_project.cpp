@@ -114,6 +114,31 @@ namespace mi_detail
     return MI_OK;
   }
 
+  // The consistent stress recovery (tuning "stress_projection" 1), the end of enqueue_stress: the accumulator's sums b_k(i) =
+  // sum N_i sigma_k JxW are packed into two vector columns, M x = b is solved unmasked by the solve above to
+  // STRESS_PROJECTION_TOL within STRESS_PROJECTION_MAX_IT iterations, and the columns are unpacked into sigma, von Mises (of the
+  // solved tensor) and W behind the accumulator, where stress_finish leaves the lumped field.  Scratch of the call, freed on return
+  constexpr double STRESS_PROJECTION_TOL    = 1e-13;
+  constexpr int    STRESS_PROJECTION_MAX_IT = 1000;
+  static int stress_consistent_solve(mi_ctx *c)
+  {
+    const size_t nn = size_t(c->mesh.nnodes), n = size_t(c->n), ncomp = size_t(c->dim * (c->dim + 1) / 2);
+    DevBuf       w;
+    HIPCHK(c, hipMalloc(&w.p, 4 * n * sizeof(double)));
+    double *b = w.d(), *x = b + 2 * n, *out = c->d_stress + nn * 8;
+    mi::launch_stress_pack(c->dim, c->d_stress, int64_t(nn), b, c->stream);
+    HIPCHK(c, hipGetLastError());
+    int       its = 0;
+    const int rc  = mass_solve_device(c, 2, 0, b, x, STRESS_PROJECTION_TOL, STRESS_PROJECTION_MAX_IT, &its, nullptr, nullptr);
+    c->stress_projection_its = its;
+    if (rc)
+      return rc;
+    mi::launch_stress_unpack(c->dim, x, c->d_stress, int64_t(nn), out, out + nn * ncomp, out + nn * (ncomp + 1), c->stream);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(c->stream)); // (the columns are freed on return)
+    return MI_OK;
+  }
+
   // b [n_which][n(dst)] on the device := the load of src's vectors which[] on the composite rule; src_sq [n_which] and the count of
   // points on the host.  dst's stream carries dst's kernels, src's stream the point evaluation, as mi_state_transfer
   static int project_load_device(mi_ctx *dst, mi_ctx *src, int n_which, const int *which, int sub, double *d_b, double *src_sq,

@@ -147,6 +147,33 @@ namespace mi
             "mi_evaluate_points");
       return n_outside;
     }
+    // the stress of the committed state at npts points of the reference configuration (mi_evaluate_stress; model as
+    // stress_field, kind MI_STRESS_AT_RAW / MI_STRESS_AT_RECOVERED): sigma [npts][dim (dim + 1) / 2] and von Mises [npts]; returns
+    // the number of points in no cell (zeros there), or -1 on a team (emulated slabs or RCCL), where the library provides none
+    // (one slab only); any other failure throws
+    int64_t evaluate_stress(int model, int kind, int dim, const std::vector<double> &xyz, std::vector<double> &sigma,
+                            std::vector<double> &von_mises) const
+    {
+      int team = 1, rccl = 0;
+      check(mi_comm_info(ctx_, &team, &rccl), "mi_comm_info");
+      if (team > 1 || rccl > 0)
+        return -1;
+      const size_t npts = xyz.size() / size_t(dim);
+      sigma.assign(npts * size_t(dim * (dim + 1) / 2), 0.0);
+      von_mises.assign(npts, 0.0);
+      int64_t n_outside = 0;
+      check(mi_evaluate_stress(ctx_, model, kind, int64_t(npts), xyz.data(), sigma.data(), von_mises.data(), nullptr, nullptr, nullptr,
+                               &n_outside),
+            "mi_evaluate_stress");
+      return n_outside;
+    }
+    // principal values [n][dim], descending, of the n tensors sigma [n][dim (dim + 1) / 2] (mi_principal_stress)
+    void principal_stress(int dim, const std::vector<double> &sigma, std::vector<double> &principal) const
+    {
+      const size_t n = sigma.size() / size_t(dim * (dim + 1) / 2);
+      principal.assign(n * size_t(dim), 0.0);
+      check(mi_principal_stress(ctx_, int64_t(n), sigma.data(), principal.data(), nullptr), "mi_principal_stress");
+    }
     // this device's six state vectors := the L2 projection of src's fields onto its space (mi_state_project: the load on the
     // composite rule sub^dim x QGauss(p + 2) per cell, the consistent-mass solve on the free dofs, device to device); the
     // iteration count, residual and the two integrals of |w|^2 into info where wanted.  false on a team (emulated slabs or

@@ -5,6 +5,10 @@
 // are skipped.  A row of probes.log: the time, then for every probe in the file's order its displacement (dim numbers) and its
 // velocity (dim numbers), 17 significant digits -- the finite-element fields themselves (Device::evaluate_points), so a probe
 // that is no node (FSI3's point A, the middle of the flap's end: a cell centre of the 18 x 3 flap) needs no post-processing.
+// MI_PROBES_STRESS=raw|recovered appends to every probe's columns its stress (dim (dim + 1) / 2 numbers, xx yy zz xy xz yz or
+// xx yy xy) and von Mises stress (Device::evaluate_stress: the element's own stress at the point, or the recovered nodal field
+// interpolated; the linear executable's model is MI_STRESS_LINEAR, the nonlinear one's MI_STRESS_NEOHOOKE; the header line says
+// which); any other value is a start-up error, and without the variable the file is what it was.
 // A probe outside the mesh is a start-up error that names the point.  On a team the library evaluates no points: said once, no
 // log is written.  Without the variable nothing is read, written or printed.
 #pragma once
@@ -24,12 +28,22 @@ namespace mi
   class ProbeLog
   {
   public:
-    // which_u, which_v: the model's displacement and velocity (MI_V_* / MI_L_*)
-    void open(const Device &dev, int dim, int which_u, int which_v)
+    // which_u, which_v: the model's displacement and velocity (MI_V_* / MI_L_*); stress_model: MI_STRESS_NEOHOOKE / MI_STRESS_LINEAR
+    void open(const Device &dev, int dim, int which_u, int which_v, int stress_model)
     {
       const char *file = std::getenv("MI_PROBES");
       if (!file || !*file)
         return;
+      if (const char *kind = std::getenv("MI_PROBES_STRESS"))
+        {
+          if (std::string(kind) == "raw")
+            stress_kind_ = MI_STRESS_AT_RAW;
+          else if (std::string(kind) == "recovered")
+            stress_kind_ = MI_STRESS_AT_RECOVERED;
+          else
+            throw std::runtime_error(std::string("MI_PROBES_STRESS: '") + kind + "' is neither raw nor recovered");
+          stress_model_ = stress_model;
+        }
       std::ifstream in(file);
       if (!in)
         throw std::runtime_error(std::string("MI_PROBES: cannot read ") + file);
@@ -67,8 +81,15 @@ namespace mi
             throw std::runtime_error(msg.str());
           }
       out_.open("probes.log");
-      out_ << "# t, then displacement and velocity (" << dim << " numbers each) of each of " << cells.size() << " probes of " << file
-           << ", per completed time window\n";
+      if (stress_kind_ < 0)
+        out_ << "# t, then displacement and velocity (" << dim << " numbers each) of each of " << cells.size() << " probes of " << file
+             << ", per completed time window\n";
+      else
+        out_ << "# t, then displacement and velocity (" << dim << " numbers each), the "
+             << (stress_kind_ == MI_STRESS_AT_RAW ? "raw" : "recovered") << " stress of model " << stress_model_
+             << (stress_model_ == MI_STRESS_LINEAR ? " (linear)" : " (neo-Hookean Cauchy)") << " (" << dim * (dim + 1) / 2
+             << " numbers: " << (dim == 3 ? "xx yy zz xy xz yz" : "xx yy xy") << ") and its von Mises stress of each of "
+             << cells.size() << " probes of " << file << ", per completed time window\n";
     }
     bool active() const { return out_.is_open(); }
     void write(double t)
@@ -77,18 +98,30 @@ namespace mi
         return;
       std::vector<double> values;
       dev_->evaluate_points(which_, dim_, xyz_, values);
-      const size_t npts = xyz_.size() / size_t(dim_), d = size_t(dim_);
+      const size_t npts = xyz_.size() / size_t(dim_), d = size_t(dim_), ncomp = d * (d + 1) / 2;
+      std::vector<double> sigma, von_mises;
+      if (stress_kind_ >= 0)
+        dev_->evaluate_stress(stress_model_, stress_kind_, dim_, xyz_, sigma, von_mises);
       out_ << std::setprecision(17) << t;
       for (size_t k = 0; k < npts; ++k)
-        for (size_t w = 0; w < 2; ++w)
-          for (size_t c = 0; c < d; ++c)
-            out_ << ' ' << values[(w * npts + k) * d + c];
+        {
+          for (size_t w = 0; w < 2; ++w)
+            for (size_t c = 0; c < d; ++c)
+              out_ << ' ' << values[(w * npts + k) * d + c];
+          if (stress_kind_ >= 0)
+            {
+              for (size_t c = 0; c < ncomp; ++c)
+                out_ << ' ' << sigma[k * ncomp + c];
+              out_ << ' ' << von_mises[k];
+            }
+        }
       out_ << '\n' << std::flush;
     }
 
   private:
     const Device       *dev_ = nullptr;
     int                 dim_ = 0;
+    int                 stress_kind_ = -1, stress_model_ = 0; // MI_PROBES_STRESS=raw|recovered: MI_STRESS_AT_*, or -1 without it
     std::vector<int>    which_;
     std::vector<double> xyz_;
     std::ofstream       out_;

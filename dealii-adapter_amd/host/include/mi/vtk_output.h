@@ -18,6 +18,10 @@
 // reaction_model >= 0 (the executables' MI_VTK_REACTIONS=1): the point-data vector `reaction_force` behind whatever the stress
 // switches add (before the cell data) -- the out-of-balance force of mi_reactions on the constrained dofs of the patch point's
 // node, zero elsewhere: the force the support exerts there.  Without it the file is byte for byte what it was.
+// principal_model >= 0 (the executables' MI_VTK_PRINCIPAL=1): point data `principal_stress`, dim components per point in
+// descending order, behind the stress arrays (before reaction_force) -- the principal values of that nodal stress field
+// (mi_principal_stress on the nodal tensors; the field is computed for this alone where MI_VTK_STRESS is not set).  The
+// directions are not written.  Without it the file is byte for byte what it was.
 #pragma once
 #include <cmath>
 #include <fstream>
@@ -119,7 +123,8 @@ namespace mi
   // team collectives (ncclAllReduce under RCCL), which hang or pair up with the wrong collective when only one rank
   // enters them.  write = false (ranks > 0): take part in the gathers, write nothing.
   inline void write_vtk(const Device &dev, int dim, int p, const int reps[3], const std::string &path, bool write = true,
-                        bool higher_order = true, int stress_model = -1, int stress_error_model = -1, int reaction_model = -1)
+                        bool higher_order = true, int stress_model = -1, int stress_error_model = -1, int reaction_model = -1,
+                        int principal_model = -1)
   {
     const int64_t       nn = mi_n_nodes(dev.ctx()), n = mi_n_dofs(dev.ctx());
     std::vector<double> xyz(size_t(nn) * dim), u(size_t(n), 0.0);
@@ -132,6 +137,18 @@ namespace mi
         have_stress = dev.stress_field(stress_model, dim, sig, vm);
         if (!have_stress && write)
           std::cout << "\t MI_VTK_STRESS: mi_stress_field runs in one process only, no stress is written on an RCCL team" << std::endl;
+      }
+    std::vector<double> principal;
+    bool                have_principal = false;
+    if (principal_model >= 0)
+      {
+        std::vector<double> psig, pvm;
+        have_principal = principal_model == stress_model ? have_stress : dev.stress_field(principal_model, dim, psig, pvm);
+        if (have_principal)
+          dev.principal_stress(dim, principal_model == stress_model ? sig : psig, principal);
+        else if (write)
+          std::cout << "\t MI_VTK_PRINCIPAL: mi_stress_field runs in one process only, no principal stress is written on an RCCL team"
+                    << std::endl;
       }
     std::vector<double> eta_cell;
     bool                have_error = false;
@@ -179,7 +196,7 @@ namespace mi
 
     std::vector<double> pts(size_t(ncells) * npc * 3, 0.0), disp(size_t(ncells) * npc * 3, 0.0),
       strain(size_t(ncells) * npc * dim * dim, 0.0);
-    std::vector<int64_t> node((size_t)npc, 0), pnode(have_stress || have_react ? size_t(ncells) * npc : 0, 0); // pnode: the node of every patch point
+    std::vector<int64_t> node((size_t)npc, 0), pnode(have_stress || have_react || have_principal ? size_t(ncells) * npc : 0, 0); // pnode: the node of every patch point
     for (int64_t c = 0; c < ncells; ++c)
       {
         const int ci[3] = {int(c % rr[0]), int((c / rr[0]) % rr[1]), int(c / (int64_t(rr[0]) * rr[1]))};
@@ -251,7 +268,7 @@ namespace mi
                     gx[i][j] += gu[i][k] * Fi[k][j]; // grad_x u: gradient in the (displaced) output mapping
                 }
             const size_t q = size_t(c) * npc + a;
-            if (have_stress || have_react)
+            if (have_stress || have_react || have_principal)
               pnode[q] = node[size_t(a)];
             for (int d = 0; d < dim; ++d)
               {
@@ -333,6 +350,18 @@ namespace mi
         out << "SCALARS von_mises double 1\nLOOKUP_TABLE default\n";
         for (int64_t i = 0; i < npts; ++i)
           out << vm[size_t(pnode[size_t(i)])] << '\n';
+      }
+    if (have_principal)
+      {
+        out << "SCALARS principal_stress double " << dim << "\nLOOKUP_TABLE default\n";
+        for (int64_t i = 0; i < npts; ++i)
+          {
+            const double *l = &principal[size_t(pnode[size_t(i)]) * dim];
+            out << l[0] << ' ' << l[1];
+            if (dim == 3)
+              out << ' ' << l[2];
+            out << '\n';
+          }
       }
     if (have_react)
       {

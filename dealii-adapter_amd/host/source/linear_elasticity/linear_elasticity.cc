@@ -196,7 +196,8 @@ namespace Linear_Elasticity
                   !std::getenv("MI_VTK_LINEAR_CELLS"), // higher-order cells as the reference (:1222-1225); the switch: linear sub-cells
                   std::getenv("MI_VTK_STRESS") && std::atoi(std::getenv("MI_VTK_STRESS")) != 0 ? MI_STRESS_LINEAR : -1, // + nodal stress
                   std::getenv("MI_VTK_STRESS_ERROR") && std::atoi(std::getenv("MI_VTK_STRESS_ERROR")) != 0 ? MI_STRESS_LINEAR : -1, // + eta_K
-                  std::getenv("MI_VTK_REACTIONS") && std::atoi(std::getenv("MI_VTK_REACTIONS")) != 0 ? MI_STRESS_LINEAR : -1); // + reaction force
+                  std::getenv("MI_VTK_REACTIONS") && std::atoi(std::getenv("MI_VTK_REACTIONS")) != 0 ? MI_STRESS_LINEAR : -1, // + reaction force
+                  std::getenv("MI_VTK_PRINCIPAL") && std::atoi(std::getenv("MI_VTK_PRINCIPAL")) != 0 ? MI_STRESS_LINEAR : -1); // + principal stresses
     timer.leave_subsection("Output results");
   }
 
@@ -206,7 +207,7 @@ namespace Linear_Elasticity
   {
     make_grid();
     setup_system();
-    probes.open(*device, dim, MI_L_DISPLACEMENT, MI_L_VELOCITY);
+    probes.open(*device, dim, MI_L_DISPLACEMENT, MI_L_VELOCITY, MI_STRESS_LINEAR);
     reactions.open(*device, MI_STRESS_LINEAR);
     output_results();
 

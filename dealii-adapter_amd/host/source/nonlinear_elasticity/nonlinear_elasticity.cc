@@ -52,7 +52,7 @@ namespace Nonlinear_Elasticity
   {
     make_grid();
     system_setup();
-    probes.open(*device, dim, MI_V_TOTAL_DISPLACEMENT, MI_V_VELOCITY);
+    probes.open(*device, dim, MI_V_TOTAL_DISPLACEMENT, MI_V_VELOCITY, MI_STRESS_NEOHOOKE);
     reactions.open(*device, MI_STRESS_NEOHOOKE);
     output_results();
 
@@ -486,7 +486,8 @@ namespace Nonlinear_Elasticity
                   !std::getenv("MI_VTK_LINEAR_CELLS"), // higher-order cells as the reference (:1222-1225); the switch: linear sub-cells
                   std::getenv("MI_VTK_STRESS") && std::atoi(std::getenv("MI_VTK_STRESS")) != 0 ? MI_STRESS_NEOHOOKE : -1, // + nodal stress
                   std::getenv("MI_VTK_STRESS_ERROR") && std::atoi(std::getenv("MI_VTK_STRESS_ERROR")) != 0 ? MI_STRESS_NEOHOOKE : -1, // + eta_K
-                  std::getenv("MI_VTK_REACTIONS") && std::atoi(std::getenv("MI_VTK_REACTIONS")) != 0 ? MI_STRESS_NEOHOOKE : -1); // + reaction force
+                  std::getenv("MI_VTK_REACTIONS") && std::atoi(std::getenv("MI_VTK_REACTIONS")) != 0 ? MI_STRESS_NEOHOOKE : -1, // + reaction force
+                  std::getenv("MI_VTK_PRINCIPAL") && std::atoi(std::getenv("MI_VTK_PRINCIPAL")) != 0 ? MI_STRESS_NEOHOOKE : -1); // + principal stresses
     std::cout << "\t Output written to " << name.str() << " \n" << std::endl;
     timer.leave_subsection("Output results");
   }

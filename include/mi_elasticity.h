@@ -339,6 +339,44 @@ int mi_reactions(mi_ctx *ctx, int model, const double *about /* [dim] or NULL = 
  *   MI_EINVAL. */
 int mi_evaluate_points(mi_ctx *ctx, int n_which, const int *which, int64_t npts, const double *xyz, double *values,
                        double *gradients, int64_t *cell, int64_t *n_outside);
+/* Stress at arbitrary points: the stress gauge.  npts points X of the REFERENCE configuration, located exactly as
+ * mi_evaluate_points locates them -- INSIDE, OUTSIDE, FOUND, the choice on shared faces and the NaN rule are its definitions,
+ * the same device functions.  model as mi_stress_field (MI_STRESS_NEOHOOKE / MI_STRESS_LINEAR), the COMMITTED state.
+ * MI_STRESS_AT_RAW: sigma_h(X), the stress of the element that answers, from grad u_h at X itself.  Model 0 sigma = tau(F)/J of
+ *   the compressible neo-Hookean material at F = I + d u / d X, u = MI_V_TOTAL_DISPLACEMENT; model 1 sigma = lambda tr(eps) I +
+ *   2 mu eps, u = MI_L_DISPLACEMENT (the same slot).  Discontinuous across cells: on a shared face the value is the answering
+ *   cell's, and `cell` says which.  A requested point with det F <= 0 (model 0): MI_EINVAL "inverted element", the arrays hold no
+ *   result, the context works afterwards.  No mesh pass, no scratch beyond the point buffers.
+ * MI_STRESS_AT_RECOVERED: sigma*(X) = sum_a N_a(xi(X)) sigma*_a, the nodal field mi_stress_field(model) returns (under tuning
+ *   "stress_projection" 0 or 1), interpolated with the element's basis.  Runs that whole-mesh pass first, with its folded-cell
+ *   error; continuous across cells; at a node it is the nodal value.
+ * sigma [npts][ncomp] (required) in mi_stress_field's component order; von_mises [npts] or NULL, formed from the POINT's tensor by
+ * mi_stress_field's formulas; principal [npts][dim] or NULL: the eigenvalues of that tensor in DESCENDING order; directions
+ * [npts][dim][dim] or NULL: row k the unit eigenvector of principal[k] (see mi_principal_stress); cell [npts] or NULL;
+ * n_outside or NULL.  An outside point gets cell -1 and zeros (its directions: the coordinate axes), is counted, and the call
+ * returns MI_OK.  npts = 0: MI_OK, no array is written.
+ * The contract of mi_evaluate_points: modifies no state vector, record, matrix, hierarchy, counter or timing -- a following
+ * mi_newmark_step / mi_linear_step returns the bits it would have returned without the call; needs no matrix ("fine_level" 0
+ * and 1, after a "linear_operator" 1 or 2 set-up); 2D and 3D, degrees 1 to 4; two calls return the same bits.  Undecomposed
+ * contexts only: MI_EINVAL "one slab only".  A NULL ctx, xyz or sigma, a bad model or kind, npts < 0: MI_EINVAL. */
+#define MI_STRESS_AT_RAW       0
+#define MI_STRESS_AT_RECOVERED 1
+int mi_evaluate_stress(mi_ctx *ctx, int model, int kind, int64_t npts, const double *xyz /* [npts][dim] */,
+                       double *sigma /* [npts][ncomp] */, double *von_mises /* [npts] or NULL */,
+                       double *principal /* [npts][dim] descending, or NULL */, double *directions /* [npts][dim][dim] or NULL */,
+                       int64_t *cell /* or NULL */, int64_t *n_outside /* or NULL */);
+/* Principal stresses of n symmetric tensors, host arrays in and out (as mi_block_gram): sigma [n][ncomp] in mi_stress_field's
+ * component order, principal [n][dim] in descending order, directions [n][dim][dim] or NULL with row k the unit eigenvector of
+ * principal[k].  The kernel mi_evaluate_stress runs on its points' tensors, one thread per tensor: 3D the cyclic Jacobi method
+ * on the 3 x 3 matrix with a fixed count of 8 sweeps; 2D the closed form m +- hypot(d, xy), m = (xx + yy) / 2, d = (xx - yy) / 2.
+ * Sign: the component of largest magnitude of each eigenvector is positive, the first such on ties.  Equal eigenvalues keep the
+ * order their diagonal entries had, and a degenerate tensor (hydrostatic, zero) gets an orthonormal basis -- a definition, always
+ * the same one, not a property of the tensor.  Two calls return the same bits.  Measured against the tensor (not against another
+ * solver's vectors, which depend on the gaps): |sigma v - lambda v|_2 and |V^T V - I| are a few units of round-off times
+ * |sigma|_F.  Reads and modifies no state; any context of the tensors' dimension, teams included.
+ * n = 0: MI_OK.  A NULL ctx, sigma or principal, n < 0: MI_EINVAL. */
+int mi_principal_stress(mi_ctx *ctx, int64_t n, const double *sigma /* [n][ncomp] */, double *principal /* [n][dim] */,
+                        double *directions /* [n][dim][dim] or NULL */);
 /* State transfer between meshes: dst's six state vectors MI_V_TOTAL_DISPLACEMENT .. MI_V_ACCELERATION_OLD := src's fields at
  * dst's nodes, device to device.  BY DEFINITION mi_evaluate_points of src at mi_get_node_coords(dst) for the six vectors, written
  * into dst's vectors with every dof that dst flags constrained (mi_get_constrained) set to exactly 0 -- the same kernel, the same
@@ -805,6 +843,21 @@ int mi_set_profiling(mi_ctx *ctx, int enable);
  *  spmv_as_smoother     0 | 1 | 2                  tests: mi_spmv / mi_bench_spmv apply the smoother's form of the operator -
  *                                                  | 2: mi_spmv applies M^-1, one V-cycle of the last solve's hierarchy
  *  mg_scale_lmax_percent 10..400                   tests: spoil the eigenvalue estimates once                           -
+ *  stress_projection    0 | 1                      nodal stress sigma*: 0 the lumped projection b_i / W_i, every bit as without -
+ *                                                  the key | 1 the CONSISTENT one, the L2 best approximation: the colour passes
+ *                                                  leave b_k(i) = sum N_i sigma_k JxW and W_i, then M sigma*_k = b_k is solved
+ *                                                  with the unit-density consistent mass of mi_mass_apply, unmasked, the ncomp
+ *                                                  scalar fields packed as components of two vector columns (3D xx yy zz |
+ *                                                  xy xz yz, 2D xx yy | xy 0), by mi_mass_solve's device solve to the fixed
+ *                                                  tolerance 1e-13 in at most 1,000 iterations; von Mises from the solved
+ *                                                  tensor, weight stays W_i.  Governs mi_stress_field, mi_stress_error,
+ *                                                  mi_evaluate_stress (RECOVERED) and the VTK stress output alike (one nodal
+ *                                                  array).  Not converged: MI_ENOCONV_LIN from the entry point that asked.
+ *                                                  A DEFINITION for model 1: b is integrated on QGauss(p+1), M on QGauss(p+2)
+ *                                                  (model 0: both on QGauss(p+2), where sigma* minimises mi_stress_error's eta
+ *                                                  over all nodal fields).  On a team the setter returns MI_EINVAL and the key
+ *                                                  stays 0.  Read-backs "stress_projection" and "stress_projection_its"
+ *                                                  (iterations of the last solve; 0 under key 0)
  *
  * Further switches of the experiments build only (read at creation; diagnostics): MI_MG_NU, MI_MG_NU_COARSE, MI_MG_RATIO, MI_MG_KIND,
  * MI_MG_BLOCK, MI_MG_COARSEST, MI_MG_DENSE, MI_MG_FACTOR, MI_MG_SAFETY, MI_MG_POWER_ITS,
