@@ -96,6 +96,10 @@ class ProjectInfo(C.Structure):
                 ("src_sq", C.c_double * 6), ("dst_sq", C.c_double * 6)]
 
 
+class ExplicitInfo(C.Structure):
+    _fields_ = [("steps_done", C.c_int32), ("inverted_step", C.c_int32), ("dt", C.c_double), ("kinetic_lumped", C.c_double)]
+
+
 class MiError(RuntimeError):
     def __init__(self, code, msg, partial=None):
         super().__init__("mi_elasticity error %d: %s" % (code, msg))
@@ -206,6 +210,12 @@ def lib():
         L.mi_dense_sym_eig.argtypes = [C.c_int, dp, dp, dp, dp]
         L.mi_tangent_modes.argtypes = [vp, C.c_int, C.c_double, C.c_int, dp, dp, dp, C.POINTER(C.c_int)]
         for f in ("mi_linear_modes", "mi_tangent_modes", "mi_block_gram", "mi_block_combine", "mi_dense_sym_eig"):
+            getattr(L, f).restype = C.c_int
+        L.mi_explicit_setup.argtypes = [vp, C.c_double, C.c_int]
+        L.mi_explicit_run.argtypes = [vp, C.c_int, C.POINTER(ExplicitInfo)]
+        L.mi_explicit_get_mass.argtypes = [vp, dp]
+        L.mi_explicit_stable_dt.argtypes = [vp, C.c_int, dp, dp]
+        for f in ("mi_explicit_setup", "mi_explicit_run", "mi_explicit_get_mass", "mi_explicit_stable_dt"):
             getattr(L, f).restype = C.c_int
         L.mi_set_profiling.argtypes = [vp, C.c_int]
         L.mi_get_timings.argtypes = [vp, C.POINTER(Timings)]
@@ -771,6 +781,35 @@ class Context:
             raise MiError(rc, lib().mi_last_error(self.h).decode(), partial=out)
         self._chk(rc)
         return out
+
+    # ---- explicit central differences of the nonlinear model (mi_explicit_*)
+    def explicit_setup(self, dt, init_acceleration=True):
+        """the lumped masses and the step of the following explicit_run calls; init_acceleration: V_A, V_A_OLD := minv F(u) of the
+        committed state (V_DELTA := 0), else the state stays as it is"""
+        self._chk(lib().mi_explicit_setup(self.h, float(dt), int(bool(init_acceleration))))
+
+    def explicit_run(self, n, check=True):
+        """n explicit steps on the device, one read-back: dict(rc, steps_done, inverted_step (-1: none), dt, kinetic_lumped).  A step
+        whose force pass finds det F <= 0 ends the run: MiError (code MI_EINVAL, .partial that dict), or with check=False the dict"""
+        info = ExplicitInfo()
+        rc = lib().mi_explicit_run(self.h, int(n), C.byref(info))
+        out = dict(rc=rc, steps_done=info.steps_done, inverted_step=info.inverted_step, dt=info.dt, kinetic_lumped=info.kinetic_lumped)
+        if rc != MI_OK and check:
+            raise MiError(rc, lib().mi_last_error(self.h).decode(), partial=out)
+        return out
+
+    def explicit_mass(self):
+        """the lumped masses [n]: rho times the row sums of the consistent mass of mass_apply"""
+        m = np.zeros(self.n)
+        self._chk(lib().mi_explicit_get_mass(self.h, _dp(m)))
+        return m
+
+    def explicit_stable_dt(self, krylov_steps=40):
+        """(lambda_max, dt_crit): the largest Ritz value of krylov_steps Lanczos steps for K_T phi = lambda M_L phi at the committed
+        state -- a lower bound of lambda_max -- and 2 / sqrt of it; multiply dt_crit by a safety factor"""
+        lam, dt = C.c_double(0), C.c_double(0)
+        self._chk(lib().mi_explicit_stable_dt(self.h, int(krylov_steps), C.byref(lam), C.byref(dt)))
+        return lam.value, dt.value
 
     def linear_apply(self, which, x):
         """y = K x (0), M x (1), A x (2) through the device kernels of the current set-up; 3: one V-cycle of its multigrid"""

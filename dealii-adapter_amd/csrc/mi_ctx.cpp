@@ -977,7 +977,9 @@ namespace mi_detail
   // the enqueue part of assemble_system for one slab (no host synchronisation).
   // residual_only: system_rhs alone (same numbers as the full pass); the tangent, its diagonal and the SpMV-side
   // copy keep the state of the last full assembly
-  int enqueue_assembly(mi_ctx *c, bool residual_only)
+  // acc: the acceleration field of the inertia term (null: MI_V_ACCELERATION, as ever; mi_explicit_run hands a zero vector)
+  // force_only (with acc a zero vector, residual_only): the one-launch point passes run their instances without the acceleration
+  int enqueue_assembly(mi_ctx *c, bool residual_only, const double *acc, bool force_only)
   {
     // tangent_matrix = 0 (:1054) is implied: the first cell that touches a block stores instead of adding
     // (system_rhs = 0, :1055 -- except where residual_gather writes every entry of it: the one-launch point pass of 3D Q2,
@@ -989,6 +991,8 @@ namespace mi_detail
     HIPCHK(c, hipMemsetAsync(c->d_sc + SC_INVERTED, 0, sizeof(double), c->stream));
     mi::AsmParams p  = asm_params(c);
     p.residual_only  = residual_only ? 1 : 0;
+    if (acc)
+      p.acc = acc;
     // matrix-free fine level: the tangent pass IS the residual kernel, handed the record pointers (it then writes the
     // state its residual was formed at); the diagonal blocks follow from the records below
     const bool mf_tangent = c->mf_fine && !residual_only;
@@ -1012,7 +1016,7 @@ namespace mi_detail
         p.cell_count = int32_t(c->mesh.ncells);
         p.res_slots  = c->d_mf_yc; // (the product's slot array: no product is in flight during an assembly)
         p.slot_dst   = c->d_mf_dst;
-        mi::launch_point_pass_slots(p, c->stream);
+        mi::launch_point_pass_slots(p, c->stream, force_only && residual_only);
         mi::launch_residual_gather(c->d_mf_yc, c->d_mf_slot_base, c->d_mf_src, c->d_cmask, c->vec(MI_V_SYSTEM_RHS),
                                    int64_t(c->mesh.nnodes) * 3, c->stream);
       }
@@ -1025,7 +1029,7 @@ namespace mi_detail
         for (int d = 0; d < 3; ++d)
           pp.body[d] = p.body[d];
         pp.rho = p.rho, pp.rec = residual_only ? nullptr : c->d_qrec_q3, pp.inverted = p.inverted;
-        mi::launch_mf_point_pass_q3(f, pp, int32_t(c->mesh.ncells), c->stream);
+        mi::launch_mf_point_pass_q3(f, pp, int32_t(c->mesh.ncells), c->stream, force_only && residual_only);
         mi::launch_residual_gather(c->d_mf_yc, c->d_mf_slot_base, c->d_mf_src, c->d_cmask, c->vec(MI_V_SYSTEM_RHS),
                                    int64_t(c->mesh.nnodes) * 3, c->stream);
       }
@@ -2276,7 +2280,7 @@ namespace mi_detail
                     c->d_pred[0][0], c->d_pred[0][1], c->d_pred[1][0], c->d_pred[1][1], c->d_pred[2][0], c->d_pred[2][1], c->d_pred[3][0], c->d_pred[3][1],
                     c->d_pred_saved[0][0], c->d_pred_saved[0][1], c->d_pred_saved[1][0], c->d_pred_saved[1][1], c->d_pred_saved[2][0],
                     c->d_pred_saved[2][1], c->d_pred_saved[3][0], c->d_pred_saved[3][1], c->d_energy, c->d_energy_box,
-                    c->d_stress, c->d_stress_tab, c->d_stress_err, c->d_cell_orig, c->d_cell_pos, c->d_pe, c->d_node_xyz, c->d_react};
+                    c->d_stress, c->d_stress_tab, c->d_stress_err, c->d_cell_orig, c->d_cell_pos, c->d_pe, c->d_node_xyz, c->d_react, c->d_explicit};
     for (void *p : ptrs)
       if (p)
         hipFree(p);
@@ -4093,6 +4097,11 @@ int mi_set_tuning(mi_ctx *c, const char *key, int value)
           m->face_slots = value;
           continue;
         }
+      if (k == "explicit_force_only" && (value == 0 || value == 1)) // mi_explicit_*: force-only instances of the one-launch passes (1) | zero vector
+        {
+          m->explicit_force_only = value;
+          continue;
+        }
       if (k == "modes_block_product" && (value == 0 || value == 1)) // mi_tangent_modes: block product where eligible (1) | column by column
         {
           m->modes_block_product = value;
@@ -4345,6 +4354,8 @@ int mi_get_tuning(mi_ctx *c, const char *key, int *value)
     *value = m->stress_projection;
   else if (k == "stress_projection_its") // iterations of the last consistent stress solve (0 under "stress_projection" 0; no setter)
     *value = m->stress_projection_its;
+  else if (k == "explicit_force_only")
+    *value = m->explicit_force_only;
   else if (k == "modes_block_product")
     *value = m->modes_block_product;
   else if (k == "spmm_launches") // launches of the block product sell_spmm so far (no setter)
@@ -4650,3 +4661,5 @@ int mi_bench_assemble(mi_ctx *c, int reps, double *ms_per_assembly)
 // consistent mass and L2 projection (mi_mass_apply, mi_mass_solve, mi_project_load, mi_state_project): part of this translation
 // unit, as csrc/mi_modes.cpp is of mi_linear.cpp -- it uses enqueue_point_eval and the helpers above
 #include "mi_project.cpp"
+// explicit central differences (mi_explicit_setup, mi_explicit_run, mi_explicit_get_mass, mi_explicit_stable_dt): likewise
+#include "mi_explicit.cpp"

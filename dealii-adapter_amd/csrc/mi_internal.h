@@ -280,6 +280,15 @@ struct mi_ctx
   // nodal forces and reactions (mi_reactions), allocated on first use: accumulator [nnodes][8] | load [n] | terms [4][n] |
   // forces [n] | face slots of its own (the size of d_face_slots) | chunk results | the result (mi::REACT_NOUT); reads d_node_xyz
   double   *d_react      = nullptr;
+  // explicit central differences (mi_explicit_setup; mi_explicit.cpp), allocated by the first set-up: lumped masses [n] | their
+  // inverses, 0 on constrained dofs [n] | a zero vector, the force pass's acceleration field [n] | the partials of the kinetic
+  // sum [MAX_PART] | four words: the first folded step of a run (0: none), sum m v^2, two scalars of the Lanczos.
+  // explicit_dt: the step of the last set-up (0: none yet)
+  double   *d_explicit   = nullptr;
+  double    explicit_dt  = 0.0;
+  // tuning "explicit_force_only": 1 (default) the force passes of mi_explicit_* run the instances of the one-launch point passes
+  // that leave the acceleration out (3D Q2 level, 3D Q3 level under "point_pass_q3" 1; the same bits) | 0 every pass reads the zero vector
+  int       explicit_force_only = 1;
   uint16_t *d_off   = nullptr;
   uint8_t  *d_cmask = nullptr;
   double   *h_pinned = nullptr; // pinned host scratch (scalars, flags, interface buffer)
@@ -396,7 +405,7 @@ namespace mi_detail
   int  create_member(Team &T, const mi_mesh_desc *md, const mi_material_desc *mat, const mi_newmark_desc *nm, int rank,
                      mi_ctx **out);
   void destroy_team(Team *T);
-  int  enqueue_assembly(mi_ctx *c, bool residual_only = false);
+  int  enqueue_assembly(mi_ctx *c, bool residual_only = false, const double *acc = nullptr, bool force_only = false);
   // y = M x for the device blocks x, y [nrhs][n] (nrhs <= mi::MASS_MAX_RHS; diag: y [n] = the diagonal of M), the unit-density
   // consistent mass of mi_mass_apply, enqueued on c's stream (mi_project.cpp)
   int  enqueue_mass_apply(mi_ctx *c, int nrhs, int masked, bool diag, const double *x, double *y);

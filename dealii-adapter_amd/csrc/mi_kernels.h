@@ -479,6 +479,18 @@ namespace mi
     int64_t n;
   };
 
+  // explicit central differences (explicit_start, explicit_advance): the state and the force of one slab, the inverted word
+  // of the force pass and the word that keeps the first folded step of a run (0: none), both doubles on the device
+  struct ExplicitParams
+  {
+    double       *u, *v, *a, *du;
+    const double *F, *minv, *inverted;
+    double       *stop;
+    double        dt;
+    int64_t       n;
+    int           step; // 1-based step of the run (explicit_advance)
+  };
+
   // index-space transfer between two lattices (see lattice_interp / lattice_restrict)
   struct LatticeParams
   {
@@ -545,7 +557,7 @@ namespace mi
   // ... the level's point pass in one launch ("point_pass_q3" 1; see mf_point_pass_q3): the residual of every cell into its slots
   // (MfParams::yc / dst / slot_inline, the product's), from u + du and the acceleration; with pp.rec set, the records of
   // launch_mf_records_q3 into it as well (null: the residual-only pass).  launch_residual_gather then sums the slots into system_rhs
-  void launch_mf_point_pass_q3(const MfParams &p, const MfPointPass &pp, int32_t cell_count, hipStream_t s);
+  void launch_mf_point_pass_q3(const MfParams &p, const MfPointPass &pp, int32_t cell_count, hipStream_t s, bool force_only = false);
   // energy diagnostics: every cell's strain energy, kinetic energy and body-force potential into e.cell_e, by the kernel of
   // (dim, degree) -- energy_q3, energy_q2 (p.conn, p.tab1d, p.cverts / p.cellbox) or energy_cells; generic: energy_cells on
   // 3D Q2 / Q3 too (cross-check).  -1: no kernel for the element.  launch_energy_sum: the cells' numbers in a fixed order into
@@ -639,7 +651,7 @@ namespace mi
   void launch_mf_linear_diag_blk_q2(const MfParams &p, const MfLinearOp &op, int32_t cell_count, double *slots6, hipStream_t s);
   // the matrix-free fine level's point pass over ALL cells in one launch (assemble_q2sf<true> with the residual into slots:
   // AsmParams::res_slots / slot_dst; cell_begin = 0, cell_count = all) and the sum of the slots into system_rhs
-  void launch_point_pass_slots(const AsmParams &p, hipStream_t s);
+  void launch_point_pass_slots(const AsmParams &p, hipStream_t s, bool force_only = false); // force_only: the acceleration is zero and not read
   void launch_residual_gather(const double *slots3, const int32_t *slot_base, const int32_t *slot_src, const uint8_t *cmask, double *rhs,
                               int64_t ndofs, hipStream_t s);
   void launch_mf_diag_gather(const double *slots6, const int32_t *slot_base, const int32_t *slot_src, const uint8_t *cmask,
@@ -716,6 +728,17 @@ namespace mi
   void launch_newmark_acceleration(const NewmarkParams &p, hipStream_t s);
   void launch_newmark_finish(const NewmarkParams &p, hipStream_t s);
   void launch_vec_add(double *y, const double *x, int64_t n, hipStream_t s);
+  // explicit central differences: lumped masses from w = M 1; the first du of a run; one committed step + the next du; the sum of
+  // m v^2 into *out through `grid` fixed-order partials (commit: *_OLD := new, du := 0 as well); the Lanczos update
+  // y := minv y - alpha q - beta qprev (qprev may be null)
+  void launch_explicit_masses(int dim, const double *w, const uint8_t *cmask, double rho, double *mass, double *minv, int64_t n, hipStream_t s);
+  void launch_explicit_start(const ExplicitParams &p, hipStream_t s);
+  void launch_explicit_advance(const ExplicitParams &p, hipStream_t s);
+  void launch_explicit_finish(bool commit, const NewmarkParams &p, const double *mass, double *du, double *part, int grid, double *out,
+                              hipStream_t s);
+  void launch_weighted_sq(const double *mass, const double *x, int64_t n, double *part, int grid, double *out, hipStream_t s); // *out = sum m x^2
+  void launch_lanczos_update(double *y, const double *minv, const double *q, const double *qprev, double alpha, double beta, int64_t n,
+                             hipStream_t s);
   void launch_gather_nodes(int dim, const double *v, const int32_t *nodes, int n, double *out, hipStream_t s);
   void launch_scatter_nodes(int dim, double *v, const int32_t *nodes, int n, const double *in, hipStream_t s);
   // ---- block-vector algebra of the eigensolver (mi_linear_modes): column-major blocks, column j at base + j * ld

@@ -789,10 +789,14 @@ namespace mi
     return q2sf_pair_base(i, j) + (i == j ? q2sf_sym6(k, l) : k * 3 + l);
   }
 
-  template <bool RES_ONLY, bool RSLOTS = false>
+  // NOACC (the force pass of mi_explicit_run, "explicit_force_only" 1): the acceleration field is identically zero -- its gather
+  // and its interpolation to the points are compiled out, accq stays +0.0, which is what interpolating zeros gives: the same bits
+  // as the pass reading a zero vector
+  template <bool RES_ONLY, bool RSLOTS = false, bool NOACC = false>
   __global__ __launch_bounds__(RES_ONLY ? 64 : 256, RES_ONLY ? 4 : 3) void assemble_q2sf(AsmParams prm)
   {
     static_assert(RES_ONLY || !RSLOTS, "the residual goes to slots in the residual-only form alone");
+    static_assert(!NOACC || (RES_ONLY && RSLOTS), "the force-only form exists for the one-launch point pass alone");
     constexpr int NPC = 27, FS = 66, NF = 46; // field stride (padded: fields of different ij on different banks), fields
     constexpr int PS = 20, PW = 9 * PS, AO = 552;
     constexpr int MASSF = NF - 1;                       // the mass field
@@ -1004,14 +1008,15 @@ namespace mi
               {
                 const int64_t g    = int64_t(node) * 3 + c;
                 s0[c * NPC + lane] = prm.u[g] + prm.du[g]; // get_total_solution, :580-588
-                accn[c]            = prm.acc[g];
+                if constexpr (!NOACC)
+                  accn[c] = prm.acc[g];
               }
           }
         // ---- two interpolations to the points: pass 0 = u (gradients), pass 1 = acceleration (values; only the residual
         // needs it: the tangent form takes it after barrier (1), beside the contractions, the residual-only form has no
         // contractions to put it beside and takes it here)
         interp(0);
-        if constexpr (RES_ONLY)
+        if constexpr (RES_ONLY && !NOACC)
           {
             stage_acc();
             interp(1);
@@ -4202,7 +4207,10 @@ namespace mi
   constexpr int MFQ3_VX = 480, MFQ3_VA = 672, MFQ3_VB = 912, MFQ3_VM = 4 * MFQ3_QS;
   static_assert(MFQ3_VX >= 2 * 240 && MFQ3_VB + 300 <= MFQ3_R0, "the value pass lies behind A and inside R0");
   static_assert(MFQ3_VM >= MFQ3_VX && MFQ3_VM + 3 * MFQ3_QS <= MFQ3_VB, "the point values lie over X' and A' and below B'");
-  template <bool BOX>
+  // NOACC (the force pass of mi_explicit_run, "explicit_force_only" 1): the acceleration field is identically zero and its gather
+  // is compiled out -- the second wave stages 0 - body without a load.  The value pass E1'-E3' stays: the body force rides on it
+  // (acc - body is interpolated as one quantity), and dropping it would change the bits of the body term
+  template <bool BOX, bool NOACC = false>
   __global__ __launch_bounds__(MFQ3_NT, BOX ? 3 : 2) void mf_point_pass_q3(MfParams prm, MfPointPass pp)
   {
     __shared__ double R0[MFQ3_R0], R1[MFQ3_R1], sT[40];
@@ -4225,7 +4233,7 @@ namespace mi
         {
 #pragma unroll
           for (int c = 0; c < 3; ++c)
-            R0[MFQ3_VX + c * MFQ3_NPC + a] = pp.acc[int64_t(node) * 3 + c] - pp.body[c];
+            R0[MFQ3_VX + c * MFQ3_NPC + a] = (NOACC ? 0.0 : pp.acc[int64_t(node) * 3 + c]) - pp.body[c];
         }
     }
     __syncthreads();
@@ -10299,6 +10307,140 @@ namespace mi
       }
   }
 
+  // ---- explicit central differences (mi_explicit_setup / mi_explicit_run), velocity-Verlet form with the lumped mass.
+  // Every sum of the scheme is spelled with its rounding, so that a step taken inside a run and one that begins a run give the
+  // same bits: du = fma(dt^2 / 2, a, dt v);  a' = minv F;  v' = fma(dt / 2, a + a', v);  u' = u + du.
+  __device__ __forceinline__ double explicit_predict(double dt, double hdt2, double v, double a)
+  {
+    return __fma_rn(hdt2, a, __dmul_rn(dt, v));
+  }
+  // two consecutive doubles: one 16-byte access where the array's base allows it (al), else two 8-byte ones (vector `which` of
+  // the context's block starts at which * n doubles: an odd n leaves the odd vectors on an 8-byte boundary)
+  __device__ __forceinline__ double2 explicit_ld2(const double *p, int64_t i, bool al)
+  {
+    if (al)
+      return *reinterpret_cast<const double2 *>(p + i);
+    return make_double2(p[i], p[i + 1]);
+  }
+  __device__ __forceinline__ void explicit_st2(double *p, int64_t i, bool al, double2 x)
+  {
+    if (al)
+      *reinterpret_cast<double2 *>(p + i) = x;
+    else
+      p[i] = x.x, p[i + 1] = x.y;
+  }
+  __device__ __forceinline__ bool explicit_al16(const void *p)
+  {
+    return (reinterpret_cast<uintptr_t>(p) & 15) == 0;
+  }
+  // lumped masses from the row sums w = M 1 of the unit-density consistent mass: m = rho w on every dof, minv = 1 / m on free
+  // dofs and 0 on constrained ones
+  __global__ __launch_bounds__(256) void explicit_masses(int dim, const double *__restrict__ w, const uint8_t *__restrict__ cmask, double rho,
+                                                         double *__restrict__ mass, double *__restrict__ minv, int64_t n)
+  {
+    const int64_t i = int64_t(blockIdx.x) * 256 + threadIdx.x;
+    if (i >= n)
+      return;
+    const bool   con = (cmask[i / dim] >> int(i % dim)) & 1;
+    const double m   = rho * w[i];
+    mass[i]          = m;
+    minv[i]          = con ? 0.0 : 1.0 / m;
+  }
+  // the first du of a run: du = dt v + dt^2 / 2 a of the committed state; clears the word that keeps the folded step
+  __global__ __launch_bounds__(256) void explicit_start(ExplicitParams p)
+  {
+    const int64_t i = 2 * (int64_t(blockIdx.x) * 256 + threadIdx.x);
+    if (i == 0)
+      *p.stop = 0.0;
+    if (i >= p.n)
+      return;
+    const double hdt2 = 0.5 * p.dt * p.dt;
+    if (i + 1 < p.n)
+      {
+        const double2 v = explicit_ld2(p.v, i, explicit_al16(p.v)), a = explicit_ld2(p.a, i, explicit_al16(p.a));
+        explicit_st2(p.du, i, explicit_al16(p.du), make_double2(explicit_predict(p.dt, hdt2, v.x, a.x), explicit_predict(p.dt, hdt2, v.y, a.y)));
+      }
+    else
+      p.du[i] = explicit_predict(p.dt, hdt2, p.v[i], p.a[i]);
+  }
+  // Step `step` of a run, after the force pass at u + du wrote F and the pass's inverted word: commit it (a' = minv F, v, u) and
+  // predict the du of the next step, two dofs per thread.  The one decision: when the pass found det F <= 0, or an earlier step
+  // of the call did, nothing is written.  Every thread reads both words at entry.  The word that keeps the folded step is
+  // written (by one thread) only when the pass's word is set -- a launch in which every thread returns whatever it read there.
+  __global__ __launch_bounds__(256) void explicit_advance(ExplicitParams p)
+  {
+    const bool folded = *p.inverted > 0.0, stopped = *p.stop != 0.0;
+    if (folded || stopped)
+      {
+        if (folded && !stopped && blockIdx.x == 0 && threadIdx.x == 0)
+          *p.stop = double(p.step);
+        return;
+      }
+    const int64_t i = 2 * (int64_t(blockIdx.x) * 256 + threadIdx.x);
+    if (i >= p.n)
+      return;
+    const double hdt = 0.5 * p.dt, hdt2 = 0.5 * p.dt * p.dt;
+    if (i + 1 < p.n)
+      {
+        const bool    al_u = explicit_al16(p.u), al_v = explicit_al16(p.v), al_a = explicit_al16(p.a), al_d = explicit_al16(p.du);
+        const double2 F = explicit_ld2(p.F, i, explicit_al16(p.F)), mi = explicit_ld2(p.minv, i, explicit_al16(p.minv));
+        const double2 du = explicit_ld2(p.du, i, al_d), u = explicit_ld2(p.u, i, al_u), v = explicit_ld2(p.v, i, al_v),
+                      a = explicit_ld2(p.a, i, al_a);
+        const double2 an = make_double2(__dmul_rn(mi.x, F.x), __dmul_rn(mi.y, F.y));
+        const double2 vn = make_double2(__fma_rn(hdt, __dadd_rn(a.x, an.x), v.x), __fma_rn(hdt, __dadd_rn(a.y, an.y), v.y));
+        explicit_st2(p.u, i, al_u, make_double2(__dadd_rn(u.x, du.x), __dadd_rn(u.y, du.y)));
+        explicit_st2(p.v, i, al_v, vn);
+        explicit_st2(p.a, i, al_a, an);
+        explicit_st2(p.du, i, al_d, make_double2(explicit_predict(p.dt, hdt2, vn.x, an.x), explicit_predict(p.dt, hdt2, vn.y, an.y)));
+      }
+    else
+      {
+        const double an = __dmul_rn(p.minv[i], p.F[i]);
+        const double vn = __fma_rn(hdt, __dadd_rn(p.a[i], an), p.v[i]);
+        p.u[i]          = __dadd_rn(p.u[i], p.du[i]);
+        p.v[i]          = vn;
+        p.a[i]          = an;
+        p.du[i]         = explicit_predict(p.dt, hdt2, vn, an);
+      }
+  }
+  // partials of sum_i m_i v_i^2 over [0, n) in a fixed order (one per workgroup, chunks as dot_partials); COMMIT: the end of a
+  // run as well -- the *_OLD vectors := the new ones, du := 0
+  template <bool COMMIT>
+  __global__ __launch_bounds__(256) void explicit_finish(NewmarkParams p, const double *__restrict__ mass, double *du, double *part)
+  {
+    __shared__ double s_red[4];
+    const int64_t per = (p.n + gridDim.x - 1) / gridDim.x;
+    const int64_t i0 = blockIdx.x * per, i1 = imin64(p.n, i0 + per);
+    double        s  = 0.0;
+    for (int64_t i = i0 + threadIdx.x; i < i1; i += 256)
+      {
+        const double v = p.v[i];
+        s += mass[i] * v * v;
+        if (COMMIT)
+          {
+            p.u_old[i] = p.u[i];
+            p.v_old[i] = v;
+            p.a_old[i] = p.a[i];
+            du[i]      = 0.0;
+          }
+      }
+    s = block_sum<256>(s, s_red);
+    if (threadIdx.x == 0)
+      part[blockIdx.x] = s;
+  }
+  // Lanczos step of mi_explicit_stable_dt in the lumped-mass inner product: w = minv y - alpha q - beta q_prev, written over y
+  __global__ __launch_bounds__(256) void lanczos_update(double *y, const double *__restrict__ minv, const double *__restrict__ q,
+                                                        const double *__restrict__ qprev, double alpha, double beta, int64_t n)
+  {
+    const int64_t i = int64_t(blockIdx.x) * 256 + threadIdx.x;
+    if (i >= n)
+      return;
+    double w = minv[i] * y[i] - alpha * q[i];
+    if (qprev)
+      w -= beta * qprev[i];
+    y[i] = w;
+  }
+
   // ---- linear model (linear_elasticity.cc:378-454, :579-586)
   // f = F + body; rhs = theta dt f + (1-theta) dt F_old; F_old = f; v_old = v; d_old = d;
   // w = theta (1-theta) dt^2 v + dt d      (so that  M v - K w  completes the right-hand side with 2 SpMVs)
@@ -10777,13 +10919,16 @@ namespace mi
     else
       hipLaunchKernelGGL((mf_gather<false, true>), dim3(grid), dim3(256), 0, s, MfSlots<false>{p}, ndofs, dotv, partials, own0, own_n);
   }
-  void launch_point_pass_slots(const AsmParams &p, hipStream_t s)
+  void launch_point_pass_slots(const AsmParams &p, hipStream_t s, bool force_only)
   {
     if (p.cell_count <= 0)
       return;
     AsmParams q = p;
     q.xcd_chunk = (p.cell_count + 7) / 8;
-    hipLaunchKernelGGL((assemble_q2sf<true, true>), dim3(q.xcd_chunk * 8), dim3(64), 0, s, q);
+    if (force_only)
+      hipLaunchKernelGGL((assemble_q2sf<true, true, true>), dim3(q.xcd_chunk * 8), dim3(64), 0, s, q);
+    else
+      hipLaunchKernelGGL((assemble_q2sf<true, true>), dim3(q.xcd_chunk * 8), dim3(64), 0, s, q);
   }
   void launch_residual_gather(const double *slots3, const int32_t *slot_base, const int32_t *slot_src, const uint8_t *cmask, double *rhs,
                               int64_t ndofs, hipStream_t s)
@@ -10844,11 +10989,12 @@ namespace mi
     else
       hipLaunchKernelGGL(kern, dim3(cell_count), dim3(MFQ3_NT), 0, s, p);
   }
-  void launch_mf_point_pass_q3(const MfParams &p, const MfPointPass &pp, int32_t cell_count, hipStream_t s)
+  void launch_mf_point_pass_q3(const MfParams &p, const MfPointPass &pp, int32_t cell_count, hipStream_t s, bool force_only)
   {
     if (cell_count <= 0)
       return;
-    auto *kern = p.cellbox ? mf_point_pass_q3<true> : mf_point_pass_q3<false>;
+    auto *kern = force_only ? (p.cellbox ? mf_point_pass_q3<true, true> : mf_point_pass_q3<false, true>) :
+                              (p.cellbox ? mf_point_pass_q3<true> : mf_point_pass_q3<false>);
     hipLaunchKernelGGL(kern, dim3(cell_count), dim3(MFQ3_NT), 0, s, p, pp);
   }
   // the generic post-processing kernels (energy_cells, stress_cells, stress_error_cells): threads per workgroup by element.
@@ -11569,6 +11715,39 @@ namespace mi
   void launch_vec_add(double *y, const double *x, int64_t n, hipStream_t s)
   {
     hipLaunchKernelGGL(vec_add, dim3(int((n + 255) / 256)), dim3(256), 0, s, y, x, n);
+  }
+  void launch_explicit_masses(int dim, const double *w, const uint8_t *cmask, double rho, double *mass, double *minv, int64_t n, hipStream_t s)
+  {
+    hipLaunchKernelGGL(explicit_masses, dim3(int((n + 255) / 256)), dim3(256), 0, s, dim, w, cmask, rho, mass, minv, n);
+  }
+  void launch_explicit_start(const ExplicitParams &p, hipStream_t s)
+  {
+    hipLaunchKernelGGL(explicit_start, dim3(int(((p.n + 1) / 2 + 255) / 256)), dim3(256), 0, s, p);
+  }
+  void launch_explicit_advance(const ExplicitParams &p, hipStream_t s)
+  {
+    hipLaunchKernelGGL(explicit_advance, dim3(int(((p.n + 1) / 2 + 255) / 256)), dim3(256), 0, s, p);
+  }
+  void launch_explicit_finish(bool commit, const NewmarkParams &p, const double *mass, double *du, double *part, int grid, double *out,
+                              hipStream_t s)
+  {
+    if (commit)
+      hipLaunchKernelGGL((explicit_finish<true>), dim3(grid), dim3(256), 0, s, p, mass, du, part);
+    else
+      hipLaunchKernelGGL((explicit_finish<false>), dim3(grid), dim3(256), 0, s, p, mass, du, part);
+    hipLaunchKernelGGL(finish_sum, dim3(1), dim3(256), 0, s, part, grid, out);
+  }
+  void launch_weighted_sq(const double *mass, const double *x, int64_t n, double *part, int grid, double *out, hipStream_t s)
+  {
+    NewmarkParams p{};
+    p.v = const_cast<double *>(x), p.n = n; // (explicit_finish<false> reads p.v and p.n alone)
+    hipLaunchKernelGGL((explicit_finish<false>), dim3(grid), dim3(256), 0, s, p, mass, (double *)nullptr, part);
+    hipLaunchKernelGGL(finish_sum, dim3(1), dim3(256), 0, s, part, grid, out);
+  }
+  void launch_lanczos_update(double *y, const double *minv, const double *q, const double *qprev, double alpha, double beta, int64_t n,
+                             hipStream_t s)
+  {
+    hipLaunchKernelGGL(lanczos_update, dim3(int((n + 255) / 256)), dim3(256), 0, s, y, minv, q, qprev, alpha, beta, n);
   }
   void launch_linear_rhs_prepare(const LinearParams &p, hipStream_t s)
   {

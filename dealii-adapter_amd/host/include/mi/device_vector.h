@@ -208,6 +208,15 @@ namespace mi
         check(rc, "mi_tangent_modes");
       return rc;
     }
+    // explicit central differences of the nonlinear model (mi_explicit_setup / mi_explicit_run / mi_explicit_stable_dt; one slab
+    // only: on a team the library's refusal is thrown).  explicit_run: a step whose force pass finds det F <= 0 ends the run, the
+    // library's message ("inverted element ... at explicit step k") is thrown with info filled
+    void explicit_setup(double dt, bool init_acceleration) { check(mi_explicit_setup(ctx_, dt, init_acceleration ? 1 : 0), "mi_explicit_setup"); }
+    void explicit_run(int n_steps, mi_explicit_info &info) { check(mi_explicit_run(ctx_, n_steps, &info), "mi_explicit_run"); }
+    void explicit_stable_dt(double &lambda_max, double &dt_crit, int krylov_steps = 40)
+    {
+      check(mi_explicit_stable_dt(ctx_, krylov_steps, &lambda_max, &dt_crit), "mi_explicit_stable_dt");
+    }
     void    check(int rc, const char *what) const
     {
       if (rc != MI_OK)

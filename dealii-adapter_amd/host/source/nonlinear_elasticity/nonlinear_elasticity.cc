@@ -72,10 +72,15 @@ namespace Nonlinear_Elasticity
 
         adapter.read_data(time.get_delta_t(), external_stress);
 
-        // Newton-Raphson; solution_delta lives on the device and is zeroed inside
-        solve_nonlinear_timestep();
-        // total_displacement += solution_delta; update_acceleration/velocity/old_variables (:139-144)
-        device->check(mi_newmark_finish_step(device->ctx()), "mi_newmark_finish_step");
+        if (explicit_mode) // MI_EXPLICIT=1: the step as explicit substeps on the device, which commit the state themselves
+          solve_explicit_timestep();
+        else
+          {
+            // Newton-Raphson; solution_delta lives on the device and is zeroed inside
+            solve_nonlinear_timestep();
+            // total_displacement += solution_delta; update_acceleration/velocity/old_variables (:139-144)
+            device->check(mi_newmark_finish_step(device->ctx()), "mi_newmark_finish_step");
+          }
         log_step_json();
 
         timer.enter_subsection("Advance adapter");
@@ -281,6 +286,13 @@ namespace Nonlinear_Elasticity
           else if (std::atoi(f) != 0)
             device->check(mi_set_tuning(device->ctx(), "mf_diag_lag", 1), "mi_set_tuning");
         }
+      // 1: explicit central differences with a lumped mass instead of the Newmark step (one slab; see solve_explicit_timestep)
+      if (const char *f = std::getenv("MI_EXPLICIT"))
+        explicit_mode = std::atoi(f) != 0;
+      if (const char *f = std::getenv("MI_EXPLICIT_SAFETY"))
+        explicit_safety = std::atof(f);
+      if (explicit_mode && !(explicit_safety > 0.0 && explicit_safety <= 1.0))
+        throw std::runtime_error("MI_EXPLICIT_SAFETY must lie in (0, 1]");
       // 4: the multigrid smoother of a 3D Q3 matrix-free level integrates with the element's full-order rule (5: the assembly's)
       if (const char *f = std::getenv("MI_SMOOTHER_QUADRATURE_Q3"))
         if (mi_set_tuning(device->ctx(), "smoother_quadrature_q3", std::atoi(f)) != MI_OK)
@@ -409,6 +421,35 @@ namespace Nonlinear_Elasticity
       throw std::runtime_error("No convergence in nonlinear solver!"); // :497-498
   }
 
+  // MI_EXPLICIT=1: the time step of the parameter file as n_sub explicit steps of dt / n_sub, n_sub = ceil(dt / (s dt_crit)).  The
+  // traction was set once for the time step (read_data), as for an implicit step; a folded cell ends the run with the library's
+  // message.  Checkpoints of an implicit coupling go through the six state vectors, which the explicit steps keep as a Newmark
+  // step does (*_OLD = new at the end); after a reload the run continues from the restored acceleration
+  template <int dim>
+  void Solid<dim>::solve_explicit_timestep()
+  {
+    std::cout << std::endl
+              << "Timestep " << time.get_timestep() << " @ " << std::fixed << time.current() << "s" << std::endl;
+    timer.enter_subsection("Explicit steps");
+    if (!explicit_started || (time.get_timestep() - 1) % 10 == 0)
+      {
+        double lambda_max = 0.0;
+        device->explicit_stable_dt(lambda_max, explicit_dt_crit);
+        std::cout << "\t explicit: lambda_max >= " << std::scientific << std::setprecision(6) << lambda_max << ", dt_crit = " << explicit_dt_crit
+                  << std::endl;
+      }
+    const double dt   = time.get_delta_t();
+    explicit_substeps = std::max(1, int(std::ceil(dt / (explicit_safety * explicit_dt_crit))));
+    device->explicit_setup(dt / explicit_substeps, !explicit_started);
+    explicit_started = true;
+    device->explicit_run(explicit_substeps, explicit_info);
+    timer.leave_subsection();
+    last_newton_iterations = last_lin_iterations = 0;
+    error_residual.u = error_update.u = 0.0;
+    std::cout << "\t explicit: " << explicit_substeps << " substeps of " << std::scientific << std::setprecision(6) << explicit_info.dt
+              << " s, kinetic energy (lumped) " << explicit_info.kinetic_lumped << std::endl;
+  }
+
   template <int dim>
   void Solid<dim>::print_conv_header()
   {
@@ -470,6 +511,9 @@ namespace Nonlinear_Elasticity
     if (have_serr)
       out << ", \"stress_error\": " << serr.error << ", \"stress_norm\": " << serr.norm << ", \"stress_error_relative\": " << serr.relative
           << ", \"stress_error_max_cell\": " << serr.max_cell;
+    if (explicit_mode)
+      out << ", \"explicit_substeps\": " << explicit_substeps << ", \"explicit_dt\": " << explicit_info.dt
+          << ", \"kinetic_lumped\": " << explicit_info.kinetic_lumped;
     out << "}\n";
   }
 

@@ -48,6 +48,7 @@ namespace Nonlinear_Elasticity
     void make_grid();
     void system_setup();
     void solve_nonlinear_timestep();
+    void solve_explicit_timestep(); // MI_EXPLICIT=1
     void output_results() const;
     void report_tangent_modes(int k); // MI_TANGENT_MODES=k
     static void print_conv_header();
@@ -89,5 +90,12 @@ namespace Nonlinear_Elasticity
     unsigned int last_newton_iterations = 0, last_lin_iterations = 0;
     bool         use_device_direct = true; // "Solver type = Direct": mi_direct_solve until it reports "too large"
     void         log_step_json() const;
+    // MI_EXPLICIT=1: every time step becomes n_sub = ceil(dt / (s dt_crit)) explicit central-difference steps of dt / n_sub on the
+    // device (mi_explicit_run), s = MI_EXPLICIT_SAFETY (default 0.8); dt_crit from mi_explicit_stable_dt before the first step and
+    // again every 10th
+    bool             explicit_mode = false, explicit_started = false;
+    double           explicit_safety = 0.8, explicit_dt_crit = 0.0;
+    int              explicit_substeps = 0;
+    mi_explicit_info explicit_info{};
   };
 } // namespace Nonlinear_Elasticity

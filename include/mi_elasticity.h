@@ -554,6 +554,76 @@ int mi_linear_modes(mi_ctx *ctx, int n_modes, double tol, int max_it, double *la
 int mi_tangent_modes(mi_ctx *ctx, int n_modes, double tol, int max_it, double *lambda /* n_modes */,
                      double *modes /* [n_modes][n_dofs] or NULL */, double *residual /* n_modes or NULL */, int *its /* or NULL */);
 
+/* ---- explicit dynamics of the NONLINEAR model: central differences in velocity-Verlet form with a lumped mass ----------------
+ * For short transients far below the structure's period: a step is one residual-only pass and one streaming kernel -- no tangent,
+ * no solve, no Newton loop.  The lumped mass is m_i = rho W_i on every component of node i, W_i = sum_q N_i JxW on the assembly's
+ * rule QGauss(p + 2): the row sum of the consistent mass of mi_mass_apply (positive for FE_Q of degrees 1-4).  minv_i = 1 / m_i on
+ * free dofs and 0 on the dofs mi_get_constrained flags.  Given the committed u, v, a (MI_V_TOTAL_DISPLACEMENT, MI_V_VELOCITY,
+ * MI_V_ACCELERATION) and the step dt:
+ *     du = dt v + dt^2 / 2 a
+ *     F  = -f_int(u + du) + rho b W + Neumann(u + du, MI_V_EXTERNAL_STRESS), masked: what mi_assemble_residual leaves in
+ *          MI_V_SYSTEM_RHS when MI_V_ACCELERATION is zero and MI_V_SOLUTION_DELTA = du (the pass reads a zero vector of the
+ *          call's own in place of the acceleration; MI_V_ACCELERATION itself is not zeroed)
+ *     a' = minv F;   v <- v + dt / 2 (a + a');   u <- u + du;   a <- a'
+ * The traction is held over the steps of one call.  The force pass is whichever pass the context's keys select ("fine_level" 0 / 1,
+ * "point_pass_q3" 0 / 1); 2D and 3D, degrees 1-4.  Undecomposed contexts only: an emulated or RCCL team gets MI_EINVAL "one slab
+ * only".  The calls touch no tangent, record, hierarchy or hierarchy flag, no "count_cg_*" counter and no stored start vector of
+ * "cg_warm_start" (mi_explicit_stable_dt excepted, see there).  One timing slot moves: with mi_set_profiling on, every force pass
+ * is stamped in MI_T_ASSEMBLE_RESIDUAL, as the pass of mi_assemble_residual is.  After mi_linear_setup the calls still step the
+ * NONLINEAR model on the shared state vectors; they select the tangent's side of the context first, as mi_tangent_modes does.
+ *   Tuning key "explicit_force_only" (1 default | 0; read back by mi_get_tuning): 1, the force passes of the two one-launch point
+ * passes -- the 3D Q2 matrix-free level's (assemble_q2sf) and the 3D Q3 level's under "point_pass_q3" 1 (mf_point_pass_q3) -- run
+ * instances that do not read the acceleration (a template flag: Q2 without the gather and the interpolation N a, Q3 without the
+ * gather; the value pass stays there because the body force rides on it); 0, every pass reads the call's zero vector through the
+ * parent's instances.  Both forms return the same bits (==, the sign of a zero aside); every other element family reads the zero
+ * vector whatever the key says.  Not provided: teams, the linear model, mass scaling, an
+ * element-wise step estimate, damping, releasing the tangent array of a context that only steps explicitly. */
+typedef struct mi_explicit_info
+{
+  int32_t steps_done;     /* steps committed by the call                                                      */
+  int32_t inverted_step;  /* the 1-based step whose force pass found det F <= 0, -1: none                     */
+  double  dt;             /* the step of the last mi_explicit_setup                                           */
+  double  kinetic_lumped; /* 1/2 sum_i m_i v_i^2 of the state the call leaves, summed in a fixed order        */
+} mi_explicit_info;
+/* Forms the lumped masses on the device (first call: M 1 through the mass kernels of mi_mass_apply; 3 n_dofs doubles are kept
+ * with the context: masses, inverses, a zero vector) and sets the step dt > 0 of the following mi_explicit_run calls.
+ * init_acceleration 1: MI_V_SOLUTION_DELTA := 0, then MI_V_ACCELERATION and MI_V_ACCELERATION_OLD := minv F(u) of the committed
+ * state -- the one change to the six state vectors; MI_V_SYSTEM_RHS holds that F.  A committed state with det F <= 0: MI_EINVAL
+ * "inverted element", the acceleration untouched.  init_acceleration 0: the state stays as it is (continuing an explicit run with
+ * another dt, or after mi_state_restore).  May be called again; cheap apart from the optional force pass.  dt <= 0 or not finite,
+ * another init_acceleration, a team: MI_EINVAL with nothing changed. */
+int mi_explicit_setup(mi_ctx *ctx, double dt, int init_acceleration);
+/* n_steps steps of the scheme above, enqueued on the context's stream as plain launches: per step the force pass and
+ * explicit_advance (commits the step and predicts the next du), one explicit_start before and one explicit_finish after them;
+ * no host synchronisation between steps, one read-back at the end.  The device takes the one decision of a step: if the pass of
+ * step k reports det F <= 0, step k and all later steps of the call commit nothing (their passes still run), a device word keeps
+ * k, and the call returns MI_EINVAL "inverted element ... at explicit step k" with info->steps_done = k - 1, info->inverted_step =
+ * k and the six state vectors those after step k - 1 bit for bit (what a call with n_steps = k - 1 leaves).
+ *   Afterwards the *_OLD vectors equal the new ones, as mi_newmark_finish_step leaves them, MI_V_SOLUTION_DELTA is 0 and
+ * MI_V_SYSTEM_RHS holds the force of the last pass.  A run of n steps equals n runs of one step bit for bit, and two runs from the
+ * same state return the same bytes: every sum of the update is written with its rounding, the kinetic sum goes through
+ * fixed-order partials, nothing is added atomically.  n_steps = 0: no vector is written, info is filled.
+ *   MI_EINVAL with nothing changed: no mi_explicit_setup yet, n_steps < 0, a NULL argument, a team, a context whose tangent array a
+ * "linear_operator" 1 set-up has released.  A force pass that cannot be enqueued (no kernel, a HIP error) ends the run after the
+ * steps before it: those stay committed, the *_OLD vectors and the delta are finished as after any run, info is filled with the
+ * steps done, and the pass's error code is returned. */
+int mi_explicit_run(mi_ctx *ctx, int n_steps, mi_explicit_info *info);
+/* the lumped masses m [n_dofs] (global dof order, constrained dofs included): a test hook; forms them if no set-up has */
+int mi_explicit_get_mass(mi_ctx *ctx, double *m /* n_dofs */);
+/* Stability limit of the scheme at the committed state: *lambda_max = the largest Ritz value theta of krylov_steps >= 1 Lanczos
+ * steps (40 is a good default; at most the number of free dofs are taken) for K_T phi = lambda M_L phi on the free dofs, in the
+ * inner product of the lumped mass M_L, and *dt_crit = 2 / sqrt(theta).  theta is a LOWER bound of lambda_max, so dt_crit lies
+ * above the true limit by that much: a caller multiplies it by a safety factor (the executable: 0.8).
+ *   The call zeroes MI_V_SOLUTION_DELTA and MI_V_NEWTON_UPDATE and runs the assembly of mi_assemble at the committed state, as
+ * mi_tangent_modes does, without the refresh of the hierarchy (which is left marked stale).  Products go through the context's own
+ * operator A (assembled, or matrix-free with "fine_level" 1) minus alpha_1 rho M x from the matrix-free mass, as mi_tangent_modes
+ * forms them.  The start vector is the eigensolvers' fixed hashed one and every sum has a fixed order: two calls return the same
+ * bits.  No reorthogonalisation: the largest Ritz value does not need it.
+ *   Effects: none on the six state vectors or MI_V_EXTERNAL_STRESS; tangent, diagonal, records and MI_V_SYSTEM_RHS are what the
+ * assembly wrote; 5 n_dofs doubles are allocated for the call and freed.  Forms the lumped masses if no set-up has.  A folded
+ * state: MI_EINVAL "inverted element" from the assembly.  A NULL argument, krylov_steps < 1, a team: MI_EINVAL. */
+int mi_explicit_stable_dt(mi_ctx *ctx, int krylov_steps, double *lambda_max, double *dt_crit);
+
 /* per-vector device snapshots: what `old_state_data[i] = *state_variables[i]` (adapter.h:457-460) and its
  * inverse (:481-482) become when VectorType is a handle to a device-resident vector */
 typedef struct mi_snapshot mi_snapshot;
